@@ -27,6 +27,10 @@ Contract (one JSON line on rank 0):
     duration measured with HIP events on the library's stream during the timed region;
   * `cpu_baseline`: the CPU oracle (a port with Ceres-equivalent semantics, NOT Ceres --
     Ceres/Eigen are not installable here) timed on the host cores on the same problem.
+  * `--dump-outputs DIR`: after the timed steps, what the timed path computed is written as float64 DIR/<name>.npy -- the
+    blocks ssba_solve_end hands back to the caller (the lowest-cost iterate since the last restart: poses, points and, for C3,
+    normals and the shared lighting blocks; whole joint problem when N > 1) and the cost column of the iteration log of
+    those steps.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -259,9 +263,22 @@ def host_description():
     return {"nproc": os.cpu_count() or 1, "usable_cpus": usable, "cpu_model": model}
 
 
-def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False):
+def write_outputs(out_dir, outputs, limit=64 * 10 ** 6):
+    """--dump-outputs: one float64 .npy per output.  Every workload fits the limit whole (the largest, C3 on eight GPUs:
+    800 000 landmarks with positions and normals, 39 MB), so nothing is sampled."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {limit} the dump may hold")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False, dump=False):
     """One workload: build the (sharded) problem, solve it once to convergence, then time `args.steps` iterations of the
-    production path between barriers.  Returns everything the bench line reports for it (rank 0 decides what to print)."""
+    production path between barriers.  Returns everything the bench line reports for it (rank 0 decides what to print);
+    with `dump`, also the outputs of the timed steps (`outputs`, on rank 0)."""
     import torch
     from ceres_slam_amd import capi, sharding, synth
     from ceres_slam_amd.solver import StereoBA
@@ -334,11 +351,15 @@ def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False):
     period = max(int(s_conv.num_iterations) - 1, 1)
     final_cost = float(s_conv.final_cost)
     solve_wall_s, solve_device_s = float(s_conv.total_time_s), float(s_conv.device_time_s)
-    ba.poses[:] = shard.poses_init
-    ba.points[:] = shard.points_init
-    if phong:
-        ba.normals[:] = lighting["normals"]
-        ba.phong[:], ba.texture[:], ba.light[:] = lighting["phong"], lighting["texture"], lighting["light"]
+
+    def reset_params():      # the caller-owned blocks back to the initial values (ssba_solve_begin uploads them)
+        ba.poses[:] = shard.poses_init
+        ba.points[:] = shard.points_init
+        if phong:
+            ba.normals[:] = lighting["normals"]
+            ba.phong[:], ba.texture[:], ba.light[:] = lighting["phong"], lighting["texture"], lighting["light"]
+
+    reset_params()
 
     def run(n_steps, timing):
         ba.set_kernel_timing(timing)
@@ -374,6 +395,26 @@ def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    outputs = None
+    if dump:
+        # what a caller of the timed path receives: ssba_solve_end writes the best iterate back into the caller's blocks
+        ba.solve_end()
+        outputs = dict(poses=ba.poses.copy(), points=ba.points.copy(), iteration_cost=ba.iteration_log()["cost"])
+        if phong:
+            outputs.update(normals=ba.normals.copy(), phong=ba.phong.copy(), texture=ba.texture.copy(), light=ba.light.copy())
+        if world > 1:      # landmark blocks are sharded: rank 0 puts the joint problem's together
+            parts = [None] * world
+            dist.all_gather_object(parts, (shard.point_ids, {k: outputs[k] for k in ("points", "normals") if k in outputs}))
+            for k in parts[0][1]:
+                full = np.zeros((prob.num_points,) + outputs[k].shape[1:])
+                for ids, blocks in parts:
+                    full[ids] = blocks[k]
+                outputs[k] = full
+            if rank:
+                outputs = None
+        if kernel_timing:      # the instrumented pass below runs on a solve begun again from the initial values
+            reset_params()
+            ba.solve_begin(opts, ignore_convergence=True)
     # instrumented pass: the same K steps launched eagerly with every kernel bracketed by HIP
     # events on the library's stream (per-kernel durations for the roofline; agrees with
     # rocprofv3 --kernel-trace of this command)
@@ -386,7 +427,8 @@ def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False):
         ba.synchronize()
         dt_instr = time.perf_counter() - t1
     ktimes = ba.kernel_times()
-    ba.solve_end()
+    if kernel_timing or not dump:      # (the dump above has ended the solve already when nothing was begun after it)
+        ba.solve_end()
     xsize = int(ba.exchange_size()) if world > 1 else 0
     ba.close()
     if world > 1:
@@ -398,7 +440,7 @@ def measure(args, name, P, L, ctx, kernel_timing, phong=False, robust=False):
                 line_search=dict(evaluations=int(s_conv.num_line_search_steps), searches_on_device=int(s_conv.num_line_searches_on_device),
                                  searches_by_host=int(s_conv.num_line_searches_by_host)),
                 solve_device_s=solve_device_s, exchange=exchange, rccl_ranks=rccl_ranks, rccl_note=rccl_note,
-                partitioned=partition is not None, exchange_doubles=xsize, poses=P, landmarks=L)
+                partitioned=partition is not None, exchange_doubles=xsize, poses=P, landmarks=L, outputs=outputs)
 
 
 def main():
@@ -419,7 +461,11 @@ def main():
     ap.add_argument("--shared-free", type=int, default=0, help="C3 only: free shared blocks (bit 0 light, 1 Phong, 2 texture)")
     ap.add_argument("--bounds", action="store_true", help="C3 only: the driver's bounds on the Phong / texture blocks")
     ap.add_argument("--dogleg", type=int, default=-1, help="-1 LM (dataset_vo), 0 TRADITIONAL_DOGLEG, 1 SUBSPACE_DOGLEG")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)         # children; never returns
@@ -456,7 +502,10 @@ def main():
     C2P, C2L = synth.CONFIGS["C2"]
     # the joint problem: C4 is a fixed size (strong-scaled over the ranks); the C2-shaped configurations grow with the ranks
     P, L = (P1, L1) if cfg == "C4" else (P1 * world, L1 * world)
-    m = measure(args, cfg, P, L, ctx, kernel_timing=not args.no_kernel_timing, phong=phong, robust=robust)
+    m = measure(args, cfg, P, L, ctx, kernel_timing=not args.no_kernel_timing, phong=phong, robust=robust,
+                dump=args.dump_outputs is not None)
+    if m["outputs"] is not None:
+        write_outputs(args.dump_outputs, m["outputs"])
     weak = strong = single = single_c2 = None
     if world == 8 and args.config is None and not args.no_weak_secondary:
         weak = measure(args, "C2", C2P * world, C2L * world, ctx, kernel_timing=False)

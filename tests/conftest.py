@@ -22,6 +22,17 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture(scope="session")
+def torch_sees_a_gpu():
+    """Whether torch finds a GPU, asked in a child process.  torch ships its own HIP runtime; once libssba.so has mapped
+    ROCm's, importing torch maps a second one, and only the runtime that opens the device first sees it -- so the test
+    process, which runs GPU tests after CPU tests, never imports torch itself."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                       capture_output=True, text=True, timeout=600, check=True)
+    return r.stdout.split()[-1] == "1"
+
+
+@pytest.fixture(scope="session")
 def c1_problem():
     from ceres_slam_amd import synth
     return synth.make_config("C1")

@@ -55,11 +55,10 @@ def test_defaults_are_the_ceres_1x_defaults():
     assert o.min_lm_diagonal == 1e-6 and o.max_lm_diagonal == 1e32
 
 
-def test_status_strings_and_no_cpu_fallback():
+def test_status_strings_and_no_cpu_fallback(torch_sees_a_gpu):
     lib = capi.load()
     assert b"no CPU fallback" in lib.ssba_status_string(-5)
-    import torch
-    if not torch.cuda.is_available():
+    if not torch_sees_a_gpu:
         # without a GPU the product path must fail loudly, never compute on the CPU
         cam = capi.Camera(1, 1, 0, 0, 1)
         h = ctypes.c_void_p()

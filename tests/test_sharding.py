@@ -401,12 +401,11 @@ def _bench(args, env_extra, timeout=900):
     return r, [json.loads(ln) for ln in lines]
 
 
-def test_bench_gpus_n_starts_its_own_ranks_and_relays_their_exit_code():
+def test_bench_gpus_n_starts_its_own_ranks_and_relays_their_exit_code(torch_sees_a_gpu):
     """`python bench.py --gpus 2` typed without a launcher starts two ranks as child processes (before the parent touches a
     GPU).  On this CPU-only box every rank stops with the library's "no CPU fallback" message; the parent must relay a
     non-zero exit code and print no bench line."""
-    import torch
-    if torch.cuda.is_available():
+    if torch_sees_a_gpu:
         pytest.skip("CPU-only check of the launcher (the GPU rehearsal below covers the working path)")
     r, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {"SSBA_BENCH_BACKEND": "gloo"}, timeout=600)
     assert r.returncode != 0

@@ -1,0 +1,466 @@
+"""Extended-precision reference for the reduced camera system (CPU only).
+
+Everything that cancels -- the stereo rows, their Gram products and the landmark elimination of the Schur complement -- is
+evaluated in ``np.longdouble`` (80-bit on x86-64: unit roundoff 2^-64 against fp64's 2^-53) from the fp64 inputs the device
+received, which long double holds exactly.  The system is the one the device factorises (``k_assemble_reduced`` /
+``k_finish_reduced``): UNSCALED coordinates, the Jacobi scale s = 1 / (1 + sqrt(diag H)) taken at the linearisation point,
+the Levenberg-Marquardt diagonal clamp(diag(H) s^2, 1e-6, 1e32) / (radius s^2) on pose and landmark blocks, and
+
+    S = A_pp - sum_j W_j V_j^-1 W_j^T,    rhs = -(g_p - sum_j W_j V_j^-1 g_l,j),    S delta_p = rhs.
+
+Unary pose rows (prior, sun sensor) are passed in as fp64 blocks; their rounding enters the bounds as c u |H_unary|.
+
+The bars derived here all use u = 2^-53 (the precision of the side under test):
+
+* backward error  eta = |rhs - S x|_inf / (|S|_inf |x|_inf + |rhs|_inf), residual in long double;
+* entrywise assembly bound  E = (m + c) u (|A_pp| + sum_j kappa(V_j) |W_j| |V_j^-1| |W_j|^T), m the number of terms summed into
+  the entry -- large exactly where the Schur complement cancels, which a fixed relative bar is not;
+* covariance bound  |S^-1| E |S^-1| (first-order propagation) plus the solve term.
+
+Imports neither torch nor libssba.so.
+"""
+from __future__ import annotations
+
+import numpy as np
+import scipy.linalg as sla
+
+LD = np.longdouble
+assert np.finfo(LD).nmant >= 63, "long double is not extended precision on this platform: the reference would be fp64"
+
+U = 2.0 ** -53            # unit roundoff of the side under test
+C_TERMS = 16              # the c of gamma = (m + c) u: the rounding of one row / one 3x3 inverse, independent of m
+SOLVE_C = 4096            # eta <= SOLVE_C u;  |x - x*| / |x*| <= SOLVE_C u kappa_2
+DENSE_EIG_MAX = 2000      # kappa_2 from eigvalsh up to this size, from the extreme eigenvalues of the band above
+
+
+# ---------------------------------------------------------------------------------------------------------------- stereo rows
+def huber_weight(sq, a, dtype=LD):
+    """sqrt(rho') of the Huber loss at s = |r|^2 (Ceres corrector with rho'' <= 0: r and J scaled by sqrt(rho'))."""
+    sq = np.asarray(sq, dtype=dtype)
+    if not a > 0:
+        return np.ones_like(sq)
+    a = dtype(a)
+    out = sq > a * a
+    return np.where(out, np.sqrt(a / np.sqrt(np.where(out, sq, dtype(1)))), dtype(1))
+
+
+def stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a=0.0, dtype=LD):
+    """Residuals and closed-form local Jacobians (the route of np_reference.NumpyBA.residuals) in `dtype`.
+
+    stiffness: one 3x3 matrix or one per observation (N, 3, 3).  Returns a dict with cost, r (N,3), Jp (N,3,6), Jl (N,3,3)
+    -- corrected by sqrt(rho') -- and the magnitudes the fp64 rounding of each row is relative to: rabs (N,3) for the
+    residual (pred - z cancels), Jpa / Jla for the Jacobians (q = R p + t cancels when the point is far from the origin).
+    """
+    f = lambda v: np.asarray(v, dtype=dtype)
+    k, j = np.asarray(obs_pose, np.int64), np.asarray(obs_point, np.int64)
+    T, p, z = f(poses)[k], f(points)[j], f(obs_uvd)
+    S = f(stiffness)
+    S = np.broadcast_to(S.reshape(3, 3), (k.shape[0], 3, 3)) if S.size == 9 else S.reshape(-1, 3, 3)
+    fu, fv, cu, cv, b = (dtype(cam[n]) for n in ("fu", "fv", "cu", "cv", "b"))
+    t, R = T[:, :3], T[:, 3:].reshape(-1, 3, 3)
+    q = np.einsum("nij,nj->ni", R, p) + t
+    iz = dtype(1) / q[:, 2]
+    pred = np.stack([fu * q[:, 0] * iz + cu, fv * q[:, 1] * iz + cv, fu * b * iz], 1)
+    r = np.einsum("nij,nj->ni", S, pred - z)
+    sq = (r * r).sum(1)
+    w = huber_weight(sq, huber_a, dtype)
+    if huber_a > 0:
+        a = dtype(huber_a)
+        rho0 = np.where(sq > a * a, 2 * a * np.sqrt(sq) - a * a, sq)
+    else:
+        rho0 = sq
+    N = q.shape[0]
+    Jpi = np.zeros((N, 3, 3), dtype=dtype)
+    Jpi[:, 0, 0] = fu * iz
+    Jpi[:, 0, 2] = -fu * q[:, 0] * iz * iz
+    Jpi[:, 1, 1] = fv * iz
+    Jpi[:, 1, 2] = -fv * q[:, 1] * iz * iz
+    Jpi[:, 2, 2] = -fu * b * iz * iz
+    A = np.einsum("nij,njk->nik", S, Jpi)
+    G = np.zeros((N, 3, 6), dtype=dtype)
+    G[:, 0, 0] = G[:, 1, 1] = G[:, 2, 2] = 1
+    G[:, 0, 4], G[:, 0, 5] = q[:, 2], -q[:, 1]
+    G[:, 1, 3], G[:, 1, 5] = -q[:, 2], q[:, 0]
+    G[:, 2, 3], G[:, 2, 4] = q[:, 1], -q[:, 0]
+    Jp = np.einsum("nij,njk->nik", A, G) * w[:, None, None]
+    Jl = np.einsum("nij,njk->nik", A, R) * w[:, None, None]
+    # magnitudes (fp64 is enough): alpha = how much larger the terms of q are than q itself
+    q64, R64, p64, t64 = (np.asarray(v, np.float64) for v in (q, R, p, t))
+    alpha = 1.0 + (np.abs(R64) @ np.abs(p64)[..., None])[..., 0].max(1) / np.abs(q64[:, 2]) + np.abs(t64).max(1) / np.abs(q64[:, 2])
+    Jp64, Jl64, w64 = np.abs(np.asarray(Jp, np.float64)), np.abs(np.asarray(Jl, np.float64)), np.asarray(w, np.float64)
+    rabs = np.einsum("nij,nj->ni", np.abs(np.asarray(S, np.float64)),
+                     alpha[:, None] * np.abs(np.asarray(pred, np.float64)) + np.abs(np.asarray(z, np.float64))) * w64[:, None]
+    Jpa = Jp64 + alpha[:, None, None] * Jp64.max((1, 2))[:, None, None]
+    Jla = Jl64 + alpha[:, None, None] * Jl64.max((1, 2))[:, None, None]
+    return dict(cost=dtype(0.5) * rho0.sum(), r=r * w[:, None], Jp=Jp, Jl=Jl, rabs=rabs, Jpa=Jpa, Jla=Jla, alpha=alpha)
+
+
+# ------------------------------------------------------------------------------------------------------------ Schur assembly
+def inv3(V):
+    """Inverses of a stack of 3x3 matrices by the adjugate (numpy.linalg does not take long double)."""
+    a, b, c = V[:, 0, 0], V[:, 0, 1], V[:, 0, 2]
+    d, e, f = V[:, 1, 0], V[:, 1, 1], V[:, 1, 2]
+    g, h, i = V[:, 2, 0], V[:, 2, 1], V[:, 2, 2]
+    C = np.stack([e * i - f * h, c * h - b * i, b * f - c * e,
+                  f * g - d * i, a * i - c * g, c * d - a * f,
+                  d * h - e * g, b * g - a * h, a * e - b * d], 1).reshape(-1, 3, 3)
+    det = a * C[:, 0, 0] + b * C[:, 1, 0] + c * C[:, 2, 0]
+    return C / det[:, None, None]
+
+
+def _segments(keys):
+    """Sorted order of `keys` and the segment starts of equal keys (for np.add.reduceat)."""
+    order = np.argsort(keys, kind="stable")
+    ks = keys[order]
+    starts = np.flatnonzero(np.concatenate([[True], ks[1:] != ks[:-1]])) if ks.size else np.zeros(0, np.int64)
+    return order, ks, starts
+
+
+def _damping(h, s, radius):
+    if radius is None:
+        return np.zeros_like(h)
+    s2 = s * s
+    return np.clip(h * s2, LD(1e-6), LD(1e32)) / (LD(radius) * s2)
+
+
+class SchurSystem:
+    """The damped (radius) or undamped (radius=None) reduced camera system in long double, stored as 6x6 blocks.
+
+    free_idx: free index of every pose (-1 constant).  H_unary / g_unary (n x n and n, fp64, free-pose coordinates): unary
+    pose rows already summed; Ha_unary their magnitude sum |J|^T |J| (unary_pose_blocks).  The Schur terms are summed in
+    chunks into the distinct 6x6 blocks, so a C2-sized system (14 million observation pairs) fits in memory.
+
+    E is a bound on the fp64 rounding of each entry, not a relative bar: where a landmark is nearly unobserved in depth
+    (undamped V_j, kappa(V_j) ~ 1e12 and more) its terms exceed S itself and the check only bounds the cancellation.
+    """
+
+    def __init__(self, rows, obs_pose, obs_point, free_idx, num_points, radius=None, H_unary=None, g_unary=None,
+                 Ha_unary=None):
+        k = np.asarray(obs_pose, np.int64)
+        j = np.asarray(obs_point, np.int64)
+        fidx = np.asarray(free_idx, np.int64)
+        self.nf = nf = int((fidx >= 0).sum())
+        self.n = 6 * nf
+        f = fidx[k]
+        Jp, Jl, r = rows["Jp"], rows["Jl"], rows["r"]
+        Jpa, Jla, rabs = rows["Jpa"], rows["Jla"], rows["rabs"]
+        fr = f >= 0
+        # ---- landmark blocks (undamped Gram, scale, damping, inverse)
+        V_i = np.einsum("nai,naj->nij", Jl, Jl)
+        g_i = np.einsum("nai,na->ni", Jl, r)
+        order, lk, st = _segments(j)
+        self.lm = lk[st]                                            # landmarks present
+        V = np.add.reduceat(V_i[order], st, axis=0)
+        gl = np.add.reduceat(g_i[order], st, axis=0)
+        hl = np.diagonal(V, axis1=1, axis2=2).copy()
+        sl = LD(1) / (LD(1) + np.sqrt(hl))
+        V[:, [0, 1, 2], [0, 1, 2]] += _damping(hl, sl, radius)
+        Vinv = inv3(V)
+        self.V, self.Vinv, self.gl = V, Vinv, gl
+        slot = np.full(num_points, -1, np.int64)
+        slot[self.lm] = np.arange(self.lm.shape[0])
+        self.slot_of_obs = slot[j]
+        V64 = np.asarray(V, np.float64)
+        self.kappa_V = np.linalg.cond(V64)
+        Via = np.abs(np.asarray(Vinv, np.float64))
+        # ---- pose blocks
+        Hp_i = np.einsum("nai,naj->nij", Jp, Jp)
+        gp_i = np.einsum("nai,na->ni", Jp, r)
+        Hpa_i = np.einsum("nai,naj->nij", Jpa, Jpa)
+        gpa_i = np.einsum("nai,na->ni", Jpa, rabs)
+        n = self.n
+        Hd = np.zeros((nf, 6, 6), dtype=LD)
+        gp = np.zeros((nf, 6), dtype=LD)
+        Hda = np.zeros((nf, 6, 6))
+        gpa = np.zeros((nf, 6))
+        m_diag = np.zeros(nf)
+        o2, fk, st2 = _segments(f[fr])
+        if fk.size:
+            sel = np.flatnonzero(fr)[o2]
+            fu = fk[st2]
+            Hd[fu] = np.add.reduceat(Hp_i[sel], st2, axis=0)
+            gp[fu] = np.add.reduceat(gp_i[sel], st2, axis=0)
+            Hda[fu] = np.add.reduceat(Hpa_i[sel], st2, axis=0)
+            gpa[fu] = np.add.reduceat(gpa_i[sel], st2, axis=0)
+            m_diag[fu] = np.diff(np.concatenate([st2, [fk.size]]))
+        if H_unary is not None:
+            for a in range(nf):
+                Hd[a] += np.asarray(H_unary[6 * a: 6 * a + 6, 6 * a: 6 * a + 6], LD)
+                gp[a] += np.asarray(g_unary[6 * a: 6 * a + 6], LD)
+                Hda[a] += Ha_unary[6 * a: 6 * a + 6, 6 * a: 6 * a + 6]
+                gpa[a] += np.abs(g_unary[6 * a: 6 * a + 6])
+        hp = np.diagonal(Hd, axis1=1, axis2=2).copy()
+        self.sp = LD(1) / (LD(1) + np.sqrt(hp))
+        dmp = _damping(hp, self.sp, radius)
+        Hd[:, range(6), range(6)] += dmp
+        Hda[:, range(6), range(6)] += np.asarray(dmp, np.float64)
+        # ---- Schur terms: every ordered pair of free observations of one landmark
+        W = np.einsum("nai,naj->nij", Jp, Jl)                       # 6x3 per observation
+        Wa = np.einsum("nai,naj->nij", Jpa, Jla)
+        self.W = W
+        s_of = self.slot_of_obs
+        X = np.einsum("nij,njk->nik", W, Vinv[s_of])               # W V^-1
+        Xa = np.einsum("nij,njk->nik", Wa, Via[s_of] * self.kappa_V[s_of][:, None, None])
+        # rhs: rhs = -(g_p - sum W V^-1 g_l)
+        rl = np.zeros((nf, 6), dtype=LD)
+        rla = np.zeros((nf, 6))
+        gla = np.zeros((self.lm.shape[0], 3))
+        np.add.at(gla, s_of, np.einsum("nai,na->ni", Jla, rabs))
+        obs_f = np.flatnonzero(fr)
+        if obs_f.size:
+            o3, fk3, st3 = _segments(f[obs_f])
+            sel = obs_f[o3]
+            fu = fk3[st3]
+            rl[fu] = np.add.reduceat(np.einsum("nij,nj->ni", X[sel], gl[s_of[sel]]), st3, axis=0)
+            rla[fu] = np.add.reduceat(np.einsum("nij,nj->ni", Xa[sel], gla[s_of[sel]]), st3, axis=0)
+        self.rhs = -(gp - rl).reshape(n)
+        tmax = float(np.diff(np.concatenate([st, [lk.size]])).max()) if lk.size else 0.0
+        m_rhs = np.repeat(m_diag * (1.0 + tmax), 6)
+        # Schur blocks: every ordered pair (a, b) of free observations of one landmark, summed into the distinct blocks
+        oj, lj, stj = _segments(s_of[obs_f])
+        obs_sorted = obs_f[oj]
+        cnt = np.diff(np.concatenate([stj, [obs_sorted.size]]))
+        pairs = []
+        for t in np.unique(cnt):
+            idx = obs_sorted[stj[cnt == t][:, None] + np.arange(t)[None, :]]          # (n_t, t)
+            pairs.append((np.repeat(idx, t, axis=1).ravel(), np.tile(idx, (1, t)).ravel()))
+        pa = np.concatenate([p[0] for p in pairs]) if pairs else np.zeros(0, np.int64)
+        pb = np.concatenate([p[1] for p in pairs]) if pairs else np.zeros(0, np.int64)
+        pkeys = f[pa] * nf + f[pb]
+        diag_keys = np.arange(nf) * (nf + 1)
+        self.keys = np.unique(np.concatenate([pkeys, diag_keys]))
+        K = self.keys.size
+        blocks = np.zeros((K, 6, 6), dtype=LD)
+        blocka = np.zeros((K, 6, 6))
+        counts = np.zeros(K)
+        CH = 1 << 18
+        for c0 in range(0, pa.size, CH):
+            aa, bb = pa[c0: c0 + CH], pb[c0: c0 + CH]
+            slot_k = np.searchsorted(self.keys, pkeys[c0: c0 + CH])
+            o, ks, stc = _segments(slot_k)
+            u = ks[stc]
+            blocks[u] -= np.add.reduceat(np.einsum("nij,nkj->nik", X[aa[o]], W[bb[o]]), stc, axis=0)
+            blocka[u] += np.add.reduceat(np.einsum("nij,nkj->nik", Xa[aa[o]], Wa[bb[o]]), stc, axis=0)
+            counts[u] += np.diff(np.concatenate([stc, [o.size]]))
+        dslot = np.searchsorted(self.keys, diag_keys)
+        blocks[dslot] += Hd
+        blocka[dslot] += Hda
+        counts[dslot] += m_diag
+        self.blocks = blocks
+        self.m = counts
+        self.E_blocks = ((self.m + C_TERMS) * U)[:, None, None] * blocka
+        if H_unary is not None:      # unary rows: rounding of the device's closed forms, c u |H_unary|
+            for i, key in enumerate(self.keys):
+                a, b = key // nf, key % nf
+                self.E_blocks[i] += C_TERMS * U * Ha_unary[6 * a: 6 * a + 6, 6 * b: 6 * b + 6]
+        self.E_rhs = (m_rhs + C_TERMS) * U * (gpa + rla).reshape(n)
+        self.rows = rows
+        self._k, self._j, self._f = k, j, f
+
+    # ---- views
+    def dense(self, dtype=LD):
+        """S as a dense n x n array (small systems)."""
+        M = np.zeros((self.n, self.n), dtype=dtype)
+        nf = self.nf
+        for key, B in zip(self.keys, self.blocks):
+            a, b = key // nf, key % nf
+            M[6 * a: 6 * a + 6, 6 * b: 6 * b + 6] = B
+        return M
+
+    def dense_bound(self):
+        M = np.zeros((self.n, self.n))
+        nf = self.nf
+        for key, B in zip(self.keys, self.E_blocks):
+            a, b = key // nf, key % nf
+            M[6 * a: 6 * a + 6, 6 * b: 6 * b + 6] = B
+        return M
+
+    def assembly_excess(self, S_dev, rhs_dev):
+        """max over entries of |S_dev - S| / E and |rhs_dev - rhs| / E_rhs (<= 1 passes); inf if S_dev has a non-zero entry
+        outside the blocks the reference forms."""
+        nf = self.nf
+        a, b = self.keys // nf, self.keys % nf
+        r6 = np.arange(6)
+        ri = (6 * a)[:, None, None] + r6[None, :, None]
+        ci = (6 * b)[:, None, None] + r6[None, None, :]
+        Sd = np.asarray(S_dev)
+        d = np.abs(np.asarray(Sd[ri, ci], LD) - self.blocks).astype(np.float64)
+        worst = float((d / np.maximum(self.E_blocks, 1e-300)).max())
+        covered = np.zeros((nf, nf), bool)
+        covered[a, b] = True
+        outside = ~np.repeat(np.repeat(covered, 6, axis=0), 6, axis=1)
+        if np.any(Sd[outside] != 0):
+            return float("inf"), float("inf")
+        d = np.abs(np.asarray(rhs_dev, LD) - self.rhs).astype(np.float64)
+        return worst, float((d / np.maximum(self.E_rhs, 1e-300)).max())
+
+    # ---- back-substitution and the model cost change from a given pose step
+    def back_substitute(self, dp_free):
+        """delta_l = V^-1 (-g_l - W^T delta_p) in long double from the free-pose step (nf*6); (landmarks present, 3)."""
+        x = np.asarray(dp_free, LD).reshape(-1, 6)
+        Wt = np.zeros((self.lm.shape[0], 3), dtype=LD)
+        fr = self._f >= 0
+        np.add.at(Wt, self.slot_of_obs[fr], np.einsum("nij,ni->nj", self.W[fr], x[self._f[fr]]))
+        return np.einsum("nij,nj->ni", self.Vinv, -self.gl - Wt)
+
+    def model_cost_change(self, dp_free, dl_present):
+        """-J delta . (r + J delta / 2) in long double and the magnitude sum of its terms."""
+        x = np.asarray(dp_free, LD).reshape(-1, 6)
+        y = np.asarray(dl_present, LD)
+        fr = self._f >= 0
+        Jd = np.einsum("nai,ni->na", self.rows["Jl"], y[self.slot_of_obs])
+        Jd[fr] += np.einsum("nai,ni->na", self.rows["Jp"][fr], x[self._f[fr]])
+        r = self.rows["r"]
+        terms = -(Jd * (r + LD(0.5) * Jd))
+        return terms.sum(), float(np.abs(np.asarray(Jd * r, np.float64)).sum() + 0.5 * np.abs(np.asarray(Jd * Jd, np.float64)).sum()), terms.size
+
+
+def free_index(num_poses, obs_pose, pose_const):
+    seen = np.bincount(np.asarray(obs_pose, np.int64), minlength=num_poses) > 0
+    free = ~np.asarray(pose_const, bool) & seen
+    fidx = np.full(num_poses, -1, np.int64)
+    fidx[free] = np.arange(int(free.sum()))
+    return fidx
+
+
+# ------------------------------------------------------------------------------------------------------------ refined solve
+def _band_lower(S64, bw):
+    n = S64.shape[0]
+    ab = np.zeros((bw + 1, n))
+    for d in range(bw + 1):
+        ab[d, : n - d] = np.diagonal(S64, -d)
+    return ab
+
+
+def _band_matvec(abL, x):
+    """y = S x for symmetric S given by its lower band (long double)."""
+    y = abL[0] * x
+    n = x.shape[0]
+    for d in range(1, abL.shape[0]):
+        y[d:] += abL[d, : n - d] * x[: n - d]
+        y[: n - d] += abL[d, : n - d] * x[d:]
+    return y
+
+
+def bandwidth(S):
+    """Lower bandwidth of a dense symmetric matrix."""
+    rows, cols = np.nonzero(np.asarray(S) != 0)
+    return int((rows - cols).max()) if rows.size else 0
+
+
+def refined_solve(S, rhs, band=None, max_iter=40):
+    """x with S x = rhs: fp64 Cholesky (banded when `band` -- the lower bandwidth -- is given) and iterative refinement
+    with the residual in long double; stops when the correction stalls.  Returns (x in long double, kappa_2 estimate).
+
+    The result is as accurate as the long-double residual allows: componentwise, cond(S, x) 2^-64 plus the last
+    correction (Skeel); normwise at worst kappa_2 2^-64, 2^11 times below the fp64 bar 4096 u kappa_2 the tests use.
+    """
+    S = np.asarray(S)
+    S64 = np.asarray(S, np.float64)
+    b = np.asarray(rhs, LD)
+    if band is None:
+        fac = sla.cho_factor(S64, lower=True)
+        solve = lambda v: sla.cho_solve(fac, v)
+        SL = np.asarray(S, LD)
+        matvec = lambda v: SL @ v
+    else:
+        ab = _band_lower(S64, band)
+        abL = _band_lower(np.asarray(S, LD), band) if S.dtype == LD else ab.astype(LD)
+        cb = sla.cholesky_banded(ab, lower=True)
+        solve = lambda v: sla.cho_solve_banded((cb, True), v)
+        matvec = lambda v: _band_matvec(abL, v)
+    x = np.asarray(solve(np.asarray(b, np.float64)), LD)
+    prev = np.inf
+    for _ in range(max_iter):
+        res = b - matvec(x)
+        dx = solve(np.asarray(res, np.float64))
+        x = x + np.asarray(dx, LD)
+        nd = float(np.abs(dx).max())
+        if nd <= 2.0 ** -66 * float(np.abs(x).max()) or nd >= 0.5 * prev:
+            break
+        prev = nd
+    return x, kappa2(S64, band)
+
+
+def kappa2(S64, band=None):
+    n = S64.shape[0]
+    if n <= DENSE_EIG_MAX or band is None:
+        w = np.linalg.eigvalsh(0.5 * (S64 + S64.T))
+        return float(w[-1] / w[0])
+    ab = _band_lower(S64, band)
+    lo = sla.eigvals_banded(ab, lower=True, select="i", select_range=(0, 0))[0]
+    hi = sla.eigvals_banded(ab, lower=True, select="i", select_range=(n - 1, n - 1))[0]
+    return float(hi / lo)
+
+
+# ------------------------------------------------------------------------------------------------------------ bound helpers
+def backward_error(S, rhs, x):
+    """eta = |rhs - S x|_inf / (|S|_inf |x|_inf + |rhs|_inf), residual in long double."""
+    SL, b, xl = np.asarray(S, LD), np.asarray(rhs, LD), np.asarray(x, LD)
+    res = np.abs(np.asarray(b - SL @ xl, np.float64)).max()
+    Sn = np.abs(np.asarray(S, np.float64)).sum(1).max()
+    return float(res / (Sn * np.abs(np.asarray(x, np.float64)).max() + np.abs(np.asarray(rhs, np.float64)).max()))
+
+
+def backward_error_banded(S, rhs, x, band):
+    abL = _band_lower(np.asarray(S, np.float64), band).astype(LD)
+    res = np.abs(np.asarray(np.asarray(rhs, LD) - _band_matvec(abL, np.asarray(x, LD)), np.float64)).max()
+    A = np.abs(_band_lower(np.asarray(S, np.float64), band))
+    rs = A[0].copy()
+    n = rs.shape[0]
+    for d in range(1, A.shape[0]):
+        rs[d:] += A[d, : n - d]
+        rs[: n - d] += A[d, : n - d]
+    return float(res / (rs.max() * np.abs(np.asarray(x, np.float64)).max() + np.abs(np.asarray(rhs, np.float64)).max()))
+
+
+def forward_error(x, x_true):
+    x_true = np.asarray(x_true, LD)
+    return float(np.sqrt(((np.asarray(x, LD) - x_true) ** 2).sum() / (x_true ** 2).sum()))
+
+
+def solve_bars(kappa, oracle_bar=1e-8):
+    """(eta bar, forward-error bar): SOLVE_C u and SOLVE_C u kappa_2, never looser than the oracle parity bar."""
+    return SOLVE_C * U, min(SOLVE_C * U * kappa, oracle_bar)
+
+
+def covariance_truth(S_ld, f, band=None):
+    """6x6 block of S^-1 of free pose f from six refined solves (S in long double)."""
+    n = S_ld.shape[0]
+    cols = []
+    for c in range(6):
+        e = np.zeros(n)
+        e[6 * f + c] = 1.0
+        x, kap = refined_solve(S_ld, e, band)
+        cols.append(x[6 * f: 6 * f + 6])
+    return np.stack(cols, 1), kap
+
+
+def covariance_bound(S64, E, f, kappa, cov_true):
+    """Entrywise bound on |cov_dev - cov_true| for a device covariance formed from an S within E of the truth: the first-
+    order propagation |S^-1| E |S^-1| of the assembly error, plus the solve term SOLVE_C u kappa_2 max|cov|."""
+    Si = np.abs(np.linalg.inv(S64))
+    rows = Si[6 * f: 6 * f + 6]
+    return rows @ E @ rows.T + SOLVE_C * U * kappa * float(np.abs(np.asarray(cov_true, np.float64)).max())
+
+
+def unary_pose_blocks(poses, factors, fidx):
+    """H = J^T J, g = J^T r and |J|^T |J| of pose-prior (type 0) and sun-sensor (type 1) rows in fp64, free-pose
+    coordinates: the reference formulas of np_reference with complex-step Jacobians through SE3 Plus.  Without a loss."""
+    import np_reference as npr
+    n = 6 * int((np.asarray(fidx) >= 0).sum())
+    H, g, Ha = np.zeros((n, n)), np.zeros(n), np.zeros((n, n))
+    for fct in factors:
+        assert fct.get("huber", 0.0) == 0.0 and fct["type"] in (0, 1)
+        k = fct["pose"]
+        if fct["type"] == 0:
+            fun = lambda X: npr.pose_prior_residual(X, np.asarray(fct["data"]), np.asarray(fct["stiffness"]).reshape(6, 6))
+        else:
+            d = np.asarray(fct["data"])
+            fun = lambda X: npr.sun_sensor_residual(X, d[:3], d[3:6], np.asarray(fct["stiffness"]).reshape(2, 2), d[6], d[7])
+        r, J = fun(poses[k]).real, npr.se3_complex_step_jacobian(fun, poses[k])
+        sl = slice(6 * int(fidx[k]), 6 * int(fidx[k]) + 6)
+        H[sl, sl] += J.T @ J
+        g[sl] += J.T @ r
+        Ha[sl, sl] += np.abs(J).T @ np.abs(J)
+    return H, g, Ha

@@ -239,6 +239,65 @@ class NumpyBA:
         return x_p, x_l, log
 
 
+# ---- unary pose rows of the sun-aided driver (tests/dataset_vo_sun.cpp:80-124) ------------------------------
+def so3_log(R):
+    """so3group.hpp:293-348 (works on complex matrices for complex-step differentiation)."""
+    axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sin_a = 0.5 * np.sqrt((axis * axis).sum())
+    cos_a = 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)
+    # atan2 for complex arguments: angle + first-order imaginary part
+    ang = np.arctan2(sin_a.real, cos_a.real)
+    d = (cos_a.real * sin_a.imag - sin_a.real * cos_a.imag) / (sin_a.real ** 2 + cos_a.real ** 2) if np.iscomplexobj(R) else 0.0
+    angle = ang + 1j * d if np.iscomplexobj(R) else ang
+    if abs(ang) <= np.finfo(float).eps:         # first-order branch: vee(C - I)
+        return 0.5 * axis
+    return 0.5 * angle * axis / sin_a
+
+
+def pose_prior_residual(T, T_ref, S):
+    """PoseErrorAutomatic (pose_error.hpp:22-55): S [t_ref - R_res t ; log(R_ref R^T)] (complex-step safe)."""
+    R, Rr = T[3:].reshape(3, 3), T_ref[3:].reshape(3, 3)
+    Rres = Rr @ R.T
+    e = np.concatenate([T_ref[:3] - Rres @ T[:3], so3_log(Rres)])
+    return S @ e
+
+
+def sun_sensor_residual(T, oc, eg, S, taz, tzen):
+    """SunSensorErrorAutomatic (sun_sensor_error.hpp:35-104): azimuth / zenith differences (complex-step safe)."""
+    R = T[3:].reshape(3, 3)
+    oc, eg = oc / np.linalg.norm(oc), eg / np.linalg.norm(eg)
+    sc = R @ eg
+
+    def azzen(v):
+        y = v[1]
+        zen = np.arccos(-y.real) + (1j * y.imag / np.sqrt(1 - y.real ** 2) if np.iscomplexobj(v) else 0.0)
+        x, z = v[0], v[2]
+        az = np.arctan2(x.real, z.real) + (1j * (z.real * x.imag - x.real * z.imag) / (x.real ** 2 + z.real ** 2) if np.iscomplexobj(v) else 0.0)
+        return az, zen
+    eaz, ezen = azzen(sc)
+    oaz, ozen = azzen(oc)
+    raz, rzen = eaz - oaz, ezen - ozen
+    if raz.real > np.pi:
+        raz -= 2 * np.pi
+    elif raz.real < -np.pi:
+        raz += 2 * np.pi
+    if abs(raz.real) > taz:
+        raz = 0.0
+    if abs(rzen.real) > tzen:
+        rzen = 0.0
+    return S @ np.array([raz, rzen])
+
+
+def se3_complex_step_jacobian(fun, T, h=1e-30):
+    """d fun(Plus(T, eps)) / d eps at eps = 0 by complex step (rows x 6)."""
+    J = []
+    for c in range(6):
+        e = np.zeros(6, dtype=complex)
+        e[c] = 1j * h
+        J.append(fun(se3_plus(T.astype(complex), e)).imag / h)
+    return np.array(J).T
+
+
 # ---- Phong lighting rows: forward formulas only (complex-step differentiable) ----------------
 def _fmax0(col):      # utils/utils.hpp:16-19 with a = 0
     return 0.0 * col if 0.0 >= col.real else col

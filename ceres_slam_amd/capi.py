@@ -36,7 +36,7 @@ SYMBOLS = [
     "ssba_add_lighting_observations", "ssba_border_system", "ssba_set_shared_block_bounds", "ssba_set_point_blocks_constant", "ssba_release_cached_memory",
     "ssba_set_partition", "ssba_ransac_samples", "ssba_frontend_ransac", "ssba_add_pose_prior", "ssba_add_sun_observation", "ssba_add_relative_pose",
     "ssba_pose_covariance", "ssba_rccl_unique_id", "ssba_set_rccl", "ssba_frontend_vo",
-    "ssba_rccl_describe", "ssba_rccl_ranks", "ssba_armijo_trace", "ssba_debug_stamps",
+    "ssba_rccl_describe", "ssba_rccl_ranks", "ssba_armijo_trace", "ssba_debug_stamps", "ssba_covariance_blocks",
 ]
 
 
@@ -55,6 +55,13 @@ class Options(C.Structure):
                 ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
                 ("parameter_tolerance", C.c_double), ("trust_region_strategy_type", C.c_int32),
                 ("dogleg_type", C.c_int32)]
+
+
+COV_POSE, COV_POINT = 0, 1      # ssba_cov_block kinds (SSBA_COV_POSE / SSBA_COV_POINT)
+
+
+class CovBlock(C.Structure):
+    _fields_ = [("kind_a", C.c_uint32), ("index_a", C.c_uint32), ("kind_b", C.c_uint32), ("index_b", C.c_uint32)]
 
 
 LEVENBERG_MARQUARDT, DOGLEG = 0, 1
@@ -153,6 +160,7 @@ def load():
     L.ssba_add_sun_observation.argtypes = [H, C.c_uint32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double]
     L.ssba_add_relative_pose.argtypes = [H, C.c_uint32, C.c_uint32, _dp, _dp, C.c_double]
     L.ssba_pose_covariance.argtypes = [H, C.c_uint32, _dp]
+    L.ssba_covariance_blocks.argtypes = [H, C.POINTER(CovBlock), C.c_uint64, _dp]
     L.ssba_ransac_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_int, _u32p]
     L.ssba_frontend_ransac.argtypes = [C.POINTER(Camera), C.c_int, C.c_uint32, _u32p, _dp, _dp, _u32p, C.c_uint32, C.c_double, _dp,
                                        C.POINTER(C.c_uint8), _u32p, _dp]

@@ -327,8 +327,10 @@ def Solve(options: SolverOptions, problem: Problem, summary: SolverSummary, devi
 
 
 class Covariance:
-    """ceres::Covariance for diagonal pose blocks (tests/dataset_vo_sun.cpp:159-183): Compute evaluates the requested
-    blocks of (J^T J)^-1 in the tangent space at the problem's current values; False on a rank-deficient system."""
+    """ceres::Covariance (tests/dataset_vo_sun.cpp:159-183): Compute evaluates the requested blocks of (J^T J)^-1 in the
+    tangent space at the problem's current values; False on a rank-deficient system.  Pairs may be (pose | point,
+    pose | point).  A request made only of diagonal pose blocks runs ssba_pose_covariance per pose, as it always has;
+    any other request is one ssba_covariance_blocks call."""
 
     class Options:
         num_threads = 1
@@ -339,13 +341,24 @@ class Covariance:
 
     def Compute(self, covariance_blocks, problem: Problem, device: int = -1) -> bool:
         self._blocks = {}
+        pairs = [(_addr(a), _addr(b)) for a, b in covariance_blocks]
+        known = lambda x: x in problem._pose_blocks or x in problem._point_blocks
+        for a, b in pairs:
+            if not (known(a) and known(b)):
+                self.message = "a requested parameter block is not in the problem"
+                return False
+        diagonal_poses = all(a == b and a in problem._pose_blocks for a, b in pairs)
         ba = _lower(problem, device)
         try:
-            for a, b in covariance_blocks:
-                if _addr(a) != _addr(b) or _addr(a) not in problem._pose_blocks:
-                    self.message = "only diagonal pose blocks are supported"
-                    return False
-                self._blocks[_addr(a)] = ba.pose_covariance(problem._pose_blocks[_addr(a)][0])
+            if diagonal_poses:
+                for a, _ in pairs:
+                    self._blocks[(a, a)] = ba.pose_covariance(problem._pose_blocks[a][0])
+            else:
+                def ref(x):
+                    return ("pose", problem._pose_blocks[x][0]) if x in problem._pose_blocks else ("point", problem._point_blocks[x][0])
+                out = ba.covariance_blocks([(ref(a), ref(b)) for a, b in pairs])
+                for (a, b), blk in zip(pairs, out):
+                    self._blocks[(a, b)] = blk
         except capi.SsbaError as e:
             self.message = str(e)
             self._blocks = {}
@@ -354,8 +367,28 @@ class Covariance:
             ba.close()
         return True
 
+    def _get(self, a, b):
+        a, b = _addr(a), _addr(b)
+        if (a, b) in self._blocks:
+            return self._blocks[(a, b)]
+        if (b, a) in self._blocks:
+            return self._blocks[(b, a)].T
+        return None
+
     def GetCovarianceBlockInTangentSpace(self, a, b, out) -> bool:
-        if _addr(a) != _addr(b) or _addr(a) not in self._blocks:
+        """Any computed pair, in either order: 6 x 6, 6 x 3, 3 x 6 or 3 x 3."""
+        blk = self._get(a, b)
+        if blk is None:
             return False
-        np.asarray(out).reshape(6, 6)[:] = self._blocks[_addr(a)]
+        np.asarray(out).reshape(blk.shape)[:] = blk
+        return True
+
+    def GetCovarianceBlock(self, a, b, out) -> bool:
+        """The same in the blocks' ambient coordinates: points only (a pose's ambient block is 12 x 12 and is refused)."""
+        blk = self._get(a, b)
+        if blk is None or blk.shape != (3, 3):
+            self.message = ("GetCovarianceBlock: a pose's ambient covariance (12 x 12) is not available; use "
+                            "GetCovarianceBlockInTangentSpace") if blk is not None else "block not computed"
+            return False
+        np.asarray(out).reshape(3, 3)[:] = blk
         return True

@@ -2354,6 +2354,243 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     return SSBA_OK;
 }
 
+// device buffers of one ssba_covariance_blocks call, released on every return
+namespace {
+struct CallBuffers {
+    std::vector<void *> v;
+    ~CallBuffers() { for (void *q : v) (void)hipFree(q); }
+    hipError_t get(void **out, size_t bytes) {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) { v.push_back(q); *out = q; }
+        return e;
+    }
+};
+}  // namespace
+
+// ceres::Covariance for any (pose | point, pose | point) pairs (include/ssba.h).  Windowed layout: the band of Sigma from one
+// selected inversion of the kept factors (ssba_covariance.hip), columns of Sigma from multi-right-hand-side sweeps for the
+// poses whose blocks lie outside it; general layout: columns of Sigma for every pose the request touches, DN_BS / 6 poses
+// per blocked Cholesky solve.  The landmark blocks follow from those in one launch.
+int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
+    ApiTimer api_timer("ssba_covariance_blocks");
+    if (!p || (num && (!blocks || !out))) return SSBA_ERR_INVALID_ARGUMENT;
+    if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    bool any_point = false;
+    for (uint64_t q = 0; q < num; ++q) {
+        const ssba_cov_block &b = blocks[q];
+        if (b.kind_a > SSBA_COV_POINT || b.kind_b > SSBA_COV_POINT) { set_error("covariance: unknown block kind"); return SSBA_ERR_INVALID_ARGUMENT; }
+        if (b.index_a >= (b.kind_a == SSBA_COV_POINT ? p->L : p->P) || b.index_b >= (b.kind_b == SSBA_COV_POINT ? p->L : p->P)) {
+            set_error("covariance: block index out of range");
+            return SSBA_ERR_INVALID_ARGUMENT;
+        }
+        any_point |= b.kind_a == SSBA_COV_POINT || b.kind_b == SSBA_COV_POINT;
+    }
+    // residual blocks per point (and, below, the observing poses of the requested ones)
+    std::vector<uint32_t> nobs;
+    if (any_point) {
+        nobs.assign(p->L, 0);
+        for (uint32_t j : p->obs_point) ++nobs[j];
+    }
+    for (uint64_t q = 0; q < num; ++q) {
+        const ssba_cov_block &b = blocks[q];
+        if ((b.kind_a == SSBA_COV_POINT && !nobs[b.index_a]) || (b.kind_b == SSBA_COV_POINT && !nobs[b.index_b])) {
+            set_error("covariance: a point without residual blocks");
+            return SSBA_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (uint64_t q = 0; q < num; ++q)
+        if (blocks[q].kind_a == SSBA_COV_POINT && blocks[q].kind_b == SSBA_COV_POINT && blocks[q].index_a != blocks[q].index_b) {
+            set_error("covariance: (point, point) blocks of two different points are not available");
+            return SSBA_ERR_UNSUPPORTED;
+        }
+    if (p->lighting() || p->d.phong || p->xfn || p->world_size > 1 || p->d.part) {
+        set_error("covariance: not available on partitioned or landmark-sharded problems or with lighting terms");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    int rc;
+    if (p->d.cb && (rc = refinalize_without_closure_border(p, "covariance"))) return rc;
+    if (p->d.wide && (rc = refinalize_without_wide(p, "covariance"))) return rc;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    const bool dense = d.dense;
+    const int nf = d.nfree;
+
+    // the requested blocks as jobs of k_cov_jobs, and the poses whose columns of Sigma are needed
+    std::vector<uint64_t> off(num + 1, 0);
+    for (uint64_t q = 0; q < num; ++q)
+        off[q + 1] = off[q] + (blocks[q].kind_a == SSBA_COV_POINT ? 3 : 6) * (blocks[q].kind_b == SSBA_COV_POINT ? 3 : 6);
+    const uint64_t total = off[num];
+    std::vector<uint32_t> dev_of;
+    if (any_point) {
+        dev_of.assign(p->L, 0xFFFFFFFFu);
+        for (size_t l = 0; l < p->user_of_dev.size(); ++l)
+            if (p->user_of_dev[l] != 0xFFFFFFFFu) dev_of[p->user_of_dev[l]] = (uint32_t)l;
+    }
+    std::vector<uint8_t> want((size_t)nf, 0);
+    std::vector<uint8_t> track_want;             // points whose observing free poses all need columns (general layout)
+    std::vector<int> pp_pose;                    // windowed: point -> index into pp_lo / pp_hi (pose-point requests)
+    std::vector<int> pp_lo, pp_hi;               // super-block range of the point's observing free poses
+    std::vector<CovJob> jobs;
+    std::vector<std::pair<int, uint32_t>> pp_check;     // windowed: (free pose, point) to test against the band
+    for (uint64_t q = 0; q < num; ++q) {
+        const ssba_cov_block &b = blocks[q];
+        const bool pa = b.kind_a == SSBA_COV_POINT, pb = b.kind_b == SSBA_COV_POINT;
+        const int fa = pa ? 0 : p->pose_free[b.index_a], fb = pb ? 0 : p->pose_free[b.index_b];
+        if (fa < 0 || fb < 0 || ((pa || pb) && p->points_const)) continue;      // constant block: zeros
+        CovJob J{};
+        J.off = (long long)off[q];
+        if (!pa && !pb) {
+            J.kind = COV_JOB_POSE_POSE;
+            J.a = std::min(fa, fb); J.b = std::max(fa, fb); J.tr = fa > fb;
+            if (dense || J.b / SBP - J.a / SBP > 1) want[J.b] = 1;
+        } else if (pa && pb) {
+            J.kind = COV_JOB_POINT;
+            J.a = 0; J.b = (int)dev_of[b.index_a];
+            if (dense) { if (track_want.empty()) track_want.assign(p->L, 0); track_want[b.index_a] = 1; }
+        } else {
+            const int f = pa ? fb : fa;
+            const uint32_t j = pa ? b.index_a : b.index_b;
+            J.kind = COV_JOB_POSE_POINT;
+            J.a = f; J.b = (int)dev_of[j]; J.tr = pa;
+            if (dense) want[f] = 1;
+            else pp_check.emplace_back(f, j);
+        }
+        jobs.push_back(J);
+    }
+    if (!pp_check.empty() || !track_want.empty()) {
+        if (!pp_check.empty()) {
+            pp_pose.assign(p->L, -1);
+            for (auto &c : pp_check)
+                if (pp_pose[c.second] < 0) { pp_pose[c.second] = (int)pp_lo.size(); pp_lo.push_back(INT32_MAX); pp_hi.push_back(-1); }
+        }
+        for (size_t n = 0; n < p->obs_point.size(); ++n) {
+            const uint32_t j = p->obs_point[n];
+            const int f = p->pose_free[p->obs_pose[n]];
+            if (f < 0) continue;
+            if (!track_want.empty() && track_want[j]) want[f] = 1;
+            if (!pp_pose.empty() && pp_pose[j] >= 0) {
+                const int k = pp_pose[j];
+                pp_lo[k] = std::min(pp_lo[k], f / SBP);
+                pp_hi[k] = std::max(pp_hi[k], f / SBP);
+            }
+        }
+        for (auto &c : pp_check) {       // the pose's blocks with the point's observing poses lie outside the band
+            const int k = pp_pose[c.second], I = c.first / SBP;
+            if (pp_hi[k] >= 0 && (pp_hi[k] - I > 1 || I - pp_lo[k] > 1)) want[c.first] = 1;
+        }
+    }
+    std::vector<int> slot((size_t)std::max(nf, 1), -1), slot_pose;
+    for (int f = 0; f < nf; ++f)
+        if (want[f]) { slot[f] = (int)slot_pose.size(); slot_pose.push_back(f); }
+    const int nslots = (int)slot_pose.size();
+
+    CallBuffers B;
+    double *d_out = nullptr, *cols = nullptr;
+    int *d_fail = nullptr, *d_slot = nullptr;
+    CovJob *d_jobs = nullptr;
+    CovSrc src{};
+    ssba_options o;
+    ssba_default_options(&o);
+    if (!dense) {
+        if (nslots && !d.Spb) {      // multi-right-hand-side buffers are only allocated with a border: add them now
+            drop_graph(p);
+            if ((rc = dzero(p, &d.Spb, (size_t)d.nf_pad * 6 * NBP))) return rc;
+            if ((rc = dzero(p, &d.Zb, (size_t)d.nf_pad * 6 * NBP))) return rc;
+            for (int l = 0; l < d.n_levels; ++l)
+                if ((rc = dzero(p, &d.lev[l].B, (size_t)d.lev[l].n * BD * NBP))) return rc;
+            if (configure_border()) { set_error("hipFuncSetAttribute(border kernels) failed"); return SSBA_ERR_HIP; }
+        }
+        SelInv si{};
+        size_t nsc = 0;
+        for (int l = 0; l < d.n_levels; ++l) { si.sc_off[l] = (int)nsc; nsc += (size_t)d.lev[l].n; }
+        const size_t bb = (size_t)BD * BD;
+        HIPCHECK(B.get((void **)&si.sd, ((size_t)d.Nsb * bb) * sizeof(double)));
+        HIPCHECK(B.get((void **)&si.sc, (nsc * bb) * sizeof(double)));
+        HIPCHECK(B.get((void **)&si.ws, ((size_t)std::max(1, d.lev[0].n / 2) * 5 * bb) * sizeof(double)));
+        if ((rc = begin_hook(p, &o, 1e300))) return rc;        // radius -> infinity: no Levenberg-Marquardt damping in S
+        launch_linearize(L, d);
+        launch_schur(L, d);
+        launch_finish_check(L, d);
+        launch_bcr(L, d, false);       // the selected inversion and the sweeps need the factors of every level
+        launch_selinv(L, d, si);
+        const long nrow = (long)d.nf_pad * 6;
+        if (nslots) {
+            HIPCHECK(B.get((void **)&cols, ((size_t)nslots * 6 * nrow) * sizeof(double)));
+            constexpr int PER = NBP / 6;       // 5 poses per sweep
+            std::vector<double> unit((size_t)PER * 6 * NBP, 0.0);
+            for (int s0 = 0; s0 < nslots; s0 += PER) {
+                const int nq = std::min(PER, nslots - s0);
+                HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
+                std::fill(unit.begin(), unit.end(), 0.0);
+                for (int q = 0; q < nq; ++q) {
+                    for (int c = 0; c < 6; ++c) unit[(size_t)q * 6 * NBP + (size_t)c * NBP + 6 * q + c] = 1.0;
+                    HIPCHECK(hipMemcpyAsync(d.Spb + (size_t)slot_pose[s0 + q] * 6 * NBP, unit.data() + (size_t)q * 6 * NBP,
+                                            (size_t)6 * NBP * sizeof(double), hipMemcpyHostToDevice, L.stream));
+                }
+                HIPCHECK(hipStreamSynchronize(L.stream));
+                launch_bcr_multi_rhs(L, d);
+                launch_cov_gather(L, d.Zb, cols, s0, nq, nrow);
+            }
+            HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
+        }
+        src.sd = si.sd;
+        src.sc0 = si.sc;
+        src.nrow = nrow;
+        // the factors and the band must be complete before the buffers they came from are released (hipFree synchronises)
+    } else {
+        const size_t lda = (size_t)d.dn_pad;
+        HIPCHECK(B.get((void **)&cols, ((size_t)std::max(nslots, 1) * 6 * lda) * sizeof(double)));
+        constexpr int PER = DN_BS / 6;       // 10 poses per blocked Cholesky solve
+        const double one = 1.0;
+        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {     // (no column needed: one solve still checks the system)
+            const int nq = std::min(PER, nslots - s0);
+            if ((rc = begin_hook(p, &o, 1e300))) return rc;
+            launch_linearize(L, d);
+            launch_dense_schur(L, d);
+            HIPCHECK(hipMemsetAsync(d.dn_S + lda * lda, 0, (size_t)DN_BS * lda * sizeof(double), L.stream));
+            for (int q = 0; q < nq; ++q)
+                for (int c = 0; c < 6; ++c)
+                    HIPCHECK(hipMemcpyAsync(d.dn_S + (lda + 6 * q + c) * lda + (size_t)slot_pose[s0 + q] * 6 + c, &one, sizeof one,
+                                            hipMemcpyHostToDevice, L.stream));
+            launch_finish_check(L, d);
+            launch_dense_solve(L, d, std::max(1, 6 * nq));
+            if (nq > 0)
+                HIPCHECK(hipMemcpyAsync(cols + (size_t)s0 * 6 * lda, d.dn_S + lda * lda, (size_t)nq * 6 * lda * sizeof(double),
+                                        hipMemcpyDeviceToDevice, L.stream));
+            HIPCHECK(hipStreamSynchronize(L.stream));
+            HIPCHECK(hipGetLastError());
+            if ((rc = fetch_state(p))) return rc;
+            if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+        }
+        src.nrow = (long)lda;
+    }
+    src.cols = cols;
+    if (nslots) {
+        HIPCHECK(B.get((void **)&d_slot, (slot.size()) * sizeof(int)));
+        HIPCHECK(hipMemcpyAsync(d_slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, L.stream));
+        src.slot = d_slot;
+    }
+    HIPCHECK(B.get((void **)&d_out, ((size_t)total) * sizeof(double)));
+    HIPCHECK(B.get((void **)&d_fail, (1) * sizeof(int)));
+    HIPCHECK(hipMemsetAsync(d_out, 0, (size_t)total * sizeof(double), L.stream));
+    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), L.stream));
+    if (!jobs.empty()) {
+        HIPCHECK(B.get((void **)&d_jobs, (jobs.size()) * sizeof(CovJob)));
+        HIPCHECK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(CovJob), hipMemcpyHostToDevice, L.stream));
+        launch_cov_jobs(L, d, src, d_jobs, (int)jobs.size(), d_out, d_fail);
+    }
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    if ((rc = fetch_state(p))) return rc;
+    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    int fail = 0;
+    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
+    if (fail) { set_error("covariance: the block of a requested point is not positive definite"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    if (total) HIPCHECK(hipMemcpy(out, d_out, (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    return SSBA_OK;
+}
+
 int ssba_border_system(ssba_problem *p, uint32_t *nb_out, double *S_pb, double *S_bb, double *rhs_b, double *delta_b) {
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;

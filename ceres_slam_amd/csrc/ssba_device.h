@@ -1,4 +1,4 @@
-// Device functions shared by the solver kernels (ssba_kernels.hip, ssba_phong_solver.hip).
+// Device functions shared by the solver kernels (ssba_kernels.hip, ssba_phong_solver.hip, ssba_covariance.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -609,5 +609,40 @@ static __device__ __forceinline__ void ph_dogleg_border_lane(const Dev &d) {
     o[0] = gsq; o[1] = nsq; o[2] = dot; o[3] = 0.0; o[4] = 0.0; o[5] = 0.0;
 }
 
+
+// Observations of one landmark.  Windowed layout (DN = false): TW slots of the landmark's window in the
+// transposed ELL arrays, present where the mask bit is set.  General layout (DN = true, ssba_dense.hip):
+// the landmark's contiguous range of the landmark-major observation arrays.
+template <bool DN> struct LmObs;
+template <> struct LmObs<false> {
+    uint32_t mask, win;
+    size_t obase;
+    __device__ __forceinline__ LmObs(const Dev &d, int l, uint32_t m)
+        : mask(m), win(d.lm_win[l]), obase((size_t)(l >> 6) * (TW * LMG) + (l & 63)) {}
+    __device__ __forceinline__ int count() const { return TW; }
+    __device__ __forceinline__ bool has(int s) const { return (mask >> s) & 1u; }
+    __device__ __forceinline__ uint32_t pose(const Dev &d, int s) const { return d.win_pose[win * TW + s]; }
+    __device__ __forceinline__ double u(const Dev &d, int s) const { return d.ou[obase + s * LMG]; }
+    __device__ __forceinline__ double v(const Dev &d, int s) const { return d.ov[obase + s * LMG]; }
+    __device__ __forceinline__ double dd(const Dev &d, int s) const { return d.od[obase + s * LMG]; }
+    __device__ __forceinline__ void stiffness(const Dev &d, int, double S[9]) const {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) S[c] = d.S[c];
+    }
+};
+template <> struct LmObs<true> {
+    uint32_t b, n;
+    __device__ __forceinline__ LmObs(const Dev &d, int l, uint32_t) : b(d.dn_lm_start[l]), n(d.dn_lm_start[l + 1] - d.dn_lm_start[l]) {}
+    __device__ __forceinline__ int count() const { return (int)n; }
+    __device__ __forceinline__ bool has(int) const { return true; }
+    __device__ __forceinline__ uint32_t pose(const Dev &d, int s) const { return d.dn_obs_pose[b + s]; }
+    __device__ __forceinline__ double u(const Dev &d, int s) const { return d.dn_u[b + s]; }
+    __device__ __forceinline__ double v(const Dev &d, int s) const { return d.dn_v[b + s]; }
+    __device__ __forceinline__ double dd(const Dev &d, int s) const { return d.dn_d[b + s]; }
+    __device__ __forceinline__ void stiffness(const Dev &d, int s, double S[9]) const {     // per residual block when given
+#pragma unroll
+        for (int c = 0; c < 9; ++c) S[c] = d.dn_Sobs ? d.dn_Sobs[(size_t)(b + s) * 9 + c] : d.S[c];
+    }
+};
 
 }  // namespace ssba

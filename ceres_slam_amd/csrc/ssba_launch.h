@@ -163,4 +163,26 @@ void launch_wide_finish(Launcher &L, const Dev &d, bool fused);
 bool launch_ctrl_fusable(const Dev &d);       // ssba_kernels.hip: k_check forms the linearisation sums itself on this layout
 void launch_wide_solve(Launcher &L, const Dev &d);
 
+// covariance blocks (ssba_covariance.hip, ssba_covariance_blocks)
+struct SelInv {                  // selected inversion of the block-tridiagonal S on its pattern
+    double *sd;                  // Nsb blocks: Sigma_II at level-0 block positions
+    double *sc;                  // sum of the levels' n blocks: level l's Sigma_{k,k-1} at sc + sc_off[l] blocks (level 0 first)
+    double *ws;                  // 5 blocks of workspace per odd block of level 0
+    int sc_off[MAX_LEVELS];
+};
+struct CovSrc {                  // where k_cov_jobs reads blocks of Sigma from
+    const double *sd, *sc0;      // band of the windowed layout (SelInv::sd, level 0 of SelInv::sc), or null
+    const double *cols;          // solved columns: slot q, column c at cols + (6 q + c) nrow
+    const int *slot;             // free pose -> column slot or -1 (null: none)
+    long nrow;
+};
+enum { COV_JOB_POSE_POSE = 0, COV_JOB_POINT = 1, COV_JOB_POSE_POINT = 2 };
+struct CovJob {
+    int kind, a, b, tr;          // a: free pose, b: free pose (pose-pose) or device landmark; tr: store the transpose
+    long long off;               // first double of the block in the packed output
+};
+void launch_selinv(Launcher &L, const Dev &d, const SelInv &si);
+void launch_cov_jobs(Launcher &L, const Dev &d, const CovSrc &src, const CovJob *jobs, int n, double *out, int *fail);
+void launch_cov_gather(Launcher &L, const double *Zb, double *cols, int slot0, int nq, long nrow);
+
 }  // namespace ssba

@@ -261,6 +261,32 @@ class StereoBA:
         capi.check(self.lib.ssba_pose_covariance(self.h, int(pose), capi.dptr(cov)), "ssba_pose_covariance")
         return cov
 
+    def covariance_blocks(self, pairs) -> list:
+        """Blocks of (J^T J)^-1 for (("pose" | "point", index), ("pose" | "point", index)) pairs in one call
+        (ssba_covariance_blocks): 6 x 6 / 6 x 3 / 3 x 6 / 3 x 3 arrays in request order."""
+        kinds = {"pose": capi.COV_POSE, "point": capi.COV_POINT, capi.COV_POSE: capi.COV_POSE, capi.COV_POINT: capi.COV_POINT}
+        req = np.zeros((max(len(pairs), 1), 4), dtype=np.uint32)      # ssba_cov_block rows: kind_a, index_a, kind_b, index_b
+        for i, ((ka, ia), (kb, ib)) in enumerate(pairs):
+            req[i] = (kinds[ka], ia, kinds[kb], ib)
+        req = req[:len(pairs)]
+        dims = np.where(req[:, [0, 2]] == capi.COV_POINT, 3, 6)
+        size = dims[:, 0] * dims[:, 1]
+        off = np.concatenate([[0], np.cumsum(size)])
+        out = np.zeros(max(int(off[-1]), 1))
+        capi.check(self.lib.ssba_covariance_blocks(self.h, np.ascontiguousarray(req).ctypes.data_as(C.POINTER(capi.CovBlock)), len(pairs),
+                                                   capi.dptr(out)), "ssba_covariance_blocks")
+        return [out[off[i]:off[i + 1]].reshape(dims[i, 0], dims[i, 1]).copy() for i in range(len(pairs))]
+
+    def pose_marginals(self) -> np.ndarray:
+        """(P, 6, 6): every pose's marginal covariance in one call (zeros for constant poses)."""
+        P = self.poses.shape[0]
+        return np.array(self.covariance_blocks([(("pose", k), ("pose", k)) for k in range(P)])).reshape(P, 6, 6)
+
+    def point_marginals(self) -> np.ndarray:
+        """(L, 3, 3): every point's marginal covariance in one call."""
+        L = self.points.shape[0]
+        return np.array(self.covariance_blocks([(("point", j), ("point", j)) for j in range(L)])).reshape(L, 3, 3)
+
     def border_system(self):
         """Border blocks of the last lm_step (free shared blocks): S_pb, S_bb (damped), rhs_b, delta_b."""
         nb = C.c_uint32()

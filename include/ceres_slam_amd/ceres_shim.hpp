@@ -29,7 +29,7 @@
 //     problem.AddResidualBlock(PoseErrorAutomatic::Create(T_ref, stiffness6x6), NULL, pose_k1);
 //     ceres::Covariance covariance(covariance_options);
 //     covariance.Compute(covar_blocks, &problem);
-//     covariance.GetCovarianceBlockInTangentSpace(pose, pose, out36);
+//     covariance.GetCovarianceBlockInTangentSpace(pose, pose, out36);     // (pose | point, pose | point) pairs
 //
 // The shim recognises the typed cost functions of this path and lowers them to observation
 // tables; it does NOT run arbitrary user functors on the GPU -- any other CostFunction is
@@ -39,6 +39,7 @@
 #ifndef CERES_SLAM_AMD_CERES_SHIM_HPP_
 #define CERES_SLAM_AMD_CERES_SHIM_HPP_
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -636,9 +637,12 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
     }
 }
 
-// ceres::Covariance for pose blocks (tests/dataset_vo_sun.cpp:159-183): Compute evaluates the requested diagonal pose
-// blocks of (J^T J)^-1 in the tangent space at the problem's current parameter values (loss-corrected Jacobian, as
-// Ceres' default apply_loss_function = true); GetCovarianceBlockInTangentSpace copies one out (6x6 row-major).
+// ceres::Covariance (tests/dataset_vo_sun.cpp:159-183): Compute evaluates the requested blocks of (J^T J)^-1 in the
+// tangent space at the problem's current parameter values (loss-corrected Jacobian, as Ceres' default
+// apply_loss_function = true).  Pairs may be (pose | point, pose | point).  A request made only of diagonal pose blocks runs
+// ssba_pose_covariance per pose (as it always has); any other request is one ssba_covariance_blocks call.
+// GetCovarianceBlockInTangentSpace copies a computed pair out in either order (row-major, 6 x 6 / 6 x 3 / 3 x 6 / 3 x 3);
+// GetCovarianceBlock does the same in ambient coordinates, which exist for points only (a pose's would be 12 x 12).
 class Covariance {
  public:
     struct Options {
@@ -657,33 +661,81 @@ class Covariance {
         if (P.pose_blocks_.empty()) { message_ = "no pose blocks"; return false; }
         int rc = 0;
         const char *where = shim_prepare(P, &rc);      // the handle of the preceding Solve when nothing changed since
+        bool diagonal_poses = true;
+        std::vector<ssba_cov_block> req;
         for (size_t i = 0; !where && i < blocks.size(); ++i) {
-            double *a = const_cast<double *>(blocks[i].first);
-            if (blocks[i].first != blocks[i].second || !P.pose_index_.count(a)) {
-                message_ = "only diagonal pose blocks are supported";
-                rc = SSBA_ERR_UNSUPPORTED;
+            double *a = const_cast<double *>(blocks[i].first), *b = const_cast<double *>(blocks[i].second);
+            ssba_cov_block r;
+            if (!kind_index(P, a, &r.kind_a, &r.index_a) || !kind_index(P, b, &r.kind_b, &r.index_b)) {
+                message_ = "a requested parameter block is not in the problem";
+                rc = SSBA_ERR_INVALID_ARGUMENT;
                 where = "Covariance::Compute";
                 break;
             }
-            Block b;
-            b.ptr = blocks[i].first;
-            if ((rc = ssba_pose_covariance(P.h_, P.pose_index_[a], b.cov))) where = "ssba_pose_covariance";
-            else blocks_.push_back(b);
+            diagonal_poses = diagonal_poses && a == b && r.kind_a == SSBA_COV_POSE;
+            req.push_back(r);
+        }
+        if (!where && diagonal_poses) {
+            for (size_t i = 0; !where && i < blocks.size(); ++i) {
+                Block b(blocks[i].first, blocks[i].second, 6, 6);
+                if ((rc = ssba_pose_covariance(P.h_, req[i].index_a, b.cov.data()))) where = "ssba_pose_covariance";
+                else blocks_.push_back(b);
+            }
+        } else if (!where) {
+            size_t total = 0;
+            for (size_t i = 0; i < req.size(); ++i) total += dim(req[i].kind_a) * dim(req[i].kind_b);
+            std::vector<double> out(total > 0 ? total : 1);
+            if ((rc = ssba_covariance_blocks(P.h_, req.data(), req.size(), out.data()))) where = "ssba_covariance_blocks";
+            for (size_t i = 0, o = 0; !where && i < req.size(); ++i) {
+                Block b(blocks[i].first, blocks[i].second, dim(req[i].kind_a), dim(req[i].kind_b));
+                std::copy(out.begin() + o, out.begin() + o + b.cov.size(), b.cov.begin());
+                o += b.cov.size();
+                blocks_.push_back(b);
+            }
         }
         if (where && message_.empty()) message_ = std::string(where) + ": " + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
         if (where) blocks_.clear();
         return where == nullptr;     // like Ceres: false on a rank-deficient Jacobian (no gauge constraint)
     }
     bool GetCovarianceBlockInTangentSpace(const double *a, const double *b, double *out) const {
-        if (a != b) return false;
+        for (const Block &blk : blocks_) {
+            if (blk.a == a && blk.b == b) { std::memcpy(out, blk.cov.data(), blk.cov.size() * sizeof(double)); return true; }
+            if (blk.a == b && blk.b == a) {      // the transpose of a computed pair
+                for (int r = 0; r < blk.rows; ++r)
+                    for (int c = 0; c < blk.cols; ++c) out[(size_t)c * blk.rows + r] = blk.cov[(size_t)r * blk.cols + c];
+                return true;
+            }
+        }
+        return false;
+    }
+    // ambient coordinates: a point's are its tangent space; a pose's (12 x 12 over the stored 3x4 matrix) are refused
+    bool GetCovarianceBlock(const double *a, const double *b, double *out) {
         for (const Block &blk : blocks_)
-            if (blk.ptr == a) { std::memcpy(out, blk.cov, sizeof blk.cov); return true; }
+            if ((blk.a == a && blk.b == b) || (blk.a == b && blk.b == a)) {
+                if (blk.rows != 3 || blk.cols != 3) {
+                    message_ = "GetCovarianceBlock: the ambient covariance of a pose block (12 x 12) is not available; use "
+                               "GetCovarianceBlockInTangentSpace";
+                    return false;
+                }
+                return GetCovarianceBlockInTangentSpace(a, b, out);
+            }
         return false;
     }
     const std::string &message() const { return message_; }
 
  private:
-    struct Block { const double *ptr; double cov[36]; };
+    struct Block {
+        Block(const double *a_, const double *b_, int r, int c) : a(a_), b(b_), rows(r), cols(c), cov((size_t)r * c) {}
+        const double *a, *b;
+        int rows, cols;
+        std::vector<double> cov;
+    };
+    static int dim(uint32_t kind) { return kind == SSBA_COV_POINT ? 3 : 6; }
+    static bool kind_index(Problem &P, double *x, uint32_t *kind, uint32_t *index) {
+        if (P.pose_index_.count(x)) { *kind = SSBA_COV_POSE; *index = P.pose_index_[x]; return true; }
+        if (P.point_index_.count(x)) { *kind = SSBA_COV_POINT; *index = P.point_index_[x]; return true; }
+        return false;
+    }
     Options options_;
     std::vector<Block> blocks_;
     std::string message_;

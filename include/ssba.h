@@ -399,6 +399,28 @@ SSBA_API int ssba_add_sun_observation(ssba_problem *p, uint32_t pose, const doub
  * SSBA_ERR_NUMERICAL_FAILURE when the system is rank deficient (Ceres: "Covariance computation failed"). */
 SSBA_API int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]);
 
+/* ssba_covariance_blocks replaces ceres::Covariance::Compute + GetCovarianceBlock(InTangentSpace) for any list of
+ * (pose | point, pose | point) pairs, computed in one call.  out receives the blocks one after another in request order,
+ * each row-major and dim(a) x dim(b) with dim(pose) = 6 (tangent space) and dim(point) = 3: the block of (J^T J)^-1 at the
+ * caller's current parameters (undamped, Huber-corrected, the system ssba_pose_covariance inverts).
+ *   (pose i, pose j): Sigma_ij; (j, i) is its transpose.  (point l, point l): Sigma_ll = V^-1 + V^-1 W^T Sigma_TT W V^-1.
+ *   (pose i, point l) / (point l, pose i): -Sigma_iT W V^-1 / its transpose (T: the free poses that observe l).
+ *   Blocks touching a constant pose, or a point while points are held constant: zeros (as Ceres).
+ *   (point l, point m), l != m: SSBA_ERR_UNSUPPORTED.  Index out of range, unknown kind, a point without residual blocks:
+ *   SSBA_ERR_INVALID_ARGUMENT.  Reduced system or a needed landmark block not positive definite: SSBA_ERR_NUMERICAL_FAILURE.
+ *   Lighting terms, landmark-sharded or partitioned handles: SSBA_ERR_UNSUPPORTED.
+ * Windowed layout: one selected inversion of the block-tridiagonal reduced system (its diagonal and sub-diagonal super-blocks)
+ * plus one multi-right-hand-side sweep per 5 poses whose blocks lie outside that band.  General layout: one blocked
+ * Cholesky solve per 10 poses the request touches (requested poses and the observing poses of requested points).
+ * State rules, closure border and long tracks as ssba_pose_covariance: a closure-border or a wide (13..24 observation) handle
+ * is finalized again onto the general layout the first time, which is only possible before its first solve begins
+ * (afterwards SSBA_ERR_STATE; ask before solving, or set SSBA_NO_CLOSURE_BORDER=1 / SSBA_NO_WIDE=1).  A later ssba_solve
+ * runs exactly as if the call had not been made. */
+#define SSBA_COV_POSE 0
+#define SSBA_COV_POINT 1
+typedef struct { uint32_t kind_a, index_a, kind_b, index_b; } ssba_cov_block;
+SSBA_API int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out);
+
 /* ---- front end: the VO initial guess --------------------------------- */
 /* ssba_frontend_ransac replaces, for `num_pairs` pairs of consecutive states at once,
  *   PointCloudAligner::compute_transformation_and_inliers (src/ceres_slam/point_cloud_aligner.cpp:64-136)

@@ -1233,7 +1233,6 @@ int ssba_finalize(ssba_problem *p) {
         int &flags = done[p->device];
         if (!(flags & 1)) {
             if (upload_pair_table(p->launcher.stream)) { set_error("pair table upload failed"); return SSBA_ERR_HIP; }
-            if (upload_bcr_tables(p->launcher.stream)) { set_error("BCR tile table upload failed"); return SSBA_ERR_HIP; }
             if (configure_schur()) { set_error("hipFuncSetAttribute(k_schur_windows) failed"); return SSBA_ERR_HIP; }
             if (configure_kernels()) { set_error("hipFuncSetAttribute failed"); return SSBA_ERR_HIP; }
             if (configure_dense()) { set_error("hipFuncSetAttribute(k_dn_*_mf) failed"); return SSBA_ERR_HIP; }
@@ -1455,10 +1454,9 @@ static int enqueue_batch(ssba_problem *p) {
 }
 
 // single GPU, LM, windowed stereo layout: the linearisation kernels commit the accepted step (ssba_kernels.hip:
-// launch_linearize); SSBA_NO_FUSE_ALL=1 keeps the k_commit launch (A/B, tests)
+// launch_linearize)
 static bool fuse_all_launches(const ssba_problem *p) {
-    static const bool off = [] { const char *e = getenv("SSBA_NO_FUSE_ALL"); return e && e[0] == '1'; }();
-    return !off && !p->xfn && !p->d.constrained && !p->d.nb && p->opt.trust_region_strategy_type != 1 && launch_can_fuse_all(p->d);
+    return !p->xfn && !p->d.constrained && !p->d.nb && p->opt.trust_region_strategy_type != 1 && launch_can_fuse_all(p->d);
 }
 
 static int enqueue_kernels(ssba_problem *p) {

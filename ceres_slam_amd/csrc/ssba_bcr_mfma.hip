@@ -1,6 +1,6 @@
 // Block factor / reduce kernels of the reduced-camera solve on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).
 //
-// Same contract as the first-generation kernels in ssba_bcr.hip (kept there as the cross-check, SSBA_BCR_LEGACY=1):
+// The factor and reduce steps of the block cyclic reduction in ssba_bcr.hip:
 //   k_bcr_factor_mf:  D = G G^T ; YL = G^-1 L ; YU = G^-1 U^T ; yr = G^-1 r      (G stored lower, 1/G_kk on its diagonal)
 //   k_bcr_reduce_mf:  D' = D - YU^T YU - YL^T YL ; L' = -YU^T YL ; r' = r - YU^T yr - YL^T yr
 //
@@ -107,7 +107,11 @@ struct FactorOps {
     bool pinned, gLL, gUU, gUL;
 };
 
-// operands and destinations of one block: mirrors k_bcr_factor (ssba_bcr.hip).  false: this block has nothing to do.
+// operands and destinations of one block.  false: this block has nothing to do.
+// Cyclic reduction (which = 0 / 1): odd block 2 bx + 1 of level `lev` (the single block when top), everything in place.
+// Parallel cyclic reduction (which = 2, which = 3: the separator system): block bx of the plan's level at stride 2^lev; D
+// and r stay (the reduce kernel updates them in place), the products go to the plan's buffers; the last step (top) is in
+// place.  Couplings with an even index are stored transposed (trL / trU).
 // ride: the border columns (d.nb > 0: free shared blocks, closure border) go through the factorisation as two more
 // column tiles of the right-hand sides -- yB = G^-1 B, what k_bcrm_fwd (ssba_border.hip) did in a launch of its own
 static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top, int which, int bx, bool copier, bool ride, FactorOps &o) {
@@ -121,6 +125,7 @@ static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top
         const BcrLevel &B = which == 3 ? d.slev[0] : d.lev[d.pcr.level];
         const int blk = bx, s = 1 << lev, last = B.n - 1;
         if (P.pin0 && lev == 0 && blk == 1 && copier) {
+            // from the next step on block 1 carries its coupling to the pinned block 0 (odd index: stored untransposed)
             const double2 *s2 = reinterpret_cast<const double2 *>(B.L + (size_t)BD * BD);
             double2 *d2 = reinterpret_cast<double2 *>(P.Lbuf + (size_t)BD * BD);
             for (int e = threadIdx.x; e < BD * BD / 2; e += MF_THREADS) d2[e] = s2[e];
@@ -138,8 +143,9 @@ static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top
             o.Lg = P.Lbuf + (size_t)blk * BD * BD;
             o.Ug = (P.pin1 && blk + s > last) ? P.Ubuf + (size_t)blk * BD * BD : P.LbufT + (size_t)(o.hasU ? blk + s : blk) * BD * BD;
         }
+        // the pinned last block folds this block in now and moves on: keep the coupling to it
         if (P.pin1 && blk + s == last) o.saveU = P.Ubuf + (size_t)blk * BD * BD;
-        const size_t so = P.keep ? (size_t)lev * B.n + blk : (size_t)blk;
+        const size_t so = P.keep ? (size_t)lev * B.n + blk : (size_t)blk;      // per-step slots when the border follows
         o.oD = top ? B.D + (size_t)blk * BD * BD : (P.keep ? P.Gs + so * BD * BD : nullptr);
         o.oYL = o.hasL ? P.YL + so * BD * BD : nullptr;
         o.oYU = o.hasU ? P.YU + so * BD * BD : nullptr;
@@ -1315,7 +1321,10 @@ static __device__ __forceinline__ void reduce_job(const ReduceJob &J, double *ld
 
 // 1-D grid of xcd_grid(blocks, ny) workgroups, ny = 3 (+ 2 for the coupling to a pinned last block).  Parallel cyclic
 // reduction (which >= 2): D', r' in place, L' (+ its transpose) into the plan's buffers.  Plain levels (which = 0):
-// D', r', L' of the next level.  Same operand rules as k_bcr_reduce (ssba_bcr.hip).
+// D', r', L' of the next level; a coupling with an even index is stored transposed.  In a parallel step block e folds in
+// both neighbours e -+ s:  D_e -= YU(e-s)^T YU(e-s) + YL(e+s)^T YL(e+s),  r_e -= YU(e-s)^T yr(e-s) + YL(e+s)^T yr(e+s),
+// L'_e = -YU(e-s)^T YL(e-s) (stored untransposed and transposed), and U'_e = -YL(e+s)^T YU(e+s) only where that is a
+// coupling to the pinned last block.
 __global__ __launch_bounds__(MF_THREADS) void k_bcr_reduce_mf(Dev d, int lev, int which, int nblocks, int ny, int ride, int x_lo) {
     const StateFlags sf = state_flags_vmem(d.st);       // tested after the operand reads have been issued (ssba_device.h)
     extern __shared__ __align__(16) double lds[];
@@ -1369,7 +1378,8 @@ __global__ __launch_bounds__(MF_THREADS) void k_bcr_reduce_mf(Dev d, int lev, in
         const BcrLevel &N = d.lev[lev + 1];
         const int m = bx, e = 2 * m, t = threadIdx.x;
         if (L.pin && m == L.n / 2) {
-            // pinned end of a partitioned chain: carried over unchanged (see k_bcr_reduce)
+            // pinned end of a partitioned chain (old index n-1, odd): carried over unchanged as the new last block; its
+            // coupling to the new block before it is the old L[n-1] (no fill-in: old n-2 is its direct neighbour)
             if (sf.dead()) return;
             const int src = L.n - 1;
             if (y == 0) {
@@ -1453,14 +1463,14 @@ void launch_pcr_fused_top(Launcher &L, const Dev &d, int n, int steps, int solve
     LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), solve ? sh_solve : 0, d, steps, 1, which, n, 1, 0, NRT, solve);
 }
 
-// ny_legacy: 2, or 3 with the coupling to a pinned last block (the grid.y of k_bcr_reduce)
-void launch_bcr_reduce_mf(Launcher &L, const Dev &d, int nblocks, int ny_legacy, int lev, int which, bool ride) {
-    // ny_legacy == 3 (a partitioned chain whose last block is pinned): the blocks e with e + s inside the chain and
+// ny: 2, or 3 with the coupling to a pinned last block
+void launch_bcr_reduce_mf(Launcher &L, const Dev &d, int nblocks, int ny, int lev, int which, bool ride) {
+    // ny == 3 (a partitioned chain whose last block is pinned): the blocks e with e + s inside the chain and
     // e + 2 s beyond its last block also compute the coupling of e to that block -- two more workgroups each, listed
     // after the 3 n regular ones (a 5 n grid with 2 n - 2 s workgroups that return at once held a CU's LDS each while
     // they did: 17-21 us per launch against 11.6)
     int n_extra = 0, x_lo = 0;
-    if (ny_legacy == 3 && which >= 2) {
+    if (ny == 3 && which >= 2) {
         const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
         const BcrLevel &B = which == 3 ? d.slev[0] : d.lev[d.pcr.level];
         const int s = 1 << lev, last = B.n - 1, hi = P.pin1 ? last - 1 : last;

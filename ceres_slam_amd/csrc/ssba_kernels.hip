@@ -2,15 +2,16 @@
 //
 // Kernel classes (one LM iteration, in launch order; DESIGN.md has the roofline
 // of each):
-//   k_linearize_landmarks  per-landmark H_ll, g_l, cost        (HBM stream, 1 lane/landmark)
+//   k_linearize_landmarks_w  per-landmark H_ll, g_l, cost      (HBM stream, SP waves per 64 landmarks)
 //   k_linearize_poses      per-pose H_pp, g_p                   (gather, 1 block/pose)
+//   k_linearize_both       the two passes above in one launch   (window layout up to 262 144 landmarks)
 //   k_schur_windows        sum_j (W C^-1)_a W_b^T per window    (fp64 FMA bound, output-stationary)
 //   k_assemble_reduced     slabs -> block-tridiagonal S, rhs    (HBM)
 //   k_finish_reduced       Jacobi scale + LM damping on diag(S)
 //   k_check                Ceres FinalizeIterationAndCheck...   (1 block)
-//   k_bcr_factor/reduce/backsub  block cyclic reduction of S    (latency bound, log2 levels)
+//   k_bcr_factor_mf/reduce_mf/backsub  block cyclic reduction of S    (latency bound, log2 levels; ssba_bcr*.hip)
 //   k_pose_update          candidate poses = Plus(x, delta_p)
-//   k_backsub_eval         delta_l, model cost change, candidate cost (HBM stream)
+//   k_backsub_eval_w       delta_l, model cost change, candidate cost (HBM stream, SP waves per 64 landmarks)
 //   k_decide               step quality, accept/reject, radius  (1 block)
 //   k_commit / k_best      x <- candidate, best <- x
 //
@@ -46,67 +47,6 @@ int upload_pair_table(hipStream_t s) {
 }
 
 // ------------------------------------------------------------------ kernels ---
-
-// One lane per landmark.  Streams the ELL observation arrays (coalesced), gathers the
-// (few, shared) pose blocks through L1/L2.  Writes H_ll (6), g_l (3) component-major and
-// per-block partials {cost, |x_l|^2, max|g_l|}.  At iteration 0 also the Jacobi scale.
-template <bool DN> __global__ __launch_bounds__(256) void k_linearize_landmarks(Dev d) {
-    const State &st = *d.st;
-    if (st.terminated || !st.need_linearize) return;
-    __shared__ double sm[4];
-    const int l = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t mask = d.lm_mask[l];
-    double cost = 0.0, xn = 0.0, gm = 0.0;
-    if (mask) {
-        const LmObs<DN> ob(d, l, mask);
-        const double px = d.pts[l], py = d.pts[(size_t)d.Lpad + l], pz = d.pts[2 * (size_t)d.Lpad + l];
-        double h[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
-        for (int s = 0; s < ob.count(); ++s) {
-            if (!ob.has(s)) continue;
-            const uint32_t k = ob.pose(d, s);
-            const double *T = d.poses + (size_t)k * 12;
-            ObsLin o;
-            double Sk[9];
-            ob.stiffness(d, s, Sk);
-            obs_linearize_S(d, Sk, T, px, py, pz, ob.u(d, s), ob.v(d, s), ob.dd(d, s), o);
-            double Jl[9];
-            jac_point(o, T, Jl);
-            cost += o.half_rho;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                h[0] += Jl[3 * i] * Jl[3 * i];
-                h[1] += Jl[3 * i] * Jl[3 * i + 1];
-                h[2] += Jl[3 * i] * Jl[3 * i + 2];
-                h[3] += Jl[3 * i + 1] * Jl[3 * i + 1];
-                h[4] += Jl[3 * i + 1] * Jl[3 * i + 2];
-                h[5] += Jl[3 * i + 2] * Jl[3 * i + 2];
-                g[0] += Jl[3 * i] * o.r[i];
-                g[1] += Jl[3 * i + 1] * o.r[i];
-                g[2] += Jl[3 * i + 2] * o.r[i];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 6; ++c) d.hll[(size_t)c * d.Lpad + l] = h[c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d.gl[(size_t)c * d.Lpad + l] = g[c];
-        if (st.iteration == 0) {   // Jacobi scaling, computed once [trust_region_minimizer.cc]
-            const double hd[3] = {h[0], h[3], h[5]};
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                d.sl[(size_t)c * d.Lpad + l] = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(hd[c])) : 1.0;
-        }
-        xn = px * px + py * py + pz * pz;
-        gm = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
-    }
-    const double c0 = block_sum(cost, sm);
-    const double c1 = block_sum(xn, sm);
-    const double c2 = block_max(gm, sm);
-    if (threadIdx.x == 0) {
-        d.part_lin[blockIdx.x * 4 + 0] = c0;
-        d.part_lin[blockIdx.x * 4 + 1] = c1;
-        d.part_lin[blockIdx.x * 4 + 2] = c2;
-    }
-}
 
 // One block per pose: gathers that pose's observations through the pose-major
 // reference list, accumulates the 21 unique entries of H_pp and g_p in registers and
@@ -365,10 +305,10 @@ template <bool DN, int SP> __global__ __launch_bounds__(64 * SP) void k_lineariz
     const bool commit = fuse && st.accepted;
     lin_landmarks_w_body<DN, SP>(d, st, (int)blockIdx.x, commit ? d.cand_poses : d.poses, commit ? d.cand_pts : d.pts, commit);
 }
-// Both linearisation passes of the window layout in ONE launch: the first n_groups work-groups are k_linearize_landmarks_w<false,
+// Both linearisation passes of the window layout in ONE launch: the first n_groups work-groups are lin_landmarks_w_body<false,
 // LMW_SPLIT>'s, the others k_linearize_poses<false, 128, 5>'s -- same block shape, neither reads what the other writes (with the
 // commit folded in both read the candidate buffers and write x).  The second pass's ramp fills the first one's tail: 31.1 -> 28.4 us
-// at C2 (0.3458 -> 0.3431 ms per iteration, same bits).  SSBA_LIN_TWO_LAUNCHES=1 keeps the two launches (A/B, tests).
+// at C2 (0.3458 -> 0.3431 ms per iteration, same bits).
 __global__ __launch_bounds__(LP_THREADS) void k_linearize_both(Dev d, int fuse, int n_groups) {
     static_assert(LP_THREADS == 64 * LMW_SPLIT, "one block shape for both passes");
     const State &st = *d.st;
@@ -920,92 +860,6 @@ __global__ __launch_bounds__(256) void k_pose_update(Dev d, int fuse_best) {
         d.part_pose[blockIdx.x * NPP + 3] = c3;
     }
 }
-
-// One lane per landmark: back-substitution delta_l = -C^-1 (g_l + sum_s W_s^T delta_p,s),
-// candidate point, model cost change -(J d)^T (r + J d / 2) and candidate cost, all in
-// one pass over the landmark's observations (second sweep hits L1/L2).
-template <bool DN> __global__ __launch_bounds__(256) void k_backsub_eval(Dev d) {
-    const State &st = *d.st;
-    if (st.terminated) return;
-    __shared__ double sm[4];
-    const int l = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t mask = d.lm_mask[l];
-    double ccost = 0.0, mcc = 0.0, dn = 0.0, nonfinite = 0.0;
-    const double px = d.pts[l], py = d.pts[(size_t)d.Lpad + l], pz = d.pts[2 * (size_t)d.Lpad + l];
-    double nx = px, ny = py, nz = pz;
-    if (mask && !st.step_failed) {
-        const LmObs<DN> ob(d, l, mask);
-        const double gl[3] = {d.gl[l], d.gl[(size_t)d.Lpad + l], d.gl[2 * (size_t)d.Lpad + l]};
-        double tt[3] = {gl[0], gl[1], gl[2]};
-        // With e = J_p delta_p of an observation the model cost change -(J d)^T (r + J d / 2) of this landmark's
-        // observations is  -(sum e.r + dl.g_l) - (sum e.e + 2 dl.(tt - g_l) + dl^T H_ll dl) / 2 :
-        // one linearisation pass instead of two (H_ll and g_l are those of this linearisation point)
-        double er = 0.0, ee = 0.0;
-        for (int s = 0; s < ob.count(); ++s) {
-            if (!ob.has(s)) continue;
-            const uint32_t k = ob.pose(d, s);
-            const int f = d.pose_free[k];
-            if (f < 0) continue;
-            const double *T = d.poses + (size_t)k * 12;
-            ObsLin o;
-            double Sk[9];
-            ob.stiffness(d, s, Sk);
-            obs_linearize_S(d, Sk, T, px, py, pz, ob.u(d, s), ob.v(d, s), ob.dd(d, s), o);
-            const double *dp = d.x0 + (size_t)f * 6;      // (as in k_backsub_eval_w: no Jacobians formed)
-            double jd[3], y[3];
-            pose_step_rows(o, dp, jd);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { er += jd[i] * o.r[i]; ee += jd[i] * jd[i]; }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) y[c] = o.A[c] * jd[0] + o.A[3 + c] * jd[1] + o.A[6 + c] * jd[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) tt[c] += T[3 + c] * y[0] + T[6 + c] * y[1] + T[9 + c] * y[2];
-        }
-        double h[6], dmp[3], Ci[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) h[c] = d.hll[(size_t)c * d.Lpad + l];
-        landmark_damping(d, st, l, h, dmp);
-        double dl[3] = {0, 0, 0};
-        if (inv3_spd(h, dmp, Ci)) {
-            dl[0] = -(Ci[0] * tt[0] + Ci[1] * tt[1] + Ci[2] * tt[2]);
-            dl[1] = -(Ci[1] * tt[0] + Ci[3] * tt[1] + Ci[4] * tt[2]);
-            dl[2] = -(Ci[2] * tt[0] + Ci[4] * tt[1] + Ci[5] * tt[2]);
-        } else {
-            nonfinite = 1.0;
-        }
-        if (!isfinite(dl[0]) || !isfinite(dl[1]) || !isfinite(dl[2])) nonfinite = 1.0;
-        nx = px + dl[0]; ny = py + dl[1]; nz = pz + dl[2];
-        dn = dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2];
-        {
-            const double hd0 = h[0] * dl[0] + h[1] * dl[1] + h[2] * dl[2], hd1 = h[1] * dl[0] + h[3] * dl[1] + h[4] * dl[2],
-                         hd2 = h[2] * dl[0] + h[4] * dl[1] + h[5] * dl[2];
-            const double dg = dl[0] * gl[0] + dl[1] * gl[1] + dl[2] * gl[2];
-            const double dt = dl[0] * (tt[0] - gl[0]) + dl[1] * (tt[1] - gl[1]) + dl[2] * (tt[2] - gl[2]);
-            mcc = -(er + dg) - 0.5 * (ee + 2.0 * dt + (dl[0] * hd0 + dl[1] * hd1 + dl[2] * hd2));
-        }
-        for (int s = 0; s < ob.count(); ++s) {
-            if (!ob.has(s)) continue;
-            const uint32_t k = ob.pose(d, s);
-            double Sk[9];
-            ob.stiffness(d, s, Sk);
-            ccost += obs_cost_S(d, Sk, d.cand_poses + (size_t)k * 12, nx, ny, nz, ob.u(d, s), ob.v(d, s), ob.dd(d, s));
-        }
-    }
-    d.cand_pts[l] = nx;
-    d.cand_pts[(size_t)d.Lpad + l] = ny;
-    d.cand_pts[2 * (size_t)d.Lpad + l] = nz;
-    const double a = block_sum(ccost, sm);
-    const double b = block_sum(mcc, sm);
-    const double c = block_sum(dn, sm);
-    const double e = block_sum(nonfinite, sm);
-    if (threadIdx.x == 0) {
-        d.part_eval[blockIdx.x * 4 + 0] = a;
-        d.part_eval[blockIdx.x * 4 + 1] = b;
-        d.part_eval[blockIdx.x * 4 + 2] = c;
-        d.part_eval[blockIdx.x * 4 + 3] = e;
-    }
-}
-
 
 // The body of the Ceres trust-region loop after the candidate evaluation: step validity,
 // parameter / function tolerance, step quality, accept / reject, radius update.
@@ -1939,25 +1793,15 @@ void launch_reset(Launcher &L, const Dev &d, const Options &o) {
 // Window layout: several lanes per landmark pay off while one lane per landmark leaves the SIMDs short of waves (C2: 1.5
 // waves per SIMD); from ~4 waves per SIMD on the plain mapping wins (C4: 15 600 waves; measured 0.106 / 0.224 ms vs
 // 0.133 / 0.272 ms for the split kernels).
-// r04: above that size the window kernels run with ONE wave per 64 landmarks (SP = 1: the plain mapping's lane count) instead
-// of handing the problem to the generic kernels -- those lack the folded control work (commit inside the linearisation, best
-// copy inside the evaluation, k_check's sums per group), so C4 on one GPU paid five dependent single-block launches (60 us) per
-// iteration that C2 does not have.
-static bool lm_split(const Dev &d) {
-    static const bool cliff = [] { const char *e = getenv("SSBA_LM_CLIFF"); return e && e[0] == '1'; }();      // r03's bound (A/B)
-    return !d.dense && !d.phong && (!cliff || d.Lpad <= 262144);
-}
+// r04: above that size the window kernels run with ONE wave per 64 landmarks (SP = 1: the plain mapping's lane count) and keep
+// the folded control work (commit inside the linearisation, best copy inside the evaluation, k_check's sums per group): the
+// one-lane-per-landmark kernels they replaced cost C4 on one GPU five dependent single-block launches (60 us) per iteration.
+static bool lm_split(const Dev &d) { return !d.dense && !d.phong; }
 static int lm_sp(const Dev &d) { return d.Lpad <= 262144 ? LMW_SPLIT : 1; }
-// General layout (landmark-major lists): waves per 64 landmarks of the two landmark passes; 0 = one lane per landmark in
-// work-groups of 256 (the r03 kernels; SSBA_DN_SPLIT=0/1/2/4 for A/B).
-static int dn_sp(const Dev &d) {
-    static const int forced = [] { const char *e = getenv("SSBA_DN_SPLIT"); return e ? atoi(e) : -1; }();
-    if (!d.dense || d.phong) return 0;
-    if (forced >= 0) return forced == 1 || forced == 2 || forced == 4 ? forced : 0;
-    return d.Lpad <= 131072 ? 4 : (d.Lpad <= 262144 ? 2 : 1);
-}
-// entries of part_lin / part_eval: one per group of 64 landmarks, or per block of 256
-static int lm_parts(const Dev &d) { return lm_split(d) || dn_sp(d) ? d.n_groups : d.n_lm_blocks; }
+// General layout (landmark-major lists, stereo blocks): waves per 64 landmarks of the two landmark passes
+static int dn_sp(const Dev &d) { return d.Lpad <= 131072 ? 4 : (d.Lpad <= 262144 ? 2 : 1); }
+// entries of part_lin / part_eval: one per group of 64 landmarks (stereo blocks), or per block of 256 (lighting terms)
+static int lm_parts(const Dev &d) { return d.phong ? d.n_lm_blocks : d.n_groups; }
 
 // fuse_ctrl (single GPU, windowed stereo layout; see k_check): k_reduce_lin's sums are formed by k_check
 // r04: the general layout too (stereo blocks: wide super-blocks and blocked Cholesky) -- k_check forms the sums of k_reduce_lin and
@@ -1967,9 +1811,9 @@ static bool ctrl_fusable(const Dev &d) { return !d.part && (!d.dense || !d.phong
 // decision and those kernels in any mode, so the partitioned multi-GPU solve takes it too
 // lighting terms with free shared blocks: k_pose_update / k_dogleg_vec get one more work-group for the border entries
 static int border_block(const Dev &d) { return d.phong && d.nb ? 1 : 0; }
-static bool best_fusable(const Dev &d) { return !d.nb && (d.phong ? !d.dense : (lm_split(d) || dn_sp(d) > 0)); }       // (free shared blocks have a best copy of their own: k_best)
+static bool best_fusable(const Dev &d) { return !d.nb && !(d.phong && d.dense); }       // (free shared blocks have a best copy of their own: k_best)
 bool launch_ctrl_fusable(const Dev &d) { return ctrl_fusable(d); }
-bool launch_can_fuse_all(const Dev &d) { return ctrl_fusable(d) && !d.phong && (lm_split(d) || dn_sp(d) > 0); }
+bool launch_can_fuse_all(const Dev &d) { return ctrl_fusable(d) && !d.phong; }
 // fuse_all (single GPU, LM, windowed stereo layout, launch_can_fuse_all): the linearisation kernels commit the accepted
 // step on the way (no k_commit launch)
 // skip_reduce (partitioned solve): k_sep_pack(.., n_lin_parts) forms the sums of the partials
@@ -1978,18 +1822,15 @@ void launch_linearize(Launcher &L, const Dev &d, bool fuse_ctrl, bool fuse_all, 
     if (d.phong) {
         launch_ph_linearize(L, d);
     } else {
-        static const bool one_launch = [] { const char *e = getenv("SSBA_LIN_TWO_LAUNCHES"); return !(e && e[0] == '1'); }();
-        if (one_launch && lm_split(d) && lm_sp(d) == LMW_SPLIT && !d.dense) {
+        if (lm_split(d) && lm_sp(d) == LMW_SPLIT) {
             LAUNCH(KC_LIN_LM, k_linearize_both, dim3(d.n_groups + xcd_contiguous_grid(d.P)), dim3(LP_THREADS), 0, d, fuse_all ? 1 : 0, d.n_groups);
             if (!fuse_ctrl && !skip_reduce) LAUNCH(KC_SMALL, k_reduce_lin, dim3(1), dim3(256), 0, d, lm_parts(d));
             return;
         }
-        if (lm_split(d) && lm_sp(d) == LMW_SPLIT) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<false, LMW_SPLIT>), dim3(d.n_groups), dim3(64 * LMW_SPLIT), 0, d, fuse_all ? 1 : 0);
-        else if (lm_split(d)) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
+        if (lm_split(d)) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
         else if (dn_sp(d) == 4) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 4>), dim3(d.n_groups), dim3(256), 0, d, fuse_all ? 1 : 0);
         else if (dn_sp(d) == 2) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 2>), dim3(d.n_groups), dim3(128), 0, d, fuse_all ? 1 : 0);
-        else if (dn_sp(d) == 1) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
-        else LAUNCH(KC_LIN_LM, (d.dense ? k_linearize_landmarks<true> : k_linearize_landmarks<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
+        else LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
         // 128 lanes per pose, five observations in flight per lane (sweep on C2, profiles/r02_pose_kernel_shape.txt: 64 / 128 / 192 /
         // 256 / 512 lanes x 3-10 observations: 24.5 us here, 31 us for 256 x 3, 51 us for 512 x 3)
         LAUNCH(KC_LIN_POSE, (d.dense ? k_linearize_poses<true, LP_THREADS, LP_CHUNK> : k_linearize_poses<false, LP_THREADS, LP_CHUNK>), dim3(xcd_contiguous_grid(d.P)), dim3(LP_THREADS), 0, d, fuse_all ? 1 : 0);
@@ -2036,8 +1877,7 @@ void launch_update_eval(Launcher &L, const Dev &d, bool fuse_reduce, bool fuse_b
     else if (lm_split(d)) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
     else if (dn_sp(d) == 4) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 4>), dim3(d.n_groups), dim3(256), 0, d, pose_update_done ? 2 : fb);
     else if (dn_sp(d) == 2) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 2>), dim3(d.n_groups), dim3(128), 0, d, pose_update_done ? 2 : fb);
-    else if (dn_sp(d) == 1) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
-    else LAUNCH(KC_BACKSUB_EVAL, (d.dense ? k_backsub_eval<true> : k_backsub_eval<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
+    else LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
     if (!fuse_reduce) LAUNCH(KC_SMALL, k_reduce_eval, dim3(1), dim3(256), 0, d, lm_parts(d), d.part ? 1 : 0);
 }
 

@@ -1010,7 +1010,7 @@ template <bool DN> __global__ __launch_bounds__(256) void k_ph_border_landmarks(
 // k_ph_linpose_invert).  The landmark pass puts 1 564 waves on a machine that holds 2 048 at its register count -- one under-filled
 // round; in ONE launch, landmark groups first, the pose work-groups fill what it leaves: 53 + 54 us -> 96 at C3 (-11 us per
 // iteration, same bits).  The border pass of the landmarks (k_ph_border_landmarks) in the same launch as well: slower by 19 us -- the
-// three bodies in one kernel need 292 bytes of scratch per lane at two waves per SIMD.  SSBA_PH_LIN_LAUNCHES=1 keeps the launches apart.
+// three bodies in one kernel need 292 bytes of scratch per lane at two waves per SIMD.
 __global__ __launch_bounds__(256, 2) void k_ph_linearize_all(Dev d, int n_lm) {
     const int b = (int)blockIdx.x;
     if (b < n_lm) { ph_lin_landmarks_body<false>(d, b); return; }
@@ -1725,8 +1725,7 @@ static bool ph_invert_with_poses(const Dev &d) {
     return !d.dense && !d.nb && !(e && e[0] == '1');
 }
 void launch_ph_linearize(Launcher &L, const Dev &d) {
-    static const bool separate = [] { const char *e = getenv("SSBA_PH_LIN_LAUNCHES"); return e && e[0] == '1'; }();
-    if (!separate && d.nb && !d.dense && !ph_invert_with_poses(d)) {
+    if (d.nb && !d.dense) {
         LAUNCH(KC_LIN_LM, k_ph_linearize_all, dim3(d.n_lm_blocks + xcd_contiguous_grid(d.P)), dim3(256), 0, d, d.n_lm_blocks);
         LAUNCH(KC_BORDER, k_ph_border_landmarks<false>, dim3(d.n_lm_blocks), dim3(256), 0, d);
         if (d.lmMV) LAUNCH(KC_BORDER, k_ph_hpb, dim3(d.P * d.M), dim3(64), 0, d);

@@ -238,7 +238,7 @@ typedef struct {
 SSBA_API int ssba_set_kernel_timing(ssba_problem *p, int mode);
 SSBA_API int ssba_kernel_times(ssba_problem *p, ssba_kernel_time *rows, int32_t capacity, int32_t *num);
 
-/* Diagnostic builds only (-DSSBA_STAMPS: tools/stamps_bcr.py, tools/bcr_bench.hip): copies the first n (<= 8192) in-kernel
+/* Diagnostic builds only (-DSSBA_STAMPS, -DWD_STAMPS: tools/stamps_wide.py, tools/bcr_bench.hip): copies the first n (<= 8192) in-kernel
  * time stamps of the handle's debug buffer; the buffer stays zero in a normal build. */
 SSBA_API int ssba_debug_stamps(ssba_problem *p, unsigned long long *out, int n);
 

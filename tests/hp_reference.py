@@ -95,6 +95,282 @@ def stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, hub
     return dict(cost=dtype(0.5) * rho0.sum(), r=r * w[:, None], Jp=Jp, Jl=Jl, rabs=rabs, Jpa=Jpa, Jla=Jla, alpha=alpha)
 
 
+# ----------------------------------------------------------------------------------------------------------- lighting rows
+H_CS = 2.0 ** -100        # complex step: exact power of two, so value + i h f' carries f' to long-double accuracy
+DELTA_MAG = 2.0 ** -52    # relative perturbation for the rounding magnitudes (below fp64's own u: no guard is crossed
+                          # unless the row is within fp64 rounding of it, where either branch is a correct fp64 answer)
+C_ROW = 16                # the c of the row bar c u mag
+
+
+def _dot3(a, b):
+    return (a * b).sum(-1)
+
+
+def _se3_columns(T, h):
+    """SE3Perturbation Plus at eps = i h e_c, c = 0..5, on stacked poses (N, 12): (6, N, 12).  At eps = 0 Ceres takes the
+    first-order branch of so3_exp (np_reference.jacobians_complex_step), so Plus(T, eps) = [(I + eps_r^) t + eps_t, (I + eps_r^) R]."""
+    N = T.shape[0]
+    out = np.repeat(T[None], 6, axis=0)
+    t, R = T[:, :3], T[:, 3:].reshape(N, 3, 3)
+    for c in range(3):
+        out[c, :, c] = out[c, :, c] + 1j * h
+        phi = np.zeros(3)
+        phi[c] = 1.0
+        W = np.array([[0, -phi[2], phi[1]], [phi[2], 0, -phi[0]], [-phi[1], phi[0], 0]]) * (1j * h)
+        out[3 + c, :, :3] = t + np.einsum("ij,nj->ni", W, t)
+        out[3 + c, :, 3:] = (R + np.einsum("ij,njk->nik", W, R)).reshape(N, 9)
+    return out
+
+
+def _phong_eval(light_type, x, pert, cdt):
+    """(r_int (N,), J_int (N,19), r_nrm (N,3), J_nrm (N,3,9) = [pose 6 | normal 3]) by complex step in `cdt` through the
+    forward formulas of np_reference and the reference's Plus operators, at the inputs `x` (already in `cdt`)."""
+    import np_reference as npr
+    h = H_CS
+    T, p, n, ph, kd, light, col, st, nobs, Sn = (x[k] for k in ("T", "p", "n", "phong", "kd", "light", "colour",
+                                                                "stiffness", "nobs", "Sn"))
+    N = T.shape[0]
+    e3 = np.eye(3) * (1j * h)
+
+    def f_int(T=T, p=p, n=n, ph=ph, kd=kd, light=light):
+        return npr.intensity_residual(light_type, T, p, n, ph, kd, light, col, st, dtype=cdt, pert=pert)
+
+    def f_nrm(T=T, n=n):
+        R = T[:, 3:].reshape(N, 3, 3)
+        nc = np.einsum("nij,nj->ni", R, n)
+        if pert is not None:
+            nc = pert("nc", nc)
+        return np.einsum("nij,nj->ni", Sn, nc - nobs)
+
+    Ts = _se3_columns(T, h)
+    r0 = f_int()
+    # Ceres chains d r / d x at the block's value x with the plus-Jacobian (I - x x^T / |x|^2) / |x| of
+    # UnitVectorPerturbation: the same as the complex step through Plus only when |x| = 1, since Plus(x, 0) = x / |x|
+    plus = lambda v, e: v + (e - (_dot3(e, v) / _dot3(v, v))[:, None] * v) / np.sqrt(_dot3(v, v))[:, None]
+    J = np.zeros((N, 19), dtype=LD if cdt == np.clongdouble else np.float64)
+    for c in range(6):
+        J[:, c] = f_int(T=Ts[c]).imag / h
+    for c in range(3):
+        J[:, 6 + c] = f_int(p=p + e3[c]).imag / h
+        J[:, 9 + c] = f_int(n=plus(n, np.broadcast_to(e3[c], n.shape))).imag / h
+        J[:, 12 + c] = f_int(ph=ph + e3[c]).imag / h
+        J[:, 16 + c] = f_int(light=(light + e3[c]) if light_type == 0 else plus(light, np.broadcast_to(e3[c], light.shape))).imag / h
+    J[:, 15] = f_int(kd=kd + 1j * h).imag / h
+    rn = f_nrm()
+    Jn = np.zeros((N, 3, 9), dtype=J.dtype)
+    for c in range(6):
+        Jn[:, :, c] = f_nrm(T=Ts[c]).imag / h
+    for c in range(3):
+        Jn[:, :, 6 + c] = f_nrm(n=plus(n, np.broadcast_to(e3[c], n.shape))).imag / h
+    return r0.real, J, rn.real, Jn
+
+
+_PH_INPUTS = (("T", 12), ("p", 3), ("n", 3), ("phong", 3), ("kd", 1), ("light", 3), ("colour", 1), ("stiffness", 1),
+              ("nobs", 3), ("Sn", 9))
+_PH_UNITS = ("q", "nc", "ell", "cd", "m")
+
+
+def phong_rows(light_type, poses, points, normals, phong, texture, light, colour, stiffness, normal_obs, normal_stiffness,
+               dtype=LD, mags=True):
+    """The intensity row (point light: light_type 0, directional: 1) and the three normal rows of every observation, with
+    their local Jacobians, in `dtype` -- by complex step in the matching complex type through np_reference's forward
+    formulas (and so through their branches: ldn <= 0, mu2 <= 0 and s <= 0 guards, the fmax 0 / fmin 1 clamp with a zero
+    gradient where it fires, the normalised directional light) and the reference's Plus operators.
+
+    Arguments per observation as for capi.phong_evaluate: poses (N,12), points, normals (N,3), phong (N,3), texture (N,),
+    colour (N,); light (3), stiffness (scalar), normal_obs (N,3), normal_stiffness (3,3).  Returns r_int (N,), J_int
+    (N,19) = [pose 6 | position 3 | normal 3 | Phong 3 | texture 1 | light 3], r_nrm (N,3), J_np (N,3,6), J_nn (N,3,3),
+    the branch flags of every row, and (mags=True) a rounding magnitude of each value: mag_r_int, mag_J_int, mag_r_nrm,
+    mag_J_np, mag_J_nn.
+
+    The bar on an fp64 evaluation is |fp64 - truth| <= C_ROW u mag, where mag is the first-order sensitivity of the
+    quantity Q (a residual or one Jacobian entry) to relative perturbations of each of its inputs x_k and of its
+    intermediate vectors y_k (q = R p + t, nc = R n, ell, cd, the mirror direction m), component by component:
+
+        mag = |Q| + sum_k |x_k dQ/dx_k| + sum_k |y_k dQ/dy_k|.
+
+    fp64 evaluates Q as the exact function of inputs and intermediates each carrying a relative error of at most a few u
+    (one rounding per stored value, the two or three of a 3-term dot product, the few ulps of log, exp, the rsqrt of
+    ph_rsqrt / ph_rcp); to first order |fp64 - Q| <= sum_k gamma_k |x_k dQ/dx_k| with gamma_k <= 4 u for all of them.  The
+    perturbation of an input x_k stands for the rounding of the first products formed from it (R p + t cancels when the
+    point is far: then |p dQ/dp| is large), that of the intermediates for the rounding of the normalisations, the dot
+    products (ldn = ell.nc, s = m.cd: |m_i cd_i| / s is large for s near 0) and the differences (mt = 2 ldn nc - ell,
+    v = light - q).  exp(alpha log s) has the relative error |alpha log s| u of the logarithm, which is exactly the relative
+    sensitivity to alpha.  C_ROW = 16 = 4 x 4 u: four such terms adding in the same direction beyond the bound on each.
+    Where a clamp fires both Q and mag are 0 except d r / d colour, d r / d stiffness: the bar is then exact zero gradients.
+    The derivatives are measured, not derived: one extra complex-step evaluation per perturbation at x_k (1 + DELTA_MAG)
+    in long double, so mag carries a relative error of 2^-64 / DELTA_MAG = 2^-12.
+    """
+    cdt = np.clongdouble if dtype == LD else complex
+    c = lambda v: np.asarray(v, dtype=cdt)
+    N = np.asarray(poses).shape[0]
+    x = dict(T=c(poses), p=c(points), n=c(normals), phong=c(phong).reshape(N, 3), kd=c(texture).reshape(N),
+             light=c(np.broadcast_to(np.asarray(light, np.float64), (N, 3))), colour=c(colour).reshape(N),
+             stiffness=c(stiffness), nobs=c(normal_obs), Sn=c(np.broadcast_to(np.asarray(normal_stiffness, np.float64).reshape(3, 3), (N, 3, 3))))
+    x["stiffness"] = np.broadcast_to(x["stiffness"], (N,)).copy()
+    r, J, rn, Jn = _phong_eval(light_type, x, None, cdt)
+    out = dict(r_int=r, J_int=J, r_nrm=rn, J_np=Jn[:, :, :6], J_nn=Jn[:, :, 6:])
+    out.update(_phong_branches(light_type, x))
+    if not mags:
+        return out
+    base = [np.abs(np.asarray(v, np.float64)) for v in (r, J, rn, Jn)]
+    acc = [b.copy() for b in base]
+    ref = [np.asarray(v, LD) for v in (r, J, rn, Jn)]
+
+    def add(res, rel):
+        for a, v, r0 in zip(acc, res, ref):
+            d = np.abs(np.asarray((np.asarray(v, LD) - r0), np.float64))
+            a += d / rel.reshape((-1,) + (1,) * (d.ndim - 1))
+
+    for name, width in _PH_INPUTS:
+        flat = x[name].reshape(N, -1)
+        for k in range(flat.shape[1]):
+            y = dict(x)
+            f2 = flat.copy()
+            f2[:, k] = f2[:, k] * (1 + DELTA_MAG)
+            xr = np.abs(np.asarray(flat[:, k].real, np.float64))
+            if not np.any(xr > 0):
+                continue
+            rel = np.abs(np.asarray((f2[:, k] - flat[:, k]).real, np.float64)) / np.maximum(xr, 1e-300)
+            y[name] = f2.reshape(x[name].shape)
+            add(_phong_eval(light_type, y, None, cdt), np.where(xr > 0, rel, np.inf))
+    for name in _PH_UNITS:
+        for k in range(3):
+            def pert(nm, v, name=name, k=k):
+                if nm != name:
+                    return v
+                v = v.copy()
+                v[..., k] = v[..., k] * (1 + DELTA_MAG)
+                return v
+            add(_phong_eval(light_type, x, pert, cdt), np.full(N, DELTA_MAG))
+    acc[1][:, :6] += _pose_chain_terms(light_type, x, J, cdt)
+    acc[1][:, 9:12] += _projection_terms(light_type, x, "n", cdt)
+    if light_type == 1:
+        acc[1][:, 16:19] += _projection_terms(light_type, x, "light", cdt)
+    acc[3][:, :, 6:] += _normal_row_projection_terms(x)
+    out.update(mag_r_int=acc[0], mag_J_int=acc[1], mag_r_nrm=acc[2], mag_J_np=acc[3][:, :, :6], mag_J_nn=acc[3][:, :, 6:])
+    return out
+
+
+def _pose_chain_terms(light_type, x, J, cdt):
+    """|d r / d eps| through q alone, through nc alone, and through the light alone, for the six pose columns.  The pose
+    Jacobian is the sum of these three chains and cancels where the row is invariant (a rigid motion of the camera moves
+    q, nc and a point light together: the rotation columns are exactly 0; the translation columns lose the light chain),
+    so its rounding is relative to the terms, which no perturbation of an input sees: the symmetry survives every one."""
+    import np_reference as npr
+    h = H_CS
+    N = x["T"].shape[0]
+    out = np.zeros((N, 6))
+    for c in range(6):
+        e = np.zeros(3)
+        e[c % 3] = 1.0
+        step = lambda v: (np.broadcast_to(e * (1j * h), v.shape) if c < 3 else np.cross(e * (1j * h), v))
+        parts = []
+        for target in ("q", "nc"):
+            if target == "nc" and c < 3:
+                parts.append(np.zeros(N, LD))
+                continue
+            pert = lambda nm, v, target=target: v + step(v) if nm == target else v
+            parts.append(np.asarray(npr.intensity_residual(light_type, x["T"], x["p"], x["n"], x["phong"], x["kd"], x["light"],
+                                                           x["colour"], x["stiffness"], dtype=cdt, pert=pert).imag / h, LD))
+        rest = np.asarray(J[:, c], LD) - parts[0] - parts[1]
+        out[:, c] = sum(np.abs(np.asarray(v, np.float64)) for v in (parts[0], parts[1], rest))
+    return out
+
+
+def _projection_terms(light_type, x, name, cdt):
+    """|g| + |g.x| |x| / |x|^2 of the UnitVectorPerturbation plus-Jacobian (I - x x^T / |x|^2) / |x| applied to the
+    gradient g with respect to the raw vector x (the normal, or a directional light): the two terms cancel where g is
+    nearly parallel to x, which no relative perturbation of x sees."""
+    import np_reference as npr
+    h = H_CS
+    v = np.asarray(x[name].real, LD)
+    g = np.zeros(v.shape, LD)
+    for c in range(3):
+        y = dict(x)
+        e = np.zeros(3)
+        e[c] = 1.0
+        y[name] = x[name] + e * (1j * h)
+        g[:, c] = np.asarray(npr.intensity_residual(light_type, y["T"], y["p"], y["n"], y["phong"], y["kd"], y["light"], y["colour"],
+                                                    y["stiffness"], dtype=cdt).imag / h, LD)
+    n2 = (v * v).sum(1)
+    proj = np.abs((g * v).sum(1))[:, None] * np.abs(v) / n2[:, None]
+    return np.asarray((np.abs(g) + proj) / np.sqrt(n2)[:, None], np.float64)
+
+
+def _normal_row_projection_terms(x):
+    """The same two terms for the normal rows: g = Sn R (rows of Sn R against the unit normal)."""
+    n = np.asarray(x["n"].real, LD)
+    R = np.asarray(x["T"].real, LD)[:, 3:].reshape(-1, 3, 3)
+    G = np.einsum("nij,njk->nik", np.asarray(x["Sn"].real, LD), R)
+    n2 = (n * n).sum(1)
+    proj = np.abs(np.einsum("nij,nj->ni", G, n))[:, :, None] * np.abs(n)[:, None, :] / n2[:, None, None]
+    return np.asarray((np.abs(G) + proj) / np.sqrt(n2)[:, None, None], np.float64)
+
+
+def _phong_branches(light_type, x):
+    """Which side of each guard every intensity row is on, in long double (for the tests that build edge batches)."""
+    R = np.asarray(x["T"].real, LD)[:, 3:].reshape(-1, 3, 3)
+    t = np.asarray(x["T"].real, LD)[:, :3]
+    q = np.einsum("nij,nj->ni", R, np.asarray(x["p"].real, LD)) + t
+    nc = np.einsum("nij,nj->ni", R, np.asarray(x["n"].real, LD))
+    lc = np.einsum("nij,nj->ni", R, np.asarray(x["light"].real, LD))
+    v = lc + t - q if light_type == 0 else lc
+    ell = v / np.sqrt((v * v).sum(1))[:, None]
+    cd = -q / np.sqrt((q * q).sum(1))[:, None]
+    ldn = (ell * nc).sum(1)
+    mt = 2 * ldn[:, None] * nc - ell
+    mu2 = (mt * mt).sum(1)
+    s = (mt * cd).sum(1) / np.sqrt(np.where(mu2 > 0, mu2, 1))
+    ph = np.asarray(x["phong"].real, LD)
+    kd = np.asarray(x["kd"].real, LD)
+    col = np.where(ldn > 0, kd * ldn, 0) + np.where((mu2 > 0) & (s > 0), ph[:, 1] * np.where(s > 0, s, 1) ** ph[:, 2], 0)
+    return dict(ldn=ldn, mu2=mu2, s=s, col=col)
+
+
+def phong_observation_rows(cam, poses, points, normals, obs_pose, obs_point, obs_uvd, stiffness, lighting, huber_a=0.0,
+                           shared_free=0, dtype=LD, phong=None):
+    """The seven rows of every observation of a config-3 problem (stereo 3 with the Huber corrector, intensity 1, normal
+    3), as SchurSystem takes them: r (N,7), Jp (N,7,6), Jl (N,7,6) = [position | normal], and the border Jb (N,7,nb) of the
+    free shared blocks in the order of np_reference.phong_lm_step and ssba_border_system: light 3, Phong 3M, textures M.
+    With the rounding magnitudes rabs, Jpa, Jla, Jba of the rows (stereo_rows; phong_rows).  `phong`: the "phong" entry of
+    an earlier call on the same observations (the lighting rows do not depend on the loss or on which blocks are free)."""
+    k, j = np.asarray(obs_pose, np.int64), np.asarray(obs_point, np.int64)
+    lt = lighting
+    st = stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a, dtype)
+    mat = np.asarray(lt["material_of_point"], np.int64)[j]
+    ph = phong if phong is not None else phong_rows(lt["light_type"], np.asarray(poses)[k], np.asarray(points)[j], np.asarray(normals)[j],
+                    np.asarray(lt["phong"])[mat], np.asarray(lt["texture"])[mat], lt["light"], lt["intensity"],
+                    lt["int_stiffness"], lt["normal_obs"], lt["normal_stiffness"], dtype)
+    N = k.shape[0]
+    M = len(lt["texture"])
+    r = np.zeros((N, 7), dtype=dtype)
+    Jp, Jl = np.zeros((N, 7, 6), dtype=dtype), np.zeros((N, 7, 6), dtype=dtype)
+    rabs, Jpa, Jla = np.zeros((N, 7)), np.zeros((N, 7, 6)), np.zeros((N, 7, 6))
+    r[:, :3], Jp[:, :3], Jl[:, :3, :3] = st["r"], st["Jp"], st["Jl"]
+    rabs[:, :3], Jpa[:, :3], Jla[:, :3, :3] = st["rabs"], st["Jpa"], st["Jla"]
+    r[:, 3], Jp[:, 3], Jl[:, 3] = ph["r_int"], ph["J_int"][:, :6], ph["J_int"][:, 6:12]
+    rabs[:, 3], Jpa[:, 3], Jla[:, 3] = ph["mag_r_int"], ph["mag_J_int"][:, :6], ph["mag_J_int"][:, 6:12]
+    r[:, 4:], Jp[:, 4:], Jl[:, 4:, 3:] = ph["r_nrm"], ph["J_np"], ph["J_nn"]
+    rabs[:, 4:], Jpa[:, 4:], Jla[:, 4:, 3:] = ph["mag_r_nrm"], ph["mag_J_np"], ph["mag_J_nn"]
+    cols = []
+    if shared_free & 1:
+        cols += [(np.zeros(N, np.int64) + c, 16 + c) for c in range(3)]
+    nb = 3 if shared_free & 1 else 0
+    if shared_free & 2:
+        cols += [(nb + 3 * mat + c, 12 + c) for c in range(3)]
+        nb += 3 * M
+    if shared_free & 4:
+        cols += [(nb + mat, 15)]
+        nb += M
+    Jb, Jba = np.zeros((N, 7, nb), dtype=dtype), np.zeros((N, 7, nb))
+    for col, src in cols:
+        Jb[np.arange(N), 3, col] = ph["J_int"][:, src]
+        Jba[np.arange(N), 3, col] = ph["mag_J_int"][:, src]
+    return dict(cost=st["cost"] + LD(0.5) * ((r[:, 3:] ** 2).sum()), r=r, Jp=Jp, Jl=Jl, rabs=rabs, Jpa=Jpa, Jla=Jla,
+                Jb=Jb, Jba=Jba, phong=ph)
+
+
 # ------------------------------------------------------------------------------------------------------------ Schur assembly
 def inv3(V):
     """Inverses of a stack of 3x3 matrices by the adjugate (numpy.linalg does not take long double)."""
@@ -106,6 +382,22 @@ def inv3(V):
                   d * h - e * g, b * g - a * h, a * e - b * d], 1).reshape(-1, 3, 3)
     det = a * C[:, 0, 0] + b * C[:, 1, 0] + c * C[:, 2, 0]
     return C / det[:, None, None]
+
+
+def inv_spd(V):
+    """Inverses of a stack of symmetric positive definite matrices by Cholesky, in the dtype of V (long double)."""
+    n = V.shape[-1]
+    Lf = np.zeros_like(V)
+    for i in range(n):
+        for j in range(i + 1):
+            t = V[:, i, j] - (Lf[:, i, :j] * Lf[:, j, :j]).sum(1)
+            Lf[:, i, j] = np.sqrt(t) if i == j else t / Lf[:, j, j]
+    Li = np.zeros_like(V)                     # L^-1 by forward substitution
+    for i in range(n):
+        Li[:, i, i] = 1 / Lf[:, i, i]
+        for j in range(i):
+            Li[:, i, j] = -(Lf[:, i, j:i] * Li[:, j:i, j]).sum(1) / Lf[:, i, i]
+    return np.einsum("nki,nkj->nij", Li, Li)
 
 
 def _segments(keys):
@@ -154,8 +446,10 @@ class SchurSystem:
         gl = np.add.reduceat(g_i[order], st, axis=0)
         hl = np.diagonal(V, axis1=1, axis2=2).copy()
         sl = LD(1) / (LD(1) + np.sqrt(hl))
-        V[:, [0, 1, 2], [0, 1, 2]] += _damping(hl, sl, radius)
-        Vinv = inv3(V)
+        d = Jl.shape[-1]
+        self.d = d
+        V[:, range(d), range(d)] += _damping(hl, sl, radius)
+        Vinv = inv3(V) if d == 3 else inv_spd(V)
         self.V, self.Vinv, self.gl = V, Vinv, gl
         slot = np.full(num_points, -1, np.int64)
         slot[self.lm] = np.arange(self.lm.shape[0])
@@ -204,7 +498,7 @@ class SchurSystem:
         # rhs: rhs = -(g_p - sum W V^-1 g_l)
         rl = np.zeros((nf, 6), dtype=LD)
         rla = np.zeros((nf, 6))
-        gla = np.zeros((self.lm.shape[0], 3))
+        gla = np.zeros((self.lm.shape[0], d))
         np.add.at(gla, s_of, np.einsum("nai,na->ni", Jla, rabs))
         obs_f = np.flatnonzero(fr)
         if obs_f.size:
@@ -256,6 +550,60 @@ class SchurSystem:
         self.E_rhs = (m_rhs + C_TERMS) * U * (gpa + rla).reshape(n)
         self.rows = rows
         self._k, self._j, self._f = k, j, f
+        self.nb = 0
+        if "Jb" in rows and rows["Jb"].shape[-1]:
+            self._border(rows, radius, X, Xa, Via, gla, fr, m_rhs)
+
+    def _border(self, rows, radius, X, Xa, Via, gla, fr, m_rhs):
+        """The border of free shared columns (light 3, Phong 3M, textures M: np_reference.phong_lm_step's order):
+            S_pb = A_pb - sum_j W_j V_j^-1 Y_j^T,  S_bb = A_bb + D_b - sum_j Y_j V_j^-1 Y_j^T,
+            rhs_b = -(g_b - sum_j Y_j V_j^-1 g_l,j),  Y_j = sum over the observations of j of J_b^T J_l,
+        damped as ssba_border_system reports it: the Jacobi scale s_b = 1 / (1 + sqrt(diag A_bb)) of the undamped border
+        diagonal and D_b = clamp(h s_b^2, 1e-6, 1e32) / (radius s_b^2).  E extends to the border as to S: every border entry
+        sums over all observations and landmarks, so m = N + L there."""
+        Jb, Jba, Jl, Jla, Jp, Jpa, r, rabs = (rows[k] for k in ("Jb", "Jba", "Jl", "Jla", "Jp", "Jpa", "r", "rabs"))
+        nb, nf, L = Jb.shape[-1], self.nf, self.lm.shape[0]
+        self.nb = nb
+        so = self.slot_of_obs
+        Y = np.zeros((L, nb, self.d), dtype=LD)
+        Ya = np.zeros((L, nb, self.d))
+        np.add.at(Y, so, np.einsum("nab,nai->nbi", Jb, Jl))
+        np.add.at(Ya, so, np.einsum("nab,nai->nbi", Jba, Jla))
+        self.Y = Y
+        A_bb = np.einsum("nab,nac->bc", Jb, Jb)
+        A_bba = np.einsum("nab,nac->bc", Jba, Jba)
+        g_b = np.einsum("nab,na->b", Jb, r)
+        g_ba = np.einsum("nab,na->b", Jba, rabs)
+        hb = np.diagonal(A_bb).copy()
+        self.sb = LD(1) / (LD(1) + np.sqrt(hb))
+        Db = _damping(hb, self.sb, radius)
+        YVi = np.einsum("lbi,lij->lbj", Y, self.Vinv)
+        YVia = np.einsum("lbi,lij->lbj", Ya, Via * self.kappa_V[:, None, None])
+        self.S_bb = A_bb + np.diag(Db) - np.einsum("lbj,lcj->bc", YVi, Y)
+        self.rhs_b = -(g_b - np.einsum("lbj,lj->b", YVi, self.gl))
+        S_pb = np.zeros((nf, 6, nb), dtype=LD)
+        S_pba = np.zeros((nf, 6, nb))
+        fo = np.flatnonzero(fr)
+        fk = self._f[fo]
+        np.add.at(S_pb, fk, np.einsum("nai,nab->nib", Jp[fo], Jb[fo]) - np.einsum("nij,nbj->nib", X[fo], Y[so[fo]]))
+        np.add.at(S_pba, fk, np.einsum("nai,nab->nib", Jpa[fo], Jba[fo]) + np.einsum("nij,nbj->nib", Xa[fo], Ya[so[fo]]))
+        self.S_pb = S_pb.reshape(6 * nf, nb)
+        m = float(Jb.shape[0] + L + C_TERMS)
+        self.E_bb = m * U * (A_bba + np.diag(np.asarray(Db, np.float64)) + np.einsum("lbj,lcj->bc", YVia, Ya))
+        self.E_pb = m * U * S_pba.reshape(6 * nf, nb)
+        self.E_rhs_b = m * U * (g_ba + np.einsum("lbj,lj->b", YVia, gla))
+
+    def border_excess(self, S_pb, S_bb, rhs_b):
+        """max |dev - truth| / E over S_pb, S_bb and rhs_b (<= 1 passes)."""
+        out = []
+        for dev, ref, E in ((S_pb, self.S_pb, self.E_pb), (S_bb, self.S_bb, self.E_bb), (rhs_b, self.rhs_b, self.E_rhs_b)):
+            dd = np.abs(np.asarray(np.asarray(dev, LD) - ref, np.float64))
+            out.append(float((dd / np.maximum(E, 1e-300)).max()))
+        return tuple(out)
+
+    def bordered(self):
+        """[S S_pb; S_pb^T S_bb] and [rhs; rhs_b] as dense long-double arrays."""
+        return (np.block([[self.dense(), self.S_pb], [self.S_pb.T, self.S_bb]]), np.concatenate([self.rhs, self.rhs_b]))
 
     # ---- views
     def dense(self, dtype=LD):
@@ -295,20 +643,25 @@ class SchurSystem:
         return worst, float((d / np.maximum(self.E_rhs, 1e-300)).max())
 
     # ---- back-substitution and the model cost change from a given pose step
-    def back_substitute(self, dp_free):
-        """delta_l = V^-1 (-g_l - W^T delta_p) in long double from the free-pose step (nf*6); (landmarks present, 3)."""
+    def back_substitute(self, dp_free, db=None):
+        """delta_l = V^-1 (-g_l - W^T delta_p - Y^T delta_b) in long double from the free-pose step (nf*6) and the border
+        step; (landmarks present, d)."""
         x = np.asarray(dp_free, LD).reshape(-1, 6)
-        Wt = np.zeros((self.lm.shape[0], 3), dtype=LD)
+        Wt = np.zeros((self.lm.shape[0], self.d), dtype=LD)
+        if self.nb:
+            Wt += np.einsum("lbi,b->li", self.Y, np.asarray(db, LD))
         fr = self._f >= 0
         np.add.at(Wt, self.slot_of_obs[fr], np.einsum("nij,ni->nj", self.W[fr], x[self._f[fr]]))
         return np.einsum("nij,nj->ni", self.Vinv, -self.gl - Wt)
 
-    def model_cost_change(self, dp_free, dl_present):
+    def model_cost_change(self, dp_free, dl_present, db=None):
         """-J delta . (r + J delta / 2) in long double and the magnitude sum of its terms."""
         x = np.asarray(dp_free, LD).reshape(-1, 6)
         y = np.asarray(dl_present, LD)
         fr = self._f >= 0
         Jd = np.einsum("nai,ni->na", self.rows["Jl"], y[self.slot_of_obs])
+        if self.nb:
+            Jd += np.einsum("nab,b->na", self.rows["Jb"], np.asarray(db, LD))
         Jd[fr] += np.einsum("nai,ni->na", self.rows["Jp"][fr], x[self._f[fr]])
         r = self.rows["r"]
         terms = -(Jd * (r + LD(0.5) * Jd))

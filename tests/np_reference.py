@@ -299,50 +299,66 @@ def se3_complex_step_jacobian(fun, T, h=1e-30):
 
 
 # ---- Phong lighting rows: forward formulas only (complex-step differentiable) ----------------
+# They take one observation (1-D vectors) or a stack of them (leading dimensions), and `dtype`: complex (the fp64 complex
+# step) or np.clongdouble (the long-double reference, tests/hp_reference.py).  The one-observation fp64 path is the original
+# arithmetic, bit for bit.  `pert(name, value)`, when given, returns a replacement for the intermediate unit vectors
+# (nc, ell, cd, m) and for q: hp_reference perturbs them to measure how the rows depend on their rounding.
+def _dot(a, b):
+    return a @ b if a.ndim == 1 else (a * b).sum(-1)
+
+
+def _mv(R, p):
+    return R @ p if R.ndim == 2 else np.einsum("...ij,...j->...i", R, p)
+
+
 def _fmax0(col):      # utils/utils.hpp:16-19 with a = 0
-    return 0.0 * col if 0.0 >= col.real else col
+    return np.where(0.0 >= col.real, 0.0 * col, col)
 
 
 def _fmin1(col):      # utils/utils.hpp:22-25 with a = 1
-    return 1.0 + 0.0 * col if 1.0 <= col.real else col
+    return np.where(1.0 <= col.real, 1.0 + 0.0 * col, col)
 
 
-def phong_shade(nc, ell, cd, kd, ks, alpha):
+def phong_shade(nc, ell, cd, kd, ks, alpha, dtype=complex, pert=None):
     """lighting/phong.hpp:25-51,59-104,136-139 (ambient = 0)."""
-    nc, ell, cd = (np.asarray(v, dtype=complex) for v in (nc, ell, cd))
-    diffuse = 0.0
-    ldn = ell @ nc
-    if np.all(np.isfinite(ell)) and not (ldn.real <= 0):
-        diffuse = kd * ldn
-    specular = 0.0
-    mt = 2 * ldn * nc - ell
-    if not ((mt @ mt).real <= 0):
-        m = mt / np.sqrt(mt @ mt)
-        s = m @ cd
-        if not (s.real <= 0):
-            specular = ks * s ** alpha
+    nc, ell, cd = (np.asarray(v, dtype=dtype) for v in (nc, ell, cd))
+    kd, ks, alpha = (np.asarray(v, dtype=dtype) for v in (kd, ks, alpha))
+    ldn = _dot(ell, nc)
+    lit = np.isfinite(ell).all(-1) & ~(ldn.real <= 0)
+    diffuse = np.where(lit, kd * ldn, 0.0)
+    mt = 2 * ldn[..., None] * nc - ell
+    mu2 = _dot(mt, mt)
+    seen = ~(mu2.real <= 0)
+    m = mt / np.sqrt(np.where(seen, mu2, 1.0))[..., None]
+    if pert is not None:
+        m = pert("m", m)
+    s = _dot(m, cd)
+    seen &= ~(s.real <= 0)
+    specular = np.where(seen, ks * np.where(seen, s, 1.0) ** alpha, 0.0)
     col = 1.0 * (0.0 + diffuse + specular) + 0j
     return _fmin1(_fmax0(col))
 
 
 def unit_vector_plus(x, delta):
     """perturbations.hpp:98-102"""
-    y = x + delta - (delta @ x) / (x @ x) * x
-    return y / np.sqrt(y @ y)
+    y = x + delta - (_dot(delta, x) / _dot(x, x))[..., None] * x
+    return y / np.sqrt(_dot(y, y))[..., None]
 
 
-def intensity_residual(light_type, T, p, n, phong, kd, light, colour, stiffness):
+def intensity_residual(light_type, T, p, n, phong, kd, light, colour, stiffness, dtype=complex, pert=None):
     """intensity_error_point_light.hpp:24-96 / intensity_error_directional_light.hpp:24-96"""
-    t, R = T[:3], T[3:].reshape(3, 3)
-    q, nc = R @ p + t, R @ n
+    t, R = T[..., :3], T[..., 3:].reshape(T.shape[:-1] + (3, 3))
+    keep = (lambda name, v: v) if pert is None else pert
+    q, nc = keep("q", _mv(R, p) + t), keep("nc", _mv(R, n))
     if light_type == 0:
-        v = (R @ light + t) - q                       # point_light.hpp:79-81
-        ell = v / np.sqrt(v @ v)
+        v = (_mv(R, light) + t) - q                    # point_light.hpp:79-81
+        ell = v / np.sqrt(_dot(v, v))[..., None]
     else:
-        d = R @ light                                 # directional_light.hpp:32-35 normalises
-        ell = d / np.sqrt(d @ d)
-    cd = -q / np.sqrt(q @ q)
-    return stiffness * (phong_shade(nc, ell, cd, kd, phong[1], phong[2]) - colour)
+        d = _mv(R, light)                              # directional_light.hpp:32-35 normalises
+        ell = d / np.sqrt(_dot(d, d))[..., None]
+    cd = -q / np.sqrt(_dot(q, q))[..., None]
+    ell, cd = keep("ell", ell), keep("cd", cd)
+    return stiffness * (phong_shade(nc, ell, cd, kd, phong[..., 1], phong[..., 2], dtype, pert) - colour)
 
 
 def intensity_jacobian_complex_step(light_type, T, p, n, phong, kd, light, colour, stiffness, h=1e-30):

@@ -223,17 +223,23 @@ def _check_against_truth(tag, sy, S, rhs, dp, dl, mcc, fidx, prob_points):
     ex_S, ex_rhs = sy.assembly_excess(S, rhs)
     _report(tag + " assembly", S_over_E=ex_S, rhs_over_E=ex_rhs)
     assert ex_S <= 1.0 and ex_rhs <= 1.0, (tag, ex_S, ex_rhs)
+    _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points)
+
+
+def _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points, db=None):
     x = dp[fidx >= 0].ravel()
     # delta_l from the device's own delta_p, per landmark within (t_j + c) u kappa(V_j) |V^-1| (|J_l|^T |r| + |J_l|^T |J_p| |delta_p|)
     # -- the device forms W^T delta_p as J_l^T (J_p delta_p) from re-linearised rows (k_backsub_eval), so the magnitudes are those
     # of the rows (Jla, Jpa, rabs: hp_reference.stereo_rows), not of |W| -- plus 2 u (|p_j| + |delta_l,j|): the hook reports
     # delta_l as fl(p + delta_l) - p (candidate minus current point)
-    dl_ref = sy.back_substitute(x)
+    dl_ref = sy.back_substitute(x, db)
     rows, fr, so = sy.rows, sy._f >= 0, sy.slot_of_obs
-    gla = np.zeros((sy.lm.shape[0], 3))
+    gla = np.zeros((sy.lm.shape[0], sy.d))
     np.add.at(gla, so, np.einsum("nai,na->ni", rows["Jla"], rows["rabs"]))
     jdp = np.einsum("naj,nj->na", rows["Jpa"][fr], np.abs(x.reshape(-1, 6))[sy._f[fr]])
     np.add.at(gla, so[fr], np.einsum("nai,na->ni", rows["Jla"][fr], jdp))
+    if sy.nb:       # the border step enters as J_l^T (J_b delta_b)
+        np.add.at(gla, so, np.einsum("nai,na->ni", rows["Jla"], np.einsum("nab,b->na", rows["Jba"], np.abs(db))))
     mag = np.einsum("nij,nj->ni", np.abs(np.asarray(sy.Vinv, np.float64)), gla).max(1)
     t = np.bincount(sy.slot_of_obs, minlength=sy.lm.shape[0])
     pts = np.abs(prob_points[sy.lm]).max(1)
@@ -241,7 +247,7 @@ def _check_against_truth(tag, sy, S, rhs, dp, dl, mcc, fidx, prob_points):
     err = np.abs(np.asarray(np.asarray(dl[sy.lm], hp.LD) - dl_ref, np.float64)).max(1)
     _report(tag + " back-substitution", worst_over_bound=float((err / bound).max()))
     assert np.all(err <= bound), (tag, float((err / bound).max()))
-    mref, mag_m, nt = sy.model_cost_change(x, dl[sy.lm])
+    mref, mag_m, nt = sy.model_cost_change(x, dl[sy.lm], db)
     mb = (nt + hp.C_TERMS) * hp.U * mag_m
     _report(tag + " model cost change", err=abs(mcc - float(mref)), bound=mb)
     assert abs(mcc - float(mref)) <= mb

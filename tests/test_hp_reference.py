@@ -178,3 +178,266 @@ def test_oracle_with_sun_and_prior_blocks_satisfies_the_derived_bounds(radius):
         cov = np.asarray(cov, np.float64)
         bound = hp.covariance_bound(np.asarray(S_ld, np.float64), E, f, kap, cov)
         assert np.all(np.abs(inv2[6 * f: 6 * f + 6, 6 * f: 6 * f + 6] - cov) <= bound)
+
+
+# ---- the device's intensity row (ssba_phong_device.h intensity_residual) in fp64 numpy, for the checks that the bars reject
+# ---- a plausible kernel error
+RSQ_EST = 2.0 ** -23      # modelled error of the f64 reciprocal(-square-root) estimates: the ISA gives them 2^29 ulp
+
+
+def _rsqrt(a, newton):
+    r = (1.0 / np.sqrt(a)) * (1 + RSQ_EST)          # the estimate at its worst
+    for _ in range(newton):
+        r = r * (1.5 - 0.5 * a * r * r)
+    return r
+
+
+def _rcp(a, newton):
+    r = (1.0 / a) * (1 + RSQ_EST)
+    for _ in range(newton):
+        r = r + (1.0 - a * r) * r
+    return r
+
+
+def _dot3(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+def _neg_skew(g, a):
+    return np.stack([-g[:, 1] * a[:, 2] + g[:, 2] * a[:, 1], g[:, 0] * a[:, 2] - g[:, 2] * a[:, 0], -g[:, 0] * a[:, 1] + g[:, 1] * a[:, 0]], 1)
+
+
+def _device_intensity(light_type, T, p, n, phong, kd, light, colour, stiffness, newton=2, pow_alpha=None):
+    """ssba_phong_device.h intensity_residual in fp64 numpy (one lane per row)."""
+    T, p, n = (np.asarray(v, np.float64) for v in (T, p, n))
+    N = T.shape[0]
+    R = T[:, 3:].reshape(N, 3, 3)
+    light = np.broadcast_to(np.asarray(light, np.float64), (N, 3))
+    rs = lambda a: _rsqrt(a, newton)
+    q = np.stack([R[:, i, 0] * p[:, 0] + R[:, i, 1] * p[:, 1] + R[:, i, 2] * p[:, 2] + T[:, i] for i in range(3)], 1)
+    nc = np.stack([R[:, i, 0] * n[:, 0] + R[:, i, 1] * n[:, 1] + R[:, i, 2] * n[:, 2] for i in range(3)], 1)
+    lc = np.stack([R[:, i, 0] * light[:, 0] + R[:, i, 1] * light[:, 1] + R[:, i, 2] * light[:, 2] + (T[:, i] if light_type == 0 else 0.0) for i in range(3)], 1)
+    v = lc - q if light_type == 0 else lc
+    rrho, rqn = rs(_dot3(v, v)), rs(_dot3(q, q))
+    ell, cd = v * rrho[:, None], -q * rqn[:, None]
+    kd, ks, alpha = np.asarray(kd, np.float64), phong[:, 1], phong[:, 2]
+    g_ell, g_nc, g_cd, mat = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((N, 3))
+    ldn = _dot3(ell, nc)
+    lit = ldn > 0
+    diffuse = np.where(lit, kd * ldn, 0.0)
+    g_ell += np.where(lit[:, None], kd[:, None] * nc, 0.0)
+    g_nc += np.where(lit[:, None], kd[:, None] * ell, 0.0)
+    mat[:, 0] = np.where(lit, ldn, 0.0)
+    mt = 2.0 * ldn[:, None] * nc - ell
+    mu2 = _dot3(mt, mt)
+    seen = mu2 > 0
+    rmu = rs(np.where(seen, mu2, 1.0))
+    m = mt * rmu[:, None]
+    s = _dot3(m, cd)
+    spec = seen & (s > 0)
+    ss = np.where(spec, s, 1.0)
+    ls = np.log(ss)
+    sa = np.exp(alpha * ls) if pow_alpha is None else ss ** pow_alpha(alpha)
+    specular = np.where(spec, ks * sa, 0.0)
+    gs = ks * alpha * (sa * _rcp(ss, newton))
+    w = (cd - m * ss[:, None]) * rmu[:, None]
+    nw = _dot3(nc, w)
+    sp = spec[:, None]
+    g_ell += np.where(sp, gs[:, None] * (2.0 * nc * nw[:, None] - w), 0.0)
+    g_nc += np.where(sp, gs[:, None] * 2.0 * (ldn[:, None] * w + ell * nw[:, None]), 0.0)
+    g_cd += np.where(sp, gs[:, None] * m, 0.0)
+    mat[:, 1] = np.where(spec, sa, 0.0)
+    mat[:, 2] = np.where(spec, ks * sa * ls, 0.0)
+    col = 1.0 * (0.0 + diffuse + specular)
+    cl = (0.0 >= col) | (1.0 <= col)
+    col = np.clip(col, 0.0, 1.0)
+    for g in (g_ell, g_nc, g_cd, mat):
+        g[cl] = 0.0
+    r = stiffness * (col - colour)
+    le, ce = _dot3(ell, g_ell), _dot3(cd, g_cd)
+    gv = (g_ell - ell * le[:, None]) * rrho[:, None]
+    gc = -(g_cd - cd * ce[:, None]) * rqn[:, None]
+    g_q = gc - (gv if light_type == 0 else 0.0)
+    J = np.zeros((N, 19))
+    J[:, 0:3] = stiffness * (g_q + (gv if light_type == 0 else 0.0))
+    J[:, 3:6] = stiffness * (_neg_skew(g_q, q) + _neg_skew(g_nc, nc) + _neg_skew(gv, lc))
+    J[:, 6:9] = stiffness * np.einsum("ni,nij->nj", g_q, R)
+
+    def unit_plus(g, x):
+        inv = rs(_dot3(x, x))
+        gx = _dot3(g, x) * inv * inv
+        return (g - gx[:, None] * x) * inv[:, None]
+    J[:, 9:12] = stiffness * unit_plus(np.einsum("ni,nij->nj", g_nc, R), n)
+    J[:, 13], J[:, 14], J[:, 15] = stiffness * mat[:, 1], stiffness * mat[:, 2], stiffness * mat[:, 0]
+    t3 = np.einsum("ni,nij->nj", gv, R)
+    J[:, 16:19] = stiffness * (t3 if light_type == 0 else unit_plus(t3, light))
+    return r, J
+
+
+def _phong_batch(light_type, seed=7, P=8, L=60):
+    prob, ph = synth.make_phong_problem(P, L, track_len=5, seed=seed, light_type=light_type)
+    d = ph.as_oracle_dict("perturbed")
+    k, j = prob.obs_pose.astype(np.int64), prob.obs_point.astype(np.int64)
+    m = np.asarray(d["material_of_point"], np.int64)[j]
+    args = (light_type, prob.poses_init[k], prob.points_init[j], d["normals"][j], d["phong"][m], d["texture"][m], d["light"],
+            d["intensity"], d["int_stiffness"])
+    return args, d["normal_obs"], d["normal_stiffness"]
+
+
+def _row_excess(rows, r, J):
+    """max |value - truth| / (C_ROW u mag) over the intensity residuals and over the Jacobian entries."""
+    er = np.abs(np.asarray(np.asarray(r, hp.LD) - rows["r_int"], np.float64)) / np.maximum(hp.C_ROW * hp.U * rows["mag_r_int"], 1e-300)
+    eJ = np.abs(np.asarray(np.asarray(J, hp.LD) - rows["J_int"], np.float64)) / np.maximum(hp.C_ROW * hp.U * rows["mag_J_int"], 1e-300)
+    return float(er.max()), float(eJ.max())
+
+
+@pytest.mark.parametrize("light_type", [0, 1])
+def test_long_double_phong_rows_in_fp64_mode_match_complex_step_and_the_oracle(light_type):
+    """phong_rows in fp64 mode is np_reference's complex step, vectorised: the same values to a few ulps of the row's
+    magnitude; the long-double rows match the oracle's closed forms within the same row bar."""
+    args, nobs, Sn = _phong_batch(light_type)
+    r64 = hp.phong_rows(*args, nobs, Sn, dtype=np.float64, mags=False)
+    ld = hp.phong_rows(*args, nobs, Sn)
+    N = args[1].shape[0]
+    for i in range(N):
+        a = tuple(v[i] if np.ndim(v) and np.shape(v)[0] == N else v for v in args)
+        r1 = npr.intensity_residual(*a).real
+        J1 = npr.intensity_jacobian_complex_step(*a)
+        assert abs(r64["r_int"][i] - r1) <= 4 * hp.U * ld["mag_r_int"][i]
+        np.testing.assert_array_less(np.abs(r64["J_int"][i] - J1), 4 * hp.U * ld["mag_J_int"][i] + 1e-300)
+        r2, J2 = orc.intensity_residual(*a, jac=True)
+        rn, Jnp, Jnn = orc.normal_residual(a[1], a[3], nobs[i], Sn, jac=True)
+        assert abs(r2 - float(ld["r_int"][i])) <= hp.C_ROW * hp.U * ld["mag_r_int"][i]
+        np.testing.assert_array_less(np.abs(J2 - np.asarray(ld["J_int"][i], np.float64)), hp.C_ROW * hp.U * ld["mag_J_int"][i] + 1e-300)
+        np.testing.assert_array_less(np.abs(rn - np.asarray(ld["r_nrm"][i], np.float64)), hp.C_ROW * hp.U * ld["mag_r_nrm"][i] + 1e-300)
+        np.testing.assert_array_less(np.abs(Jnp - np.asarray(ld["J_np"][i], np.float64)), hp.C_ROW * hp.U * ld["mag_J_np"][i] + 1e-300)
+        np.testing.assert_array_less(np.abs(Jnn - np.asarray(ld["J_nn"][i], np.float64)), hp.C_ROW * hp.U * ld["mag_J_nn"][i] + 1e-300)
+
+
+def test_long_double_phong_rows_reproduce_the_light_test_answers():
+    """The reference's light_test scene (test_oracle_phong): shade 0.27697118 (diffuse only) and 0.48917229."""
+    from test_oracle_phong import ALPHA, KD, KS, LIGHT, V28, V245
+    T = np.concatenate([np.zeros(3), np.eye(3).ravel()])[None].repeat(2, 0)
+    p = np.stack([V28[0], V245[0]])
+    n = np.stack([V28[1], V245[1]])
+    rows = hp.phong_rows(0, T, p, n, np.array([[0.1, KS, ALPHA]] * 2), np.full(2, KD), LIGHT, np.zeros(2), 1.0,
+                         np.zeros((2, 3)), np.eye(3), mags=False)
+    np.testing.assert_allclose(np.asarray(rows["r_int"], np.float64), [0.27697118, 0.48917229], atol=5e-9)
+
+
+@pytest.mark.parametrize("light_type", [0, 1])
+@pytest.mark.parametrize("seed", [7, 3])
+def test_device_arithmetic_meets_the_row_bar_and_plausible_errors_do_not(light_type, seed):
+    """The device's intensity row, restated in fp64 numpy, is within C_ROW u mag of the long-double row; the same row with
+    ONE Newton step on the hardware rsqrt / rcp estimates (modelled at their 2^-23 worst), or with the specular term
+    computed as pow(s, float32(alpha)), is rejected by more than a factor 10.  With one Newton step the residual itself
+    is off by only ~5x its bar: it meets the rsqrt error once, in the normalisation of ell and cd, where the Jacobian meets
+    it two or three times over (ell and g_v, cd and g_c, the unit-vector projection) -- the Jacobian carries the check."""
+    args, nobs, Sn = _phong_batch(light_type, seed)
+    rows = hp.phong_rows(*args, nobs, Sn)
+    er, eJ = _row_excess(rows, *_device_intensity(*args))
+    assert er <= 1.0 and eJ <= 1.0, (er, eJ)
+    er1, eJ1 = _row_excess(rows, *_device_intensity(*args, newton=1))
+    assert eJ1 > 10 and er1 > 2, (er1, eJ1)
+    erp, eJp = _row_excess(rows, *_device_intensity(*args, pow_alpha=lambda a: a.astype(np.float32).astype(np.float64)))
+    assert erp > 10 and eJp > 10, (erp, eJp)
+
+
+# ---- the long-double reduced system with 6-D landmarks and the border of free shared blocks -----------------------------
+def _phong_system(light_type, shared_free, radius, huber=0.0, seed=7):
+    prob, ph = synth.make_phong_problem(8, 60, track_len=5, seed=seed, light_type=light_type)
+    d = ph.as_oracle_dict("perturbed" if shared_free else "truth")
+    rows = hp.phong_observation_rows(prob.camera, prob.poses_init, prob.points_init, d["normals"], prob.obs_pose, prob.obs_point,
+                                     prob.obs_uvd, prob.stiffness(), d, huber, shared_free)
+    fidx = hp.free_index(prob.num_poses, prob.obs_pose, np.eye(1, prob.num_poses, 0, dtype=bool)[0])
+    sy = hp.SchurSystem(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, radius)
+    return prob, d, sy, fidx
+
+
+def _solve_bordered(sy):
+    A, b = sy.bordered() if sy.nb else (sy.dense(), sy.rhs)
+    x, _ = hp.refined_solve(A, b)
+    return x[: sy.n], x[sy.n:]
+
+
+@pytest.mark.parametrize("light_type", [0, 1])
+@pytest.mark.parametrize("shared_free,nb", [(0, 0), (1, 3), (4, 4), (6, 16), (7, 19)])
+def test_long_double_bordered_step_matches_the_sparse_phong_step(light_type, shared_free, nb):
+    """The long-double reduced system, solved and back-substituted, is np_reference.phong_lm_step's direct sparse solve of
+    the whole damped system (complex-step rows through Plus) to the fp64 level: pose, landmark and border steps and the
+    model cost change."""
+    for radius in (1e4, 3.0):
+        prob, d, sy, fidx = _phong_system(light_type, shared_free, radius)
+        assert sy.nb == nb and sy.d == 6
+        x, db = _solve_bordered(sy)
+        dl = sy.back_substitute(x, db)
+        mcc, _, _ = sy.model_cost_change(x, dl, db)
+        out = npr.phong_lm_step(prob.camera, prob.poses_init, prob.points_init, d["normals"], prob.obs_pose, prob.obs_point,
+                                prob.obs_uvd, prob.stiffness(), d, radius, shared_free=shared_free)
+        assert hp.forward_error(out[0][1:].ravel(), x) < 1e-10
+        assert hp.forward_error(out[1][sy.lm].ravel(), dl.ravel()) < 1e-10
+        assert float(mcc) == pytest.approx(out[2], rel=1e-10)
+        if nb:
+            assert hp.forward_error(out[4], db) < 1e-10
+
+
+@pytest.mark.parametrize("light_type", [0, 1])
+@pytest.mark.parametrize("shared_free", [0, 7])
+def test_oracle_phong_reduced_system_is_within_the_assembly_bound(light_type, shared_free):
+    prob, d, sy, fidx = _phong_system(light_type, shared_free, 5.0)
+    op = orc.OracleProblem(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd,
+                           prob.stiffness(), lighting=d, shared_free=shared_free)
+    A, b, _ = op.reduced_system(5.0)
+    n = sy.n
+    ex_S, ex_rhs = sy.assembly_excess(A[:n, :n], b[:n])
+    assert ex_S <= 1.0 and ex_rhs <= 1.0, (ex_S, ex_rhs)
+    if shared_free:
+        assert max(sy.border_excess(A[:n, n:], A[n:, n:], b[n:])) <= 1.0
+
+
+def test_assembly_and_border_bars_reject_plausible_kernel_errors():
+    """One plausible kernel error at a time, on a copy of the long-double answer; each is rejected by more than 10x:
+    one landmark's Schur term left out of S, one observation's texture column left out of S_pb, the light columns'
+    gradient left out of rhs_b, and a delta_l whose normal rows are ignored."""
+    prob, d, sy, fidx = _phong_system(0, 7, 5.0)
+    n = sy.n
+    S = np.asarray(sy.dense(), np.float64)
+    # (1) S without the Schur term of the landmark with the most free observations
+    so, fr = sy.slot_of_obs, sy._f >= 0
+    obs0 = np.flatnonzero((so == np.bincount(so[fr]).argmax()) & fr)
+    assert obs0.size >= 3
+    X = np.einsum("nij,njk->nik", sy.W, sy.Vinv[so])
+    S1 = np.asarray(sy.dense(), hp.LD)
+    for a in obs0:
+        for b in obs0:
+            fa, fb = sy._f[a], sy._f[b]
+            S1[6 * fa: 6 * fa + 6, 6 * fb: 6 * fb + 6] += X[a] @ sy.W[b].T
+    assert sy.assembly_excess(np.asarray(S1, np.float64), np.asarray(sy.rhs, np.float64))[0] > 10
+    assert sy.assembly_excess(S, np.asarray(sy.rhs, np.float64))[0] <= 1.0
+    # (2) S_pb without observation i's texture column (the last M columns; the observation's material)
+    i = int(np.flatnonzero(fr)[3])
+    M = len(d["texture"])
+    c = sy.nb - M + int(d["material_of_point"][prob.obs_point[i]])
+    Spb = np.asarray(sy.S_pb, hp.LD).copy()
+    Jp, Jb = sy.rows["Jp"][i], sy.rows["Jb"][i]
+    Spb[6 * sy._f[i]: 6 * sy._f[i] + 6, c] -= Jp.T @ Jb[:, c]
+    ok = sy.border_excess(np.asarray(sy.S_pb, np.float64), np.asarray(sy.S_bb, np.float64), np.asarray(sy.rhs_b, np.float64))
+    assert max(ok) <= 1.0
+    assert sy.border_excess(np.asarray(Spb, np.float64), sy.S_bb, sy.rhs_b)[0] > 10
+    # (3) rhs_b without the light columns' gradient
+    g_light = np.einsum("na,na->", sy.rows["Jb"][:, :, 0], sy.rows["r"])
+    rb = np.asarray(sy.rhs_b, hp.LD).copy()
+    rb[:3] += np.einsum("nab,na->b", sy.rows["Jb"][:, :, :3], sy.rows["r"])
+    assert g_light != 0 and sy.border_excess(sy.S_pb, sy.S_bb, np.asarray(rb, np.float64))[2] > 10
+    # (4) delta_l from a system whose landmark blocks ignore the normal rows
+    x, db = _solve_bordered(sy)
+    dl = sy.back_substitute(x, db)
+    rows2 = dict(sy.rows)
+    for k in ("Jl", "Jla"):
+        rows2[k] = sy.rows[k].copy()
+        rows2[k][:, 4:] = 0
+    sy2 = hp.SchurSystem(rows2, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 5.0)
+    dl_bad = sy2.back_substitute(x, db)
+    err = np.abs(np.asarray(dl_bad - dl, np.float64)).max(1)
+    bound = (np.bincount(so, minlength=sy.lm.shape[0]) + hp.C_TERMS) * hp.U * sy.kappa_V * np.abs(np.asarray(dl, np.float64)).max(1)
+    assert (err / bound).max() > 10

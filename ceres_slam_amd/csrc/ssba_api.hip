@@ -2263,6 +2263,78 @@ int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius, double *
     return SSBA_OK;
 }
 
+// One dogleg step from scratch: the kernels of a solve iteration in its order (linearisation, Schur assembly damped at
+// radius 1 / mu, reduced solve with the border, launch_dogleg_eval stage 0), then the vectors and the scalar state copied out.
+int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, double mu, double *gn_p, double *gn_l, double *gn_b,
+                     double *v_p, double *v_l, double *v_b, double *scalars) {
+    if (!p || !(radius > 0.0) || !(mu > 0.0)) return SSBA_ERR_INVALID_ARGUMENT;
+    if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    ssba_options opt;
+    if (o) opt = *o; else ssba_default_options(&opt);
+    if (opt.dogleg_type != 0 && opt.dogleg_type != 1) return SSBA_ERR_INVALID_ARGUMENT;
+    opt.trust_region_strategy_type = 1;
+    if (p->d.cb) {      // as ssba_solve_begin: DOGLEG runs on the general path
+        int rc = refinalize_without_closure_border(p, "DOGLEG");
+        if (rc) return rc;
+    }
+    int rc = begin_hook(p, &opt, radius);      // (dl_reuse = 0: the step is computed from scratch)
+    if (rc) return rc;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    HIPCHECK(hipMemcpyAsync(reinterpret_cast<char *>(d.st) + offsetof(State, mu), &mu, sizeof mu, hipMemcpyHostToDevice, L.stream));
+    launch_linearize(L, d);
+    if (d.dense) launch_dense_schur(L, d); else launch_schur(L, d);
+    launch_finish_check(L, d);
+    if (d.dense) launch_dense_solve(L, d);
+    else { launch_bcr(L, d); if (d.nb) launch_border_solve(L, d); }
+    launch_dogleg_eval(L, d, 0);
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    rc = fetch_state(p);
+    if (rc) return rc;
+    const State &st = *p->h_state;
+    if (st.step_failed) return SSBA_ERR_NUMERICAL_FAILURE;
+    const int nf = d.nfree, ld = d.phong ? 6 : 3;
+    if (gn_p) {
+        std::vector<double> x((size_t)d.nf_pad * 6);
+        HIPCHECK(hipMemcpy(x.data(), d.x0, x.size() * sizeof(double), hipMemcpyDeviceToHost));
+        memset(gn_p, 0, (size_t)p->P * 6 * sizeof(double));
+        for (int f = 0; f < nf; ++f)
+            for (int c = 0; c < 6; ++c) gn_p[6 * (size_t)p->free_pose[f] + c] = x[6 * (size_t)f + c];
+    }
+    if (v_p && p->P) HIPCHECK(hipMemcpy(v_p, d.vp, (size_t)p->P * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t Lp = (size_t)d.Lpad;
+    for (int which = 0; which < 2; ++which) {
+        double *out = which ? v_l : gn_l;
+        if (!out) continue;
+        std::vector<double> a(Lp * ld);
+        HIPCHECK(hipMemcpy(a.data(), which ? d.vl : d.dl_gn, a.size() * sizeof(double), hipMemcpyDeviceToHost));
+        memset(out, 0, (size_t)p->L * ld * sizeof(double));
+        for (size_t l = 0; l < Lp; ++l) {
+            const uint32_t j = p->user_of_dev[l];
+            if (j == 0xFFFFFFFFu) continue;
+            for (int c = 0; c < ld; ++c) out[(size_t)ld * j + c] = a[c * Lp + l];
+        }
+    }
+    if ((gn_b || v_b) && d.nb) {
+        std::vector<double> bs((size_t)BS_COUNT);
+        HIPCHECK(hipMemcpy(bs.data(), d.bsys, bs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < d.nb; ++c) {
+            if (gn_b) gn_b[c] = bs[BS_DB + c];
+            if (v_b) v_b[c] = bs[BS_VB + c];
+        }
+    }
+    if (scalars) {
+        const double s[SSBA_DOGLEG_NUM_SCALARS] = {
+            st.grad_norm * st.grad_norm, st.gn_norm * st.gn_norm, st.g_dot_gn, st.dl_jv2, st.dl_jg2, st.dl_jvg,
+            st.alpha, st.beta, st.gamma, st.dl_step_norm, st.dl_mcc, (double)st.sub_one_dim,
+            st.sub_e[0][0], st.sub_e[0][1], st.sub_e[1][0], st.sub_e[1][1], st.sub_g[0], st.sub_g[1],
+            st.sub_B[0], st.sub_B[1], st.sub_B[2]};
+        memcpy(scalars, s, sizeof s);
+    }
+    return SSBA_OK;
+}
+
 // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block (tests/dataset_vo_sun.cpp:159-183):
 // the pose's 6x6 block of (J^T J)^-1 in local coordinates = the same block of the inverse of the (undamped) reduced
 // camera system.  Six unit right-hand sides go through the block-cyclic-reduction factors of S.

@@ -6,10 +6,32 @@ Everything here is a direct call into libssba.so; numpy is used for host buffers
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
 from . import capi
+
+
+class DoglegStep(NamedTuple):
+    """What ssba_dogleg_step returns (include/ssba.h): the Gauss-Newton step and v of the poses, landmarks and free shared
+    blocks, the six sums |gradient_|^2, |gn|_D^2, gradient_ . gn, |J v|^2, |J gn|^2, Jv . Jgn, and the scalar chain."""
+    gn_p: np.ndarray
+    gn_l: np.ndarray
+    gn_b: np.ndarray
+    v_p: np.ndarray
+    v_l: np.ndarray
+    v_b: np.ndarray
+    sums: np.ndarray
+    alpha: float
+    beta: float
+    gamma: float
+    step_norm: float
+    mcc: float
+    one_dim: bool
+    sub_e: np.ndarray
+    sub_g: np.ndarray
+    sub_B: np.ndarray
 
 
 class StereoBA:
@@ -310,3 +332,20 @@ class StereoBA:
         capi.check(self.lib.ssba_lm_step(self.h, C.byref(o), radius, capi.dptr(S) if want_S else None, capi.dptr(rhs),
                                          capi.dptr(dp), capi.dptr(dl), C.byref(mcc)), "ssba_lm_step")
         return S, rhs, dp, dl, mcc.value
+
+    def dogleg_step(self, radius: float, mu: float, options: capi.Options = None) -> DoglegStep:
+        """One dogleg step from scratch (ssba_dogleg_step): options.dogleg_type picks TRADITIONAL / SUBSPACE."""
+        P, L = self.poses.shape[0], self.points.shape[0]
+        ld = 6 if self.normals is not None else 3
+        nb = C.c_uint32()
+        capi.check(self.lib.ssba_border_system(self.h, C.byref(nb), None, None, None, None), "ssba_border_system")
+        nb = int(nb.value)
+        gp, vp, gl, vl = np.zeros((P, 6)), np.zeros((P, 6)), np.zeros((L, ld)), np.zeros((L, ld))
+        gb, vb = np.zeros(max(nb, 1)), np.zeros(max(nb, 1))
+        sc = np.zeros(capi.DOGLEG_NUM_SCALARS)
+        o = options or capi.default_options()
+        capi.check(self.lib.ssba_dogleg_step(self.h, C.byref(o), radius, mu, capi.dptr(gp), capi.dptr(gl), capi.dptr(gb),
+                                             capi.dptr(vp), capi.dptr(vl), capi.dptr(vb), capi.dptr(sc)), "ssba_dogleg_step")
+        return DoglegStep(gn_p=gp, gn_l=gl, gn_b=gb[:nb], v_p=vp, v_l=vl, v_b=vb[:nb], sums=sc[0:6], alpha=sc[6], beta=sc[7],
+                          gamma=sc[8], step_norm=sc[9], mcc=sc[10], one_dim=bool(sc[11]), sub_e=sc[12:16].reshape(2, 2),
+                          sub_g=sc[16:18], sub_B=sc[18:21])

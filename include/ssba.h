@@ -275,6 +275,24 @@ SSBA_API int ssba_evaluate(ssba_problem *p, double *cost, double *g_p, double *g
  * model cost change.  Any output may be NULL. */
 SSBA_API int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius, double *S,
                  double *rhs, double *delta_p, double *delta_l, double *model_cost_change);
+/* One DOGLEG step from scratch at the caller's current parameters: the kernels of a solve iteration in its order
+ * (linearisation, the reduced system damped at radius 1/mu, its solve with the border of free shared blocks, the dogleg
+ * vectors and scalars) with trust-region radius `radius`; o->dogleg_type selects TRADITIONAL (0) or SUBSPACE (1), the
+ * strategy field is ignored.  Unscaled coordinates, in user index order:
+ *   gn_p, v_p (P*6): Gauss-Newton step and v = s^2 g / D^2 of the poses (constant poses 0);
+ *   gn_l, v_l (L*3, or L*6 with lighting observations): the same of the landmarks;
+ *   gn_b, v_b (nb, column order of ssba_border_system): the same of the free shared blocks;
+ *   scalars (SSBA_DOGLEG_NUM_SCALARS):
+ *     [0..5]   |gradient_|^2, |gn|_D^2, gradient_ . gn, |J v|^2, |J gn|^2, Jv . Jgn (the first two squared from the norms
+ *              the state keeps)
+ *     [6..10]  alpha (Cauchy step), beta, gamma (delta = beta gn + gamma v), |delta|_D, model cost change of delta
+ *     [11]     1 when the subspace of (gradient_, gn) is one-dimensional
+ *     [12..15] subspace basis u_i = e[i][0] gradient_ + e[i][1] gn: e00, e01, e10, e11
+ *     [16..20] subspace model g (2) and B (upper triangle: B00, B01, B11)
+ *   (SUBSPACE only for [11..20]; TRADITIONAL leaves them 0).  Any output may be NULL. */
+#define SSBA_DOGLEG_NUM_SCALARS 21
+SSBA_API int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, double mu, double *gn_p,
+                     double *gn_l, double *gn_b, double *v_p, double *v_l, double *v_b, double *scalars);
 /* The scalar state machine of the projected line search [Ceres 1.x line_search.cc ArmijoLineSearch::DoSearch, CUBIC
  * interpolation; bounds: tests/dataset_ba_phong.cpp:143-181] replayed on a given sequence of evaluations: phi(0),
  * phi'(0), max |direction|, then values[k] / gradients[k] = phi, phi' at the k-th step it asks for (steps_out[k], capacity

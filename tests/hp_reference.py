@@ -817,3 +817,326 @@ def unary_pose_blocks(poses, factors, fidx):
         g[sl] += J.T @ r
         Ha[sl, sl] += np.abs(J).T @ np.abs(J)
     return H, g, Ha
+
+
+# ---------------------------------------------------------------------------------------------------------------- dogleg
+# Ceres' DoglegStrategy (dogleg_strategy.cc) written in Jacobi-scaled coordinates, as Ceres writes it: J_s = J diag(s) with
+# s = 1 / (1 + sqrt(diag(J^T J))) at the linearisation point, D^2 = clamp(diag(J_s^T J_s), min_lm_diagonal, max_lm_diagonal),
+# gradient_ = J_s^T r / D, the Gauss-Newton step of (J_s^T J_s + mu D^2) in D-scaled space, the Cauchy point, TRADITIONAL_DOGLEG
+# and SUBSPACE_DOGLEG; steps are returned in unscaled coordinates, delta = beta delta_gn + gamma v with v = s^2 g / D^2.
+# The device (k_dogleg_vec / k_dogleg_gn / k_dogleg_interp) restates all of this in unscaled coordinates and takes the
+# row-space products from an expanded identity; here every J x is formed row by row.
+C_DL_ROW = 16             # c_row: rounding of one row value J x (one 3- to 19-term dot product and the row's own rounding)
+
+
+def _rel_residual(T1, T2, T_ref, S):
+    """RelativePoseErrorAutomatic: S log(T_ref T1 T2^-1) with the reference's log = [translation ; axis-angle]."""
+    import np_reference as npr
+    R1, R2, Rr = T1[3:].reshape(3, 3), T2[3:].reshape(3, 3), T_ref[3:].reshape(3, 3)
+    R12 = R1 @ R2.T
+    t = Rr @ (T1[:3] - R12 @ T2[:3]) + T_ref[:3]
+    return S @ np.concatenate([t, npr.so3_log(Rr @ R12)])
+
+
+def unary_rows(poses, factors):
+    """Rows of the pose-only residual blocks (prior 0, sun 1, relative 2 between pose and pose2): one entry per block with
+    r (m), and (pose, J (m x 6)) per pose it touches -- fp64 complex-step Jacobians through SE3 Plus, Huber-corrected like the
+    stereo rows (sqrt(rho') on r and J)."""
+    import np_reference as npr
+    out = []
+    for fct in factors:
+        S = np.asarray(fct["stiffness"], np.float64)
+        d = np.asarray(fct["data"], np.float64)
+        if fct["type"] == 0:
+            fun = lambda X: npr.pose_prior_residual(X, d[:12], S.reshape(6, 6))
+            r, blocks = fun(poses[fct["pose"]]).real, [(fct["pose"], npr.se3_complex_step_jacobian(fun, poses[fct["pose"]]))]
+        elif fct["type"] == 1:
+            fun = lambda X: npr.sun_sensor_residual(X, d[:3], d[3:6], S.reshape(2, 2), d[6], d[7])
+            r, blocks = fun(poses[fct["pose"]]).real, [(fct["pose"], npr.se3_complex_step_jacobian(fun, poses[fct["pose"]]))]
+        else:
+            k1, k2 = fct["pose"], fct["pose2"]
+            T1, T2 = poses[k1], poses[k2]
+            r = _rel_residual(T1, T2, d[:12], S.reshape(6, 6)).real
+            J1 = npr.se3_complex_step_jacobian(lambda X: _rel_residual(X, T2.astype(complex), d[:12], S.reshape(6, 6)), T1)
+            J2 = npr.se3_complex_step_jacobian(lambda X: _rel_residual(T1.astype(complex), X, d[:12], S.reshape(6, 6)), T2)
+            blocks = [(k1, J1), (k2, J2)]
+        w = float(huber_weight(np.float64((r * r).sum()), fct.get("huber", 0.0), np.float64))
+        out.append(dict(r=np.asarray(r * w, LD), blocks=[(k, np.asarray(J * w, LD)) for k, J in blocks]))
+    return out
+
+
+class DoglegReference:
+    """J of one linearisation point as row groups over one parameter vector [free poses (6 nf) | landmarks present (d each) |
+    free shared blocks (nb)] in long double, and the dogleg quantities of Ceres computed from it.
+
+    rows: stereo_rows / phong_observation_rows; unary: unary_rows (or None); mu: the Levenberg-Marquardt regulariser of the
+    Gauss-Newton step (SchurSystem at radius 1 / mu).  Unary rows carry fp64 Jacobians (complex step): their rounding enters
+    every bar through the magnitude Ja = |J| with c_row."""
+
+    def __init__(self, rows, obs_pose, obs_point, fidx, num_points, mu, unary=None, min_diag=1e-6, max_diag=1e32):
+        fidx = np.asarray(fidx, np.int64)
+        self.mu, self.min_diag, self.max_diag = mu, min_diag, max_diag
+        unary = unary or []
+        nf = int((fidx >= 0).sum())
+        # unary blocks summed as the SchurSystem takes them; the off-diagonal (relative-pose) blocks are added to S below
+        n = 6 * nf
+        Hu, gu, Hua = np.zeros((n, n), LD), np.zeros(n, LD), np.zeros((n, n))
+        for b in unary:
+            for k, J in b["blocks"]:
+                if fidx[k] < 0:
+                    continue
+                a = slice(6 * fidx[k], 6 * fidx[k] + 6)
+                gu[a] += J.T @ b["r"]
+                for k2, J2 in b["blocks"]:
+                    if fidx[k2] >= 0:
+                        c = slice(6 * fidx[k2], 6 * fidx[k2] + 6)
+                        Hu[a, c] += J.T @ J2
+                        Hua[a, c] += np.abs(np.asarray(J, np.float64)).T @ np.abs(np.asarray(J2, np.float64))
+        self.sy = sy = SchurSystem(rows, obs_pose, obs_point, fidx, num_points, 1.0 / mu, H_unary=Hu if unary else None,
+                                   g_unary=gu if unary else None, Ha_unary=Hua if unary else None)
+        self.nf, self.d, self.nb, self.Lp = nf, sy.d, sy.nb, sy.lm.shape[0]
+        self.o_l = 6 * nf
+        self.o_b = self.o_l + self.d * self.Lp
+        self.N = self.o_b + self.nb
+        sink = self.N                               # column of constant poses: x[sink] = 0
+        f = fidx[np.asarray(obs_pose, np.int64)]
+        cp = np.where(f[:, None] >= 0, 6 * f[:, None] + np.arange(6), sink)
+        cl = self.o_l + self.d * sy.slot_of_obs[:, None] + np.arange(self.d)
+        groups = [dict(r=rows["r"], blocks=[(rows["Jp"], rows["Jpa"], cp), (rows["Jl"], rows["Jla"], cl)])]
+        if self.nb:
+            cb = np.broadcast_to(self.o_b + np.arange(self.nb), (cl.shape[0], self.nb))
+            groups[0]["blocks"].append((rows["Jb"], rows["Jba"], cb))
+        for b in unary:
+            blk = []
+            for k, J in b["blocks"]:
+                col = np.full((1, 6), sink) if fidx[k] < 0 else (6 * fidx[k] + np.arange(6))[None]
+                blk.append((J[None], np.abs(np.asarray(J, np.float64))[None], col))
+            groups.append(dict(r=b["r"][None], blocks=blk))
+        self.groups = groups
+        self.unary_offdiag = Hu.copy()
+        for a in range(nf):
+            self.unary_offdiag[6 * a: 6 * a + 6, 6 * a: 6 * a + 6] = 0
+        # gradient, diag(J^T J) and their rounding magnitudes, per column
+        g, h = np.zeros(self.N + 1, LD), np.zeros(self.N + 1, LD)
+        ga, ha, m = np.zeros(self.N + 1), np.zeros(self.N + 1), np.zeros(self.N + 1)
+        rab = rows["rabs"]
+        for gi, G in enumerate(groups):
+            ra = rab if gi == 0 else np.abs(np.asarray(G["r"], np.float64))
+            for J, Ja, col in G["blocks"]:
+                np.add.at(g, col, np.einsum("nmw,nm->nw", J, G["r"]))
+                np.add.at(h, col, np.einsum("nmw,nmw->nw", J, J))
+                np.add.at(ga, col, np.einsum("nmw,nm->nw", Ja, ra))
+                np.add.at(ha, col, np.einsum("nmw,nmw->nw", Ja, Ja))
+                np.add.at(m, col, np.ones(col.shape))
+        self.g, self.h, self.ga, self.ha, self.m = g[:-1], h[:-1], ga[:-1], ha[:-1], m[:-1]
+        self.s = LD(1) / (LD(1) + np.sqrt(self.h))
+        self.D2 = np.clip(self.s * self.s * self.h, LD(min_diag), LD(max_diag))
+        self.clamped = (self.s * self.s * self.h < LD(min_diag)) | (self.s * self.s * self.h > LD(max_diag))
+        self.grad_ = self.s * self.g / np.sqrt(self.D2)            # gradient_ (D-scaled space)
+        self.v = self.s * self.s * self.g / self.D2               # unscaled image of gradient_ / D
+        self.t_max = int(np.bincount(sy.slot_of_obs).max()) if sy.slot_of_obs.size else 0
+
+    # ---- vectors
+    def split(self, x):
+        """(poses free (nf, 6), landmarks present (Lp, d), border (nb)) of a parameter vector."""
+        x = np.asarray(x)
+        return x[: self.o_l].reshape(-1, 6), x[self.o_l: self.o_b].reshape(-1, self.d), x[self.o_b:]
+
+    def pack(self, xp_free, xl_present, xb=None):
+        parts = [np.asarray(xp_free, LD).ravel(), np.asarray(xl_present, LD).ravel()]
+        if self.nb:
+            parts.append(np.asarray(xb, LD).ravel())
+        return np.concatenate(parts)
+
+    def gauss_newton(self, band=None):
+        """delta_gn (unscaled, long double) of (J^T J + mu D^2 / s^2) delta = -g, the kappa_2 of the reduced system it came
+        from: the long-double SchurSystem at radius 1 / mu and a refined solve -- equivalently, in Ceres' D-scaled space,
+        D delta / s solves (J_s^T J_s + mu D^2) y = -J_s^T r."""
+        sy = self.sy
+        if self.nb:
+            A, b = sy.bordered()
+            A[: sy.n, : sy.n] += self.unary_offdiag
+        else:
+            A, b = sy.dense(), sy.rhs
+            A = A + self.unary_offdiag
+        x, kap = refined_solve(A, b, band)
+        xp, xb = x[: sy.n], x[sy.n:]
+        xl = sy.back_substitute(xp, xb if self.nb else None)
+        return self.pack(xp, xl, xb), kap
+
+    # ---- row-space sums
+    def jx(self, x):
+        """J x of every row group, row by row (long double)."""
+        xe = np.concatenate([np.asarray(x, LD), [LD(0)]])
+        return [sum(np.einsum("nmw,nw->nm", J, xe[col]) for J, _, col in G["blocks"]) for G in self.groups]
+
+    def jx_mag(self, x):
+        """sum over blocks of Ja |x| per row (the magnitude every term of a one-pass J x sum is bounded by)."""
+        xe = np.concatenate([np.abs(np.asarray(x, np.float64)), [0.0]])
+        return [sum(np.einsum("nmw,nw->nm", Ja, xe[col]) for _, Ja, col in G["blocks"]) for G in self.groups]
+
+    def c_sum(self):
+        """c of the summation bar c u sum |terms| of the device's six sums: t_max observations in one lane (plus the 36 products
+        of a 6x6 quadratic form and the unary rows of one pose), two 256-lane tree reductions (8 levels each), the partials
+        of the final pass (ceil(parts / 256) per lane), C_TERMS for the rest."""
+        parts = (self.Lp + 255) // 256 + (self.nf + 255) // 256 + 1
+        return self.t_max + 36 + 16 + (parts + 255) // 256 + C_TERMS
+
+    def row_sums(self, x, y):
+        """(x.J^T J.y row by row, its bar) -- the bar (c_sum + 2 c_row) u sum_rows mag(x) mag(y) bounds every term of the
+        device's expansion dl^T H dl + 2 dl.(tt - g_l) + |e|^2 and the rounding of J itself (c_row u Ja per entry)."""
+        jx, jy = self.jx(x), self.jx(y)
+        mx, my = self.jx_mag(x), self.jx_mag(y)
+        val = sum((a * b).sum() for a, b in zip(jx, jy))
+        mag = sum(float((a * b).sum()) for a, b in zip(mx, my))
+        return val, (self.c_sum() + 2 * C_DL_ROW) * U * mag
+
+    def param_sums(self, v, gn):
+        """|gradient_|^2, |gn|_D^2 and gradient_ . gn in long double from the device's vectors, with bars: summation
+        c_sum u |terms|, and the rounding of g (the row bar (m + C_TERMS) u ga) and of s^2 / D^2 (from diag H: (m + C_TERMS) u
+        ha / h relative where unclamped, 8 u where clamped) carried through the formulas."""
+        v, gn = np.asarray(v, LD), np.asarray(gn, LD)
+        g, s2, D2 = self.g, self.s * self.s, self.D2
+        w = s2 / D2
+        eg = (self.m + C_TERMS) * U * self.ga
+        ew = np.where(self.clamped, 8 * U, (self.m + C_TERMS) * U * self.ha / np.maximum(np.asarray(self.h, np.float64), 1e-300) + 8 * U)
+        g64, w64, gn64 = (np.abs(np.asarray(t, np.float64)) for t in (g, w, gn))
+        cs = self.c_sum() * U
+        a = (w * g * g).sum()
+        ea = cs * float((w64 * g64 * g64).sum()) + float((w64 * (2 * g64 * eg + ew * g64 * g64)).sum())
+        b = (gn * gn / w).sum()
+        eb = cs * float((gn64 * gn64 / w64).sum()) + float((ew * gn64 * gn64 / w64).sum())
+        c = (g * gn).sum()
+        ec = cs * float((g64 * gn64).sum()) + float((eg * gn64).sum())
+        return (a, b, c), (ea, eb, ec)
+
+    def v_bar(self):
+        """Entrywise bar of the device's v = s^2 g / D^2: 8 u (its own rounding) plus the rounding of g and of s^2 / D^2."""
+        w64 = np.asarray(self.s * self.s / self.D2, np.float64)
+        eg = (self.m + C_TERMS) * U * self.ga
+        ew = np.where(self.clamped, 8 * U, (self.m + C_TERMS) * U * self.ha / np.maximum(np.asarray(self.h, np.float64), 1e-300) + 8 * U)
+        v64 = np.abs(np.asarray(self.v, np.float64))
+        return 8 * U * v64 + w64 * eg + ew * v64
+
+    def model_cost_change(self, delta):
+        """-delta . g - |J delta|^2 / 2 row by row, and the magnitude |delta| . |g| + sum_rows (Ja |delta|)^2."""
+        jd = self.jx(delta)
+        val = -(np.asarray(delta, LD) * self.g).sum() - LD(0.5) * sum((a * a).sum() for a in jd)
+        mag = float((np.abs(np.asarray(delta, np.float64)) * np.abs(np.asarray(self.g, np.float64))).sum())
+        mag += sum(float((a * a).sum()) for a in self.jx_mag(delta))
+        return val, mag
+
+
+# ---- the scalar chain of DoglegStrategy from the six sums (long double)
+def dogleg_scalars(sums, radius, dogleg_type):
+    """From (|gradient_|^2, |gn|_D^2, gradient_.gn, |Jv|^2, |Jgn|^2, Jv.Jgn): dict with alpha, beta, gamma (delta = beta gn +
+    gamma v, unscaled), step_norm (|delta|_D), mcc (from the sums), branch, and for SUBSPACE the model (g, B, basis) and the
+    boundary minimiser.  Branches: 'gn' (Gauss-Newton step inside), 'cauchy' (Cauchy point outside), 'dogleg' (TRADITIONAL on
+    the dogleg), 'one_dim', 'boundary' (SUBSPACE), 'fallback' (SUBSPACE found no minimum: TRADITIONAL, as Ceres)."""
+    A, Bn, C, Jv2, Jg2, Jvg = (LD(x) for x in sums)
+    r = LD(radius)
+    gnorm, gn_norm = np.sqrt(A), np.sqrt(Bn)
+    alpha = A / Jv2
+    out = dict(alpha=alpha)
+
+    def finish(beta, gamma, norm, branch):
+        out.update(beta=LD(beta), gamma=LD(gamma), step_norm=LD(norm), branch=branch)
+        out["mcc"] = -(out["beta"] * C + out["gamma"] * A) - LD(0.5) * (out["beta"] ** 2 * Jg2 + 2 * out["beta"] * out["gamma"] * Jvg
+                                                                        + out["gamma"] ** 2 * Jv2)
+        return out
+
+    def traditional():
+        if gn_norm <= r:
+            return finish(1, 0, gn_norm, "gn")
+        if alpha * gnorm >= r:
+            return finish(0, -r / gnorm, r, "cauchy")
+        # |a + t (b - a)| = r with a = -alpha gradient_, b = gn: the positive root of |b - a|^2 t^2 + 2 a.(b - a) t + |a|^2 - r^2
+        a2, ab, b2 = alpha * alpha * A, -alpha * C, Bn
+        qa, qb, qc = a2 - 2 * ab + b2, 2 * (ab - a2), a2 - r * r
+        t = (-qb + np.sqrt(qb * qb - 4 * qa * qc)) / (2 * qa)
+        gam, bet = -alpha * (1 - t), t
+        return finish(bet, gam, np.sqrt(gam * gam * A + 2 * gam * bet * C + bet * bet * Bn), "dogleg")
+
+    if dogleg_type == 0:
+        return traditional()
+    # SUBSPACE_DOGLEG: orthonormal basis of span(gradient_, gn), the longer column first (Gram-Schmidt on the 2x2 Gram)
+    p_first = A >= Bn
+    an2, bn2 = (A, Bn) if p_first else (Bn, A)
+    an = np.sqrt(an2)
+    proj = C / an
+    wn = np.sqrt(max(bn2 - proj * proj, LD(0)))
+    ia = 0 if p_first else 1
+    e = np.zeros((2, 2), LD)
+    e[0, ia] = 1 / an
+    one_dim = wn <= 2 * np.finfo(np.float64).eps * an
+    out["one_dim"] = bool(one_dim)
+    if not one_dim:     # the model is formed at the linearisation point, whatever the radius (ComputeSubspaceModel)
+        e[1, ia], e[1, 1 - ia] = -proj / (an * wn), 1 / wn
+        G = np.array([[A, C], [C, Bn]], LD)
+        JJ = np.array([[Jv2, Jvg], [Jvg, Jg2]], LD)
+        sg = e @ G[:, 0]                                   # basis . gradient_
+        sB = e @ JJ @ e.T
+        out.update(sub_e=e, sub_g=sg, sub_B=sB)
+    if gn_norm <= r:
+        return finish(1, 0, gn_norm, "gn")
+    if one_dim:
+        return finish(0, -r / gnorm, r, "one_dim")
+    y = boundary_minimum(sg, sB, r)
+    if y is None:
+        res = traditional()
+        res["branch"] = "fallback"
+        return res
+    out["y"] = y
+    gam, bet = y @ e[:, 0], y @ e[:, 1]
+    return finish(bet, gam, r, "boundary")
+
+
+def boundary_minimum(g, B, radius, grid=4096, newton=60):
+    """argmin of g.y + y^T B y / 2 over |y| = radius, independent of the quartic Ceres (and the device) solve: a dense grid in
+    theta, then Newton on f'(theta) in long double from the best grid point.  None when Newton fails to converge."""
+    g, B, r = np.asarray(g, LD), np.asarray(B, LD), LD(radius)
+
+    def f(t):
+        c, s = np.cos(t), np.sin(t)
+        return r * (g[0] * c + g[1] * s) + LD(0.5) * r * r * (B[0, 0] * c * c + 2 * B[0, 1] * c * s + B[1, 1] * s * s)
+
+    def d1(t):
+        c, s = np.cos(t), np.sin(t)
+        return r * (-g[0] * s + g[1] * c) + r * r * ((B[1, 1] - B[0, 0]) * c * s + B[0, 1] * (c * c - s * s))
+
+    def d2(t):
+        c, s = np.cos(t), np.sin(t)
+        return -r * (g[0] * c + g[1] * s) + r * r * ((B[1, 1] - B[0, 0]) * (c * c - s * s) - 4 * B[0, 1] * c * s)
+
+    th = np.arange(grid, dtype=LD) * (2 * LD(np.pi) / grid)
+    t = th[int(np.argmin(f(th)))]
+    step = LD(1)
+    for _ in range(newton):
+        h2 = d2(t)
+        if not h2 > 0:
+            return None
+        step = d1(t) / h2
+        t = t - step
+        if abs(step) <= LD(2.0) ** -60:
+            break
+    if not abs(step) <= LD(2.0) ** -50:      # (f' is evaluated to ~2^-64 of its terms: the last steps may stall above 2^-60)
+        return None
+    return np.array([r * np.cos(t), r * np.sin(t)], LD)
+
+
+def propagate(fun, sums, bars, rel=LD(2.0) ** -30):
+    """sum_i |d fun / d sums_i| bars_i by long-double central differences (fun: six sums -> dict of scalars or a number)."""
+    base = np.asarray(sums, LD)
+    keys = None
+    acc = {}
+    for i in range(6):
+        hstep = max(abs(base[i]) * rel, LD(1e-300))
+        up, dn = base.copy(), base.copy()
+        up[i] += hstep
+        dn[i] -= hstep
+        fu, fd = fun(up), fun(dn)
+        if keys is None:
+            keys = list(fu)
+        for k in keys:
+            acc[k] = acc.get(k, 0.0) + float(abs((LD(fu[k]) - LD(fd[k])) / (2 * hstep))) * float(bars[i])
+    return acc

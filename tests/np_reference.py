@@ -388,6 +388,46 @@ def intensity_jacobian_complex_step(light_type, T, p, n, phong, kd, light, colou
 
 # ---- traditional dogleg [Ceres 1.x dogleg_strategy.cc], written directly in the Jacobi-scaled
 # ---- space the way Ceres does (the C oracle works in unscaled coordinates)
+def dogleg_linearize(ba: "NumpyBA", x_p, x_l, keep, scale, mu, min_diag=1e-6, max_diag=1e32):
+    """DoglegStrategy's work at a new linearisation point, in Jacobi-scaled coordinates: J_s, D, gradient_, the Cauchy step
+    length alpha and the Gauss-Newton step (D-scaled).  scale: the Jacobi scale of the first point, or None to take it here."""
+    cost, r, Jp, Jl = ba.residuals(x_p, x_l, jac=True)
+    J = ba.sparse_jacobian(Jp, Jl)[:, keep]
+    if scale is None:
+        scale = 1.0 / (1.0 + np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel()))
+    Js = J @ sp.diags(scale)
+    rv = r.reshape(-1)
+    D = np.sqrt(np.clip(np.asarray(Js.multiply(Js).sum(0)).ravel(), min_diag, max_diag))
+    grad = (Js.T @ rv) / D                                   # ComputeGradient
+    Jg = Js @ (grad / D)
+    alpha = (grad @ grad) / (Jg @ Jg)                        # ComputeCauchyPoint
+    H = (Js.T @ Js + sp.diags(mu * D * D)).tocsc()           # ComputeGaussNewtonStep
+    gn = -D * spla.spsolve(H, Js.T @ rv)
+    return dict(Js=Js, rv=rv, D=D, grad=grad, alpha=alpha, gn=gn, scale=scale)
+
+
+def dogleg_traditional_step(state, radius):
+    """ComputeTraditionalDoglegStep: the step in D-scaled space, the same in Jacobi-scaled parameters (step / D) and its model
+    cost change -model . (r + model / 2), model = J_s step / D."""
+    D, grad, alpha, gn, Js, rv = (state[k] for k in ("D", "grad", "alpha", "gn", "Js", "rv"))
+    gnorm, nnorm = np.linalg.norm(grad), np.linalg.norm(gn)
+    if nnorm <= radius:
+        step = gn.copy()
+    elif gnorm * alpha >= radius:
+        step = -(radius / gnorm) * grad
+    else:
+        b_dot_a = -alpha * (grad @ gn)
+        a_sq = (alpha * gnorm) ** 2
+        bma = a_sq - 2 * b_dot_a + nnorm ** 2
+        c = b_dot_a - a_sq
+        d = np.sqrt(c * c + bma * (radius ** 2 - a_sq))
+        beta = (d - c) / bma if c <= 0 else (radius ** 2 - a_sq) / (d + c)
+        step = (-alpha * (1 - beta)) * grad + beta * gn
+    step_js = step / D
+    model = Js @ step_js
+    return step, step_js, -model @ (rv + 0.5 * model)
+
+
 def dogleg_solve(ba: "NumpyBA", max_iter=1000, nonmonotonic=True, f_tol=1e-6, p_tol=1e-8, min_rd=1e-3,
                  min_diag=1e-6, max_diag=1e32):
     x_p, x_l = ba.poses.copy(), ba.points.copy()
@@ -407,37 +447,10 @@ def dogleg_solve(ba: "NumpyBA", max_iter=1000, nonmonotonic=True, f_tol=1e-6, p_
     for it in range(1, max_iter + 1):
         if not reuse:
             reuse = True
-            cost, r, Jp, Jl = ba.residuals(x_p, x_l, jac=True)
-            J = ba.sparse_jacobian(Jp, Jl)[:, keep]
-            if scale is None:
-                scale = 1.0 / (1.0 + np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel()))
-            Js = J @ sp.diags(scale)
-            rv = r.reshape(-1)
-            D = np.sqrt(np.clip(np.asarray(Js.multiply(Js).sum(0)).ravel(), min_diag, max_diag))
-            grad = (Js.T @ rv) / D                                   # ComputeGradient
-            Jg = Js @ (grad / D)
-            alpha = (grad @ grad) / (Jg @ Jg)                        # ComputeCauchyPoint
-            H = (Js.T @ Js + sp.diags(mu * D * D)).tocsc()           # ComputeGaussNewtonStep
-            gn = -D * spla.spsolve(H, Js.T @ rv)
-            state = dict(Js=Js, rv=rv, D=D, grad=grad, alpha=alpha, gn=gn)
-        D, grad, alpha, gn, Js, rv = (state[k] for k in ("D", "grad", "alpha", "gn", "Js", "rv"))
-        gnorm, nnorm = np.linalg.norm(grad), np.linalg.norm(gn)
-        if nnorm <= radius:
-            step = gn.copy()
-        elif gnorm * alpha >= radius:
-            step = -(radius / gnorm) * grad
-        else:
-            b_dot_a = -alpha * (grad @ gn)
-            a_sq = (alpha * gnorm) ** 2
-            bma = a_sq - 2 * b_dot_a + nnorm ** 2
-            c = b_dot_a - a_sq
-            d = np.sqrt(c * c + bma * (radius ** 2 - a_sq))
-            beta = (d - c) / bma if c <= 0 else (radius ** 2 - a_sq) / (d + c)
-            step = (-alpha * (1 - beta)) * grad + beta * gn
+            state = dogleg_linearize(ba, x_p, x_l, keep, scale, mu, min_diag, max_diag)
+            scale = state["scale"]
+        step, step_js, mcc = dogleg_traditional_step(state, radius)
         step_norm_scaled = np.linalg.norm(step)
-        step_js = step / D
-        model = Js @ step_js
-        mcc = -model @ (rv + 0.5 * model)
         if not (mcc > 0):
             mu *= 10.0
             reuse = False

@@ -441,3 +441,390 @@ def test_assembly_and_border_bars_reject_plausible_kernel_errors():
     err = np.abs(np.asarray(dl_bad - dl, np.float64)).max(1)
     bound = (np.bincount(so, minlength=sy.lm.shape[0]) + hp.C_TERMS) * hp.U * sy.kappa_V * np.abs(np.asarray(dl, np.float64)).max(1)
     assert (err / bound).max() > 10
+
+
+# ---------------------------------------------------------------------------------------------------------------- dogleg
+def _first_numpy_dogleg(ba, mu=1e-8):
+    """The first linearisation of np_reference.dogleg_solve (its own dogleg_linearize), with the sums in unscaled terms."""
+    keep = np.concatenate([np.ones(6 * ba.nf, bool), np.repeat(ba.active, 3)])
+    st = npr.dogleg_linearize(ba, ba.poses, ba.points, keep, None, mu)
+    grad, gn, D, Js = st["grad"], st["gn"], st["D"], st["Js"]
+    Jg, Jn = Js @ (grad / D), Js @ (gn / D)
+    return dict(state=st, sums=[grad @ grad, gn @ gn, grad @ gn, Jg @ Jg, Jn @ Jn, Jg @ Jn], alpha=st["alpha"],
+                gn_unscaled=gn / D * st["scale"], v=st["scale"] * grad / D)
+
+
+def _tiny_reference(mu=1e-8, huber=0.0):
+    prob = synth.make_problem(8, 60, track_len=5, seed=7)
+    const = np.zeros(8, bool)
+    const[0] = True
+    rows = hp.stereo_rows(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd,
+                          prob.stiffness(), huber)
+    fidx = hp.free_index(8, prob.obs_pose, const)
+    return prob, hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, mu), fidx
+
+
+def _ref_sums(ref, v, gn):
+    return list(ref.param_sums(v, gn)[0]) + [ref.row_sums(x, y)[0] for x, y in ((v, v), (gn, gn), (v, gn))]
+
+
+def test_dogleg_reference_reproduces_the_numpy_first_step():
+    """TRADITIONAL_DOGLEG's first step of np_reference.dogleg_solve (sparse fp64 solve, scaled coordinates): the six sums,
+    alpha, v, the Gauss-Newton step and beta / gamma in all three branches, to fp64 accuracy."""
+    prob, ref, fidx = _tiny_reference()
+    ba = npr.NumpyBA(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(),
+                     pose_const=fidx < 0)
+    npf = _first_numpy_dogleg(ba)
+    gn, kap = ref.gauss_newton()
+    sums = _ref_sums(ref, ref.v, gn)
+    for a, b in zip(sums, npf["sums"]):
+        assert abs(float(a) - b) <= 1e-9 * abs(b), (float(a), b)
+    assert np.allclose(np.asarray(gn, np.float64), npf["gn_unscaled"], rtol=0, atol=1e-9 * np.abs(npf["gn_unscaled"]).max())
+    assert np.allclose(np.asarray(ref.v, np.float64), npf["v"], rtol=0, atol=1e-9 * np.abs(npf["v"]).max())
+    A, Bn = float(sums[0]), float(sums[1])
+    cauchy = float(sums[0] / sums[3]) * np.sqrt(A)
+    grad, gnD = npf["state"]["grad"], npf["state"]["gn"]
+    for r, branch in ((2 * np.sqrt(Bn), "gn"), (0.5 * cauchy, "cauchy"), (np.sqrt(cauchy * np.sqrt(Bn)), "dogleg")):
+        sc = hp.dogleg_scalars(sums, r, 0)
+        assert sc["branch"] == branch
+        assert abs(float(sc["alpha"]) - npf["alpha"]) <= 1e-10 * npf["alpha"]
+        # np_reference's own step (dogleg_traditional_step, D-scaled) against beta gn + gamma gradient_
+        step, _, mcc_np = npr.dogleg_traditional_step(npf["state"], r)
+        mine = float(sc["beta"]) * gnD + float(sc["gamma"]) * grad
+        assert np.allclose(mine, step, rtol=0, atol=1e-9 * np.abs(step).max()), branch
+        assert abs(float(sc["mcc"]) - mcc_np) <= 1e-9 * abs(mcc_np), (branch, float(sc["mcc"]), mcc_np)
+        # mcc from the sums equals the true model cost change of the step, row by row
+        delta = sc["beta"] * gn + sc["gamma"] * ref.v
+        m, mag = ref.model_cost_change(delta)
+        assert abs(m - sc["mcc"]) <= 1e-15 * mag
+
+
+def _oracle_problem(which):
+    from test_oracle_pose_factors import _sun_problem
+    factors = None
+    if which == "tiny":
+        prob = synth.make_problem(8, 60, track_len=5, seed=7)
+    elif which == "c1":
+        prob = synth.make_config("C1")
+    else:
+        prob, factors = _sun_problem()
+    const = np.zeros(prob.num_poses, bool)
+    if factors is None:
+        const[0] = True
+    return prob, factors, const
+
+
+@pytest.mark.parametrize("radius", ["gn", "boundary"])
+@pytest.mark.parametrize("dogleg_type", [0, 1])
+@pytest.mark.parametrize("which", ["tiny", "c1", "sun"])
+def test_dogleg_reference_reproduces_the_oracles_first_iteration(which, dogleg_type, radius):
+    """The C oracle's first DOGLEG iteration (mu 1e-8; initial radius 1e4 -- the Gauss-Newton step inside -- or the geometric
+    mean of the Cauchy and Gauss-Newton step lengths -- on the dogleg / the subspace boundary): its model cost change,
+    recovered as cost_change / relative_decrease of iteration 1, against the reference's true model cost change of the step at
+    the same radius -- within the bars of the device (sums' bars propagated, plus the row bar of the model cost change)."""
+    prob, factors, const = _oracle_problem(which)
+    rows = hp.stereo_rows(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd,
+                          prob.stiffness())
+    fidx = hp.free_index(prob.num_poses, prob.obs_pose, const)
+    un = hp.unary_rows(prob.poses_init, factors) if factors else None
+    ref = hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 1e-8, unary=un)
+    gn, _ = ref.gauss_newton()
+    (a, b, c), (ea, eb, ec) = ref.param_sums(ref.v, gn)
+    rs = [ref.row_sums(x, y) for x, y in ((ref.v, ref.v), (gn, gn), (ref.v, gn))]
+    sums, bars = [a, b, c] + [t[0] for t in rs], [ea, eb, ec] + [t[1] for t in rs]
+    r = 1e4 if radius == "gn" else float(np.sqrt(float(a / sums[3]) * float(np.sqrt(a)) * float(np.sqrt(b))))
+    sc = hp.dogleg_scalars(sums, r, dogleg_type)
+    assert sc["branch"] == ("gn" if radius == "gn" else ("dogleg", "boundary")[dogleg_type])
+    op = orc.OracleProblem(prob.camera, prob.poses_init.copy(), prob.points_init.copy(), prob.obs_pose, prob.obs_point, prob.obs_uvd,
+                           prob.stiffness(), pose_const=const.astype(np.uint8), pose_factors=factors)
+    o = orc.default_options(trust_region_strategy_type=1, dogleg_type=dogleg_type, max_num_iterations=1, initial_trust_region_radius=r)
+    _, log = op.solve(o)
+    assert log["cost"].shape[0] >= 2 and log["relative_decrease"][1] != 0
+    mcc_orc = log["cost_change"][1] / log["relative_decrease"][1]
+    m, mag = ref.model_cost_change(sc["beta"] * gn + sc["gamma"] * ref.v)
+    prop = hp.propagate(lambda s: {"mcc": hp.dogleg_scalars(s, r, dogleg_type)["mcc"]}, sums, bars)["mcc"]
+    bar = (ref.c_sum() + 2 * hp.C_DL_ROW) * hp.U * mag + prop + 16 * hp.U * abs(float(m))
+    print(which, dogleg_type, sc["branch"], float(m), mcc_orc, abs(mcc_orc - float(m)) / bar)
+    assert abs(mcc_orc - float(m)) <= bar, (which, dogleg_type, mcc_orc, float(m), bar)
+
+
+def _closed_form_problem(J, r):
+    """A linear least-squares problem with its J entered directly, as row groups of a DoglegReference-like object."""
+    class P:
+        pass
+    J, r = np.asarray(J, hp.LD), np.asarray(r, hp.LD)
+    p = P()
+    p.g, p.h = J.T @ r, (J * J).sum(0)
+    p.s = 1 / (1 + np.sqrt(p.h))
+    p.D2 = np.clip(p.s * p.s * p.h, hp.LD(1e-6), hp.LD(1e32))
+    p.J, p.r = J, r
+    return p
+
+
+@pytest.mark.parametrize("J,r", [([[2.0, 0.0], [0.0, 0.5], [1.0, 1.0]], [1.0, -3.0, 0.5]),
+                                 ([[3.0, 1.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 0.1], [1.0, 0.0, 1.0]], [0.2, 1.0, -2.0, 0.3])])
+def test_dogleg_scalars_match_the_closed_form(J, r):
+    """alpha = |gradient_|^2 / |J_s gradient_ / D|^2, the dogleg beta from |a + beta (b - a)| = radius, and the subspace boundary
+    minimum from the 2x2 eigenproblem of the model, by hand in long double -- every branch, to a few long-double ulps."""
+    p = _closed_form_problem(J, r)
+    Js = p.J * p.s
+    D = np.sqrt(p.D2)
+    grad = Js.T @ p.r / D
+    Jv = Js @ (grad / D)
+    gn = -D * _ld_solve(Js.T @ Js + hp.LD(1e-8) * np.diag(p.D2), Js.T @ p.r)
+    Jg = Js @ (gn / D)
+    sums = [grad @ grad, gn @ gn, grad @ gn, Jv @ Jv, Jg @ Jg, Jv @ Jg]
+    alpha = sums[0] / sums[3]
+    eps = 64 * np.finfo(hp.LD).eps
+    a = -alpha * grad
+    gnorm, nnorm = np.sqrt(sums[0]), np.sqrt(sums[1])
+    radius_dl = np.sqrt(alpha * gnorm * nnorm)
+    for rad, branch in ((2 * nnorm, "gn"), (0.5 * alpha * gnorm, "cauchy"), (radius_dl, "dogleg")):
+        sc = hp.dogleg_scalars(sums, rad, 0)
+        assert sc["branch"] == branch
+        assert abs(sc["alpha"] - alpha) <= eps * alpha
+        step = sc["beta"] * gn + sc["gamma"] * grad          # D-scaled space: v maps to gradient_
+        if branch == "gn":
+            assert sc["beta"] == 1 and sc["gamma"] == 0
+        elif branch == "cauchy":
+            assert np.all(np.abs(step + rad / gnorm * grad) <= eps * rad)
+        else:   # on the segment a -> gn, at the boundary
+            t = sc["beta"]
+            assert abs(np.sqrt(((a + t * (gn - a)) ** 2).sum()) - rad) <= eps * rad
+            assert np.all(np.abs(step - (a + t * (gn - a))) <= eps * rad)
+        m_true = -(step / D * p.s) @ p.g - hp.LD(0.5) * ((p.J @ (step / D * p.s)) ** 2).sum()
+        assert abs(sc["mcc"] - m_true) <= eps * abs(m_true)
+    # SUBSPACE at the dogleg radius: minimise over the circle of the orthonormal basis by the 2x2 secular equation
+    sc = hp.dogleg_scalars(sums, radius_dl, 1)
+    assert sc["branch"] == "boundary"
+    Q = np.stack([grad / gnorm, gn - (gn @ grad) / sums[0] * grad])
+    Q[1] /= np.sqrt(Q[1] @ Q[1])
+    g2 = Q @ grad
+    B2 = (Js @ (Q / D).T).T @ (Js @ (Q / D).T)
+    best = _secular_minimum(g2, B2, radius_dl)
+    step = sc["beta"] * gn + sc["gamma"] * grad
+    y = Q @ step
+    model = lambda y: g2 @ y + hp.LD(0.5) * y @ B2 @ y
+    assert abs(model(y) - model(best)) <= eps * abs(model(best))
+    assert np.all(np.abs(y - best) <= 1e-9 * radius_dl)
+
+
+def test_dogleg_scalars_one_dimensional_subspace():
+    """J = c I: gradient_ and the Gauss-Newton step are collinear, the subspace is one-dimensional and the step is the
+    scaled steepest descent to the boundary."""
+    p = _closed_form_problem(np.eye(3) * 2.0, [1.0, -2.0, 0.5])
+    Js = p.J * p.s
+    D = np.sqrt(p.D2)
+    grad = Js.T @ p.r / D
+    Jv = Js @ (grad / D)
+    gn = -D * _ld_solve(Js.T @ Js + hp.LD(1e-8) * np.diag(p.D2), Js.T @ p.r)
+    Jg = Js @ (gn / D)
+    sums = [grad @ grad, gn @ gn, grad @ gn, Jv @ Jv, Jg @ Jg, Jv @ Jg]
+    rad = 0.5 * np.sqrt(sums[1])
+    sc = hp.dogleg_scalars(sums, rad, 1)
+    assert sc["one_dim"] and sc["branch"] == "one_dim"
+    assert sc["beta"] == 0 and abs(sc["gamma"] + rad / np.sqrt(sums[0])) <= 4 * np.finfo(hp.LD).eps * abs(sc["gamma"])
+
+
+def _ld_solve(A, b):
+    A, b = np.asarray(A, hp.LD).copy(), np.asarray(b, hp.LD).copy()
+    n = len(b)
+    for c in range(n):
+        for rr in range(c + 1, n):
+            f = A[rr, c] / A[c, c]
+            A[rr] -= f * A[c]
+            b[rr] -= f * b[c]
+    x = np.zeros(n, hp.LD)
+    for rr in range(n - 1, -1, -1):
+        x[rr] = (b[rr] - A[rr, rr + 1:] @ x[rr + 1:]) / A[rr, rr]
+    return x
+
+
+def _secular_minimum(g, B, r):
+    """min of g.y + y^T B y / 2 on |y| = r: y = -(B + l I)^-1 g with |y| = r, l >= -lambda_min, by bisection in long double
+    in the eigenbasis of B (the hard case does not occur for these problems)."""
+    B64 = np.asarray(B, np.float64)
+    w, V = np.linalg.eigh(B64)
+    V = np.asarray(V, hp.LD)
+    w = np.asarray(w, hp.LD)
+    c = V.T @ np.asarray(g, hp.LD)
+    norm = lambda l: np.sqrt(((c / (w + l)) ** 2).sum())
+    lo, hi = -w[0] + hp.LD(1e-30), -w[0] + np.sqrt((c * c).sum()) / r + 1
+    for _ in range(200):
+        mid = (lo + hi) / 2
+        lo, hi = (mid, hi) if norm(mid) > r else (lo, mid)
+    y = V @ (-c / (w + (lo + hi) / 2))
+    return y * (r / np.sqrt(y @ y))
+
+
+def test_boundary_minimum_matches_the_quartic_roots():
+    """The theta-grid + Newton minimiser against the quartic of Ceres' FindMinimumOnTrustRegionBoundary solved by numpy.roots
+    on random well-separated 2-D models: same minimum value, same minimiser."""
+    rng = np.random.default_rng(5)
+    for _ in range(200):
+        A = rng.normal(size=(2, 2))
+        B = A @ A.T + 0.1 * np.eye(2)
+        g = rng.normal(size=2) * 3
+        r = float(np.exp(rng.uniform(-2, 1)))
+        if np.linalg.norm(np.linalg.solve(B, g)) <= 1.2 * r:
+            continue                   # the Gauss-Newton step lies inside: no boundary minimum is asked for
+        detB, trB = np.linalg.det(B), np.trace(B)
+        adj = np.array([[B[1, 1], -B[0, 1]], [-B[0, 1], B[0, 0]]])
+        ag = adj @ g
+        r2 = r * r
+        poly = [r2, 2 * r2 * trB, r2 * (trB ** 2 + 2 * detB) - g @ g, -2 * (g @ ag - r2 * detB * trB), r2 * detB ** 2 - ag @ ag]
+        cands = []
+        for lam in np.roots(poly):
+            if abs(lam.imag) > 1e-8 * max(1, abs(lam)):
+                continue
+            y = -np.linalg.solve(B + lam.real * np.eye(2), g)
+            y *= r / np.linalg.norm(y)
+            cands.append((g @ y + 0.5 * y @ B @ y, y))
+        fq, yq = min(cands, key=lambda t: t[0])
+        y = np.asarray(hp.boundary_minimum(g, B, r), np.float64)
+        f = g @ y + 0.5 * y @ B @ y
+        assert abs(f - fq) <= 1e-12 * max(1.0, abs(fq)), (f, fq)
+        assert np.allclose(y, yq, atol=1e-6 * r), (y, yq)
+
+
+def _device_dogleg(ref, rows, gn, radius, dogleg_type, mut=""):
+    """float64 restatement of the device's dogleg arithmetic (k_dogleg_vec, k_dogleg_gn / k_ph_dogleg_gn, k_dogleg_interp) on the
+    reference's rows: v = s^2 g / D^2 in unscaled coordinates, the row-space sums from the one-pass identity
+        x^T J^T J y = sum_l [x_l^T H_ll y_l + x_l . (tt_y - g_l) + y_l . (tt_x - g_l)] + sum_rows e_x e_y,   e = J_p x_p + J_b x_b
+    (H_ll over all rows of the landmark, constant poses included), the unary rows of each pose with the relative-pose cross
+    term counted once, and the model cost change from the six sums.  `mut` applies one plausible kernel error."""
+    f64 = lambda a: np.asarray(a, np.float64)
+    g, h = f64(ref.g), f64(ref.h)
+    s = 1.0 / (1.0 + np.sqrt(h))
+    D2 = s * s * h if mut == "unclamped" else np.clip(s * s * h, 1e-6, 1e32)
+    v = (g / D2) if mut == "no_s2" else s * s * g / D2
+    gn = f64(gn)
+    A = float((s * s * g * g / D2).sum()) if mut != "no_s2" else float((g * g / D2).sum())
+    sums = [A, float((D2 * gn * gn / (s * s)).sum()), float((g * gn).sum())]
+    sy = ref.sy
+    free = sy._f >= 0
+    so = sy.slot_of_obs
+    Jp, Jl, r = f64(rows["Jp"]), f64(rows["Jl"]), f64(rows["r"])
+    Jb = f64(rows["Jb"]) if ref.nb else None
+    gl = np.zeros((ref.Lp, ref.d))
+    np.add.at(gl, so, np.einsum("nai,na->ni", Jl, r))
+    Hrows = free if mut == "drop_const" else np.ones_like(free)
+    H = np.zeros((ref.Lp, ref.d, ref.d))
+    np.add.at(H, so[Hrows], np.einsum("nai,naj->nij", Jl[Hrows], Jl[Hrows]))
+
+    def parts(x):
+        xp, xl, xb = (f64(t) for t in ref.split(x))
+        e = np.zeros(r.shape)
+        e[free] = np.einsum("nai,ni->na", Jp[free], xp[sy._f[free]])
+        if ref.nb and mut != "no_border":
+            e += np.einsum("nab,b->na", Jb, xb)
+        t = np.zeros((ref.Lp, ref.d))
+        np.add.at(t, so, np.einsum("nai,na->ni", Jl, e))
+        return xl, e, (gl if mut == "cross_gl" else t)
+
+    def q(x, y):
+        xl, ex, tx = parts(x)
+        yl, ey, ty = parts(y)
+        val = (np.einsum("li,lij,lj->", xl, H, yl) + (xl * ty).sum() + (yl * tx).sum() + (ex * ey).sum())
+        xe, ye = np.concatenate([f64(x), [0.0]]), np.concatenate([f64(y), [0.0]])
+        for G in ref.groups[1:]:
+            a = [f64(J[0]) @ xe[col[0]] for J, _, col in G["blocks"]]
+            b = [f64(J[0]) @ ye[col[0]] for J, _, col in G["blocks"]]
+            val += sum(ai @ bi for ai, bi in zip(a, b))
+            if len(a) == 2:
+                val += (2.0 if mut == "cross_twice" else 1.0) * (a[0] @ b[1] + a[1] @ b[0])
+        return float(val)
+
+    sums += [q(v, v), q(gn, gn), q(v, gn)]
+    if mut == "g2_in_mcc":
+        chain_sums = [float((g * g).sum())] + sums[1:]
+    else:
+        chain_sums = sums
+    sc = hp.dogleg_scalars(sums, radius, dogleg_type)
+    beta, gamma = float(sc["beta"]), float(sc["gamma"])
+    if mut == "subspace_largest":
+        y = hp.boundary_minimum(-sc["sub_g"], -sc["sub_B"], radius)
+        gamma, beta = float(y @ sc["sub_e"][:, 0]), float(y @ sc["sub_e"][:, 1])
+    A_, Bn, C, Jv2, Jg2, Jvg = chain_sums
+    mcc = -(beta * C + gamma * A_) - 0.5 * (beta * beta * Jg2 + 2 * beta * gamma * Jvg + gamma * gamma * Jv2)
+    return v, sums, mcc, beta, gamma
+
+
+def _mutation_ratios(ref, rows, radius, dogleg_type, mut):
+    gn, _ = ref.gauss_newton()
+    v, sums, mcc, beta, gamma = _device_dogleg(ref, rows, gn, radius, dogleg_type, mut)
+    vr = float((np.abs(np.asarray(np.asarray(v, hp.LD) - ref.v, np.float64)) / np.maximum(ref.v_bar(), 1e-300)).max())
+    (a, b, c), (ea, eb, ec) = ref.param_sums(ref.v, gn)
+    rs = [ref.row_sums(x, y) for x, y in ((ref.v, ref.v), (gn, gn), (ref.v, gn))]
+    ref_sums, bars = [a, b, c] + [t[0] for t in rs], [ea, eb, ec] + [t[1] for t in rs]
+    sr = max(float(abs(hp.LD(x) - y)) / e for x, y, e in zip(sums, ref_sums, bars))
+    keys = ("mcc",)
+    prop = hp.propagate(lambda s: {k: hp.dogleg_scalars(s, radius, dogleg_type)[k] for k in keys}, ref_sums, bars)
+    truth = hp.dogleg_scalars(ref_sums, radius, dogleg_type)
+    delta = truth["beta"] * gn + truth["gamma"] * ref.v
+    mref, mag = ref.model_cost_change(delta)
+    mbar = (ref.c_sum() + 2 * hp.C_DL_ROW) * hp.U * mag + prop["mcc"] + 16 * hp.U * abs(float(mref))
+    mr = float(abs(hp.LD(mcc) - mref)) / mbar
+    return max(vr, sr, mr)
+
+
+def _mutation_problem():
+    """Constant poses at the start and inside the chain, Huber with outliers, a far landmark under the diagonal clamp,
+    odometry and a loop closure (relative-pose rows) -- every term the mutations below touch."""
+    from test_oracle_pose_factors import _odometry_factors
+    prob = synth.make_problem(8, 60, track_len=5, seed=7, outlier_fraction=0.15)
+    pts = prob.points_init.copy()
+    T0 = prob.poses_init[prob.obs_pose[prob.obs_point == 5][0]]
+    cam = -T0[3:].reshape(3, 3).T @ T0[:3]
+    pts[5] = cam + (pts[5] - cam) * 1e5
+    const = np.zeros(8, bool)
+    const[[0, 4]] = True
+    factors = [f for f in _odometry_factors(prob) if f["type"] == 2 and not const[f["pose"]] and not const[f["pose2"]]]
+    rows = hp.stereo_rows(prob.camera, prob.poses_init, pts, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(), 1.345)
+    fidx = hp.free_index(8, prob.obs_pose, const)
+    un = hp.unary_rows(prob.poses_init, factors)
+    ref = hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 1e-8, unary=un)
+    assert np.any(ref.clamped) and np.any(np.asarray(hp.huber_weight((np.asarray(rows["r"], np.float64) ** 2).sum(1), 1.345)) < 1)
+    rows_nh = hp.stereo_rows(prob.camera, prob.poses_init, pts, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(), 0.0)
+    return ref, rows, rows_nh
+
+
+def _dogleg_radius(ref):
+    gn, _ = ref.gauss_newton()
+    (A, Bn, _), _ = ref.param_sums(ref.v, gn)
+    jv2 = ref.row_sums(ref.v, ref.v)[0]
+    return float(np.sqrt(float(A / jv2) * float(np.sqrt(A)) * float(np.sqrt(Bn))))
+
+
+@pytest.mark.parametrize("mut,dogleg_type", [("", 0), ("", 1), ("cross_gl", 0), ("drop_const", 0), ("unclamped", 0), ("no_s2", 0),
+                                             ("g2_in_mcc", 0), ("no_huber", 0), ("cross_twice", 0), ("subspace_largest", 1)])
+def test_dogleg_bars_hold_the_device_arithmetic_and_reject_plausible_errors(mut, dogleg_type):
+    """The device's formulas restated in float64 sit within the bars of test_gpu_hp_dogleg.py (max ratio <= 0.5); each plausible
+    kernel error exceeds them by more than 10x."""
+    ref, rows, rows_nh = _mutation_problem()
+    ratio = _mutation_ratios(ref, rows_nh if mut == "no_huber" else rows, _dogleg_radius(ref), dogleg_type, mut)
+    print("mutation", mut or "none", dogleg_type, ratio)
+    if mut:
+        assert ratio > 10.0, (mut, ratio)
+    else:
+        assert ratio <= 0.5, ratio
+
+
+@pytest.mark.parametrize("mut", ["", "no_border"])
+def test_dogleg_bars_reject_a_missing_border_term(mut):
+    """Lighting terms with all shared blocks free: the border step in e_g of k_ph_dogleg_gn."""
+    prob, ph = synth.make_phong_problem(8, 60, num_materials=4, seed=4)
+    d = ph.as_oracle_dict("truth")
+    rows = hp.phong_observation_rows(prob.camera, prob.poses_init, prob.points_init, d["normals"], prob.obs_pose, prob.obs_point,
+                                     prob.obs_uvd, prob.stiffness(), d, 0.0, 7)
+    const = np.zeros(prob.num_poses, bool)
+    const[0] = True
+    fidx = hp.free_index(prob.num_poses, prob.obs_pose, const)
+    ref = hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 1e-3)
+    assert ref.nb == 19
+    ratio = _mutation_ratios(ref, rows, _dogleg_radius(ref), 0, mut)
+    print("mutation", mut or "none", ratio)
+    if mut:
+        assert ratio > 10.0, (mut, ratio)
+    else:
+        assert ratio <= 0.5, ratio

@@ -851,7 +851,14 @@ int ssba_finalize(ssba_problem *p) {
         }
         // Landmark sharding: the lighting terms of a landmark live on its rank like the stereo terms.  With
         // FREE shared blocks the border sums over all landmarks (S_pb, S_bb, reduced border gradient) are exchanged next to
-        // the reduced system (enqueue_front); that exists for the all-reduce mode, not for the partitioned reduced solve.
+        // the reduced system (enqueue_front); that exists for the all-reduce mode, not for the partitioned reduced solve, and
+        // for borders of one panel (NBP columns) only.
+        const uint32_t nb = (p->shared_const & 1u ? 0u : 3u) + (p->shared_const & 2u ? 0u : 3u * p->M) + (p->shared_const & 4u ? 0u : p->M);
+        if (nb > (uint32_t)NBP && p->world_size > 1) {
+            set_error("landmark sharding with a border of free shared blocks wider than 32 columns (more than seven materials with "
+                      "every kind free) is not available: solve on one GPU or hold a kind constant");
+            return SSBA_ERR_UNSUPPORTED;
+        }
     }
     if (N >= (1ull << 28) || L >= (1u << 27)) {
         set_error("problem too large for the 32-bit observation references of this build");
@@ -934,7 +941,10 @@ int ssba_finalize(ssba_problem *p) {
         if (!(p->shared_const & 1u)) { d.b_light = d.nb; d.nb += 3; }
         if (!(p->shared_const & 2u)) { d.b_phong = d.nb; d.nb += 3 * d.M; }
         if (!(p->shared_const & 4u)) { d.b_tex = d.nb; d.nb += d.M; }
-        if (d.nb > NBP) { set_error("border of free shared blocks wider than this build supports"); return SSBA_ERR_UNSUPPORTED; }
+        // a border of more than NBP columns is two panels of NBP (nb <= 3 + 4 SSBA_MAX_MATERIALS = 63 < NBP_MAX)
+        if (d.nb > NBP_MAX) { set_error("border of free shared blocks wider than this build supports"); return SSBA_ERR_UNSUPPORTED; }
+        d.np = d.nb > NBP ? 2 : 1;
+        d.nbw = d.np * NBP;
         // bounds only matter on free blocks; a constrained problem runs the projected line search
         for (int i = 0; i < 4; ++i) {
             d.blo[i] = p->blo[i]; d.bhi[i] = p->bhi[i];
@@ -954,17 +964,18 @@ int ssba_finalize(ssba_problem *p) {
         TRY(dupload(p, &d.pose_mat_start, dense ? dn_pose_mat_start : pose_mat_start));
         if (d.nb) {
             TRY(dzero(p, &d.lmV, (size_t)Lpad * 42)); TRY(dzero(p, &d.lmH, (size_t)Lpad * 28)); TRY(dzero(p, &d.lmG, (size_t)Lpad * 7));
-            const char *e = getenv("SSBA_BORDER_POSE_KERNEL");       // 1: the pose-by-pose kernel k_ph_border_poses (A/B, tests)
-            if (!dense && !(e && e[0] == '1')) {
+            // 1: the pose-by-pose kernel k_ph_border_poses (A/B, tests); a border of two panels always takes it
+            const char *e = getenv("SSBA_BORDER_POSE_KERNEL");
+            if (!dense && d.np == 1 && !(e && e[0] == '1')) {
                 TRY(dzero(p, &d.lmMV, (size_t)Lpad * 42));
                 TRY(dzero(p, &d.Hpb, (size_t)std::max(1, (nfree + SBP - 1) / SBP) * SBP * 6 * NBP));
                 TRY(dzero(p, &d.slabB, (size_t)n_slabs * 72 * NBP));
                 TRY(dzero(p, &d.HpbL, (size_t)P * p->M * 18));
             }
             TRY(dzero(p, &d.part_b, (size_t)(Lpad / 256 + 1) * d.M * NBV));   // + one row of column sums
-            TRY(dzero(p, &d.bsys, (size_t)BS_COUNT));
+            TRY(dzero(p, &d.bsys, (size_t)bs_count(d.nbw)));
             d.n_gram = 64;
-            TRY(dzero(p, &d.part_g, (size_t)d.n_gram * (NBP * NBP + NBP)));
+            TRY(dzero(p, &d.part_g, (size_t)d.np * d.np * d.n_gram * (NBP * NBP + NBP)));
         }
         TRY(dzero(p, &d.part_ls, (size_t)(Lpad / 256) * NLS));
         TRY(dzero(p, &d.ls_out, (size_t)NLS_OUT + NLS_MACH + NLS_X + NLS_X_RANKS));
@@ -978,7 +989,7 @@ int ssba_finalize(ssba_problem *p) {
     TRY(dupload(p, &d.sblk_start, sblk_start)); TRY(dupload(p, &d.sblk_contrib, sblk_contrib));
     TRY(dupload(p, &d.prow_start, prow_start)); TRY(dupload(p, &d.prow_contrib, prow_contrib));
     if (nborder) {      // closure border: 6 columns per border pose
-        d.cb = 1; d.nb = 6 * nborder; d.n_cb = (int)cb_a.size();
+        d.cb = 1; d.nb = 6 * nborder; d.n_cb = (int)cb_a.size(); d.np = 1; d.nbw = NBP;
         d.b_light = d.b_phong = d.b_tex = -1;
         TRY(dupload(p, &d.cb_a, cb_a)); TRY(dupload(p, &d.cb_b, cb_b));
         TRY(dupload(p, &d.cb_start, cb_start)); TRY(dupload(p, &d.cb_contrib, cb_contrib));
@@ -999,8 +1010,8 @@ int ssba_finalize(ssba_problem *p) {
     TRY(dzero(p, &d.xv, d.xv_count));
     TRY(dzero(p, &d.x0, (size_t)d.nf_pad * 6));
     if (d.nb) {
-        TRY(dzero(p, &d.Spb, (size_t)d.nf_pad * 6 * NBP));
-        TRY(dzero(p, &d.Zb, (size_t)d.nf_pad * 6 * NBP));
+        TRY(dzero(p, &d.Spb, (size_t)d.np * d.nf_pad * 6 * NBP));
+        TRY(dzero(p, &d.Zb, (size_t)d.np * d.nf_pad * 6 * NBP));
     }
     TRY(dzero(p, &d.vp, (size_t)P * 6)); TRY(dzero(p, &d.vl, (size_t)Lpad * (ph ? 6 : 3))); TRY(dzero(p, &d.dl_gn, (size_t)Lpad * (ph ? 6 : 3)));
     // BCR level plan.  Plain: all super-blocks, odd blocks eliminated level by level down to one block.
@@ -1040,7 +1051,7 @@ int ssba_finalize(ssba_problem *p) {
         std::vector<int> pos(n);
         for (int i = 0; i < n; ++i) pos[i] = i;
         for (;;) {
-            if (d.nb) TRY(dzero(p, &d.lev[lev].B, (size_t)n * BD * NBP));
+            if (d.nb) TRY(dzero(p, &d.lev[lev].B, (size_t)d.np * n * BD * NBP));
             TRY(dzero(p, &d.lev[lev].YU, (size_t)std::max(1, n / 2) * blk));
             TRY(upload_pos(pos, &d.lev[lev].pos));
             if (part ? n <= pcr_max : n == 1) break;
@@ -1072,7 +1083,8 @@ int ssba_finalize(ssba_problem *p) {
         if (pin1) TRY(dzero(p, &P.Ubuf, (size_t)n * blk));
         if (keep) {
             TRY(dzero(p, &P.Gs, slots * blk));
-            TRY(dzero(p, &P.Bb, (size_t)n * BD * NBP)); TRY(dzero(p, &P.yB, (size_t)n * BD * NBP));
+            const size_t np = d.nb ? (size_t)d.np : 1;
+            TRY(dzero(p, &P.Bb, np * n * BD * NBP)); TRY(dzero(p, &P.yB, np * n * BD * NBP));
         }
         return SSBA_OK;
     };
@@ -2317,11 +2329,11 @@ int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, doub
         }
     }
     if ((gn_b || v_b) && d.nb) {
-        std::vector<double> bs((size_t)BS_COUNT);
+        std::vector<double> bs((size_t)bs_count(d.nbw));
         HIPCHECK(hipMemcpy(bs.data(), d.bsys, bs.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (int c = 0; c < d.nb; ++c) {
-            if (gn_b) gn_b[c] = bs[BS_DB + c];
-            if (v_b) v_b[c] = bs[BS_VB + c];
+            if (gn_b) gn_b[c] = bs[bs_vec(d.nbw, BSV_DB) + c];
+            if (v_b) v_b[c] = bs[bs_vec(d.nbw, BSV_VB) + c];
         }
     }
     if (scalars) {
@@ -2668,27 +2680,28 @@ int ssba_border_system(ssba_problem *p, uint32_t *nb_out, double *S_pb, double *
     if (nb_out) *nb_out = (uint32_t)d.nb;
     if (!d.nb) return SSBA_OK;
     HIPCHECK(hipStreamSynchronize(p->launcher.stream));
-    const int nb = d.nb, nf = d.nfree;
-    std::vector<double> bs((size_t)BS_COUNT);
+    const int nb = d.nb, nf = d.nfree, w = d.nbw;
+    std::vector<double> bs((size_t)bs_count(w));
     HIPCHECK(hipMemcpy(bs.data(), d.bsys, bs.size() * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(p->h_state, d.st, sizeof(State), hipMemcpyDeviceToHost));
     if (S_pb) {
-        std::vector<double> sp((size_t)d.nf_pad * 6 * NBP);
+        const size_t rows = (size_t)d.nf_pad * 6;
+        std::vector<double> sp((size_t)d.np * rows * NBP);
         HIPCHECK(hipMemcpy(sp.data(), d.Spb, sp.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (int i = 0; i < 6 * nf; ++i)
-            for (int c = 0; c < nb; ++c) S_pb[(size_t)i * nb + c] = sp[(size_t)i * NBP + c];
+            for (int c = 0; c < nb; ++c) S_pb[(size_t)i * nb + c] = sp[bcol_at(rows, (size_t)i, c)];
     }
     const State &S = *p->h_state;
     const double radius = S.opt.strategy ? 1.0 / S.mu : S.radius;
     for (int a = 0; a < nb; ++a) {
-        if (rhs_b) rhs_b[a] = -bs[BS_RHS + a];
-        if (delta_b) delta_b[a] = bs[BS_DB + a];
+        if (rhs_b) rhs_b[a] = -bs[bs_vec(w, BSV_RHS) + a];
+        if (delta_b) delta_b[a] = bs[bs_vec(w, BSV_DB) + a];
         if (S_bb)
             for (int c = 0; c < nb; ++c) {
-                double v = bs[BS_SBB + a * NBP + c];
+                double v = bs[BS_SBB + a * w + c];
                 if (a == c) {
-                    const double s2 = bs[BS_S + a] * bs[BS_S + a];
-                    v += std::min(std::max(bs[BS_H + a] * s2, S.opt.min_lm_diag), S.opt.max_lm_diag) / (radius * s2);
+                    const double s2 = bs[bs_vec(w, BSV_S) + a] * bs[bs_vec(w, BSV_S) + a];
+                    v += std::min(std::max(bs[bs_vec(w, BSV_H) + a] * s2, S.opt.min_lm_diag), S.opt.max_lm_diag) / (radius * s2);
                 }
                 S_bb[(size_t)a * nb + c] = v;
             }

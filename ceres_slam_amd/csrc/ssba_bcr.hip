@@ -125,10 +125,11 @@ static int n_odd(const BcrLevel &lv, int pinned) { return pinned ? (lv.n - 1) / 
 
 // The border columns (free shared blocks of config 3, closure border) go through the forward part of the solve INSIDE
 // the matrix-core factor / reduce launches -- two more right-hand-side tiles -- instead of a forward + update launch per
-// level afterwards (ssba_border.hip).  SSBA_BORDER_SWEEPS=1 keeps the separate sweeps (A/B, tests).
+// level afterwards (ssba_border.hip).  SSBA_BORDER_SWEEPS=1 keeps the separate sweeps (A/B, tests).  A border of two
+// panels (nb > NBP) never rides: each panel takes the sweeps.
 bool bcr_border_rides(const Dev &d) {
     const char *e = getenv("SSBA_BORDER_SWEEPS");        // read per call: tests switch it between handles
-    return d.nb > 0 && !d.part && !d.dense && !(e && e[0] == '1');
+    return d.nb > 0 && d.nb <= NBP && !d.part && !d.dense && !(e && e[0] == '1');
 }
 
 // the decoupled last step of a plan that covers the whole chain can solve its blocks AND update their poses

@@ -8,6 +8,8 @@
 // B' = B_e - YU^T yb - YL^T yb on even blocks; backward: X_i = G^-T (yb - YL X_{i-1} - YU X_{i+1})),
 // giving Zb = S_pp^-1 S_pb, then form and solve the small border system
 //   (S_bb + D_b^2 - S_pb^T Zb) db = -g_b^ - S_pb^T x0 ,   dp = x0 - Zb db .
+// A border of NBP < nb <= 2 NBP columns is two panels of NBP columns (Dev::np): the sweeps and the Gram partials run on
+// one panel at a time (border_panel), the border system is solved 64 wide (k_border_solve_wide).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -393,15 +395,131 @@ __global__ __launch_bounds__(1024) void k_border_solve(Dev d) {
     if (t < NBP) d.bsys[BS_DB + t] = t < nb ? v : 0.0;
 }
 
+// k_border_solve for a border of two panels (nbw = NBP_MAX = 64 columns): the Gram partials of the four panel pairs
+// (k_border_gram on each pair, part_g pair-major: pair = 2 * panel of S_pb + panel of Zb; the x0 column with the first pair
+// of each S_pb panel) summed in list order, then the same register Cholesky with a lane per row -- 64 rows fill the wave.
+__global__ __launch_bounds__(256) void k_border_solve_wide(Dev d) {
+    // 256 lanes (one wave per SIMD): the factorisation's 64 doubles of row per lane need more than the 128 registers a
+    // lane of a 1024-lane work-group may have
+    constexpr int W = NBP_MAX, PG = NBP * NBP + NBP, NT = 256, PER = W * W / NT;
+    State &st = *d.st;
+    if (st.terminated || st.step_failed || st.dl_reuse) return;
+    __shared__ double T[W * (W + 1)];
+    __shared__ double rb[W];
+    const int t = threadIdx.x, nb = d.nb;
+    const size_t pair_stride = (size_t)d.n_gram * PG;
+    // entry e = t + NT k: row a = e / W, column b = e % W; its Gram sum over the partials of panel pair (a / NBP, b / NBP),
+    // in list order.  EG entries at a time with GF partials each in flight (as k_border_solve: a load per partial and entry,
+    // each waiting for the one before, would be 17 x 64 dependent trips); the x0 column rides with the first group.
+    constexpr int GF = 16, EG = 4;
+    double gv = 0.0;
+    for (int k0 = 0; k0 < PER; k0 += EG) {
+        const double *pg[EG];
+        double acc[EG];
+#pragma unroll
+        for (int j = 0; j < EG; ++j) {
+            const int e = t + NT * (k0 + j), a = e / W, b = e - a * W;
+            pg[j] = d.part_g + (size_t)(2 * (a / NBP) + b / NBP) * pair_stride + (a % NBP) * NBP + (b % NBP);
+            acc[j] = 0.0;
+        }
+        const bool xv = k0 == 0 && t < W;
+        const double *pv = d.part_g + (size_t)(2 * ((t % W) / NBP)) * pair_stride + NBP * NBP + (t % NBP);
+        for (int q0 = 0; q0 < d.n_gram; q0 += GF) {
+            double x[EG][GF], y[GF];
+#pragma unroll
+            for (int u = 0; u < GF; ++u) {
+                const bool in = q0 + u < d.n_gram;
+#pragma unroll
+                for (int j = 0; j < EG; ++j) x[j][u] = in ? pg[j][(size_t)(q0 + u) * PG] : 0.0;
+                y[u] = in && xv ? pv[(size_t)(q0 + u) * PG] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < GF; ++u) {
+#pragma unroll
+                for (int j = 0; j < EG; ++j) acc[j] += x[j][u];
+                if (xv) gv += y[u];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < EG; ++j) {
+            const int e = t + NT * (k0 + j), a = e / W, b = e - a * W;
+            T[a * (W + 1) + b] = acc[j];
+        }
+    }
+    __syncthreads();
+    const double radius = st.opt.strategy ? 1.0 / st.mu : st.radius;
+    double val[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int e = t + NT * k, a = e / W, b = e - a * W;
+        // symmetrised against rounding (only the lower triangle is read below)
+        double v = 0.5 * ((d.bsys[BS_SBB + a * W + b] - T[a * (W + 1) + b]) + (d.bsys[BS_SBB + b * W + a] - T[b * (W + 1) + a]));
+        if (a == b) {
+            if (a < nb) {
+                const double s = d.bsys[bs_vec(W, BSV_S) + a], s2 = s * s;
+                v += fmin(fmax(d.bsys[bs_vec(W, BSV_H) + a] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag) / (radius * s2);
+            } else {
+                v = 1.0;
+            }
+        } else if (a >= nb || b >= nb) {
+            v = 0.0;
+        }
+        val[k] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int e = t + NT * k, a = e / W, b = e - a * W;
+        T[a * (W + 1) + b] = val[k];
+    }
+    if (t < W) rb[t] = t < nb ? -d.bsys[bs_vec(W, BSV_RHS) + t] - gv : 0.0;
+    __syncthreads();
+    if (t >= 64) return;
+    const int i = t;
+    double row[W];
+#pragma unroll
+    for (int c = 0; c < W; ++c) row[c] = T[i * (W + 1) + c];
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const double piv = bcast(row[j], j);
+        if (!(piv > 0.0) || !isfinite(piv)) bad = true;
+        const double rs = 1.0 / sqrt(piv);
+        const double lij = row[j] * rs;
+        row[j] = lij;
+#pragma unroll
+        for (int c = j + 1; c < W; ++c) row[c] -= lij * bcast(lij, c);
+    }
+    if (bad) { if (t == 0) st.step_failed = 1; return; }
+#pragma unroll
+    for (int c = 0; c < W; ++c) T[i * (W + 1) + c] = row[c];
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    double v = rb[i];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const double yj = bcast(v, j) / bcast(row[j], j);
+        if (t == j) v = yj;
+        else if (t > j) v -= row[j] * yj;
+    }
+    for (int j = W - 1; j >= 0; --j) {
+        const double xj = bcast(v, j) / T[j * (W + 1) + j];
+        if (t == j) v = xj;
+        else if (t < j) v -= T[j * (W + 1) + t] * xj;
+    }
+    d.bsys[bs_vec(W, BSV_DB) + t] = t < nb ? v : 0.0;
+}
+
 // dp = x0 - Zb db
 __global__ __launch_bounds__(256) void k_border_apply(Dev d) {
     const State &st = *d.st;
     if (st.terminated || st.step_failed || st.dl_reuse) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.nf_pad * 6) return;
+    const double *db = d.bsys + bs_vec(d.nbw, BSV_DB);
     double v = d.x0[i];
-    for (int c = 0; c < d.nb; ++c) v -= d.Zb[(size_t)i * NBP + c] * d.bsys[BS_DB + c];
-    if (d.cb && i >= d.nchain * 6 && i < d.nfree * 6) v = d.bsys[BS_DB + (i - d.nchain * 6)];     // closure border: these poses ARE the border
+    for (int c = 0; c < d.nb; ++c) v -= d.Zb[bcol_at((size_t)d.nf_pad * 6, (size_t)i, c)] * db[c];
+    if (d.cb && i >= d.nchain * 6 && i < d.nfree * 6) v = db[i - d.nchain * 6];     // closure border: these poses ARE the border
     d.x0[i] = v;
 }
 
@@ -441,11 +559,37 @@ void launch_bcr_multi_rhs(Launcher &L, const Dev &d) {
         LAUNCH(KC_BORDER, k_bcrm_bwd, dim3(d.lev[l].n / 2), dim3(MR_THREADS), SH_BWD, d, l, 0, 0, 0);
 }
 
+static void launch_border_sweeps(Launcher &L, const Dev &d, bool rode);
+
+// panel q of a border of two panels: the per-column arrays (S_pb, Zb, the level and PCR copies) start at its columns,
+// so the NBP-column sweeps and k_border_gram run on it unchanged
+static Dev border_panel(const Dev &d, int q) {
+    Dev e = d;
+    e.Spb += (size_t)q * d.nf_pad * 6 * NBP;
+    e.Zb += (size_t)q * d.nf_pad * 6 * NBP;
+    for (int l = 0; l < d.n_levels; ++l)
+        if (e.lev[l].B) e.lev[l].B += (size_t)q * d.lev[l].n * BD * NBP;
+    if (d.pcr.level >= 0 && d.pcr.keep) {
+        e.pcr.Bb += (size_t)q * d.pcr.n * BD * NBP;
+        e.pcr.yB += (size_t)q * d.pcr.n * BD * NBP;
+    }
+    return e;
+}
+
 // after launch_bcr: x0 = S_pp^-1 (-g_p^) and the level factors are in place
 void launch_border_solve(Launcher &L, const Dev &d) {
-    // rode: launch_bcr has taken the border columns through the forward part already (yB = G^-1 B per block and level
-    // sit where k_bcrm_fwd would have left them); only the backward part is left
-    const bool rode = bcr_border_rides(d);
+    if (d.np > 1) {       // two panels: each goes through the sweeps on its own (a wide border never rides: bcr_border_rides)
+        for (int q = 0; q < d.np; ++q) launch_border_sweeps(L, border_panel(d, q), false);
+        launch_border_finish(L, d);
+        return;
+    }
+    launch_border_sweeps(L, d, bcr_border_rides(d));
+    launch_border_finish(L, d);
+}
+
+// Zb = S_pp^-1 S_pb for one panel of NBP columns.  rode: launch_bcr has taken the border columns through the forward part
+// already (yB = G^-1 B per block and level sit where k_bcrm_fwd would have left them); only the backward part is left
+static void launch_border_sweeps(Launcher &L, const Dev &d, bool rode) {
     if (d.pcr.level >= 0 && d.pcr.keep) {
         // the solve ran the parallel plan: the border columns follow through the kept factors of every step
         const int n = d.pcr.n;
@@ -458,7 +602,6 @@ void launch_border_solve(Launcher &L, const Dev &d) {
             LAUNCH(KC_BORDER, k_bcrm_fwd, dim3(n), dim3(MR_THREADS), SH_FWD, d, d.pcr.steps, 1, 2);
         }
         LAUNCH(KC_BORDER, k_bcrm_bwd, dim3(n), dim3(MR_THREADS), SH_BWD, d, 0, 1, 2, rode && bcr_rhs_rides_in_bwd(d) ? 1 : 0);
-        launch_border_finish(L, d);
         return;
     }
     const int nl = d.n_levels;
@@ -474,13 +617,23 @@ void launch_border_solve(Launcher &L, const Dev &d) {
     LAUNCH(KC_BORDER, k_bcrm_bwd, dim3(1), dim3(MR_THREADS), SH_BWD, d, nl - 1, 1, 0, 0);
     for (int l = nl - 2; l >= 0; --l)
         LAUNCH(KC_BORDER, k_bcrm_bwd, dim3(d.lev[l].n / 2), dim3(MR_THREADS), SH_BWD, d, l, 0, 0, 0);
-    launch_border_finish(L, d);
 }
 
 // with Z = S_pp^-1 S_pb in Zb: the border system, its solve, and the correction of the pose step
 void launch_border_finish(Launcher &L, const Dev &d) {
-    LAUNCH(KC_BORDER, k_border_gram, dim3(d.n_gram), dim3(1024), 0, d);
-    LAUNCH(KC_SMALL, k_border_solve, dim3(1), dim3(1024), 0, d);
+    if (d.np > 1) {       // two panels: the Gram partials of every panel pair (S_pb panel a, Zb panel b -> pair 2 a + b)
+        for (int a = 0; a < d.np; ++a)
+            for (int b = 0; b < d.np; ++b) {
+                Dev e = border_panel(d, a);
+                e.Zb = border_panel(d, b).Zb;
+                e.part_g += (size_t)(2 * a + b) * d.n_gram * (NBP * NBP + NBP);
+                LAUNCH(KC_BORDER, k_border_gram, dim3(d.n_gram), dim3(1024), 0, e);
+            }
+        LAUNCH(KC_SMALL, k_border_solve_wide, dim3(1), dim3(256), 0, d);
+    } else {
+        LAUNCH(KC_BORDER, k_border_gram, dim3(d.n_gram), dim3(1024), 0, d);
+        LAUNCH(KC_SMALL, k_border_solve, dim3(1), dim3(1024), 0, d);
+    }
     LAUNCH(KC_SMALL, k_border_apply, dim3((d.nf_pad * 6 + 255) / 256), dim3(256), 0, d);
 }
 

@@ -79,10 +79,10 @@ static __device__ __forceinline__ void check_body(Dev &d, int fused_parts, bool 
     }
     // free shared blocks: lane 0's walk below reads the blocks and their gradient from LDS (up to r04 from global memory, entry
     // by entry -- two dozen dependent round trips in front of the termination tests); the barriers of the sums publish the copy
-    __shared__ double s_sh[64], s_gb[NBP];
+    __shared__ double s_sh[64], s_gb[NBP_MAX];
     if (d.nb && lin) {
         if ((int)threadIdx.x < d.nsh && threadIdx.x < 64) s_sh[threadIdx.x] = d.sh[threadIdx.x];
-        if ((int)threadIdx.x < d.nb) s_gb[threadIdx.x] = d.bsys[BS_G + threadIdx.x];
+        if ((int)threadIdx.x < d.nb) s_gb[threadIdx.x] = d.bsys[bs_vec(d.nbw, BSV_G) + threadIdx.x];
     }
     const double gmp = block_max(gm, sm);
     const double xnp = block_sum(xn, sm);

@@ -560,10 +560,11 @@ __global__ __launch_bounds__(256) void k_dn_border_rows(Dev d, int store) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.n_dn) return;
     const size_t lda = (size_t)d.dn_pad;
-    for (int c = 0; c < d.nb; ++c) {
+    for (int c = 0; c < d.nb; ++c) {        // (1 + nb <= DN_BS rows: a border of two panels fits the block row too)
         double *row = d.dn_S + ((size_t)d.dn_pad + 1 + c) * lda;
-        if (store) d.Zb[(size_t)i * NBP + c] = row[i];         // Z = S_pp^-1 S_pb
-        else row[i] = d.Spb[(size_t)i * NBP + c];
+        const size_t at = bcol_at((size_t)d.nf_pad * 6, (size_t)i, c);
+        if (store) d.Zb[at] = row[i];         // Z = S_pp^-1 S_pb
+        else row[i] = d.Spb[at];
     }
 }
 

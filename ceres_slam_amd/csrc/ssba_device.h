@@ -560,7 +560,7 @@ static __device__ __forceinline__ void ph_border_update_block(const Dev &d, int 
         else if (in) col = d.b_tex >= 0 ? d.b_tex + (i - 3 - M3) : -1;
         double db = 0.0;    // LM: beta = 1, gamma = 0; dogleg: beta * delta_gn + gamma * v
         if (col >= 0) {
-            db = st.ls_alpha * (st.beta * d.bsys[BS_DB + col] + st.gamma * d.bsys[BS_VB + col]);
+            db = st.ls_alpha * (st.beta * d.bsys[bs_vec(d.nbw, BSV_DB) + col] + st.gamma * d.bsys[bs_vec(d.nbw, BSV_VB) + col]);
             if (!isfinite(db)) bad = 1.0;
         }
         const double x3[3] = {__shfl(old, 0, 64), __shfl(old, 1, 64), __shfl(old, 2, 64)};
@@ -597,10 +597,11 @@ static __device__ __forceinline__ void ph_dogleg_border_lane(const Dev &d) {
     const State &st = *d.st;
     if (st.terminated || st.dl_reuse) return;
     double gsq = 0.0, nsq = 0.0, dot = 0.0;
+    const int w = d.nbw;
     for (int c = 0; c < d.nb; ++c) {
-        const double s = d.bsys[BS_S + c], s2 = s * s, g = d.bsys[BS_G + c], gn = d.bsys[BS_DB + c];
-        const double D2 = fmin(fmax(d.bsys[BS_H + c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag);
-        d.bsys[BS_VB + c] = s2 * g / D2;
+        const double s = d.bsys[bs_vec(w, BSV_S) + c], s2 = s * s, g = d.bsys[bs_vec(w, BSV_G) + c], gn = d.bsys[bs_vec(w, BSV_DB) + c];
+        const double D2 = fmin(fmax(d.bsys[bs_vec(w, BSV_H) + c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag);
+        d.bsys[bs_vec(w, BSV_VB) + c] = s2 * g / D2;
         gsq += s2 * g * g / D2;
         nsq += D2 * gn * gn / s2;
         dot += g * gn;

@@ -858,7 +858,7 @@ template <bool DN> __global__ __launch_bounds__(256, 2) void k_ph_backsub_eval(D
 #pragma unroll
         for (int q = 0; q < NBQ; ++q) {
             const int c = d.nb ? bcol(d, x.mat, q) : -1;
-            dbq[q] = c >= 0 ? d.bsys[BS_DB + c] : 0.0;
+            dbq[q] = c >= 0 ? d.bsys[bs_vec(d.nbw, BSV_DB) + c] : 0.0;
         }
         // e = J_p delta_p + J_b delta_b of an observation row; tt = g_l + sum J_l^T e, and the model cost change
         // -(J d)^T (r + J d / 2) of this landmark's rows is
@@ -1104,34 +1104,37 @@ __global__ __launch_bounds__(64) void k_ph_border_colsum(Dev d) {
 
 // scatters the summed partials into the border system (one block): thread (c, c2) owns entry (c, c2) of S_bb and
 // collects its contributions -- one per material for a material's own columns, all materials for the light columns --
-// in material order (the first version did the whole scatter on one lane: 35 us)
+// in material order (the first version did the whole scatter on one lane: 35 us).  A border of two panels (nbw = 64) has
+// four entries per thread.
 __global__ __launch_bounds__(1024) void k_ph_border_reduce(Dev d) {
     const State &st = *d.st;
     if (st.terminated || st.dl_reuse) return;
     __shared__ double tot[SSBA_MAX_MATERIALS_DEV * NBV];
-    const int t = threadIdx.x;
-    for (int idx = t; idx < d.M * NBV; idx += 1024) tot[idx] = d.part_b[(size_t)d.n_lm_blocks * d.M * NBV + idx];
+    const int w = d.nbw;
+    for (int idx = threadIdx.x; idx < d.M * NBV; idx += 1024) tot[idx] = d.part_b[(size_t)d.n_lm_blocks * d.M * NBV + idx];
     __syncthreads();
-    const int c = t / NBP, c2 = t - c * NBP;
-    double sv = 0.0, rhs = 0.0, hh = 0.0, gg = 0.0;
-    for (int m = 0; m < d.M; ++m) {
-        const double *tm = tot + m * NBV;
-        int q = -1, q2 = -1;
+    for (int t = threadIdx.x; t < w * w; t += 1024) {
+        const int c = t / w, c2 = t - c * w;
+        double sv = 0.0, rhs = 0.0, hh = 0.0, gg = 0.0;
+        for (int m = 0; m < d.M; ++m) {
+            const double *tm = tot + m * NBV;
+            int q = -1, q2 = -1;
 #pragma unroll
-        for (int x = 0; x < NBQ; ++x) {
-            const int cc = bcol(d, (uint32_t)m, x);
-            if (cc == c) q = x;
-            if (cc == c2) q2 = x;
+            for (int x = 0; x < NBQ; ++x) {
+                const int cc = bcol(d, (uint32_t)m, x);
+                if (cc == c) q = x;
+                if (cc == c2) q2 = x;
+            }
+            if (q >= 0 && q2 >= 0) sv += tm[q <= q2 ? tri7(q, q2) : tri7(q2, q)];
+            if (q >= 0 && c2 == 0) { rhs += tm[28 + q]; hh += tm[35 + q]; gg += tm[42 + q]; }
         }
-        if (q >= 0 && q2 >= 0) sv += tm[q <= q2 ? tri7(q, q2) : tri7(q2, q)];
-        if (q >= 0 && c2 == 0) { rhs += tm[28 + q]; hh += tm[35 + q]; gg += tm[42 + q]; }
-    }
-    d.bsys[BS_SBB + c * NBP + c2] = (c < d.nb && c2 < d.nb) ? sv : 0.0;
-    if (c2 == 0) {
-        d.bsys[BS_RHS + c] = c < d.nb ? rhs : 0.0;
-        d.bsys[BS_H + c] = c < d.nb ? hh : 0.0;
-        d.bsys[BS_G + c] = c < d.nb ? gg : 0.0;
-        if (st.iteration == 0 && c < d.nb) d.bsys[BS_S + c] = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(hh)) : 1.0;
+        d.bsys[BS_SBB + c * w + c2] = (c < d.nb && c2 < d.nb) ? sv : 0.0;
+        if (c2 == 0) {
+            d.bsys[bs_vec(w, BSV_RHS) + c] = c < d.nb ? rhs : 0.0;
+            d.bsys[bs_vec(w, BSV_H) + c] = c < d.nb ? hh : 0.0;
+            d.bsys[bs_vec(w, BSV_G) + c] = c < d.nb ? gg : 0.0;
+            if (st.iteration == 0 && c < d.nb) d.bsys[bs_vec(w, BSV_S) + c] = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(hh)) : 1.0;
+        }
     }
 }
 
@@ -1216,7 +1219,7 @@ template <bool DN> __global__ __launch_bounds__(BP_THREADS) void k_ph_border_pos
             int a, col;
             if (m < d.M) { a = t / 4; col = bcol(d, (uint32_t)m, t - a * 4); }
             else { a = t / 3; col = (t < 18) ? bcol(d, 0u, 4 + (t - a * 3)) : -1; }
-            if (col >= 0) d.Spb[((size_t)f * 6 + a) * NBP + col] = v;
+            if (col >= 0) d.Spb[bcol_at((size_t)d.nf_pad * 6, (size_t)f * 6 + a, col)] = v;
         }
     }
 }
@@ -1256,8 +1259,8 @@ template <bool DN> __global__ __launch_bounds__(256, 2) void k_ph_dogleg_gn(Dev 
 #pragma unroll
         for (int q = 0; q < NBQ; ++q) {
             const int c = d.nb ? bcol(d, x.mat, q) : -1;
-            gbq[q] = c >= 0 ? d.bsys[BS_DB + c] : 0.0;
-            vbq[q] = c >= 0 ? d.bsys[BS_VB + c] : 0.0;
+            gbq[q] = c >= 0 ? d.bsys[bs_vec(d.nbw, BSV_DB) + c] : 0.0;
+            vbq[q] = c >= 0 ? d.bsys[bs_vec(d.nbw, BSV_VB) + c] : 0.0;
         }
         // ONE pass over the landmark's rows (r04: a second one formed J v and J gn row by row).  With e_g = J_p gn_p + J_b gn_b and
         // e_v = J_p v_p + J_b v_b of a row,  J gn = J_l dl + e_g  and  J v = J_l vl + e_v,  so over the landmark's rows
@@ -1450,7 +1453,7 @@ template <bool DN> __global__ __launch_bounds__(256, 2) void k_ph_ls_probe(Dev d
 #pragma unroll
         for (int q = 0; q < NBQ; ++q) {
             const int c = d.nb ? bcol(d, x.mat, q) : -1;
-            dbq[q] = c >= 0 ? st.beta * d.bsys[BS_DB + c] + st.gamma * d.bsys[BS_VB + c] : 0.0;
+            dbq[q] = c >= 0 ? st.beta * d.bsys[bs_vec(d.nbw, BSV_DB) + c] + st.gamma * d.bsys[bs_vec(d.nbw, BSV_VB) + c] : 0.0;
         }
         np_[0] = x.p[0] + sdl[0]; np_[1] = x.p[1] + sdl[1]; np_[2] = x.p[2] + sdl[2];
         unit_plus(x.n, sdl + 3, nn);
@@ -1524,8 +1527,8 @@ __device__ inline void ls_park(State &st) {
 static __device__ __forceinline__ void ls_stage_border(const Dev &d, const State &st, double *sv, double *sg) {
     const int c = threadIdx.x;
     if (c < d.nb) {
-        sv[c] = st.beta * d.bsys[BS_DB + c] + st.gamma * d.bsys[BS_VB + c];
-        sg[c] = d.bsys[BS_G + c];
+        sv[c] = st.beta * d.bsys[bs_vec(d.nbw, BSV_DB) + c] + st.gamma * d.bsys[bs_vec(d.nbw, BSV_VB) + c];
+        sg[c] = d.bsys[bs_vec(d.nbw, BSV_G) + c];
     }
 }
 // The pose part of max|delta| and g . delta for a 1024-lane work-group: entry i = 6 f + c of the pose step.  Eight trips' loads in
@@ -1592,7 +1595,7 @@ __global__ __launch_bounds__(1024) void k_ph_ls_fast(Dev d, int n_eval_parts, in
     double pmax = 0.0, pgd = 0.0, pbad = 0.0;
     ls_pose_terms(d, st, pmax, pgd);
     for (int i = threadIdx.x; i < d.n_pose_blocks + (d.nb ? 1 : 0); i += 1024) pbad += d.part_pose[i * NPP + 1];
-    __shared__ double sbv[NBP], sbg[NBP];
+    __shared__ double sbv[NBP_MAX], sbg[NBP_MAX];
     ls_stage_border(d, st, sbv, sbg);
     lmax = block_max(lmax, sm); lgd = block_sum(lgd, sm);
     pmax = block_max(pmax, sm); pgd = block_sum(pgd, sm); pbad = block_sum(pbad, sm);
@@ -1666,7 +1669,7 @@ __global__ __launch_bounds__(1024) void k_ph_ls_reduce(Dev d, int ls_round, int 
     double pmax = 0.0, pgd = 0.0, pbad = 0.0;
     ls_pose_terms(d, st, pmax, pgd);
     for (int i = threadIdx.x; i < d.n_pose_blocks + (d.nb ? 1 : 0); i += 1024) pbad += d.part_pose[i * NPP + 1];
-    __shared__ double sbv[NBP], sbg[NBP];
+    __shared__ double sbv[NBP_MAX], sbg[NBP_MAX];
     ls_stage_border(d, st, sbv, sbg);
     double cost = block_sum(acc[0], sm), dphi = block_sum(acc[1], sm), dn = block_sum(acc[2], sm), bad = block_sum(acc[3], sm);
     double lmax = block_max(acc[4], sm), lgd = block_sum(acc[5], sm);

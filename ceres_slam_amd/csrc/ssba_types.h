@@ -18,7 +18,13 @@
 //     whole region is one contiguous "exchange vector" (the only thing ranks have
 //     to all-reduce when landmarks are sharded).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#define SSBA_HD __host__ __device__
+#else
+#define SSBA_HD
+#endif
 
 namespace ssba {
 
@@ -32,7 +38,8 @@ constexpr int MAX_LEVELS = 18;          // plain levels below a parallel top of 
 constexpr int MAX_SLEVELS = 1;          // the separator system of a partitioned (multi-rank) solve: one level, parallel cyclic reduction
 constexpr int MAX_SEP = 65;             // separators = ranks - 1
 constexpr int NSCAL = 16;
-constexpr int NBP = 32;                 // padded width of the border of free shared blocks (nb <= NBP)
+constexpr int NBP = 32;                 // columns per panel of the border of free shared blocks (nb <= NBP: one panel)
+constexpr int NBP_MAX = 2 * NBP;        // widest border: two panels (nb <= 63 = 3 + 4 SSBA_MAX_MATERIALS)
 constexpr int NBQ = 7;                  // border entries one intensity row touches: [phong 3 | kd | light 3]
 constexpr int NPP = 4;                  // pose partials per block: |dx|^2, non-finite, unary-factor candidate cost, unary-factor model change
 constexpr int NDL = 6;                  // dogleg partials: |gradient_|^2, |gn|^2, gradient_.gn, |J v|^2, |J gn|^2, Jv.Jgn
@@ -256,11 +263,15 @@ struct Dev {
     double *Hpb, *HpbL;                             // nf_pad*6 x NBP   H_pb (k_ph_hpb, on linearisation); P x M x 18 light-column partials
     double *slabB;                                  // n_slabs x 72 x NBP   border tiles of the Schur items
     double *part_b;                                 // n_lm_blocks * M * NBV
-    double *Spb;                                    // nf_pad*6 x NBP   S_pb (rows of free poses)
-    double *Zb;                                     // nf_pad*6 x NBP   S_pp^-1 S_pb
-    double *part_g;                                 // gram partials: n_gram x (NBP*NBP + NBP)
+    // a border of nb > NBP columns is stored in np = 2 panels of NBP columns, panel-major: column c of a per-column array
+    // sits in panel c / NBP, each panel an NBP-strided array of its own (bcol_at); the level / PCR copies (lev[l].B,
+    // pcr.Bb, pcr.yB) likewise, one panel after the other
+    int np, nbw;                                    // panels (1 or 2), width of the border system nbw = np * NBP
+    double *Spb;                                    // np x nf_pad*6 x NBP   S_pb (rows of free poses)
+    double *Zb;                                     // np x nf_pad*6 x NBP   S_pp^-1 S_pb
+    double *part_g;                                 // gram partials: np * np panel pairs x n_gram x (NBP*NBP + NBP)
     int n_gram;
-    // border system, NBP-strided: Sbb (NBP*NBP) | rhsb | gb | hb | sb | db | vb
+    // border system, nbw-strided: Sbb (nbw*nbw) | rhsb | gb | hb | sb | db | vb (bs_vec)
     double *bsys;
     // bounds on the shared blocks (SetParameterLower/UpperBound): [ka, ks, alpha, kd]; projected Plus +
     // Armijo line search when constrained
@@ -311,7 +322,16 @@ constexpr int NLS_OUT = 8;    // cost, phi', |dx_l|^2, nonfinite_l, max|delta|, 
 // landmark sharding with bounds: the exchange vector of a line-search evaluation, behind the search state in ls_out:
 // [cost, phi', |dx_l|^2, nonfinite_l, g_l . delta_l, 0, 0, 0 | max|delta_l| of rank r in slot 8 + r (a maximum through the SUM exchange)]
 constexpr int NLS_X = 8, NLS_X_RANKS = 64;
-constexpr int BS_SBB = 0, BS_RHS = NBP * NBP, BS_G = BS_RHS + NBP, BS_H = BS_G + NBP, BS_S = BS_H + NBP,
-              BS_DB = BS_S + NBP, BS_VB = BS_DB + NBP, BS_COUNT = BS_VB + NBP;   // VB: dogleg v_b = s^2 g / D^2
+// border system of width w = Dev::nbw: S_bb (w x w) at 0, then the vectors of the BSV_* kinds, w entries each
+constexpr int BSV_RHS = 0, BSV_G = 1, BSV_H = 2, BSV_S = 3, BSV_DB = 4, BSV_VB = 5, BSV_COUNT = 6;   // VB: dogleg v_b = s^2 g / D^2
+SSBA_HD constexpr int bs_vec(int w, int kind) { return w * w + kind * w; }
+SSBA_HD constexpr int bs_count(int w) { return bs_vec(w, BSV_COUNT); }
+// the one-panel layout (nbw = NBP: every border of NBP columns or fewer, the closure border among them)
+constexpr int BS_SBB = 0, BS_RHS = bs_vec(NBP, BSV_RHS), BS_G = bs_vec(NBP, BSV_G), BS_H = bs_vec(NBP, BSV_H), BS_S = bs_vec(NBP, BSV_S),
+              BS_DB = bs_vec(NBP, BSV_DB), BS_VB = bs_vec(NBP, BSV_VB), BS_COUNT = bs_count(NBP);
+// entry (row, column c) of a panel-major per-column array of the border (Spb, Zb) with rows rows per panel
+SSBA_HD inline size_t bcol_at(size_t rows, size_t row, int c) {
+    return (size_t)(c / NBP) * rows * NBP + row * NBP + (size_t)(c % NBP);
+}
 
 }  // namespace ssba

@@ -310,14 +310,17 @@ SSBA_API int ssba_armijo_trace(const double *values, const double *gradients, in
  * (:191-193) and on a directional light (:201-204).  Landmark blocks become [position | normal]
  * (6-D local step); the shared blocks -- the light, and the Phong parameters [ka, ks, alpha] and the
  * texture kd of each material -- are a dense border of the reduced camera system, solved together
- * with the poses.
+ * with the poses.  The border has nb = 3 + 4M columns with every kind free (M <= SSBA_MAX_MATERIALS:
+ * nb <= 63); a border of more than 32 columns is kept as two panels of 32 and solves on one GPU.
  *
  * ssba_add_normal_blocks    : replaces AddParameterBlock / SetParameterization of
  *                             map_vertices[j].normal(); normals (num*3) caller-owned, updated in
  *                             place by ssba_solve like the points; num must equal the point count.
  * ssba_add_material_blocks  : material()->phong_params().data() (M*3) and texture()->data() (M),
  *                             caller-owned and updated in place when free; material_of_point maps
- *                             each point to its material (copied).  M <= SSBA_MAX_MATERIALS.
+ *                             each point to its material (copied).  M <= SSBA_MAX_MATERIALS, with
+ *                             any set of free kinds (landmark sharding: borders of at most 32
+ *                             columns, i.e. seven materials with every kind free).
  * ssba_add_light_block      : dataset.light_pos.data() (light_type 0) or light_dir.data() (1),
  *                             caller-owned, updated in place when free.
  * ssba_set_shared_block_constant : SetParameterBlockConstant on ALL blocks of one kind
@@ -346,7 +349,8 @@ SSBA_API int ssba_armijo_trace(const double *values, const double *gradients, in
  * terms shard by landmarks like the stereo terms (ssba_set_distributed); with FREE shared blocks the
  * border sums are exchanged in the all-reduce mode only (DOGLEG and bounds included: the projected line
  * search adds its sums over the ranks at every evaluation and is driven by the host in lockstep) -- the
- * partitioned reduced solve with free shared blocks returns SSBA_ERR_UNSUPPORTED. */
+ * partitioned reduced solve with free shared blocks returns SSBA_ERR_UNSUPPORTED, and so does landmark
+ * sharding with a border of more than 32 columns. */
 #define SSBA_MAX_MATERIALS 15
 enum { SSBA_BLOCK_LIGHT = 0, SSBA_BLOCK_PHONG = 1, SSBA_BLOCK_TEXTURE = 2 };
 SSBA_API int ssba_add_normal_blocks(ssba_problem *p, double *normals, uint32_t num);
@@ -359,7 +363,8 @@ SSBA_API int ssba_add_lighting_observations(ssba_problem *p, const double *inten
                                    double intensity_stiffness, const double *normal_obs,
                                    const double normal_stiffness[9], uint64_t num);
 /* test hook: the border of the last ssba_lm_step -- nb = 3 [light] + 3M [Phong] + M [texture] as
- * freed (that column order), S_pb (6*num_free_poses x nb), S_bb (nb x nb, damped), rhs_b (nb) of
+ * freed (that column order; nb <= 63, every column whichever panel holds it), S_pb
+ * (6*num_free_poses x nb), S_bb (nb x nb, damped), rhs_b (nb) of
  *   [S S_pb; S_pb^T S_bb] [delta_p; delta_b] = [rhs; rhs_b]
  * and the border step delta_b (nb).  Any output may be NULL. */
 SSBA_API int ssba_border_system(ssba_problem *p, uint32_t *nb, double *S_pb, double *S_bb, double *rhs_b,

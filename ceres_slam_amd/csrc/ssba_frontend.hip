@@ -29,46 +29,39 @@ __device__ __forceinline__ void cross3d(const double a[3], const double b[3], do
     o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// symmetric 3x3 eigen-decomposition by cyclic Jacobi rotations, eigenvalues descending, V columns
-__device__ void jacobi_eig3(const double A[9], double w[3], double V[9]) {
-    double a[9];
-    for (int i = 0; i < 9; ++i) { a[i] = A[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        const double off = a[1] * a[1] + a[2] * a[2] + a[5] * a[5];
-        if (off < 1e-300) break;
+// one-sided (Hestenes) Jacobi on a 3x3 W (row-major): plane rotations from the right until the columns of G = W V are
+// orthogonal, |g_p . g_q| <= 2^-51 |g_p||g_q| (the rounding of the dot product itself; 4 to 6 sweeps).  The singular values
+// are the column norms and V holds the right singular vectors.  Nothing is squared before the rotation angles are formed,
+// so the pair (s2, v2) keeps a relative accuracy of u s1 / s2 where an eigen-decomposition of W^T W leaves u (s1 / s2)^2.
+__device__ void jacobi_svd3(const double W[9], double G[9], double V[9]) {
+    for (int i = 0; i < 9; ++i) { G[i] = W[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 12; ++sweep) {
+        bool rotated = false;
         for (int p = 0; p < 2; ++p)
             for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[3 * p + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[3 * q + q] - a[3 * p + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double al = G[p] * G[p] + G[3 + p] * G[3 + p] + G[6 + p] * G[6 + p];
+                const double be = G[q] * G[q] + G[3 + q] * G[3 + q] + G[6 + q] * G[6 + q];
+                const double ga = G[p] * G[q] + G[3 + p] * G[3 + q] + G[6 + p] * G[6 + q];
+                if (ga == 0.0 || fabs(ga) <= 0x1p-51 * sqrt(al) * sqrt(be)) continue;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
                 for (int k = 0; k < 3; ++k) {
-                    const double akp = a[3 * k + p], akq = a[3 * k + q];
-                    a[3 * k + p] = c * akp - s * akq; a[3 * k + q] = s * akp + c * akq;
+                    const double gp = G[3 * k + p], gq = G[3 * k + q];
+                    G[3 * k + p] = c * gp - s * gq; G[3 * k + q] = s * gp + c * gq;
+                    const double vp = V[3 * k + p], vq = V[3 * k + q];
+                    V[3 * k + p] = c * vp - s * vq; V[3 * k + q] = s * vp + c * vq;
                 }
-                for (int k = 0; k < 3; ++k) {
-                    const double apk = a[3 * p + k], aqk = a[3 * q + k];
-                    a[3 * p + k] = c * apk - s * aqk; a[3 * q + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double vkp = V[3 * k + p], vkq = V[3 * k + q];
-                    V[3 * k + p] = c * vkp - s * vkq; V[3 * k + q] = s * vkp + c * vkq;
-                }
+                rotated = true;
             }
+        if (!rotated) break;
     }
-    int ord[3] = {0, 1, 2};
-    const double dg[3] = {a[0], a[4], a[8]};
-    for (int i = 0; i < 2; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (dg[ord[j]] > dg[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
-    double Vs[9];
-    for (int c = 0; c < 3; ++c) { w[c] = dg[ord[c]]; for (int r = 0; r < 3; ++r) Vs[3 * r + c] = V[3 * r + ord[c]]; }
-    for (int i = 0; i < 9; ++i) V[i] = Vs[i];
 }
 
 // PointCloudAligner::compute_transformation (point_cloud_aligner.cpp:12-62) for 3 points: W has rank <= 2, so
-// C_1_0 = U diag(1, 1, det U det V) V^T = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T.  T = [t | R row-major].
+// C_1_0 = U diag(1, 1, det U det V) V^T = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T.  The two leading singular pairs come
+// from a one-sided Jacobi SVD of W itself (the reference's Eigen::JacobiSVD works on W too): u_i = (W v_i) / s_i are the
+// two longest columns of W V.  T = [t | R row-major].
 __device__ void align3(const double s0[9], const double s1[9], double T[12]) {
     double c0[3], c1[3];
     for (int c = 0; c < 3; ++c) { c0[c] = (s0[c] + s0[3 + c] + s0[6 + c]) / 3.0; c1[c] = (s1[c] + s1[3 + c] + s1[6 + c]) / 3.0; }
@@ -79,31 +72,41 @@ __device__ void align3(const double s0[9], const double s1[9], double T[12]) {
             for (int i = 0; i < 3; ++i) v += (s1[3 * i + r] - c1[r]) * (s0[3 * i + c] - c0[c]);
             W[3 * r + c] = v / 3.0;
         }
-    double WtW[9], w[3], V[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            double v = 0.0;
-            for (int k = 0; k < 3; ++k) v += W[3 * k + r] * W[3 * k + c];
-            WtW[3 * r + c] = v;
-        }
-    jacobi_eig3(WtW, w, V);
-    const double v1[3] = {V[0], V[3], V[6]}, v2[3] = {V[1], V[4], V[7]};
-    double v3[3], u1[3], u2[3], u3[3];
-    for (int r = 0; r < 3; ++r) {
-        u1[r] = W[3 * r] * v1[0] + W[3 * r + 1] * v1[1] + W[3 * r + 2] * v1[2];
-        u2[r] = W[3 * r] * v2[0] + W[3 * r + 1] * v2[1] + W[3 * r + 2] * v2[2];
-    }
-    // W = U S V^T: u_i = W v_i / s_i.  A degenerate sample (collinear or coincident points: rank W < 2) has s_i = 0;
-    // an SVD still returns orthonormal U columns there -- complete the basis instead of dividing by zero
-    // (point_cloud_aligner.cpp:49-55 uses JacobiSVD, which does the same up to the choice of the null-space basis)
-    const double n1 = sqrt(dot3d(u1, u1));
-    if (n1 > 1e-300) { for (int r = 0; r < 3; ++r) u1[r] /= n1; }
+    double G[9], V[9], sv[3];
+    jacobi_svd3(W, G, V);
+    for (int c = 0; c < 3; ++c) sv[c] = sqrt(G[c] * G[c] + G[3 + c] * G[3 + c] + G[6 + c] * G[6 + c]);
+    int i1 = 0;                                   // the two largest singular values, the first of equals
+    if (sv[1] > sv[i1]) i1 = 1;
+    if (sv[2] > sv[i1]) i1 = 2;
+    int i2 = i1 == 0 ? 1 : 0;
+    for (int c = i2 + 1; c < 3; ++c) if (c != i1 && sv[c] > sv[i2]) i2 = c;
+    const double n1 = sv[i1], n2 = sv[i2];
+    double v1[3] = {V[i1], V[3 + i1], V[6 + i1]}, v2[3] = {V[i2], V[3 + i2], V[6 + i2]};
+    double u1[3] = {G[i1], G[3 + i1], G[6 + i1]}, u2[3] = {G[i2], G[3 + i2], G[6 + i2]};
+    double v3[3], u3[3];
+    // the accumulated rotations leave V orthonormal to a few u per rotation: bring v1, v2 back to one rounding
+    const double nv1 = sqrt(dot3d(v1, v1));
+    for (int r = 0; r < 3; ++r) v1[r] /= nv1;
+    const double dv = dot3d(v1, v2);
+    for (int r = 0; r < 3; ++r) v2[r] -= dv * v1[r];
+    const double nv2 = sqrt(dot3d(v2, v2));
+    for (int r = 0; r < 3; ++r) v2[r] /= nv2;
+    // A degenerate sample (collinear or coincident points: rank W < 2) has s_i = 0; an SVD still returns orthonormal U
+    // columns there -- complete the basis instead of dividing by zero (point_cloud_aligner.cpp:49-55 uses JacobiSVD,
+    // which does the same up to the choice of the null-space basis).  s2 <= 2^-50 s1 is below the rounding of W's own
+    // entries: such a column holds no direction.
+    if (n1 > 0.0) { for (int r = 0; r < 3; ++r) u1[r] /= n1; }
     else { u1[0] = 1.0; u1[1] = 0.0; u1[2] = 0.0; }
-    const double d12 = dot3d(u1, u2);
-    for (int r = 0; r < 3; ++r) u2[r] -= d12 * u1[r];
-    const double n2 = sqrt(dot3d(u2, u2));
-    if (n2 > 1e-12 * (n1 > 1e-300 ? n1 : 1.0)) { for (int r = 0; r < 3; ++r) u2[r] /= n2; }
-    else {      // any unit vector orthogonal to u1
+    bool have_u2 = n2 > 0x1p-50 * n1;
+    if (have_u2) {
+        for (int r = 0; r < 3; ++r) u2[r] /= n2;
+        const double d12 = dot3d(u1, u2);             // orthogonal to the rotations' stopping bound already
+        for (int r = 0; r < 3; ++r) u2[r] -= d12 * u1[r];
+        const double m2 = sqrt(dot3d(u2, u2));
+        have_u2 = m2 > 0.5;
+        if (have_u2) for (int r = 0; r < 3; ++r) u2[r] /= m2;
+    }
+    if (!have_u2) {      // any unit vector orthogonal to u1
         const int m = fabs(u1[0]) <= fabs(u1[1]) ? (fabs(u1[0]) <= fabs(u1[2]) ? 0 : 2) : (fabs(u1[1]) <= fabs(u1[2]) ? 1 : 2);
         double e[3] = {0.0, 0.0, 0.0};
         e[m] = 1.0;

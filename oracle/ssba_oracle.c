@@ -2590,43 +2590,33 @@ void orc_ransac_samples(uint32_t n, uint32_t num_iters, int variant, uint32_t *i
     }
 }
 
-/* symmetric 3x3 eigen-decomposition by cyclic Jacobi rotations: A = V diag(w) V^T, eigenvalues descending */
-static void jacobi_eig3(const double A[9], double w[3], double V[9]) {
-    double a[9];
-    memcpy(a, A, sizeof a);
-    for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        const double off = a[1] * a[1] + a[2] * a[2] + a[5] * a[5];
-        if (off < 1e-300) break;
+/* one-sided (Hestenes) Jacobi on a 3x3 W (row-major): plane rotations from the right until the columns of G = W V are
+ * orthogonal, |g_p . g_q| <= 2^-51 |g_p||g_q| (the rounding of the dot product itself; 4 to 6 sweeps); singular values =
+ * column norms, V = right singular vectors.  Nothing is squared before the angles are formed: (s2, v2) keeps u s1 / s2
+ * where eig(W^T W) leaves u (s1 / s2)^2. */
+static void jacobi_svd3(const double W[9], double G[9], double V[9]) {
+    for (int i = 0; i < 9; ++i) { G[i] = W[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 12; ++sweep) {
+        int rotated = 0;
         for (int p = 0; p < 2; ++p)
             for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[3 * p + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[3 * q + q] - a[3 * p + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double al = G[p] * G[p] + G[3 + p] * G[3 + p] + G[6 + p] * G[6 + p];
+                const double be = G[q] * G[q] + G[3 + q] * G[3 + q] + G[6 + q] * G[6 + q];
+                const double ga = G[p] * G[q] + G[3 + p] * G[3 + q] + G[6 + p] * G[6 + q];
+                if (ga == 0.0 || fabs(ga) <= 0x1p-51 * sqrt(al) * sqrt(be)) continue;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 3; ++k) {        /* A <- A J */
-                    const double akp = a[3 * k + p], akq = a[3 * k + q];
-                    a[3 * k + p] = c * akp - s * akq; a[3 * k + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; ++k) {        /* A <- J^T A */
-                    const double apk = a[3 * p + k], aqk = a[3 * q + k];
-                    a[3 * p + k] = c * apk - s * aqk; a[3 * q + k] = s * apk + c * aqk;
-                }
                 for (int k = 0; k < 3; ++k) {
-                    const double vkp = V[3 * k + p], vkq = V[3 * k + q];
-                    V[3 * k + p] = c * vkp - s * vkq; V[3 * k + q] = s * vkp + c * vkq;
+                    const double gp = G[3 * k + p], gq = G[3 * k + q];
+                    G[3 * k + p] = c * gp - s * gq; G[3 * k + q] = s * gp + c * gq;
+                    const double vp = V[3 * k + p], vq = V[3 * k + q];
+                    V[3 * k + p] = c * vp - s * vq; V[3 * k + q] = s * vp + c * vq;
                 }
+                rotated = 1;
             }
+        if (!rotated) break;
     }
-    int ord[3] = {0, 1, 2};
-    double d[3] = {a[0], a[4], a[8]};
-    for (int i = 0; i < 2; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (d[ord[j]] > d[ord[i]]) { int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
-    double Vs[9];
-    for (int c = 0; c < 3; ++c) { w[c] = d[ord[c]]; for (int r = 0; r < 3; ++r) Vs[3 * r + c] = V[3 * r + ord[c]]; }
-    memcpy(V, Vs, sizeof Vs);
 }
 
 static void cross3(const double a[3], const double b[3], double o[3]) {
@@ -2634,7 +2624,8 @@ static void cross3(const double a[3], const double b[3], double o[3]) {
 }
 
 /* PointCloudAligner::compute_transformation (point_cloud_aligner.cpp:12-62): centroids, W_1_0 = mean of
- * (p1 - c1)(p0 - c0)^T, C_1_0 = U diag(1, 1, det U det V) V^T from the SVD of W, r = c1 - C c0.  For the
+ * (p1 - c1)(p0 - c0)^T, C_1_0 = U diag(1, 1, det U det V) V^T from the SVD of W (one-sided Jacobi on W itself, the
+ * arithmetic of align3 in ssba_frontend.hip in the same order), r = c1 - C c0.  For the
  * 3-point samples of the RANSAC loop W has rank <= 2; the product is then fixed by the two leading singular
  * pairs: C = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T, whatever signs / third vectors an SVD routine returns.
  * Full-rank W (n > 3) goes through the same formula with the det correction.  T = [t | R row-major]. */
@@ -2648,26 +2639,47 @@ void orc_align_points(const double *pts0, const double *pts1, int n, double T[12
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) W[3 * r + c] += (pts1[3 * i + r] - c1[r]) * (pts0[3 * i + c] - c0[c]);
     for (int i = 0; i < 9; ++i) W[i] /= (double)n;
-    double WtW[9], w[3], V[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            double v = 0.0;
-            for (int k = 0; k < 3; ++k) v += W[3 * k + r] * W[3 * k + c];
-            WtW[3 * r + c] = v;
-        }
-    jacobi_eig3(WtW, w, V);
-    double v1[3] = {V[0], V[3], V[6]}, v2[3] = {V[1], V[4], V[7]}, v3[3], u1[3], u2[3], u3[3];
-    for (int r = 0; r < 3; ++r) {
-        u1[r] = W[3 * r] * v1[0] + W[3 * r + 1] * v1[1] + W[3 * r + 2] * v1[2];
-        u2[r] = W[3 * r] * v2[0] + W[3 * r + 1] * v2[1] + W[3 * r + 2] * v2[2];
+    double G[9], V[9], sv[3];
+    jacobi_svd3(W, G, V);
+    for (int c = 0; c < 3; ++c) sv[c] = sqrt(G[c] * G[c] + G[3 + c] * G[3 + c] + G[6 + c] * G[6 + c]);
+    int i1 = 0;                                   /* the two largest singular values, the first of equals */
+    if (sv[1] > sv[i1]) i1 = 1;
+    if (sv[2] > sv[i1]) i1 = 2;
+    int i2 = i1 == 0 ? 1 : 0;
+    for (int c = i2 + 1; c < 3; ++c) if (c != i1 && sv[c] > sv[i2]) i2 = c;
+    const double n1 = sv[i1], n2 = sv[i2];
+    double v1[3] = {V[i1], V[3 + i1], V[6 + i1]}, v2[3] = {V[i2], V[3 + i2], V[6 + i2]};
+    double u1[3] = {G[i1], G[3 + i1], G[6 + i1]}, u2[3] = {G[i2], G[3 + i2], G[6 + i2]};
+    double v3[3], u3[3];
+    /* the accumulated rotations leave V orthonormal to a few u per rotation: bring v1, v2 back to one rounding */
+    const double nv1 = sqrt(dot3(v1, v1));
+    for (int r = 0; r < 3; ++r) v1[r] /= nv1;
+    const double dv = dot3(v1, v2);
+    for (int r = 0; r < 3; ++r) v2[r] -= dv * v1[r];
+    const double nv2 = sqrt(dot3(v2, v2));
+    for (int r = 0; r < 3; ++r) v2[r] /= nv2;
+    /* rank W < 2 (collinear or coincident points): an SVD still returns orthonormal U columns -- complete the basis
+     * instead of dividing by zero.  s2 <= 2^-50 s1 is below the rounding of W's own entries: no direction in it. */
+    if (n1 > 0.0) { for (int r = 0; r < 3; ++r) u1[r] /= n1; }
+    else { u1[0] = 1.0; u1[1] = 0.0; u1[2] = 0.0; }
+    int have_u2 = n2 > 0x1p-50 * n1;
+    if (have_u2) {
+        for (int r = 0; r < 3; ++r) u2[r] /= n2;
+        const double d12 = dot3(u1, u2);             /* orthogonal to the stopping bound already */
+        for (int r = 0; r < 3; ++r) u2[r] -= d12 * u1[r];
+        const double m2 = sqrt(dot3(u2, u2));
+        have_u2 = m2 > 0.5;
+        if (have_u2) for (int r = 0; r < 3; ++r) u2[r] /= m2;
     }
-    double n1 = sqrt(dot3(u1, u1)), n2;
-    for (int r = 0; r < 3; ++r) u1[r] /= n1;
-    /* re-orthogonalise u2 against u1 (it is orthogonal in exact arithmetic) */
-    const double d12 = dot3(u1, u2);
-    for (int r = 0; r < 3; ++r) u2[r] -= d12 * u1[r];
-    n2 = sqrt(dot3(u2, u2));
-    for (int r = 0; r < 3; ++r) u2[r] /= n2;
+    if (!have_u2) {      /* any unit vector orthogonal to u1 */
+        const int m = fabs(u1[0]) <= fabs(u1[1]) ? (fabs(u1[0]) <= fabs(u1[2]) ? 0 : 2) : (fabs(u1[1]) <= fabs(u1[2]) ? 1 : 2);
+        double e[3] = {0.0, 0.0, 0.0};
+        e[m] = 1.0;
+        const double de = dot3(u1, e);
+        for (int r = 0; r < 3; ++r) u2[r] = e[r] - de * u1[r];
+        const double ne = sqrt(dot3(u2, u2));
+        for (int r = 0; r < 3; ++r) u2[r] /= ne;
+    }
     /* third pair: with V = [v1 v2 v1 x v2] (det +1) and U = [u1 u2 +-(u1 x u2)] the product
      * diag(1, 1, det U det V) maps the third term to (u1 x u2)(v1 x v2)^T whatever the sign */
     cross3(v1, v2, v3);

@@ -44,7 +44,7 @@ def huber_weight(sq, a, dtype=LD):
     return np.where(out, np.sqrt(a / np.sqrt(np.where(out, sq, dtype(1)))), dtype(1))
 
 
-def stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a=0.0, dtype=LD):
+def stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a=0.0, dtype=LD, jacobians=True):
     """Residuals and closed-form local Jacobians (the route of np_reference.NumpyBA.residuals) in `dtype`.
 
     stiffness: one 3x3 matrix or one per observation (N, 3, 3).  Returns a dict with cost, r (N,3), Jp (N,3,6), Jl (N,3,3)
@@ -70,6 +70,12 @@ def stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, hub
     else:
         rho0 = sq
     N = q.shape[0]
+    if not jacobians:       # cost, residuals and their magnitudes only (a C2-sized cost: the Jacobians are 18 of 24 values per row)
+        q64, R64, p64, t64 = (np.asarray(v, np.float64) for v in (q, R, p, t))
+        alpha = 1.0 + (np.abs(R64) @ np.abs(p64)[..., None])[..., 0].max(1) / np.abs(q64[:, 2]) + np.abs(t64).max(1) / np.abs(q64[:, 2])
+        rabs = np.einsum("nij,nj->ni", np.abs(np.asarray(S, np.float64)),
+                         alpha[:, None] * np.abs(np.asarray(pred, np.float64)) + np.abs(np.asarray(z, np.float64))) * np.asarray(w, np.float64)[:, None]
+        return dict(cost=dtype(0.5) * rho0.sum(), r=r * w[:, None], rabs=rabs, alpha=alpha)
     Jpi = np.zeros((N, 3, 3), dtype=dtype)
     Jpi[:, 0, 0] = fu * iz
     Jpi[:, 0, 2] = -fu * q[:, 0] * iz * iz
@@ -1125,11 +1131,11 @@ def boundary_minimum(g, B, radius, grid=4096, newton=60):
 
 
 def propagate(fun, sums, bars, rel=LD(2.0) ** -30):
-    """sum_i |d fun / d sums_i| bars_i by long-double central differences (fun: six sums -> dict of scalars or a number)."""
+    """sum_i |d fun / d sums_i| bars_i by long-double central differences (fun: the sums -> dict of scalars)."""
     base = np.asarray(sums, LD)
     keys = None
     acc = {}
-    for i in range(6):
+    for i in range(base.shape[0]):
         hstep = max(abs(base[i]) * rel, LD(1e-300))
         up, dn = base.copy(), base.copy()
         up[i] += hstep
@@ -1140,3 +1146,432 @@ def propagate(fun, sums, bars, rel=LD(2.0) ** -30):
         for k in keys:
             acc[k] = acc.get(k, 0.0) + float(abs((LD(fu[k]) - LD(fd[k])) / (2 * hstep))) * float(bars[i])
     return acc
+
+
+# ------------------------------------------------------------------------ the second half of a trust-region iteration
+# What happens after the step exists, from the Ceres 1.x semantics the kernels cite: the Plus operators of the local
+# parameterisations (SE3Perturbation, UnitVectorPerturbation, ParameterBlock::Plus with bounds), the cost 1/2 sum rho(|r|^2),
+# the gradient max norm |x - Plus(x, -g)|_inf of TrustRegionMinimizer::EvaluateGradientAndJacobian, and the scalar chain of
+# TrustRegionMinimizer / TrustRegionStepEvaluator / LevenbergMarquardtStrategy / DoglegStrategy.
+DBL_EPSILON = 2.0 ** -52
+C_PLUS = 24               # c of the se3_plus bar (derived in its docstring)
+C_UNIT = 16               # c of the unit_plus bar
+C_NORM = 8                # c of the step_norm / x_norm bars
+
+
+def _skew(v):
+    K = np.zeros(v.shape[:-1] + (3, 3), dtype=v.dtype)
+    K[..., 0, 1], K[..., 0, 2] = -v[..., 2], v[..., 1]
+    K[..., 1, 0], K[..., 1, 2] = v[..., 2], -v[..., 0]
+    K[..., 2, 0], K[..., 2, 1] = -v[..., 1], v[..., 0]
+    return K
+
+
+def se3_plus(T, eps, dtype=LD):
+    """SE3Perturbation: Plus(T, eps) = [E t + eps_t | E R], E = so3 exp(eps_r) = cos(a) I + (1 - cos a) n n^T + sin(a) n^ with
+    a = |eps_r|, n = eps_r / a, and the first-order branch E = I + eps_r^ for a <= DBL_EPSILON.  T (..., 12) = [t | R row-major],
+    eps (..., 6) = [translation | rotation]; fp64 inputs are held exactly.  Returns (Plus (N, 12), bar (N, 12)).
+
+    The bar c u (M_E |T| + |eps|) bounds an fp64 evaluation entrywise, M_E >= |E| being the sum of the magnitudes of the terms
+    of E: (|cos| + a |sin|) I + (|1 - cos| + |cos| + a |sin|) |n n^T| + (|sin| + a |cos|) |n^| -- the a |sin|, a |cos| parts carry
+    the rounding of the angle into cos and sin (an absolute error 3 u a of the argument), which dominates for angles far beyond
+    pi (the projected gradient of a first iteration); 1 - cos is formed from the rounded cosine, so its error is absolute in
+    u |cos|, not relative to 1 - cos (a small step: 1 - cos ~ a^2 / 2, its rounding ~ u).  Relative to those magnitudes an entry of E costs: the angle 3 u (three
+    squares, two sums, a square root), each n_i 4 u, cos / sin 2 u, 1 - cos 1 u, two products 2 u and the sum of the terms
+    2 u: 17 u with two n_i in one term.  Each output entry is a 3-term dot product plus eps_t: 4 u more, on M_E |T| + |eps|.
+    c = 24 leaves 3 u for the second-order terms.  (First-order branch: E is exact and only the 4 u remain.)"""
+    T = np.asarray(T, dtype).reshape(-1, 12)
+    eps = np.asarray(eps, dtype).reshape(-1, 6)
+    n = T.shape[0]
+    phi = eps[:, 3:]
+    ang = np.sqrt((phi * phi).sum(1))
+    small = ang <= dtype(DBL_EPSILON)
+    safe = np.where(small, dtype(1), ang)
+    a = phi / safe[:, None]
+    c, s = np.cos(safe), np.sin(safe)
+    I = np.broadcast_to(np.eye(3, dtype=dtype), (n, 3, 3))
+    aa = a[:, :, None] * a[:, None, :]
+    E = np.where(small[:, None, None], I + _skew(phi), c[:, None, None] * I + (1 - c)[:, None, None] * aa + s[:, None, None] * _skew(a))
+    f = lambda v: np.abs(np.asarray(v, np.float64))
+    a64, c64, s64 = f(safe), f(c), f(s)
+    ME = np.where(np.asarray(small)[:, None, None], f(I + _skew(phi)),
+                  (c64 + a64 * s64)[:, None, None] * f(I) + (f(1 - c) + c64 + a64 * s64)[:, None, None] * f(aa)
+                  + (s64 + a64 * c64)[:, None, None] * f(_skew(a)))
+    t, R = T[:, :3], T[:, 3:].reshape(n, 3, 3)
+    out = np.concatenate([np.einsum("nij,nj->ni", E, t) + eps[:, :3], np.einsum("nij,njk->nik", E, R).reshape(n, 9)], 1)
+    bar = C_PLUS * U * np.concatenate([np.einsum("nij,nj->ni", ME, f(t)) + f(eps[:, :3]),
+                                       np.einsum("nij,njk->nik", ME, f(R)).reshape(n, 9)], 1)
+    return out, bar
+
+
+def unit_plus(x, d, dtype=LD):
+    """UnitVectorPerturbation: Plus(x, d) = y / |y|, y = x + d - (d.x / x.x) x.  x, d (..., 3).  Returns (Plus, bar), (N, 3).
+
+    The bar on an fp64 evaluation: y sums three terms of magnitude m = |x| + |d| + s_m |x| with s_m = (|d|.|x|) / (x.x) the
+    magnitude sum of the quotient; the two dot products cost 3 u each, the quotient 1 u, s x 1 u, the two sums 2 u: 10 u m on
+    y.  The normalisation carries an error of y into every component (through |y|): |d out| <= |d y|_2 / |y|, plus 3 u |out| for
+    |y| (1.5 u) and the quotient.  c = 16 leaves 6 u m for second-order terms."""
+    x = np.asarray(x, dtype).reshape(-1, 3)
+    d = np.asarray(d, dtype).reshape(-1, 3)
+    s = (d * x).sum(1) / (x * x).sum(1)
+    y = x + d - s[:, None] * x
+    nrm = np.sqrt((y * y).sum(1))
+    out = y / nrm[:, None]
+    f = lambda v: np.abs(np.asarray(v, np.float64))
+    sm = (f(d) * f(x)).sum(1) / f((x * x).sum(1))
+    m = f(x) + f(d) + sm[:, None] * f(x)
+    bar = C_UNIT * U * (np.sqrt((m * m).sum(1)) / f(nrm))[:, None] + 3 * U * f(out)
+    return out, np.broadcast_to(bar, out.shape).copy()
+
+
+def projected_plus(light_type, light, phong, texture, db, shared_free, bounds=None, dtype=LD):
+    """ParameterBlock::Plus of the shared blocks with the border step db in the order light 3, Phong 3M, textures M (the free
+    ones only, shared_free bit 0 / 1 / 2): the sum, UnitVectorPerturbation for a directional light (light_type 1), then the
+    projection onto the box [lo, hi] -- bounds = (lo (4), hi (4)) for ka, ks, alpha, kd, or None.  Returns the new
+    (light, phong, texture) and their bars: u |x + d| for the sum (nothing where the projection fires on both sides of the
+    rounding: the bound itself is returned; u |x + d| is kept there as well, for a sum within rounding of the bound)."""
+    light = np.asarray(light, dtype).reshape(3)
+    phong = np.asarray(phong, dtype).reshape(-1, 3)
+    texture = np.asarray(texture, dtype).reshape(-1)
+    db = np.asarray(db, dtype).ravel()
+    M = texture.shape[0]
+    o = 0
+    f = lambda v: np.abs(np.asarray(v, np.float64))
+    nl, bl = light.copy(), np.zeros(3)
+    if shared_free & 1:
+        if light_type == 1:
+            nl, bl = unit_plus(light, db[:3], dtype)
+            nl, bl = nl[0], bl[0]
+        else:
+            nl = light + db[:3]
+            bl = U * f(nl)
+        o = 3
+    nph, bph = phong.copy(), np.zeros(phong.shape)
+    if shared_free & 2:
+        nph = phong + db[o: o + 3 * M].reshape(M, 3)
+        bph = U * f(nph)
+        if bounds is not None:
+            nph = np.minimum(np.maximum(nph, np.asarray(bounds[0], dtype)[:3]), np.asarray(bounds[1], dtype)[:3])
+        o += 3 * M
+    ntx, btx = texture.copy(), np.zeros(M)
+    if shared_free & 4:
+        ntx = texture + db[o: o + M]
+        btx = U * f(ntx)
+        if bounds is not None:
+            ntx = np.minimum(np.maximum(ntx, dtype(bounds[0][3])), dtype(bounds[1][3]))
+    return (nl, nph, ntx), (bl, bph, btx)
+
+
+def _unary_magnitudes(poses, factors):
+    """Rounding magnitude of every pose-only residual block (fp64): |r| + 2 sum over its poses of |d r / d T| |T|, the ambient
+    Jacobian by complex step -- log(T_ref T_1 T_2^-1) and t_ref - R_res t cancel where the poses are far from the origin, and
+    the reference pose in the data is as large as the poses (the factor 2).  Huber-corrected like unary_rows."""
+    import np_reference as npr
+    out = []
+    h = 1e-30
+    for fct in factors:
+        S = np.asarray(fct["stiffness"], np.float64)
+        d = np.asarray(fct["data"], np.float64)
+        if fct["type"] == 0:
+            funs = [(fct["pose"], lambda X: npr.pose_prior_residual(X, d[:12], S.reshape(6, 6)))]
+        elif fct["type"] == 1:
+            funs = [(fct["pose"], lambda X: npr.sun_sensor_residual(X, d[:3], d[3:6], S.reshape(2, 2), d[6], d[7]))]
+        else:
+            T1, T2 = poses[fct["pose"]].astype(complex), poses[fct["pose2"]].astype(complex)
+            funs = [(fct["pose"], lambda X: _rel_residual(X, T2, d[:12], S.reshape(6, 6))),
+                    (fct["pose2"], lambda X: _rel_residual(T1, X, d[:12], S.reshape(6, 6)))]
+        r = np.asarray(funs[0][1](poses[funs[0][0]].astype(complex)).real, np.float64)
+        mag = np.abs(r)
+        for k, fun in funs:
+            for c in range(12):
+                X = poses[k].astype(complex)
+                X[c] += 1j * h
+                mag = mag + 2 * np.abs(np.asarray(fun(X)).imag / h) * abs(poses[k][c])
+        w = float(huber_weight(np.float64((r * r).sum()), fct.get("huber", 0.0), np.float64))
+        out.append(mag * w)
+    return out
+
+
+def cost_at(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a=0.0, factors=None, lighting=None,
+            normals=None, jacobians=True):
+    """1/2 sum rho(|r|^2) over all residual blocks at (poses, points[, normals, the shared blocks in `lighting`]) in long
+    double: the stereo blocks with the Huber loss (stereo_rows), the intensity and normal blocks (phong_observation_rows; a
+    NULL loss), the unary and relative pose blocks (unary_rows: fp64 values, each with its own Huber loss).  Returns a dict:
+    cost, bar, rows (the stereo / lighting rows, for reuse; jacobians=False: stereo residuals and magnitudes only), n_terms.
+
+    The bar on an fp64 evaluation, in any summation order, has two parts.
+    (1) The rounding of each term.  A row value r carries c u rabs (rabs of stereo_rows: pred - z cancels; the C_ROW magnitudes
+        of phong_rows; _unary_magnitudes), c = 16 = C_TERMS = C_ROW, and d (1/2 rho(|r|^2)) = rho' r . dr = (w r) . (w dr): the
+        corrected rows and magnitudes as they are returned.  Twice that for the pose blocks, whose reference values are fp64.
+        The term's own arithmetic (squares, 2 a sqrt(s) - a^2 <= 3 times the term's sum of magnitudes) is part of (2).
+    (2) The summation: (N + C_TERMS) u sum |term| over the N residual blocks bounds any order of adding them (the lane, block and
+        partial-sum trees of the device), C_TERMS covering the term's own arithmetic."""
+    if lighting is not None:
+        lt = dict(lighting)
+        nrm = lt["normals"] if normals is None else normals
+        rows = phong_observation_rows(cam, poses, points, nrm, obs_pose, obs_point, obs_uvd, stiffness, lt, huber_a, 0)
+        N = rows["r"].shape[0]
+        st_cost = rows["cost"] - LD(0.5) * (rows["r"][:, 3:] ** 2).sum()
+        terms = [np.asarray(LD(0.5) * (rows["r"][:, 3] ** 2), LD), np.asarray(LD(0.5) * (rows["r"][:, 4:] ** 2).sum(1), LD)]
+        n_terms = 3 * N
+    else:
+        rows = stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a, jacobians=jacobians)
+        N = rows["r"].shape[0]
+        st_cost = rows["cost"]
+        terms = []
+        n_terms = N
+    cost = LD(0) + rows["cost"]
+    r64 = np.abs(np.asarray(rows["r"], np.float64))
+    part1 = C_TERMS * U * float((r64 * rows["rabs"]).sum())
+    mag = abs(float(st_cost)) + sum(float(t.sum()) for t in terms)
+    if factors:
+        un = unary_rows(np.asarray(poses, np.float64), factors)
+        um = _unary_magnitudes(np.asarray(poses, np.float64), factors)
+        for fct, b, m in zip(factors, un, um):
+            sw = (b["r"] * b["r"]).sum()
+            a = LD(fct.get("huber", 0.0))
+            rho = 2 * sw - a * a if (a > 0 and sw > a * a) else sw
+            cost = cost + LD(0.5) * rho
+            mag += 0.5 * abs(float(rho))
+            part1 += 2 * C_TERMS * U * float((np.abs(np.asarray(b["r"], np.float64)) * m).sum())
+        n_terms += len(factors)
+    return dict(cost=cost, bar=part1 + (n_terms + C_TERMS) * U * mag, rows=rows, n_terms=n_terms, part1=part1)
+
+
+def gradient_max_norm(ref, fidx, poses, normals=None, shared=None):
+    """max over the free blocks of |x - Plus(x, -g)|_inf [TrustRegionMinimizer::EvaluateGradientAndJacobian] from the
+    long-double gradient of a DoglegReference at this point: SE3 Plus on the free poses, the plain |g_l|_inf on the landmark
+    positions, UnitVectorPerturbation on the normals (6-wide landmark blocks), the projected Plus on the free shared blocks
+    (shared = dict(light_type, light, phong, texture, shared_free, bounds)).  Returns (value, bar).
+
+    The bar: the fp64 gradient carries (m + C_TERMS) u sum |J|^T |r| per entry (m rows in the column: ref.m, ref.ga).  Through
+    Plus: a rotation changes by at most |d g_r|_2 per radian in every entry, so an entry of E v moves by at most |d g_r|_2
+    |v|_2, the translation by |d g_t|; plus the bar of Plus itself at eps = -g.  The subtraction T - Plus(T, -g) is exact for
+    nearby values and otherwise rounds to u |T - Plus|: it is absolute in u |T| through the Plus bar, not relative to the
+    difference.  A maximum moves by no more than its largest entry bar."""
+    fidx = np.asarray(fidx, np.int64)
+    free = np.flatnonzero(fidx >= 0)
+    gp, gl, gb = ref.split(ref.g)
+    eg = (ref.m + C_TERMS) * U * ref.ga
+    egp, egl, egb = ref.split(eg)
+    best, bar = LD(0), 0.0
+    if free.size:
+        T = np.asarray(poses, LD)[free]
+        Tn, pb = se3_plus(T, -gp)
+        diff = np.abs(T - Tn)
+        T64 = np.abs(np.asarray(T, np.float64))
+        dr = np.sqrt((egp[:, 3:] ** 2).sum(1))
+        vn = np.stack([np.sqrt((T64[:, :3] ** 2).sum(1))] * 3 + [np.sqrt((T64[:, 3:].reshape(-1, 3, 3) ** 2).sum(1))[:, c % 3]
+                                                                 for c in range(9)], 1)
+        eb = dr[:, None] * vn + pb + U * np.asarray(diff, np.float64)
+        eb[:, :3] += egp[:, :3]
+        best, bar = max(best, diff.max()), max(bar, float(eb.max()))
+    if gl.size:
+        best, bar = max(best, np.abs(gl[:, :3]).max()), max(bar, float(egl[:, :3].max()))
+        if ref.d == 6:
+            x = np.asarray(normals, LD)[ref.sy.lm]
+            xn, ub = unit_plus(x, -gl[:, 3:])
+            diff = np.abs(x - xn)
+            # |d Plus / d delta| <= 1 / |y| in the 2-norm
+            y = x - gl[:, 3:] + (((gl[:, 3:] * x).sum(1) / (x * x).sum(1))[:, None]) * x
+            e2 = np.sqrt((egl[:, 3:] ** 2).sum(1)) / np.asarray(np.sqrt((y * y).sum(1)), np.float64)
+            best, bar = max(best, diff.max()), max(bar, float((ub + e2[:, None] + U * np.abs(np.asarray(x, np.float64))).max()))
+    if ref.nb:
+        sh = shared
+        neg = -gb
+        (nl, nph, ntx), (bl, bph, btx) = projected_plus(sh["light_type"], sh["light"], sh["phong"], sh["texture"], neg,
+                                                        sh["shared_free"], sh.get("bounds"))
+        o = 0
+        for on, old, new, b0, width in ((1, np.asarray(sh["light"], LD).reshape(3), nl, bl, 3),
+                                        (2, np.asarray(sh["phong"], LD).ravel(), nph.ravel(), bph.ravel(), 3 * len(sh["texture"])),
+                                        (4, np.asarray(sh["texture"], LD).ravel(), ntx.ravel(), btx.ravel(), len(sh["texture"]))):
+            if not sh["shared_free"] & on:
+                continue
+            e = egb[o: o + width]
+            if on == 1 and sh["light_type"] == 1:
+                e = np.full(3, np.sqrt((e ** 2).sum()))      # |y| >= |x| = 1 for a unit light moved in its tangent plane
+            diff = np.abs(old - new)
+            best = max(best, diff.max())
+            bar = max(bar, float((e + np.ravel(b0) + U * np.abs(np.asarray(old, np.float64))).max()))
+            o += width
+    return best, bar
+
+
+def block_norms(fidx, present, x_poses, x_points, c_poses=None, c_points=None, x_normals=None, c_normals=None, x_shared=None,
+                c_shared=None):
+    """|x|_2 (candidate None) or |candidate - x|_2 over the blocks of the reduced program, as TrustRegionMinimizer takes them:
+    12 ambient entries per free pose, 3 per landmark that has an observation (`present`), 3 per normal of such a landmark,
+    the free shared blocks (x_shared: the concatenated free entries); no constant or unobserved block.  Returns (norm, bar).
+
+    The bar: every difference (or entry) of the fp64 side carries an absolute error e_i (the candidate's own rounding, u |x_i|
+    at least, passed in by the caller through the Plus bars; here u |x_i| per entry for the subtraction and the square), and
+    d |v|_2 <= |e|_2 -- absolute in u |x|, which is what decides near convergence where |v| ~ 1e-6 and |x| ~ 100 -- plus the
+    summation (n + C_NORM) u |v|_2 / 2 of the n squares in any order and the square root."""
+    free = np.flatnonzero(np.asarray(fidx) >= 0)
+    xs = [np.asarray(x_poses, LD)[free].ravel(), np.asarray(x_points, LD)[present].ravel()]
+    cs = None if c_poses is None else [np.asarray(c_poses, LD)[free].ravel(), np.asarray(c_points, LD)[present].ravel()]
+    if x_normals is not None:
+        xs.append(np.asarray(x_normals, LD)[present].ravel())
+        if cs is not None:
+            cs.append(np.asarray(c_normals, LD)[present].ravel())
+    if x_shared is not None:
+        xs.append(np.asarray(x_shared, LD).ravel())
+        if cs is not None:
+            cs.append(np.asarray(c_shared, LD).ravel())
+    x = np.concatenate(xs)
+    v = x if cs is None else np.concatenate(cs) - x
+    nrm = np.sqrt((v * v).sum())
+    e = U * np.abs(np.asarray(x, np.float64)) * (0.0 if cs is None else 1.0)
+    return nrm, float(np.sqrt((e * e).sum())) + (0.5 * v.size + C_NORM) * U * float(nrm)
+
+
+# ---- the scalar chain
+def trust_region_options(**kw):
+    """Ceres 1.x Solver::Options defaults of the fields the chain reads (strategy 0 LM / 1 DOGLEG)."""
+    o = dict(max_num_iterations=50, use_nonmonotonic_steps=0, max_consecutive_nonmonotonic_steps=5,
+             max_num_consecutive_invalid_steps=5, max_trust_region_radius=1e16, min_trust_region_radius=1e-32,
+             min_relative_decrease=1e-3, function_tolerance=1e-6, gradient_tolerance=1e-10, parameter_tolerance=1e-8,
+             trust_region_strategy_type=0)
+    for k in kw:
+        assert k in o, k
+    o.update(kw)
+    return o
+
+
+def trust_region_state(x_cost, radius, options):
+    """The state after IterationZero: the strategy (radius, decrease_factor 2, mu 1e-8, reuse) and the step evaluator."""
+    c = LD(x_cost)
+    return dict(radius=LD(radius), decrease_factor=LD(2), mu=LD(1e-8), reuse=0, num_invalid=0,
+                se_minimum=c, se_current=c, se_reference=c, se_candidate=c, se_acc_ref=LD(0), se_acc_cand=LD(0),
+                se_num_nonmono=0,
+                se_max_nonmono=options["max_consecutive_nonmonotonic_steps"] if options["use_nonmonotonic_steps"] else 0)
+
+
+def can_continue(iteration, gmax, radius, options):
+    """FinalizeIterationAndCheckIfMinimizerCanContinue: None, or the termination ("no_convergence", "gradient", "radius")."""
+    if iteration >= options["max_num_iterations"]:
+        return "no_convergence"
+    if gmax <= options["gradient_tolerance"]:
+        return "gradient"
+    if radius <= options["min_trust_region_radius"]:
+        return "radius"
+    return None
+
+
+def _step_quality(v, st):
+    x_cost, cand, mcc = v[0], v[1], v[2]
+    # the evaluator's current cost is the x_cost of a monotonic history; it is carried as an offset of x_cost so that the bar
+    # of x_cost propagates into it
+    cur = st["se_current"] + (x_cost - st["_x_cost0"])
+    rd0 = (cur - cand) / mcc
+    rd1 = (st["se_reference"] + (x_cost - st["_x_cost0"]) * st["_ref_is_x"] - cand) / (st["se_acc_ref"] + mcc)
+    return rd0, rd1
+
+
+def trust_region_decision(x_cost, candidate_cost, mcc, step_norm, x_norm, state, options, dl_norm=None, step_valid=True,
+                          bars=None):
+    """One pass of the trust-region loop after the candidate evaluation, in long double:
+
+        step validity [ComputeTrustRegionStep: the linear solver failed or model_cost_change <= 0 -> HandleInvalidStep],
+        ParameterToleranceReached  step_norm <= parameter_tolerance (x_norm + parameter_tolerance),
+        FunctionToleranceReached   |x_cost - candidate_cost| <= function_tolerance x_cost,
+        TrustRegionStepEvaluator::StepQuality  rho = max(rho_0, rho_1), rho_0 = (current - candidate) / mcc,
+                                   rho_1 = (reference - candidate) / (accumulated_reference_model_cost_change + mcc),
+        rho > min_relative_decrease -> HandleSuccessfulStep, else HandleUnsuccessfulStep,
+        LevenbergMarquardtStrategy: accepted radius / max(1/3, 1 - (2 rho - 1)^3) capped by max_trust_region_radius and
+                                   decrease_factor = 2; rejected or invalid radius / decrease_factor, decrease_factor * 2,
+        DoglegStrategy:            accepted rho < 0.25 radius / 2, rho > 0.75 max(radius, 3 |delta|_D) (dl_norm), mu = max(1e-8,
+                                   2 mu / 10); rejected radius / 2 and the step is reused; invalid mu * 10,
+        TrustRegionStepEvaluator::StepAccepted (the non-monotonic bookkeeping).
+
+    state: trust_region_state or the "state" of an earlier call (not modified).  bars: dict of the fp64 bars of x_cost,
+    candidate_cost, mcc, step_norm, x_norm (default 0).  Returns a dict: valid, termination (None / "parameter" / "function"
+    / "failure"), cost_change, rho, rho0, rho1, accepted, radius (the new one), state (the new one), rho_bar and radius_bar
+    (the bars propagated by central differences, hp.propagate), and margins: for every comparison made, the distance of its
+    left-hand side from the threshold divided by the propagated bar of that distance (inf for a zero bar) -- a comparison
+    with margin <= 1 could go either way in fp64."""
+    o = options
+    b = dict(x_cost=0.0, candidate_cost=0.0, mcc=0.0, step_norm=0.0, x_norm=0.0)
+    b.update(bars or {})
+    st = dict(state)
+    dog = o["trust_region_strategy_type"] == 1
+    x_cost, cand, mcc, sn, xn = (LD(v) for v in (x_cost, candidate_cost, mcc, step_norm, x_norm))
+    margins = {}
+    ratio = lambda dist, bar: float("inf") if bar == 0 else abs(float(dist)) / bar
+    out = dict(margins=margins, termination=None, accepted=False, rho=None, cost_change=None)
+    margins["valid"] = ratio(mcc, b["mcc"])
+    out["valid"] = bool(step_valid and mcc > 0)
+    if not out["valid"]:
+        st["num_invalid"] += 1
+        if st["num_invalid"] >= o["max_num_consecutive_invalid_steps"]:
+            out["termination"] = "failure"
+        if dog:
+            st["mu"], st["reuse"] = st["mu"] * 10, 0
+        else:
+            st["radius"], st["decrease_factor"] = st["radius"] / st["decrease_factor"], st["decrease_factor"] * 2
+        out.update(radius=st["radius"], state=st, radius_bar=0.0, rho_bar=0.0)
+        return out
+    st["num_invalid"] = 0
+    out["cost_change"] = x_cost - cand
+    pt, ft = LD(o["parameter_tolerance"]), LD(o["function_tolerance"])
+    margins["parameter"] = ratio(sn - pt * (xn + pt), b["step_norm"] + float(pt) * b["x_norm"])
+    if sn <= pt * (xn + pt):
+        out.update(termination="parameter", radius=st["radius"], state=st, radius_bar=0.0, rho_bar=0.0)
+        return out
+    margins["function"] = ratio(abs(x_cost - cand) - ft * x_cost, b["x_cost"] * (1 + float(ft)) + b["candidate_cost"])
+    if abs(x_cost - cand) <= ft * x_cost:
+        out.update(termination="function", radius=st["radius"], state=st, radius_bar=0.0, rho_bar=0.0)
+        return out
+    # step quality: the evaluator's current / reference costs follow x_cost where they are the same number
+    q = dict(st, _x_cost0=x_cost, _ref_is_x=1 if st["se_reference"] == st["se_current"] else 0)
+    rd0, rd1 = _step_quality([x_cost, cand, mcc], q)
+    rho = max(rd0, rd1)
+    out.update(rho=rho, rho0=rd0, rho1=rd1)
+
+    def radius_after(rho_, radius):
+        if dog:
+            r = radius
+            if rho_ < 0.25:
+                r = r * LD(0.5)
+            if rho_ > 0.75:
+                r = max(r, 3 * LD(dl_norm))
+            return r
+        return min(LD(o["max_trust_region_radius"]), radius / max(LD(1) / 3, 1 - (2 * rho_ - 1) ** 3))
+
+    vals, vbars = [x_cost, cand, mcc], [b["x_cost"], b["candidate_cost"], b["mcc"]]
+    prop = propagate(lambda v: dict(rho=max(_step_quality(v, q)), radius=radius_after(max(_step_quality(v, q)), st["radius"])),
+                     vals, vbars)
+    out["rho_bar"] = prop["rho"]
+    mrd = LD(o["min_relative_decrease"])
+    margins["accept"] = ratio(rho - mrd, prop["rho"])
+    if rho > mrd:
+        out["accepted"] = True
+        if dog:
+            margins["rho_0.25"], margins["rho_0.75"] = ratio(rho - LD(0.25), prop["rho"]), ratio(rho - LD(0.75), prop["rho"])
+            out["radius_bar"] = 0.0
+            st["mu"], st["reuse"] = max(LD(1e-8), 2 * st["mu"] / 10), 0
+        else:
+            out["radius_bar"] = prop["radius"] + 8 * U * float(radius_after(rho, st["radius"]))
+            st["decrease_factor"] = LD(2)
+        st["radius"] = radius_after(rho, st["radius"])
+        # TrustRegionStepEvaluator::StepAccepted
+        st["se_current"] = cand
+        st["se_acc_cand"] = st["se_acc_cand"] + mcc
+        st["se_acc_ref"] = st["se_acc_ref"] + mcc
+        if st["se_current"] < st["se_minimum"]:
+            st["se_minimum"], st["se_num_nonmono"] = st["se_current"], 0
+            st["se_candidate"], st["se_acc_cand"] = st["se_current"], LD(0)
+        else:
+            st["se_num_nonmono"] += 1
+            if st["se_current"] > st["se_candidate"]:
+                st["se_candidate"], st["se_acc_cand"] = st["se_current"], LD(0)
+        if st["se_num_nonmono"] == st["se_max_nonmono"]:
+            st["se_reference"], st["se_acc_ref"] = st["se_candidate"], st["se_acc_cand"]
+    else:
+        out["radius_bar"] = 0.0
+        if dog:
+            st["radius"], st["reuse"] = st["radius"] * LD(0.5), 1
+        else:
+            st["radius"], st["decrease_factor"] = st["radius"] / st["decrease_factor"], st["decrease_factor"] * 2
+    out.update(radius=st["radius"], state=st)
+    return out

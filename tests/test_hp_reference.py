@@ -828,3 +828,290 @@ def test_dogleg_bars_reject_a_missing_border_term(mut):
         assert ratio > 10.0, (mut, ratio)
     else:
         assert ratio <= 0.5, ratio
+
+
+# ------------------------------------------------------------------------ the second half of a trust-region iteration
+def _rand_pose(rng, scale=50.0):
+    Q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+    Q = Q * np.sign(np.linalg.det(Q))
+    return np.concatenate([rng.normal(size=3) * scale, Q.ravel()])
+
+
+def test_se3_plus_closed_forms():
+    """Rotation about one axis in closed form, the composition Plus(Plus(T, a e), b e) = Plus(T, (a + b) e) about a fixed
+    axis, and the first-order branch at |eps_r| <= DBL_EPSILON."""
+    LD = hp.LD
+    rng = np.random.default_rng(0)
+    T = _rand_pose(rng)
+    t, R = np.asarray(T[:3], LD), np.asarray(T[3:], LD).reshape(3, 3)
+    for th in (0.3, -2.5, 1e-9, 1e4):
+        out, _ = hp.se3_plus(T, [0.25, -1.0, 2.0, 0, 0, th])
+        c, s = np.cos(LD(th)), np.sin(LD(th))
+        E = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], LD)
+        ref = np.concatenate([E @ t + np.array([0.25, -1.0, 2.0], LD), (E @ R).ravel()])
+        assert np.abs(out[0] - ref).max() <= 2.0 ** -60 * (1 + np.abs(T).max())
+    e = rng.normal(size=3)
+    e /= np.linalg.norm(e)
+    a, b = 0.7, -0.2
+    ax = lambda s: np.concatenate([np.zeros(3), np.asarray(e, LD) * LD(s)])
+    one, _ = hp.se3_plus(hp.se3_plus(T, ax(a))[0][0], ax(b))
+    both, _ = hp.se3_plus(T, ax(LD(a) + LD(b)))
+    assert np.abs(one - both).max() <= 2.0 ** -58 * (1 + np.abs(T).max())
+    # first-order branch: E = I + eps_r^ exactly up to DBL_EPSILON (beyond it Rodrigues gives the same to 2^-104), no 0 / 0 at 0
+    for ang in (2.0 ** -52, 1e-20, 2.0 ** -52 * (1 + 2.0 ** -50)):
+        out, bar = hp.se3_plus(T, np.array([0, 0, 0, ang, 0, 0]))
+        E1 = np.eye(3, dtype=LD) + np.array([[0, 0, 0], [0, 0, -ang], [0, ang, 0]], LD)
+        exact = np.concatenate([E1 @ t, (E1 @ R).ravel()])
+        assert np.abs(out[0] - exact).max() <= (0 if ang <= 2.0 ** -52 else 2.0 ** -100) and np.all(np.isfinite(bar))
+    out, _ = hp.se3_plus(T, np.zeros(6))
+    assert np.all(out[0] == np.asarray(T, LD))
+
+
+def test_se3_plus_and_unit_plus_bars_hold_for_the_oracle():
+    """The C oracle's fp64 Plus operators within the derived bars, small steps to angles far beyond pi."""
+    rng = np.random.default_rng(1)
+    worst = 0.0
+    for scale in (1e-12, 1e-6, 1e-2, 1.0, 30.0, 1e4):
+        for _ in range(50):
+            T, eps = _rand_pose(rng), rng.normal(size=6) * scale
+            ref, bar = hp.se3_plus(T, eps)
+            worst = max(worst, float((np.abs(np.asarray(orc.se3_plus(T, eps), hp.LD) - ref[0]) / bar[0].clip(1e-300)).max()))
+    assert worst <= 1.0, worst
+    worst_u = 0.0
+    for scale in (1e-12, 1e-3, 1.0, 100.0):
+        for _ in range(50):
+            x, d = rng.normal(size=3), rng.normal(size=3) * scale
+            x /= np.linalg.norm(x)
+            ref, bar = hp.unit_plus(x, d)
+            worst_u = max(worst_u, float((np.abs(np.asarray(orc.unit_vector_plus(x, d), hp.LD) - ref[0]) / bar[0]).max()))
+    assert worst_u <= 1.0, worst_u
+    print("PLUSREF se3", worst, "unit", worst_u)
+
+
+def test_unit_plus_closed_forms():
+    LD = hp.LD
+    out, _ = hp.unit_plus([0, 0, 1.0], [0.5, 0, 0.25])          # the component along x is projected out
+    assert np.abs(out[0] - np.array([0.5, 0, 1], LD) / np.sqrt(LD(1.25))).max() <= 2.0 ** -62
+    out, _ = hp.unit_plus([0, 3.0, 4.0], [0, 0.375, 0.5])        # parallel step: x / |x|
+    assert np.abs(out[0] - np.array([0, 3, 4], LD) / 5).max() <= 2.0 ** -62 and abs(float((out[0] ** 2).sum()) - 1) < 1e-18
+
+
+def test_projected_plus_clamps_after_the_add():
+    (l, ph, tx), _ = hp.projected_plus(0, [1.0, 2, 3], [[0.5, 0.875, 2.0]], [0.125], [1, 1, 1, 0.25, 0.25, -5.0, -0.5], 7,
+                                       bounds=([0, 0, 1, 0], [1, 1, np.inf, 1]))
+    assert np.all(l == [2, 3, 4]) and np.all(ph == np.array([[0.75, 1.0, 1.0]], hp.LD)) and tx[0] == 0
+    (l, ph, tx), _ = hp.projected_plus(1, [0, 0, 1.0], [[0.5, 0.9, 2.0]], [0.1], [0.5, 0, 0.25], 1)
+    assert np.abs(l - np.array([0.5, 0, 1], hp.LD) / np.sqrt(hp.LD(1.25))).max() <= 2.0 ** -62 and ph[0, 0] == 0.5
+
+
+def _tiny_problem(huber):
+    return synth.make_problem(8, 60, track_len=5, seed=7, outlier_fraction=0.1 if huber else 0.0)
+
+
+@pytest.mark.parametrize("case", ["stereo", "huber", "phong0", "phong1", "sun", "odometry_huber"])
+def test_cost_at_against_the_oracle(case):
+    """OracleProblem.cost (fp64) within the derived bar of the long-double cost."""
+    factors, lighting, huber, const = None, None, 0.0, None
+    if case in ("stereo", "huber"):
+        huber = 1.345 if case == "huber" else 0.0
+        prob = _tiny_problem(huber)
+    elif case.startswith("phong"):
+        prob, ph = synth.make_phong_problem(8, 60, track_len=5, seed=7, light_type=int(case[-1]), num_materials=4)
+        lighting = ph.as_oracle_dict("perturbed")
+    elif case == "sun":
+        from test_oracle_pose_factors import _sun_problem
+        prob, factors = _sun_problem(huber=0.5)
+        const = np.zeros(prob.num_poses, np.uint8)
+    else:
+        from test_oracle_pose_factors import _odometry_factors
+        prob = synth.make_problem(7, 100, track_len=4, seed=6)
+        factors = _odometry_factors(prob, huber=0.05)
+        const = np.zeros(prob.num_poses, np.uint8)
+    args = (prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness())
+    op = orc.OracleProblem(*args, pose_const=const, huber_a=huber, lighting=lighting, pose_factors=factors)
+    c = hp.cost_at(*args, huber_a=huber, factors=factors, lighting=lighting)
+    err = abs(float(hp.LD(op.cost()) - c["cost"]))
+    print("COSTREF", case, "cost", float(c["cost"]), "err/bar", err / c["bar"], "bar/cost", c["bar"] / float(c["cost"]))
+    assert err <= c["bar"], (err, c["bar"])
+    assert c["bar"] <= 1e-9 * float(c["cost"])              # the bar is a bar: far below the oracle-parity tolerance
+
+
+def _tiny_oracle(prob, huber):
+    return orc.OracleProblem.from_synth(prob, huber_a=huber)
+
+
+def _dl_norm(prob, huber, x_poses, x_points, radius, mu, dogleg_type):
+    """|delta|_D of the dogleg step at this point from the long-double reference."""
+    rows = hp.stereo_rows(prob.camera, x_poses, x_points, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(), huber)
+    const = np.zeros(prob.num_poses, bool)
+    const[0] = True
+    fidx = hp.free_index(prob.num_poses, prob.obs_pose, const)
+    ref = hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, mu)
+    gn, _ = ref.gauss_newton()
+    sums = list(ref.param_sums(ref.v, gn)[0]) + [ref.row_sums(x, y)[0] for x, y in ((ref.v, ref.v), (gn, gn), (ref.v, gn))]
+    return hp.dogleg_scalars(sums, radius, dogleg_type)["step_norm"]
+
+
+def _iterate(prob, huber, o_kw, k):
+    """The oracle's point after k iterations (the lowest-cost iterate: the current one while accepted costs decrease)."""
+    op = _tiny_oracle(prob, huber)
+    kw = dict(o_kw)
+    kw["max_num_iterations"] = k
+    op.solve(orc.default_options(**kw))
+    return op.poses.copy(), op.points.copy()
+
+
+def _x_norm(prob, poses, points):
+    const = np.zeros(prob.num_poses, bool)
+    const[0] = True
+    fidx = hp.free_index(prob.num_poses, prob.obs_pose, const)
+    present = np.unique(prob.obs_point)
+    return hp.block_norms(fidx, present, poses, points), fidx, present
+
+
+REPLAYS = [(s, dt, h, nm, r0) for h in (0.0, 1.345) for s, dt in ((0, 0), (1, 0), (1, 1)) for nm in (0, 1)
+           for r0 in ((1.0, 1e4) if s == 0 else (1e4,))]
+
+
+@pytest.mark.parametrize("strategy,dogleg_type,huber,nonmono,r0", REPLAYS)
+def test_trust_region_decision_replays_the_oracle_log(strategy, dogleg_type, huber, nonmono, r0):
+    """Whole oracle solves replayed by trust_region_decision from the logged costs and norms: every accept flag, every
+    radius, the termination iteration and type.  Not in the log and taken from elsewhere: x_norm (the start's, with the
+    steps taken so far as its bar -- the parameter tolerance stays beyond it), the model cost change (inverted from the
+    logged rho by the evaluator's own formulas, which the replay carries), |delta|_D of a dogleg step with rho > 0.75 (from
+    the long-double dogleg at the oracle's iterate; with outliers the Gauss-Newton step at mu = 1e-8 sends landmarks 1e6 away,
+    its norm is not determined to a per cent in fp64, and the logged radius itself is taken where it grew) and the last, unlogged iteration that meets a tolerance (LM: the
+    oracle's step at the final point, this file's Plus and the oracle's cost; DOGLEG runs end on max_num_iterations)."""
+    LD = hp.LD
+    prob = _tiny_problem(huber)
+    o_kw = dict(trust_region_strategy_type=strategy, dogleg_type=dogleg_type, use_nonmonotonic_steps=nonmono,
+                initial_trust_region_radius=r0, max_num_iterations=200 if strategy == 0 else (8 if huber else 3))
+    op = _tiny_oracle(prob, huber)
+    s, log = op.solve(orc.default_options(**o_kw))
+    n = log["cost"].shape[0]
+    opts = hp.trust_region_options(trust_region_strategy_type=strategy, use_nonmonotonic_steps=nonmono,
+                                   max_num_iterations=o_kw["max_num_iterations"])
+    st = hp.trust_region_state(log["cost"][0], r0, opts)
+    (xn0, _), fidx, present = _x_norm(prob, prob.poses_init, prob.points_init)
+    x_cost, iteration, moved, accepted_costs = LD(log["cost"][0]), 0, 0.0, [log["cost"][0]]
+    flags, monotone = [], True
+    for i in range(1, n):
+        assert hp.can_continue(iteration, log["gradient_max_norm"][i - 1], st["radius"], opts) is None
+        iteration += 1
+        invalid = log["relative_decrease"][i] == 0 and log["step_norm"][i] == 0
+        assert not invalid          # these problems produce none
+        cc, rho_log = LD(log["cost_change"][i]), LD(log["relative_decrease"][i])
+        cand = x_cost - cc
+        mcc = (st["se_current"] - cand) / rho_log
+        if (st["se_reference"] - cand) / (st["se_acc_ref"] + mcc) > rho_log * (1 + 1e-12):       # rho_1 was the larger quotient
+            mcc = (st["se_reference"] - cand) / rho_log - st["se_acc_ref"]
+        dl = None
+        if strategy == 1 and rho_log > 0.75:
+            if huber:       # (see the docstring: mu = 1e-8 and outliers)
+                dl = max(LD(log["trust_region_radius"][i]), st["radius"]) / 3
+            else:
+                assert monotone
+                xp, xl = _iterate(prob, huber, o_kw, iteration - 1)
+                dl = _dl_norm(prob, huber, xp, xl, st["radius"], float(st["mu"]), dogleg_type)
+        bars = dict(x_cost=4 * hp.U * float(x_cost), candidate_cost=4 * hp.U * float(x_cost), mcc=8 * hp.U * abs(float(mcc)),
+                    x_norm=moved)
+        d = hp.trust_region_decision(x_cost, cand, mcc, log["step_norm"][i], xn0, st, opts, dl_norm=dl, bars=bars)
+        assert d["valid"] and d["termination"] is None, (i, d["termination"], d["margins"])
+        assert d["margins"]["parameter"] > 1 and d["margins"]["accept"] > 1, (i, d["margins"])
+        assert abs(float(d["rho"] - rho_log)) <= 1e-12 * abs(float(rho_log)), (i, d["rho"], rho_log)
+        assert int(d["accepted"]) == log["step_is_successful"][i], (i, d["rho"])
+        rbar = d["radius_bar"] + (1e-8 if strategy == 1 else 1e-13) * float(d["radius"])
+        assert abs(float(d["radius"]) - log["trust_region_radius"][i]) <= rbar, (i, d["radius"], log["trust_region_radius"][i], rbar)
+        st = d["state"]
+        flags.append(int(d["accepted"]))
+        if d["accepted"]:
+            x_cost = LD(log["cost"][i])
+            moved += log["step_norm"][i]
+            monotone = monotone and log["cost"][i] < accepted_costs[-1]     # then the written-back lowest-cost iterate is the current one
+            accepted_costs.append(log["cost"][i])
+        else:
+            assert abs(float(cand) - log["cost"][i]) <= 8 * hp.U * float(x_cost)      # a rejected row logs the candidate's cost
+    assert 0 in flags or r0 == 1e4 or huber == 0.0 or nonmono       # the monotonic radius-1 outlier run rejects a step
+    end = hp.can_continue(iteration, log["gradient_max_norm"][n - 1], st["radius"], opts)
+    if end is not None:
+        assert (end, s.termination_type) in (("no_convergence", 1), ("gradient", 0), ("radius", 0)) and s.num_iterations == n
+        return
+    if not monotone:        # a non-monotonic run that accepted an increase: the oracle hands back its best point, not the last
+        assert nonmono and s.termination_type == 0
+        return
+    # the last iteration met a tolerance and was not logged: LM only (DOGLEG runs are cut by max_num_iterations above)
+    assert strategy == 0 and s.termination_type == 0
+    op2 = orc.OracleProblem(prob.camera, op.poses, op.points, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(),
+                            huber_a=huber)
+    assert op2.cost() == accepted_costs[-1] or abs(op2.cost() - accepted_costs[-1]) <= 1e-12 * accepted_costs[-1]
+    dp, dlm, mcc = op2.lm_step(float(st["radius"]))
+    cp, _ = hp.se3_plus(op.poses, dp)
+    cp = np.where((fidx >= 0)[:, None], np.asarray(cp, np.float64), op.poses)
+    cl = op.points + dlm
+    cand = orc.OracleProblem(prob.camera, cp, cl, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(), huber_a=huber).cost()
+    sn, _ = hp.block_norms(fidx, present, op.poses, op.points, cp, cl)
+    xn, _ = hp.block_norms(fidx, present, op.poses, op.points)
+    d = hp.trust_region_decision(x_cost, cand, mcc, sn, xn, st, opts)
+    assert d["termination"] in ("function", "parameter"), d
+    assert min(d["margins"][k] for k in ("parameter", "function") if k in d["margins"]) > 0
+    assert iteration + 1 == n           # the terminating iteration is the one after the last logged row
+
+
+def test_the_outlier_problem_rejects_its_third_lm_step_from_radius_one():
+    prob = _tiny_problem(1.345)
+    s, log = _tiny_oracle(prob, 1.345).solve(orc.default_options(initial_trust_region_radius=1.0))
+    assert log["step_is_successful"][3] == 0 and -0.2 < log["relative_decrease"][3] < 0, log["relative_decrease"][:5]
+
+
+def test_gradient_max_norm_and_step_norm_against_the_oracle_log():
+    """Row 0's gradient max norm and row 1's step norm of an oracle solve within the derived bars of the references."""
+    for huber in (0.0, 1.345):
+        prob = _tiny_problem(huber)
+        op = _tiny_oracle(prob, huber)
+        s, log = op.solve(orc.default_options(max_num_iterations=1, initial_trust_region_radius=1e4))
+        rows = hp.stereo_rows(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd,
+                              prob.stiffness(), huber)
+        (xn, _), fidx, present = _x_norm(prob, prob.poses_init, prob.points_init)
+        ref = hp.DoglegReference(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 1e-8)
+        g, bar = hp.gradient_max_norm(ref, fidx, prob.poses_init)
+        assert abs(float(hp.LD(log["gradient_max_norm"][0]) - g)) <= bar and bar <= 1e-9 * float(g), (g, bar)
+        assert log["step_is_successful"][1] == 1
+        sn, sbar = hp.block_norms(fidx, present, prob.poses_init, prob.points_init, op.poses, op.points)
+        assert abs(float(hp.LD(log["step_norm"][1]) - sn)) <= sbar and sbar <= 1e-12 * float(sn), (sn, sbar)
+
+
+def test_trust_region_decision_margins_and_invalid_steps():
+    """The margins measure the distance to each threshold in units of the propagated bars; an invalid step takes the LM /
+    DOGLEG StepIsInvalid path and the fifth in a row fails."""
+    o = hp.trust_region_options()
+    st = hp.trust_region_state(100.0, 10.0, o)
+    d = hp.trust_region_decision(100.0, 99.0, 2.0, 1.0, 50.0, st, o, bars=dict(x_cost=0.1, candidate_cost=0.1, mcc=0.0))
+    assert d["accepted"] and float(d["rho"]) == 0.5 and abs(d["rho_bar"] - 0.1) < 1e-6
+    assert abs(d["margins"]["accept"] - (0.5 - 1e-3) / 0.1) < 1e-4 and float(d["radius"]) == 10.0
+    d = hp.trust_region_decision(100.0, 99.0, 1.0, 1.0, 50.0, st, o)                    # rho = 1: radius * 3
+    assert float(d["radius"]) == 30.0 and d["margins"]["accept"] == float("inf")
+    d = hp.trust_region_decision(100.0, 100.5, 1.0, 1.0, 50.0, st, o)                   # rejected: radius / 2, then / 4
+    assert not d["accepted"] and float(d["radius"]) == 5.0 and float(d["state"]["decrease_factor"]) == 4.0
+    d2 = hp.trust_region_decision(100.0, 100.5, 1.0, 1.0, 50.0, d["state"], o)
+    assert float(d2["radius"]) == 1.25
+    assert hp.trust_region_decision(100.0, 100.0 - 5e-5, 1.0, 1.0, 50.0, st, o)["termination"] == "function"
+    assert hp.trust_region_decision(100.0, 99.0, 1.0, 5e-7, 50.0, st, o)["termination"] == "parameter"
+    s = st
+    for k in range(5):
+        d = hp.trust_region_decision(100.0, 99.0, -1.0, 1.0, 50.0, s, o)
+        assert not d["valid"] and d["termination"] == ("failure" if k == 4 else None)
+        s = d["state"]
+    assert float(s["radius"]) == 10.0 / (2 * 4 * 8 * 16 * 32)
+    od = hp.trust_region_options(trust_region_strategy_type=1)
+    d = hp.trust_region_decision(100.0, 99.0, -1.0, 1.0, 50.0, hp.trust_region_state(100.0, 10.0, od), od)
+    assert float(d["state"]["mu"]) == float(hp.LD(1e-8) * 10) and float(d["radius"]) == 10.0
+    d = hp.trust_region_decision(100.0, 99.0, 1.1, 1.0, 50.0, hp.trust_region_state(100.0, 10.0, od), od, dl_norm=4.0)
+    assert float(d["radius"]) == 12.0 and d["accepted"]
+    d = hp.trust_region_decision(100.0, 99.9, 1.0, 1.0, 50.0, hp.trust_region_state(100.0, 10.0, od), od, dl_norm=4.0)
+    assert float(d["radius"]) == 5.0 and d["accepted"]
+    # non-monotonic: a cost increase within the allowance is accepted against the reference cost
+    on = hp.trust_region_options(use_nonmonotonic_steps=1)
+    s = hp.trust_region_decision(100.0, 90.0, 10.0, 1.0, 50.0, hp.trust_region_state(100.0, 10.0, on), on)["state"]
+    assert float(s["se_reference"]) == 100.0 and float(s["se_current"]) == 90.0 and float(s["se_acc_ref"]) == 10.0
+    d = hp.trust_region_decision(90.0, 91.0, 1.0, 1.0, 50.0, s, on)
+    assert float(d["rho0"]) == -1.0 and abs(float(d["rho1"]) - 9.0 / 11.0) < 1e-15 and d["accepted"]

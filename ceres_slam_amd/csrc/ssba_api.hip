@@ -988,6 +988,10 @@ int ssba_finalize(ssba_problem *p) {
     TRY(dupload(p, &d.sblk_a, sblk_a)); TRY(dupload(p, &d.sblk_b, sblk_b));
     TRY(dupload(p, &d.sblk_start, sblk_start)); TRY(dupload(p, &d.sblk_contrib, sblk_contrib));
     TRY(dupload(p, &d.prow_start, prow_start)); TRY(dupload(p, &d.prow_contrib, prow_contrib));
+    if (!lay.sblk_rf.empty()) {     // odometry blocks on the windowed layout: their lists and the cross blocks J_1^T J_2
+        TRY(dupload(p, &d.sblk_rf_start, lay.sblk_rf_start)); TRY(dupload(p, &d.sblk_rf, lay.sblk_rf));
+        TRY(dzero(p, &d.pf_cross, pfs.size() * 36));
+    }
     if (nborder) {      // closure border: 6 columns per border pose
         d.cb = 1; d.nb = 6 * nborder; d.n_cb = (int)cb_a.size(); d.np = 1; d.nbw = NBP;
         d.b_light = d.b_phong = d.b_tex = -1;

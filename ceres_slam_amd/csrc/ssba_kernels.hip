@@ -126,6 +126,27 @@ template <bool DN, int NT, int CH> __device__ __forceinline__ void lin_pose_body
         const double v = wave_sum(acc[i]);
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][i] = v;
     }
+    // Windowed layout: the halves of relative-pose blocks on this pose (a chain of odometry blocks puts two on every pose) are
+    // evaluated by the whole of wave 1, each block's Jacobians once (pf_rel_wave), and summed in list order; the 28 lanes
+    // below add the sums to theirs.  Only the general layout evaluates them lane by lane like the unary blocks.
+    __shared__ double sm_rel[28];
+    bool rel = false;
+    if (!DN && d.n_pf && d.pf_owner) {
+        static_assert(DN || NT >= 128, "wave 1 evaluates the relative-pose blocks");
+        const uint32_t e0 = d.pf_start[k], e1 = d.pf_start[k + 1];
+        for (uint32_t e = e0; e < e1; ++e) rel |= d.pf_type[e] >= 2;
+        if (rel && (threadIdx.x >> 6) == 1) {
+            const int lane = threadIdx.x & 63;
+            int a = 0, c = 0;
+            if (lane < 21) { int n = lane; while (n >= 6 - a) { n -= 6 - a; ++a; } c = a + n; }
+            double v = 0.0;
+            for (uint32_t e = e0; e < e1; ++e) {
+                const int other = pf_other_pose(d, (int)e);
+                if (other >= 0) v += pf_rel_wave(d, (int)e, T, PS + (size_t)other * 12, lane, a, c);
+            }
+            if (lane < 28) sm_rel[lane] = v;
+        }
+    }
     __syncthreads();
     if (threadIdx.x < 28) {
         double v = 0.0;
@@ -138,10 +159,12 @@ template <bool DN, int NT, int CH> __device__ __forceinline__ void lin_pose_body
             // replicated and these sums are added over the ranks: ONE rank contributes the unary blocks (pf_owner)
             int a = 0, c = 0;
             if (threadIdx.x < 21) { int n = threadIdx.x; while (n >= 6 - a) { n -= 6 - a; ++a; } c = a + n; }
+            if (rel) v += sm_rel[threadIdx.x];
             for (uint32_t e = d.pf_start[k]; e < d.pf_start[k + 1]; ++e) {
                 double r[6], J[36];
                 int dim;
                 const int other = pf_other_pose(d, (int)e);
+                if (!DN && other >= 0) continue;       // done by wave 1
                 const double cost = pf_evaluate(d, (int)e, T, other >= 0 ? PS + (size_t)other * 12 : nullptr, r, J, &dim);
                 if (threadIdx.x < 21) { for (int m = 0; m < dim; ++m) v += J[6 * m + a] * J[6 * m + c]; }
                 else if (threadIdx.x < 27) { for (int m = 0; m < dim; ++m) v += J[6 * m + (threadIdx.x - 21)] * r[m]; }
@@ -570,6 +593,8 @@ __global__ __launch_bounds__(256) void k_assemble_reduced(Dev d, int fuse_finish
         uint32_t cw0[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) cw0[q] = ib0 + q < ie0 ? d.sblk_contrib[ib0 + q] : 0xFFFFFFFFu;
+        uint32_t rf0 = 0, rf1 = 0;
+        if (d.sblk_rf) { rf0 = d.sblk_rf_start[blk]; rf1 = d.sblk_rf_start[blk + 1]; }
         if (dead) return;
         int er = r, ec = c;
         if (fa == fb && c > r) { er = c; ec = r; }   // read the lower triangle: exact symmetry
@@ -589,6 +614,11 @@ __global__ __launch_bounds__(256) void k_assemble_reduced(Dev d, int fuse_finish
             for (int q = 0; q < 8; ++q) v += x[q];
         }
         v = -v;
+        if (d.sblk_rf)      // odometry blocks coupling the two poses of this block: J_a^T J_b, stored by the linearisation as J_1^T J_2
+            for (uint32_t q = rf0; q < rf1; ++q) {
+                const uint32_t ent = d.sblk_rf[q];
+                v += d.pf_cross[36 * (size_t)(ent & 0x7FFFFFFFu) + ((ent >> 31) ? c * 6 + r : r * 6 + c)];
+            }
         if (fa == fb) {
             const int k = d.free_pose[fa];
             const double h = d.hpp[(size_t)k * 21 + tri21(min(r, c), max(r, c))];

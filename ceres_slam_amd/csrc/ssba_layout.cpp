@@ -167,7 +167,22 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
     }
     if (const char *e = getenv("SSBA_FORCE_DENSE")) if (e[0] == '1') dense = dense_only = true;
     if (in.per_obs_S) dense = dense_only = true;     // per-block stiffness lives in the general layout only
-    if (!in.rel_factors.empty()) dense = dense_only = true;     // pose-pose couplings outside the landmark structure
+    // Relative-pose blocks: a block between free poses f and f + 1 (odometry) adds J_1^T J_2 to block (f, f + 1) of the
+    // reduced system, which the block-tridiagonal envelope below stores anyway; a block with one constant pose is a unary
+    // half entry.  A problem that would be windowed without them (and has stereo blocks, one GPU) stays windowed; every
+    // other coupling lies outside the landmark structure and takes the general path.
+    std::vector<uint8_t> rel_pair;      // windowed layout: free pose f is coupled to f + 1 by a relative-pose block
+    if (!in.rel_factors.empty()) {
+        bool ok = !dense && !span_violation && N > 0 && !ph && in.world_size == 1 && !in.partitioned;
+        rel_pair.assign((size_t)nfree, 0);
+        for (auto &rf : in.rel_factors) {
+            const int f1 = out.pose_free[rf.pose1], f2 = out.pose_free[rf.pose2];
+            if (f1 < 0 || f2 < 0) continue;
+            if (f1 - f2 != 1 && f2 - f1 != 1) { ok = false; break; }
+            rel_pair[(size_t)std::min(f1, f2)] = 1;
+        }
+        if (!ok) { dense = dense_only = true; rel_pair.clear(); }
+    }
     // Closure border: when the only thing outside the windowed envelope is the co-visibility span of a few landmarks
     // (a loop closure: the last states see landmarks of the first ones), the far poses of those landmarks -- at most
     // NBP / 6 = 5 -- leave the chain and become a dense border of the block-tridiagonal system, solved with the
@@ -615,7 +630,8 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
         for (auto &c : contribs) sblk_contrib[at[(size_t)c.a * (SBP + 1) + (c.b - c.a)]++] = c.c;
         for (size_t q = 0; q < nkeys; ++q) {
             const uint32_t a = (uint32_t)(q / (SBP + 1)), off = (uint32_t)(q % (SBP + 1));
-            if (kstart[q + 1] == kstart[q] && off != 0) continue;
+            const bool rel = off == 1 && !rel_pair.empty() && rel_pair[a];      // exists for its relative-pose blocks alone
+            if (kstart[q + 1] == kstart[q] && off != 0 && !rel) continue;
             sblk_a.push_back(a);
             sblk_b.push_back(a + off);
             sblk_start.push_back(kstart[q]);
@@ -623,6 +639,28 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
         sblk_start.push_back((uint32_t)contribs.size());
     }
     const uint32_t n_sblk = (uint32_t)sblk_a.size();
+    // relative-pose blocks of every block (f, f + 1): the device position of the first half entry (the entries are stored
+    // sorted by pose, the caller's order kept inside a pose), bit 31 when the block is J_2^T J_1; in the order they were added
+    std::vector<uint32_t> sblk_rf_start, sblk_rf;
+    if (!rel_pair.empty()) {
+        std::vector<uint32_t> at(P + 1, 0), pos(pfs.size());
+        for (auto &f : pfs) at[f.pose + 1]++;
+        for (uint32_t k = 0; k < P; ++k) at[k + 1] += at[k];
+        for (size_t i = 0; i < pfs.size(); ++i) pos[i] = at[pfs[i].pose]++;
+        std::vector<std::vector<uint32_t>> of_pair((size_t)nfree);
+        for (size_t i = 0; i < pfs.size(); ++i)
+            if (pfs[i].type == 2 && pfs[i].data[14] >= 0.0) {
+                const int f1 = out.pose_free[pfs[i].pose], f2 = out.pose_free[(uint32_t)pfs[i].data[12]];
+                of_pair[(size_t)std::min(f1, f2)].push_back(pos[i] | (f1 > f2 ? 0x80000000u : 0u));
+            }
+        sblk_rf_start.assign(1, 0);
+        for (uint32_t b = 0; b < n_sblk; ++b) {
+            if (sblk_b[b] == sblk_a[b] + 1) sblk_rf.insert(sblk_rf.end(), of_pair[sblk_a[b]].begin(), of_pair[sblk_a[b]].end());
+            sblk_rf_start.push_back((uint32_t)sblk_rf.size());
+        }
+        if (sblk_rf.empty()) sblk_rf_start.clear();
+        else bandwidth = std::max<uint32_t>(bandwidth, 1u);
+    }
     std::sort(prow.begin(), prow.end());
     std::vector<uint32_t> prow_start(nfree + 1, 0), prow_contrib;
     for (auto &pr : prow) prow_start[pr.first + 1]++;
@@ -663,7 +701,7 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
 #define MV(x) out.x = std::move(x)
     MV(win_pose); MV(lm_win); MV(lm_mask); MV(lm_mat); MV(pose_obs_start); MV(pose_obs_ref); MV(pose_mat_start);
     MV(ou); MV(ov); MV(od); MV(oint); MV(onx); MV(ony); MV(onz);
-    MV(slab_win); MV(slab_b); MV(slab_e); MV(sblk_a); MV(sblk_b); MV(sblk_start); MV(sblk_contrib); MV(prow_start); MV(prow_contrib);
+    MV(slab_win); MV(slab_b); MV(slab_e); MV(sblk_a); MV(sblk_b); MV(sblk_start); MV(sblk_contrib); MV(sblk_rf_start); MV(sblk_rf); MV(prow_start); MV(prow_contrib);
     MV(cb_a); MV(cb_b); MV(cb_start); MV(cb_contrib);
     MV(dn_lm_start); MV(dn_obs_pose); MV(dn_obs_lm); MV(dn_pose_start); MV(dn_pose_obs); MV(dn_zpos);
     MV(dn_u); MV(dn_v); MV(dn_d); MV(dn_Sobs); MV(dn_prec);

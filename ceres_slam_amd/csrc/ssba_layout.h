@@ -75,6 +75,7 @@ struct Layout {
     raw_vector<uint32_t> pose_obs_ref;
     raw_vector<double> ou, ov, od, oint, onx, ony, onz;
     std::vector<uint32_t> slab_win, slab_b, slab_e, sblk_a, sblk_b, sblk_start, sblk_contrib, prow_start, prow_contrib;
+    std::vector<uint32_t> sblk_rf_start, sblk_rf;                // per block: its relative-pose blocks (first half entry | bit 31: block is J_2^T J_1); empty without any
     std::vector<uint32_t> cb_a, cb_b, cb_start, cb_contrib;      // closure border
     // general layout
     std::vector<uint32_t> dn_lm_start, dn_obs_pose, dn_obs_lm, dn_pose_start, dn_pose_obs, dn_zpos;

@@ -155,4 +155,82 @@ static __device__ double pf_evaluate(const Dev &d, int f, const double *T, const
     return 0.5 * sq;
 }
 
+// One element (i, j) of both Jacobians of pf_rel, and the whole residual: what a lane of pf_rel_wave computes.  The 3 x 3
+// factors of the 6 x 6 products (R_ref v^, Jl^-1 R_ref) are needed in the lane's column only.
+static __device__ void pf_rel_element(const double *T1, const double *T2, const double *T_ref, const double *S, int i, int j, double r[6], double &j1,
+                                      double &j2) {
+    const double *R1 = T1 + 3, *R2 = T2 + 3, *Rr = T_ref + 3;
+    double R12[9], Rres[9], v[3], e[6];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R12[3 * a + b] = R1[3 * a] * R2[3 * b] + R1[3 * a + 1] * R2[3 * b + 1] + R1[3 * a + 2] * R2[3 * b + 2];
+    for (int a = 0; a < 3; ++a) v[a] = T1[a] - (R12[3 * a] * T2[0] + R12[3 * a + 1] * T2[1] + R12[3 * a + 2] * T2[2]);
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) Rres[3 * a + b] = Rr[3 * a] * R12[b] + Rr[3 * a + 1] * R12[3 + b] + Rr[3 * a + 2] * R12[6 + b];
+    for (int a = 0; a < 3; ++a) e[a] = Rr[3 * a] * v[0] + Rr[3 * a + 1] * v[1] + Rr[3 * a + 2] * v[2] + T_ref[a];
+    pf_so3_log(Rres, e + 3);
+    for (int a = 0; a < 6; ++a) {
+        double s = 0.0;
+        for (int k = 0; k < 6; ++k) s += S[6 * a + k] * e[k];
+        r[a] = s;
+    }
+    double Jr[9];
+    pf_inv_right_jacobian(e + 3, Jr);
+    const double vx[9] = {0, -v[2], v[1], v[2], 0, -v[0], -v[1], v[0], 0};
+    const int jc = j < 3 ? j : j - 3;
+    auto col = [jc](const double *M, int k) { return jc == 0 ? M[3 * k] : jc == 1 ? M[3 * k + 1] : M[3 * k + 2]; };      // no indexed private array
+    double a = 0.0, b = 0.0;
+    if (j < 3) {
+        for (int k = 0; k < 3; ++k) {
+            a += S[6 * i + k] * Rr[3 * k + jc];
+            b -= S[6 * i + k] * col(Rres, k);
+        }
+    } else {
+        const double vc[3] = {col(vx, 0), col(vx, 1), col(vx, 2)};      // column jc of v^
+        for (int k = 0; k < 3; ++k) {
+            double rv = 0.0, jl = 0.0;      // (R_ref v^)[k][jc], (Jl^-1 R_ref)[k][jc]
+            for (int q = 0; q < 3; ++q) { rv += Rr[3 * k + q] * vc[q]; jl += Jr[3 * q + k] * Rr[3 * q + jc]; }
+            a += -S[6 * i + k] * rv + S[6 * i + 3 + k] * jl;
+            b -= S[6 * i + 3 + k] * col(Jr, k);
+        }
+    }
+    j1 = a; j2 = b;
+}
+
+// A half entry of a relative-pose block (types 2 / 3) in the linearisation of the windowed layout, by ALL 64 lanes of one
+// wave: lane 6 i + j < 36 owns element (i, j) of J_1 and J_2 (one pf_rel_element instead of two whole 6 x 6 Jacobians per
+// lane); the residual, the cost and the Huber corrector are the same in every lane.  The columns a lane needs for its sum
+// come from the owners' registers (ds_bpermute, no LDS storage).  Returns the lane's term of the pose's sums as
+// lin_pose_body lays them out -- lanes 0..20: entry (a, c) of J^T J; 21..26: J^T r; 27: the cost where this half counts
+// it -- and 0 elsewhere.  The first half of a block between two free poses also writes J_1^T J_2, corrector included, to
+// d.pf_cross for k_assemble_reduced: 36 lanes, one store each, nothing else in the launch reads it.
+static __device__ double pf_rel_wave(const Dev &d, int f, const double *T, const double *T_other, int lane, int a, int c) {
+    const int type = d.pf_type[f];
+    const double *dat = d.pf_data + 18 * (size_t)f;
+    const int el = min(lane, 35), i = el / 6, j = el - 6 * i;
+    double r[6], j1, j2;
+    pf_rel_element(type == 2 ? T : T_other, type == 2 ? T_other : T, dat, d.pf_S + 36 * (size_t)f, i, j, r, j1, j2);
+    double sq = 0.0;
+    for (int m = 0; m < 6; ++m) sq += r[m] * r[m];
+    double cost = 0.5 * sq;
+    const double h = d.pf_huber[f];
+    if (h > 0.0 && sq > h * h) {        // as pf_evaluate
+        const double rs = sqrt(sq), sc = sqrt(fmax(DBL_MIN, h / rs));
+        for (int m = 0; m < 6; ++m) r[m] *= sc;
+        j1 *= sc; j2 *= sc;
+        cost = 0.5 * (2.0 * h * rs - h * h);
+    }
+    const double jt = type == 2 ? j1 : j2;
+    const int p = lane < 21 ? a : lane < 27 ? lane - 21 : 0, q = lane < 21 ? c : 0;
+    double v = 0.0, x = 0.0;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+        const double jp = __shfl(jt, 6 * m + p, 64), jq = __shfl(jt, 6 * m + q, 64);
+        v += jp * (lane < 21 ? jq : r[m]);
+        x += __shfl(j1, 6 * m + i, 64) * __shfl(j2, 6 * m + j, 64);
+    }
+    if (type == 2 && dat[14] >= 0.0 && lane < 36) d.pf_cross[36 * (size_t)f + lane] = x;
+    if (lane >= 27) v = (lane == 27 && dat[13] != 0.0) ? cost : 0.0;
+    return v;
+}
+
 }  // namespace ssba

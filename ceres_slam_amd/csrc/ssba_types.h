@@ -204,6 +204,7 @@ struct Dev {
     const uint32_t *slab_win, *slab_lm_begin, *slab_lm_end;  // n_slabs
     double *slab;                    // n_slabs*SLAB_DOUBLES
     const uint32_t *sblk_a, *sblk_b, *sblk_start, *sblk_contrib;  // n_sblk(+1), contributions
+    const uint32_t *sblk_rf_start, *sblk_rf;                     // per block: relative-pose entries (first half | bit 31: block is J_2^T J_1), or null
     const uint32_t *prow_start, *prow_contrib;                   // nfree+1, (slab*TW+slot)
     // reduced system (exchange vector) and solution
     double *xv;                      // [D0 | L0 | rhs | gpx | hdiag | scal]
@@ -286,6 +287,7 @@ struct Dev {
     const int *pf_type;                             // F
     const double *pf_data, *pf_S, *pf_huber;        // F*18, F*36, F
     double *pf_cost;                                // P: cost of the factors of each pose at the linearisation point
+    double *pf_cross;                               // F*36 or null: J_1^T J_2 of a relative-pose block at its first half entry (windowed layout; linearisation -> k_assemble_reduced)
     // general structure (tracks longer than TW, loop closures): dense reduced camera system (ssba_dense.hip)
     int dense, n_dn, dn_pad;                        // n_dn = 6 * nfree, dn_pad = n_dn rounded up to DN_BS (= row stride of dn_S)
     const uint32_t *dn_lm_start;                    // Lpad+1: observations of a landmark, landmark-major

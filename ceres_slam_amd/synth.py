@@ -291,6 +291,28 @@ def add_loop_closure(prob: StereoBAProblem, num_states: int = 3, num_landmarks: 
     return out
 
 
+def make_odometry_factors(prob: StereoBAProblem, seed: int = 0, huber: float = 0.0, loop: bool = False, prior: bool = True) -> list:
+    """RelativePoseErrorAutomatic blocks in the shape of tests/blowup_test.cpp:55-76, as ``pose_factors`` of
+    ``solver.StereoBA``: a noisy ``T_2_1`` between consecutive states from ``poses_gt`` with an SPD stiffness
+    (wheel / inertial / visual odometry), with ``loop`` one more between the first and the last state, with ``prior``
+    the pose prior on state 0 that holds the gauge (then no pose is held constant).  A chain between neighbouring free
+    poses keeps a windowed problem on the windowed layout; the loop block sends it to the general one."""
+    rng = np.random.default_rng(seed)
+    P = prob.num_poses
+    pairs = [(k, k + 1) for k in range(P - 1)] + ([(0, P - 1)] if loop else [])
+    factors = [dict(pose=0, type=0, data=prob.poses_init[0], stiffness=np.eye(6) * 1e2)] if prior else []
+    for k1, k2 in pairs:
+        (t1, R1), (t2, R2) = pose_unpack(prob.poses_gt[k1]), pose_unpack(prob.poses_gt[k2])
+        R21 = R2 @ R1.T
+        t21 = t2 - R21 @ t1
+        A = rng.normal(size=(6, 6)) * 0.3
+        eps = 0.01 * rng.normal(size=6)          # T_2_1 <- exp(eps) T_2_1 (perturbations.hpp:61-62)
+        E = so3_exp(eps[3:])
+        factors.append(dict(pose=k1, pose2=k2, type=2, data=pose_pack(E @ t21 + eps[:3], E @ R21),
+                            stiffness=(A @ A.T + np.diag([30.0] * 3 + [100.0] * 3)).ravel(), huber=huber))
+    return factors
+
+
 def make_config(name: str, **kw) -> StereoBAProblem:
     P, L = CONFIGS[name]
     kw.setdefault("track_len", CONFIG_TRACK.get(name, 12))

@@ -405,11 +405,19 @@ SSBA_API int ssba_set_point_blocks_constant(ssba_problem *p, int is_constant);
  *   stiffness, az_err_thresh, zen_err_thresh), loss, pose) (sun_sensor_error.hpp:35-104; dataset_vo_sun.cpp:80-99):
  *   azimuth / zenith of R * expected_dir_g against the observation, wrap-around, outlier thresholds; 2 residuals;
  *   stiffness 2x2 row-major.  huber_a > 0 wraps the block in ceres::HuberLoss(huber_a) (:87-92), 0 = NULL loss.
- * Both before ssba_finalize; not on constant poses; not together with lighting terms or landmark sharding yet. */
+ * Both before ssba_finalize; not on constant poses; not together with lighting terms or the partitioned reduced solve
+ * (ssba_set_partition).  Landmark sharding with the all-reduce of the reduced system takes them: one rank adds them to the sums. */
 SSBA_API int ssba_add_pose_prior(ssba_problem *p, uint32_t pose, const double T_ref[12], const double stiffness[36], double huber_a);
 /* ssba_add_relative_pose replaces problem.AddResidualBlock(RelativePoseErrorAutomatic::Create(T_2_1_ref, stiffness), loss,
  *   pose1, pose2) (include/ceres_slam/relative_pose_error.hpp:22-57; tests/blowup_test.cpp:70-76):
- *   r = stiffness * log(T_2_1_ref * T_1 * T_2^-1), 6 residuals.  Problems with such blocks run the general-structure kernels. */
+ *   r = stiffness * log(T_2_1_ref * T_1 * T_2^-1), 6 residuals.  A block with one constant pose is a unary block on the other.
+ *   Blocks between two free poses keep the windowed layout (ssba_stats.general_structure = 0) when the problem would be on it
+ *   without them (tracks <= SSBA_MAX_TRACK, co-visibility span <= 12, no per-block stereo stiffness, no closure border,
+ *   SSBA_FORCE_DENSE unset), has at least one stereo block, no lighting terms, is neither sharded nor partitioned, and every
+ *   such block joins poses whose free-pose indices differ by exactly 1 (odometry between consecutive states; a constant pose
+ *   between two free ones leaves them consecutive).  Several blocks on one pair are summed in the order they were added.
+ *   Any other block (a loop closure, a block over two or more free poses, a pose graph without stereo blocks) sends the
+ *   problem to the general-structure kernels (general_structure = 1), single GPU. */
 SSBA_API int ssba_add_relative_pose(ssba_problem *p, uint32_t pose1, uint32_t pose2, const double T_2_1_ref[12], const double stiffness[36],
                            double huber_a);
 SSBA_API int ssba_add_sun_observation(ssba_problem *p, uint32_t pose, const double observed_dir_c[3],

@@ -8,7 +8,8 @@ the Levenberg-Marquardt diagonal clamp(diag(H) s^2, 1e-6, 1e32) / (radius s^2) o
 
     S = A_pp - sum_j W_j V_j^-1 W_j^T,    rhs = -(g_p - sum_j W_j V_j^-1 g_l,j),    S delta_p = rhs.
 
-Unary pose rows (prior, sun sensor) are passed in as fp64 blocks; their rounding enters the bounds as c u |H_unary|.
+Unary pose rows (prior, sun sensor) are passed in as fp64 blocks; their rounding enters the bounds as c u |H_unary|.  Or the
+pose-only residual blocks (prior, sun sensor, relative pose) come in long double as well: pose_factor_rows, PoseFactorSums.
 
 The bars derived here all use u = 2^-53 (the precision of the side under test):
 
@@ -425,7 +426,10 @@ class SchurSystem:
     """The damped (radius) or undamped (radius=None) reduced camera system in long double, stored as 6x6 blocks.
 
     free_idx: free index of every pose (-1 constant).  H_unary / g_unary (n x n and n, fp64, free-pose coordinates): unary
-    pose rows already summed; Ha_unary their magnitude sum |J|^T |J| (unary_pose_blocks).  The Schur terms are summed in
+    pose rows already summed; Ha_unary their magnitude sum |J|^T |J| (unary_pose_blocks).  factor_sums (PoseFactorSums): the
+    long-double blocks of the pose-only residual blocks instead -- H with the off-diagonal 6x6 blocks J_1^T J_2 of the relative
+    blocks, g, and their bars: the sums of magnitudes join those of the stereo terms under (m + c) u with the blocks' rows
+    counted in m, and the rounding of the row values (C_TERMS u (mag |J| + |J| mag)) is added to E.  The Schur terms are summed in
     chunks into the distinct 6x6 blocks, so a C2-sized system (14 million observation pairs) fits in memory.
 
     E is a bound on the fp64 rounding of each entry, not a relative bar: where a landmark is nearly unobserved in depth
@@ -433,7 +437,7 @@ class SchurSystem:
     """
 
     def __init__(self, rows, obs_pose, obs_point, free_idx, num_points, radius=None, H_unary=None, g_unary=None,
-                 Ha_unary=None):
+                 Ha_unary=None, factor_sums=None):
         k = np.asarray(obs_pose, np.int64)
         j = np.asarray(obs_point, np.int64)
         fidx = np.asarray(free_idx, np.int64)
@@ -489,6 +493,17 @@ class SchurSystem:
                 gp[a] += np.asarray(g_unary[6 * a: 6 * a + 6], LD)
                 Hda[a] += Ha_unary[6 * a: 6 * a + 6, 6 * a: 6 * a + 6]
                 gpa[a] += np.abs(g_unary[6 * a: 6 * a + 6])
+        fs = self.factor_sums = factor_sums
+        free_poses = np.flatnonzero(fidx >= 0)
+        gv = np.zeros((nf, 6))
+        if fs is not None:
+            a = fidx[free_poses]
+            Hd[a] += fs.H[free_poses]
+            gp[a] += fs.g[free_poses]
+            Hda[a] += fs.Hs[free_poses]
+            gpa[a] += fs.gs[free_poses]
+            m_diag[a] += fs.m[free_poses]
+            gv[a] = fs.gv[free_poses]
         hp = np.diagonal(Hd, axis1=1, axis2=2).copy()
         self.sp = LD(1) / (LD(1) + np.sqrt(hp))
         dmp = _damping(hp, self.sp, radius)
@@ -528,7 +543,9 @@ class SchurSystem:
         pb = np.concatenate([p[1] for p in pairs]) if pairs else np.zeros(0, np.int64)
         pkeys = f[pa] * nf + f[pb]
         diag_keys = np.arange(nf) * (nf + 1)
-        self.keys = np.unique(np.concatenate([pkeys, diag_keys]))
+        cross = [] if fs is None else [(fidx[k1], fidx[k2], X) for (k1, k2), X in fs.cross.items() if fidx[k1] >= 0 and fidx[k2] >= 0]
+        cross_keys = np.array([k for a, b, _ in cross for k in (a * nf + b, b * nf + a)], np.int64)
+        self.keys = np.unique(np.concatenate([pkeys, diag_keys, cross_keys]))
         K = self.keys.size
         blocks = np.zeros((K, 6, 6), dtype=LD)
         blocka = np.zeros((K, 6, 6))
@@ -546,14 +563,24 @@ class SchurSystem:
         blocks[dslot] += Hd
         blocka[dslot] += Hda
         counts[dslot] += m_diag
+        Ev = np.zeros((K, 6, 6))
+        for a, b, X in cross:       # J_1^T J_2 at (a, b), its transpose at (b, a): no landmark need fill them
+            for key, T in ((a * nf + b, lambda M: M), (b * nf + a, lambda M: M.T)):
+                i = int(np.searchsorted(self.keys, key))
+                blocks[i] += T(X[0])
+                Ev[i] += T(X[1])
+                blocka[i] += T(X[2])
+                counts[i] += X[3]
+        if fs is not None:
+            Ev[dslot[fidx[free_poses]]] += fs.Hv[free_poses]
         self.blocks = blocks
         self.m = counts
-        self.E_blocks = ((self.m + C_TERMS) * U)[:, None, None] * blocka
+        self.E_blocks = ((self.m + C_TERMS) * U)[:, None, None] * blocka + Ev
         if H_unary is not None:      # unary rows: rounding of the device's closed forms, c u |H_unary|
             for i, key in enumerate(self.keys):
                 a, b = key // nf, key % nf
                 self.E_blocks[i] += C_TERMS * U * Ha_unary[6 * a: 6 * a + 6, 6 * b: 6 * b + 6]
-        self.E_rhs = (m_rhs + C_TERMS) * U * (gpa + rla).reshape(n)
+        self.E_rhs = (m_rhs + C_TERMS) * U * (gpa + rla).reshape(n) + gv.reshape(n)
         self.rows = rows
         self._k, self._j, self._f = k, j, f
         self.nb = 0
@@ -671,11 +698,30 @@ class SchurSystem:
         Jd[fr] += np.einsum("nai,ni->na", self.rows["Jp"][fr], x[self._f[fr]])
         r = self.rows["r"]
         terms = -(Jd * (r + LD(0.5) * Jd))
-        return terms.sum(), float(np.abs(np.asarray(Jd * r, np.float64)).sum() + 0.5 * np.abs(np.asarray(Jd * Jd, np.float64)).sum()), terms.size
+        total, mag, count = terms.sum(), float(np.abs(np.asarray(Jd * r, np.float64)).sum() + 0.5 * np.abs(np.asarray(Jd * Jd, np.float64)).sum()), terms.size
+        if self.factor_sums is not None:
+            # the rows of the pose-only blocks, with their magnitudes in place of the absolute values: C_ROW u on J and on r
+            # costs 2 C_ROW u (mag_J |x|) mag_r to first order, which (n + c) u times that product covers from n >= 16 rows on
+            fidx = np.full(self.factor_sums.H.shape[0], -1, np.int64)
+            fidx[self.factor_sums.free_poses] = np.arange(self.nf)
+            for a in self.factor_sums.rows:
+                jd, jm = np.zeros(a["r"].shape[0], LD), np.zeros(a["r"].shape[0])
+                for (k, J), (_, Jm) in zip(a["blocks"], a["mag_blocks"]):
+                    if fidx[k] >= 0:
+                        jd += J @ x[fidx[k]]
+                        jm += Jm @ np.abs(np.asarray(x[fidx[k]], np.float64))
+                total += -(jd * (a["r"] + LD(0.5) * jd)).sum()
+                mag += float((jm * a["mag_r"]).sum() + 0.5 * (jm * jm).sum())
+                count += jd.size
+        return total, mag, count
 
 
-def free_index(num_poses, obs_pose, pose_const):
+def free_index(num_poses, obs_pose, pose_const, factor_poses=None):
+    """Free index of every pose (-1: constant, or touched by nothing).  factor_poses: the poses that a pose-only residual block
+    touches -- a state without observations is free through its odometry blocks alone."""
     seen = np.bincount(np.asarray(obs_pose, np.int64), minlength=num_poses) > 0
+    if factor_poses is not None:
+        seen[np.asarray(list(factor_poses), np.int64)] = True
     free = ~np.asarray(pose_const, bool) & seen
     fidx = np.full(num_poses, -1, np.int64)
     fidx[free] = np.arange(int(free.sum()))
@@ -823,6 +869,223 @@ def unary_pose_blocks(poses, factors, fidx):
         g[sl] += J.T @ r
         Ha[sl, sl] += np.abs(J).T @ np.abs(J)
     return H, g, Ha
+
+
+# ------------------------------------------------------------------------------------------------------- pose-factor rows
+_PF_INPUTS = {0: ("T", "ref", "S"), 1: ("T", "oc", "eg", "S"), 2: ("T", "T2", "ref", "S")}
+_PF_UNITS = {0: (("R_res", 9), ("t_res", 3), ("axis", 3), ("sin_angle", 1), ("cos_angle", 1), ("angle", 1)),
+             1: (("s_c", 3), ("eaz", 1), ("ezen", 1), ("oaz", 1), ("ozen", 1)),
+             2: (("R_12", 9), ("v", 3), ("R_res", 9), ("t_res", 3), ("axis", 3), ("sin_angle", 1), ("cos_angle", 1), ("angle", 1))}
+_PF_GUARDS = {0: ("angle",), 1: ("raz", "raz_wrapped", "rzen"), 2: ("angle",)}
+
+
+def _pf_eval(tp, x, pert, outlier=None):
+    """One type of pose factor on stacked blocks `x` (complex arrays): [r (N,m), J per pose touched (N,m,6)..., the
+    uncorrected r (N,m), |r|^2 (N,), the guard quantities (N,)...] and the Huber decision.  Complex step through the forward
+    formulas of np_reference and SE3Perturbation's Plus (_se3_columns); the corrector sqrt(rho') multiplies r and J where
+    `outlier` (the decision of the unperturbed long-double |r|^2 when the magnitudes are measured)."""
+    import np_reference as npr
+    h = H_CS
+    seen = {}
+
+    def hook(name, v):
+        if pert is not None:
+            v = pert(name, v)
+        seen.setdefault(name, v)        # the first evaluation is the one at the pose itself
+        return v
+
+    if tp == 0:
+        funs = [(x["T"], lambda T: npr.pose_prior_residual(T, x["ref"], x["S"], hook))]
+    elif tp == 1:
+        funs = [(x["T"], lambda T: npr.sun_sensor_residual(T, x["oc"], x["eg"], x["S"], x["taz"], x["tzen"], hook))]
+    else:
+        funs = [(x["T"], lambda T: npr.relative_pose_residual(T, x["T2"], x["ref"], x["S"], hook)),
+                (x["T2"], lambda T: npr.relative_pose_residual(x["T"], T, x["ref"], x["S"], hook))]
+    r = funs[0][1](funs[0][0]).real
+    Js = []
+    for T, f in funs:
+        cols = _se3_columns(T, h)
+        Js.append(np.stack([f(cols[c]).imag / h for c in range(6)], -1))
+    sq = (r * r).sum(-1)
+    a = x["huber"].real
+    if outlier is None:
+        outlier = (a > 0) & (sq > a * a)
+    w = np.where(outlier, np.sqrt(np.where(outlier, a, 1) / np.sqrt(np.where(outlier, sq, 1))), 1)
+    return [r * w[:, None]] + [J * w[:, None, None] for J in Js] + [r, sq] + [seen[g].real for g in _PF_GUARDS[tp]], outlier
+
+
+def pose_factor_rows(poses, factors, dtype=LD, mags=True):
+    """Rows of the pose-only residual blocks -- pose prior (type 0), sun sensor (1), relative pose between `pose` and
+    `pose2` (2) -- in `dtype` (LD, or np.float64: the fp64 evaluation the bars are proved on), by complex step in the
+    matching complex type through np_reference's forward formulas and SE3Perturbation's Plus, as phong_rows does it.  The
+    formulas' own branches and constants are followed: the fp64 DBL_EPSILON guard of the logarithm (first-order branch
+    vee(C - I) / 2), the fp64 value of pi in the wrap of the azimuth residual, the thresholds that zero a residual angle
+    together with its gradient, and the Huber corrector sqrt(rho') on r and J, decided on |r|^2 in `dtype`.
+
+    One dict per factor, in order: r (m), blocks [(pose, J (m x 6))], cost = rho(|r|^2) / 2, sq = |r|^2 before the corrector,
+    outlier, guards {angle | raz, raz_wrapped, rzen}; and (mags=True) a rounding magnitude of every value: mag_r, mag_blocks,
+    mag_r_raw (of the uncorrected r), mag_sq, mag_guards.  The bar on an fp64 evaluation is C_ROW u mag.
+
+    mag is measured as in phong_rows: |Q| plus the first-order sensitivities of Q to relative perturbations DELTA_MAG of
+    each input (poses, the reference pose or the two directions, the stiffness) and of each intermediate that the
+    reference's formula stores, component by component.  What each intermediate stands for:
+      R_res      the 3-term dot products of R_ref R^T (R_ref R_12), which every entry of the logarithm reads; and, in
+                 t_ref - R_res t, the product whose rotation columns cancel against the motion of t (d / d eps_r of the
+                 translation rows is exactly zero: a rigid rotation moves R_res and t together) -- no perturbation of an
+                 input sees that cancellation, since Plus carries it along, but a rounded R_res breaks it;
+      R_12, v    (relative) the same for R_1 R_2^T and v = t_1 - R_12 t_2: R_12 t_2 does not change with a rotation of pose 2,
+                 and v cancels where both poses are far from the origin and close to each other;
+      t_res      the sum t_ref - R_res t (R_ref v + t_ref): cancels where the pose is far from the origin;
+      axis       the differences C_kj - C_jk, of size 2 sin(angle): near pi they cancel to the rounding of C;
+      sin_angle  the square root of the sum of squares; cos_angle: the trace minus one, which cancels near angle = 2 pi / 3
+                 and whose rounding moves atan2 by |d cos| sin near pi / 2;
+      angle      atan2 itself (added to the list the rows were first measured with: a relative change of sin_angle moves the
+                 angle and the quotient angle / sin_angle together, so at small angles it cancels out of the logarithm,
+                 while the rounding of atan2 and that of the division are independent; the off-diagonal entries of
+                 d log / d eps, ~angle / 2 beside a diagonal of 1, are differences of terms of size 1 that only this sees);
+      s_c        R e_g: 1 - y^2 and x^2 + z^2 of the angle gradients read it -- 1 / sqrt(1 - y^2) has the relative sensitivity
+                 y^2 / (1 - y^2) to y, which is the loss of 1 - y^2 as the zenith tends to 0 or pi;
+      the four angles  acos and atan2 (a few ulps each) and the differences e - o, which cancel for a small residual.
+    The Huber scale is a function of the row (w = sqrt(a / |r|)) and is perturbed with it.  Where a threshold zeroes an angle,
+    Q and mag are 0 for that angle's share: the bar is then an exact zero.  The derivatives are measured with one extra
+    evaluation per perturbation, so mag carries a relative error of 2^-64 / DELTA_MAG = 2^-12 in long double."""
+    cdt = np.clongdouble if dtype == LD else complex
+    poses = np.asarray(poses, np.float64)
+    out = [None] * len(factors)
+    for tp in (0, 1, 2):
+        idx = [i for i, f in enumerate(factors) if f["type"] == tp]
+        if not idx:
+            continue
+        N = len(idx)
+        fs = [factors[i] for i in idx]
+        dat = np.stack([np.asarray(f["data"], np.float64).ravel()[:12 if tp != 1 else 8] for f in fs])
+        m = 2 if tp == 1 else 6
+        c = lambda v: np.asarray(v, dtype=cdt)
+        x = dict(T=c(poses[[f["pose"] for f in fs]]), S=c(np.stack([np.asarray(f["stiffness"], np.float64).reshape(m, m) for f in fs])),
+                 huber=c([f.get("huber", 0.0) for f in fs]))
+        if tp == 1:
+            x.update(oc=c(dat[:, :3]), eg=c(dat[:, 3:6]), taz=c(dat[:, 6]), tzen=c(dat[:, 7]))
+        else:
+            x["ref"] = c(dat)
+        if tp == 2:
+            x["T2"] = c(poses[[f["pose2"] for f in fs]])
+        res, outlier = _pf_eval(tp, x, None)
+        nj = 2 if tp == 2 else 1
+        acc = None
+        if mags:
+            ref = [np.asarray(v, LD) for v in res]
+            acc = [np.abs(np.asarray(v, np.float64)) for v in res]
+
+            def add(res2, rel):
+                for a, v, r0 in zip(acc, res2, ref):
+                    d = np.abs(np.asarray(np.asarray(v, LD) - r0, np.float64))
+                    a += d / rel.reshape((-1,) + (1,) * (d.ndim - 1))
+
+            for name in _PF_INPUTS[tp]:
+                flat = x[name].reshape(N, -1)
+                for k in range(flat.shape[1]):
+                    xr = np.abs(np.asarray(flat[:, k].real, np.float64))
+                    if not np.any(xr > 0):
+                        continue
+                    f2 = flat.copy()
+                    f2[:, k] = f2[:, k] * (1 + DELTA_MAG)
+                    rel = np.abs(np.asarray((f2[:, k] - flat[:, k]).real, np.float64)) / np.maximum(xr, 1e-300)
+                    y = dict(x)
+                    y[name] = f2.reshape(x[name].shape)
+                    add(_pf_eval(tp, y, None, outlier)[0], np.where(xr > 0, rel, np.inf))
+            for name, width in _PF_UNITS[tp]:
+                for k in range(width):
+                    def pert(nm, v, name=name, k=k, width=width):
+                        if nm != name:
+                            return v
+                        if width == 1:
+                            return v * (1 + DELTA_MAG)
+                        v = v.reshape(v.shape[:-2] + (9,)).copy() if width == 9 else v.copy()
+                        v[..., k] = v[..., k] * (1 + DELTA_MAG)
+                        return v.reshape(v.shape[:-1] + (3, 3)) if width == 9 else v
+                    add(_pf_eval(tp, x, pert, outlier)[0], np.full(N, DELTA_MAG))
+        rdt = LD if dtype == LD else np.float64
+        for n, i in enumerate(idx):
+            f = fs[n]
+            ks = [f["pose"]] + ([f["pose2"]] if tp == 2 else [])
+            sq, a = res[nj + 2][n], rdt(f.get("huber", 0.0))
+            rho = 2 * a * np.sqrt(sq) - a * a if outlier[n] else sq
+            d = dict(r=np.asarray(res[0][n], rdt), blocks=[(k, np.asarray(res[1 + b][n], rdt)) for b, k in enumerate(ks)],
+                     cost=rdt(0.5) * rho, sq=sq, outlier=bool(outlier[n]),
+                     guards={g: res[nj + 3 + q][n] for q, g in enumerate(_PF_GUARDS[tp])})
+            if mags:
+                d.update(mag_r=acc[0][n], mag_blocks=[(k, acc[1 + b][n]) for b, k in enumerate(ks)], mag_r_raw=acc[nj + 1][n],
+                         mag_sq=acc[nj + 2][n], mag_guards={g: acc[nj + 3 + q][n] for q, g in enumerate(_PF_GUARDS[tp])})
+            out[i] = d
+    return out
+
+
+def _pf_product(A, Am, B, Bm):
+    """A^T B over the rows of one block with the two parts of its bar: (value, value rounding, sum of magnitudes)."""
+    f = lambda v: np.abs(np.asarray(v, np.float64))
+    return A.T @ B, C_TERMS * U * (Am.T @ f(B) + f(A).T @ Bm), f(A).T @ f(B)
+
+
+def factor_poses(factors):
+    return sorted({k for f in factors for k in ([f["pose"]] + ([f["pose2"]] if f["type"] == 2 else []))})
+
+
+class PoseFactorSums:
+    """What the device sums from the pose-only residual blocks, in long double from pose_factor_rows (with magnitudes) and in
+    list order: per pose H = sum J^T J and g = sum J^T r, per pair of poses of a relative block J_1^T J_2 (cross[(k1, k2)]),
+    and the cost.  `free_poses`: the poses that are free (for SchurSystem.model_cost_change); default all.
+
+    Bars.  A row value carries C_ROW u mag, so a sum of m products a_i b_i carries, to first order,
+        C_TERMS u sum (mag_a |b| + |a| mag_b)  +  (m + C_TERMS) u sum |a| |b|:
+    the rounding of the values (C_ROW = C_TERMS; Hv, gv, cross[..][1]) and the gamma_m of the summation with the c of the
+    products' own arithmetic (Hs, gs, cross[..][2] are the sums of magnitudes, m / cross[..][3] the numbers of terms), as in
+    test_pose_graph_only_with_a_prior_exactly_on_its_pose.  The cost: C_TERMS u sum |r| mag_r + (n + C_TERMS) u sum |term|
+    over the n blocks (cost_at)."""
+
+    def __init__(self, P, factors, rows, free_poses=None):
+        f = lambda v: np.abs(np.asarray(v, np.float64))
+        self.rows = rows
+        self.free_poses = np.arange(P) if free_poses is None else np.asarray(free_poses, np.int64)
+        self.H, self.g = np.zeros((P, 6, 6), LD), np.zeros((P, 6), LD)
+        self.Hv, self.Hs, self.gv, self.gs = np.zeros((P, 6, 6)), np.zeros((P, 6, 6)), np.zeros((P, 6)), np.zeros((P, 6))
+        self.m = np.zeros(P)
+        self.cross = {}
+        self.cost, self.cost_v, self.cost_s = LD(0), 0.0, 0.0
+        for fct, a in zip(factors, rows):
+            r, rm = a["r"], a["mag_r"]
+            for (k, J), (_, Jm) in zip(a["blocks"], a["mag_blocks"]):
+                for tgt, (val, v, s) in (((self.H, self.Hv, self.Hs), _pf_product(J, Jm, J, Jm)),
+                                         ((self.g, self.gv, self.gs), _pf_product(J, Jm, r[:, None], rm[:, None]))):
+                    tgt[0][k] += val.reshape(tgt[0][k].shape)
+                    tgt[1][k] += v.reshape(tgt[1][k].shape)
+                    tgt[2][k] += s.reshape(tgt[2][k].shape)
+                self.m[k] += r.shape[0]
+            if fct["type"] == 2:
+                (k1, J1), (k2, J2) = a["blocks"]
+                (_, M1), (_, M2) = a["mag_blocks"]
+                val, v, s = _pf_product(J1, M1, J2, M2)
+                X = self.cross.setdefault((k1, k2), [np.zeros((6, 6), LD), np.zeros((6, 6)), np.zeros((6, 6)), 0])
+                X[0] += val
+                X[1] += v
+                X[2] += s
+                X[3] += 6
+            self.cost += a["cost"]
+            self.cost_v += C_TERMS * U * float((f(r) * rm).sum())
+            self.cost_s += abs(float(a["cost"]))
+        self.n = len(factors)
+
+    def H_bar(self, extra_m=0.0):
+        return self.Hv + ((self.m + extra_m + C_TERMS) * U)[:, None, None] * self.Hs
+
+    def g_bar(self, extra_m=0.0):
+        return self.gv + ((self.m + extra_m + C_TERMS) * U)[:, None] * self.gs
+
+    def cross_bar(self, key):
+        X = self.cross[key]
+        return X[1] + (X[3] + C_TERMS) * U * X[2]
+
+    def cost_bar(self):
+        return self.cost_v + (self.n + C_TERMS) * U * self.cost_s
 
 
 # ---------------------------------------------------------------------------------------------------------------- dogleg

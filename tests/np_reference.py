@@ -240,52 +240,98 @@ class NumpyBA:
 
 
 # ---- unary pose rows of the sun-aided driver (tests/dataset_vo_sun.cpp:80-124) ------------------------------
-def so3_log(R):
+def _dot(a, b):
+    return a @ b if a.ndim == 1 else (a * b).sum(-1)
+
+
+def _mv(R, p):
+    return R @ p if R.ndim == 2 else np.einsum("...ij,...j->...i", R, p)
+
+
+def _keep(pert):
+    return (lambda name, v: v) if pert is None else pert
+
+
+def _rot(T):
+    return T[..., 3:].reshape(T.shape[:-1] + (3, 3))
+
+
+# The pose-factor formulas take one block (1-D pose, 2-D rotation) or a stack of them (leading dimensions), in complex (the
+# fp64 complex step) or np.clongdouble (tests/hp_reference.py: numpy carries the type of the inputs through every operation
+# here, so no `dtype` argument is needed); the one-block fp64 path is the original arithmetic, bit for bit.  `pert(name,
+# value)`, when given, returns a replacement for the intermediates the formulas store (R_res, t_res, R_12, v, axis,
+# sin_angle, cos_angle, angle, s_c, the four sun angles) and sees the guard quantities (angle, raz, raz_wrapped, rzen).
+def so3_log(R, pert=None):
     """so3group.hpp:293-348 (works on complex matrices for complex-step differentiation)."""
-    axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
-    sin_a = 0.5 * np.sqrt((axis * axis).sum())
-    cos_a = 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)
+    keep = _keep(pert)
+    axis = keep("axis", np.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1))
+    sin_a = keep("sin_angle", 0.5 * np.sqrt((axis * axis).sum(-1)))
+    cos_a = keep("cos_angle", 0.5 * (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0))
     # atan2 for complex arguments: angle + first-order imaginary part
     ang = np.arctan2(sin_a.real, cos_a.real)
     d = (cos_a.real * sin_a.imag - sin_a.real * cos_a.imag) / (sin_a.real ** 2 + cos_a.real ** 2) if np.iscomplexobj(R) else 0.0
-    angle = ang + 1j * d if np.iscomplexobj(R) else ang
-    if abs(ang) <= np.finfo(float).eps:         # first-order branch: vee(C - I)
-        return 0.5 * axis
-    return 0.5 * angle * axis / sin_a
+    angle = keep("angle", ang + 1j * d if np.iscomplexobj(R) else ang)
+    small = abs(ang) <= np.finfo(float).eps     # first-order branch: vee(C - I)
+    if R.ndim == 2:
+        if small:
+            return 0.5 * axis
+        return 0.5 * angle * axis / sin_a
+    return np.where(small[..., None], 0.5 * axis, 0.5 * angle[..., None] * axis / np.where(small, 1.0, sin_a)[..., None])
 
 
-def pose_prior_residual(T, T_ref, S):
+def pose_prior_residual(T, T_ref, S, pert=None):
     """PoseErrorAutomatic (pose_error.hpp:22-55): S [t_ref - R_res t ; log(R_ref R^T)] (complex-step safe)."""
-    R, Rr = T[3:].reshape(3, 3), T_ref[3:].reshape(3, 3)
-    Rres = Rr @ R.T
-    e = np.concatenate([T_ref[:3] - Rres @ T[:3], so3_log(Rres)])
-    return S @ e
+    keep = _keep(pert)
+    R, Rr = _rot(T), _rot(T_ref)
+    Rres = keep("R_res", Rr @ np.swapaxes(R, -1, -2))
+    e = np.concatenate([keep("t_res", T_ref[..., :3] - _mv(Rres, T[..., :3])), so3_log(Rres, pert)], -1)
+    return _mv(S, e)
 
 
-def sun_sensor_residual(T, oc, eg, S, taz, tzen):
+def relative_pose_residual(T1, T2, T_ref, S, pert=None):
+    """RelativePoseErrorAutomatic (relative_pose_error.hpp:22-40): S log(T_ref T1 T2^-1) with the reference's
+    log = [translation ; axis-angle] (complex-step safe)."""
+    keep = _keep(pert)
+    R1, R2, Rr = _rot(T1), _rot(T2), _rot(T_ref)
+    R12 = keep("R_12", R1 @ np.swapaxes(R2, -1, -2))
+    t = keep("t_res", _mv(Rr, keep("v", T1[..., :3] - _mv(R12, T2[..., :3]))) + T_ref[..., :3])
+    return _mv(S, np.concatenate([t, so3_log(keep("R_res", Rr @ R12), pert)], -1))
+
+
+def sun_sensor_residual(T, oc, eg, S, taz, tzen, pert=None):
     """SunSensorErrorAutomatic (sun_sensor_error.hpp:35-104): azimuth / zenith differences (complex-step safe)."""
-    R = T[3:].reshape(3, 3)
-    oc, eg = oc / np.linalg.norm(oc), eg / np.linalg.norm(eg)
-    sc = R @ eg
+    keep = _keep(pert)
+    R = _rot(T)
+    if T.ndim == 1:
+        oc, eg = oc / np.linalg.norm(oc), eg / np.linalg.norm(eg)
+    else:
+        oc, eg = oc / np.sqrt((oc * oc).sum(-1))[..., None], eg / np.sqrt((eg * eg).sum(-1))[..., None]
+    sc = keep("s_c", _mv(R, eg))
 
     def azzen(v):
-        y = v[1]
+        y = v[..., 1]
         zen = np.arccos(-y.real) + (1j * y.imag / np.sqrt(1 - y.real ** 2) if np.iscomplexobj(v) else 0.0)
-        x, z = v[0], v[2]
+        x, z = v[..., 0], v[..., 2]
         az = np.arctan2(x.real, z.real) + (1j * (z.real * x.imag - x.real * z.imag) / (x.real ** 2 + z.real ** 2) if np.iscomplexobj(v) else 0.0)
         return az, zen
     eaz, ezen = azzen(sc)
     oaz, ozen = azzen(oc)
-    raz, rzen = eaz - oaz, ezen - ozen
-    if raz.real > np.pi:
-        raz -= 2 * np.pi
-    elif raz.real < -np.pi:
-        raz += 2 * np.pi
-    if abs(raz.real) > taz:
-        raz = 0.0
-    if abs(rzen.real) > tzen:
-        rzen = 0.0
-    return S @ np.array([raz, rzen])
+    eaz, ezen, oaz, ozen = keep("eaz", eaz), keep("ezen", ezen), keep("oaz", oaz), keep("ozen", ozen)
+    raz, rzen = keep("raz", eaz - oaz), keep("rzen", ezen - ozen)
+    if T.ndim == 1:
+        if raz.real > np.pi:
+            raz -= 2 * np.pi
+        elif raz.real < -np.pi:
+            raz += 2 * np.pi
+        if abs(raz.real) > taz:
+            raz = 0.0
+        if abs(rzen.real) > tzen:
+            rzen = 0.0
+        return S @ np.array([raz, rzen])
+    raz = keep("raz_wrapped", np.where(raz.real > np.pi, raz - 2 * np.pi, np.where(raz.real < -np.pi, raz + 2 * np.pi, raz)))
+    raz = np.where(np.abs(raz.real) > np.real(taz), 0.0, raz)
+    rzen = np.where(np.abs(rzen.real) > np.real(tzen), 0.0, rzen)
+    return _mv(S, np.stack([raz, rzen], -1))
 
 
 def se3_complex_step_jacobian(fun, T, h=1e-30):
@@ -303,14 +349,6 @@ def se3_complex_step_jacobian(fun, T, h=1e-30):
 # step) or np.clongdouble (the long-double reference, tests/hp_reference.py).  The one-observation fp64 path is the original
 # arithmetic, bit for bit.  `pert(name, value)`, when given, returns a replacement for the intermediate unit vectors
 # (nc, ell, cd, m) and for q: hp_reference perturbs them to measure how the rows depend on their rounding.
-def _dot(a, b):
-    return a @ b if a.ndim == 1 else (a * b).sum(-1)
-
-
-def _mv(R, p):
-    return R @ p if R.ndim == 2 else np.einsum("...ij,...j->...i", R, p)
-
-
 def _fmax0(col):      # utils/utils.hpp:16-19 with a = 0
     return np.where(0.0 >= col.real, 0.0 * col, col)
 

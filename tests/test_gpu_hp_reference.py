@@ -50,10 +50,12 @@ def _default_const(P):
     return c
 
 
-def _step_case(tag, ba, prob, radius, pose_const=None):
+def _step_case(tag, ba, prob, radius, pose_const=None, factor_poses=None):
     S, rhs, dp, dl, mcc = ba.lm_step(radius)
     const = _default_const(prob.num_poses) if pose_const is None else np.asarray(pose_const, bool)
-    return _check_solve(tag, S, rhs, dp[_free_mask(prob, const)].ravel())
+    free = hp.free_index(prob.num_poses, prob.obs_pose, const, factor_poses) >= 0
+    assert 6 * int(free.sum()) == S.shape[0]
+    return _check_solve(tag, S, rhs, dp[free].ravel())
 
 
 RADII = [(1e4, 0.0), (3.0, 0.0), (1e4, 1.345)]
@@ -272,6 +274,39 @@ def test_assembly_back_substitution_and_model_cost_against_the_truth(monkeypatch
     S, rhs, dp, dl, mcc = ba.lm_step(radius)
     sy, fidx = _reference(prob, radius, huber)
     _check_against_truth(f"{which} r={radius} h={huber}", sy, S, rhs, dp, dl, mcc, fidx, prob.points_init)
+
+
+_FACTOR_ROWS = {}
+
+
+def _factor_reference(key, prob, factors, const, radius):
+    """The long-double system of a problem with pose-only residual blocks (no loss on the stereo blocks): the stereo rows and
+    the factor rows are computed once per `key` and shared by the radii."""
+    if key not in _FACTOR_ROWS:
+        rows = hp.stereo_rows(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness())
+        fidx = hp.free_index(prob.num_poses, prob.obs_pose, np.asarray(const, bool), hp.factor_poses(factors))
+        sums = hp.PoseFactorSums(prob.num_poses, factors, hp.pose_factor_rows(prob.poses_init, factors), np.flatnonzero(fidx >= 0))
+        _FACTOR_ROWS[key] = rows, fidx, sums
+    rows, fidx, sums = _FACTOR_ROWS[key]
+    return hp.SchurSystem(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, radius, factor_sums=sums), fidx
+
+
+@pytest.mark.parametrize("radius", [1e4, 3.0])
+@pytest.mark.parametrize("huber", [0.0, 0.05])
+@pytest.mark.parametrize("layout", ["windowed", "general"])
+def test_assembly_with_sun_and_prior_blocks_against_the_truth(monkeypatch, layout, huber, radius):
+    """S, rhs, delta_l and the model cost change of the sun-and-prior problem entrywise against the long-double system with the
+    long-double factor blocks, on both layouts (the unary lanes of lin_pose_body; SSBA_FORCE_DENSE=1: pf_evaluate in the general
+    kernels)."""
+    from test_oracle_pose_factors import _sun_problem
+    if layout == "general":
+        monkeypatch.setenv("SSBA_FORCE_DENSE", "1")
+    prob, factors = _sun_problem(huber=huber)
+    ba = _pose_factor_pair(prob, factors)
+    assert ba.stats().general_structure == int(layout == "general")
+    S, rhs, dp, dl, mcc = ba.lm_step(radius)
+    sy, fidx = _factor_reference(("sun", huber), prob, factors, np.zeros(prob.num_poses, bool), radius)
+    _check_against_truth(f"sun_prior {layout} h={huber} r={radius}", sy, S, rhs, dp, dl, mcc, fidx, prob.points_init)
 
 
 # ------------------------------------------------------------------------------------------------------- (C) the covariance

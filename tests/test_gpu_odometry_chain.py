@@ -17,7 +17,8 @@ from ceres_slam_amd import capi, synth
 from ceres_slam_amd.solver import StereoBA
 from oracle import oracle as orc
 from test_gpu_edge_cases import assert_fixed_count_parity
-from test_gpu_hp_reference import _step_case
+import hp_reference as hp
+from test_gpu_hp_reference import _check_against_truth, _factor_reference, _step_case
 from test_gpu_pose_factors import _rel
 from test_oracle_pose_factors import _odometry_factors
 
@@ -148,16 +149,35 @@ def test_windowed_and_general_layout_agree(monkeypatch, name, radius, huber):
 # ------------------------------------------------------------------------------------------------------------------ 4. long double
 @pytest.mark.parametrize("radius", [1e4, 20.0, 3.0])
 @pytest.mark.parametrize("huber", [0.0, 0.05])
-@pytest.mark.parametrize("name", ["p1_c11", "p1", "p1_c12"])
+@pytest.mark.parametrize("name", ["p1_c11", "p1", "p1_c12", "p1_c23", "p3_c4"])
 def test_step_with_odometry_chain_is_fp64_accurate(name, huber, radius):
     """The windowed assembly and solve at the derived bars of test_gpu_hp_reference (eta <= 4096 u, forward error <= min(4096 u
-    kappa_2, 1e-8) against the refined solve of the device's own system).  _step_case takes the free poses to be the observed,
-    non-constant states (hp_reference.free_index), which p3_c4 violates (its states 5-8 are free through odometry alone): the
-    uncut p1 and p1_c12 stand in for it."""
+    kappa_2, 1e-8) against the refined solve of the device's own system).  The states 24-26 of p1_c23 and 5-8 of p3_c4 are free
+    through odometry alone."""
     prob, const = _problem(name)
     ba = _handle(name, huber)
-    assert ba.stats().general_structure == 0 and ba.stats().num_superblocks == 3
-    _step_case(f"odometry_chain {name} h={huber} r={radius}", ba, prob, radius, pose_const=const.astype(bool))
+    assert ba.stats().general_structure == 0 and ba.stats().num_superblocks == (1 if name == "p3_c4" else 3)
+    _step_case(f"odometry_chain {name} h={huber} r={radius}", ba, prob, radius, pose_const=const.astype(bool),
+               factor_poses=hp.factor_poses(_odometry_factors(prob, loop=False)))
+
+
+@pytest.mark.parametrize("radius", [1e4, 3.0])
+@pytest.mark.parametrize("huber", [0.0, 0.05])
+@pytest.mark.parametrize("name,factors", [("p1_c11", "chain"), ("p1_c12", "chain"), ("p1_c23", "chain"), ("p3_c4", "chain"), ("p1", "loop")])
+def test_assembled_system_with_odometry_blocks_against_the_truth(name, factors, huber, radius):
+    """S (every entry: the cross blocks J_1^T J_2 of pf_cross in both orientations and the blocks that landmarks and odometry
+    fill together), rhs, delta_l and the model cost change against the long-double system with the long-double factor blocks.
+    Windowed: pf_rel_wave and k_assemble_reduced, the cut at 11 and at 23 leaving the block across a super-block boundary to the
+    odometry block alone, p1_c23 and p3_c4 with states free through odometry alone; p1 with the loop block: pf_evaluate in the
+    general kernels."""
+    prob, const = _problem(name)
+    ba = _handle(name, huber, factors)
+    assert ba.stats().general_structure == int(factors == "loop")
+    S, rhs, dp, dl, mcc = ba.lm_step(radius)
+    fl = _odometry_factors(prob, loop=factors == "loop", huber=huber)
+    sy, fidx = _factor_reference((name, factors, huber), prob, fl, const, radius)
+    assert sy.n == S.shape[0]
+    _check_against_truth(f"odometry {name} {factors} h={huber} r={radius}", sy, S, rhs, dp, dl, mcc, fidx, prob.points_init)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- 5. solves

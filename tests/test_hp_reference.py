@@ -1115,3 +1115,265 @@ def test_trust_region_decision_margins_and_invalid_steps():
     assert float(s["se_reference"]) == 100.0 and float(s["se_current"]) == 90.0 and float(s["se_acc_ref"]) == 10.0
     d = hp.trust_region_decision(90.0, 91.0, 1.0, 1.0, 50.0, s, on)
     assert float(d["rho0"]) == -1.0 and abs(float(d["rho1"]) - 9.0 / 11.0) < 1e-15 and d["accepted"]
+
+
+# ------------------------------------------------------------------------------------------------------- pose-factor rows
+import pose_factor_edges as pfe
+
+PF_BATCHES = ["prior", "sun", "relative_a", "relative_b", "relative_huber"]
+
+
+def _pf_ratios(rows, got):
+    """Worst |got - truth| / (C_ROW u mag) over the residuals and over the Jacobians; `got`: (r, [J per pose]) per factor."""
+    wr = wj = 0.0
+    for a, (r, Js) in zip(rows, got):
+        assert len(Js) == len(a["blocks"])
+        dr = np.abs(np.asarray(np.asarray(r, hp.LD) - a["r"], np.float64))
+        bar = hp.C_ROW * hp.U * a["mag_r"]
+        if dr.any():
+            wr = max(wr, float((dr / np.maximum(bar, 1e-300)).max()))
+        for J, (_, Jt), (_, m) in zip(Js, a["blocks"], a["mag_blocks"]):
+            dj = np.abs(np.asarray(np.asarray(J, hp.LD) - Jt, np.float64))
+            if dj.any():
+                wj = max(wj, float((dj / np.maximum(hp.C_ROW * hp.U * m, 1e-300)).max()))
+    return wr, wj
+
+
+@pytest.mark.parametrize("name", PF_BATCHES)
+def test_fp64_pose_factor_rows_meet_the_row_bar_on_every_edge_batch(name):
+    """The proof that C_ROW u mag is a bar the reference's own formulas meet in fp64: np_reference in complex128 against the
+    long-double rows, on every row of every edge batch (none left out), after the batch has shown that it holds its edges."""
+    poses, factors = pfe.batches()[name]
+    rows = pfe.truth(name)
+    pfe.assert_edges(name, poses, factors, rows)
+    r64 = hp.pose_factor_rows(poses, factors, dtype=np.float64, mags=False)
+    assert len(r64) == len(rows) == len(factors)
+    assert [a["outlier"] for a in r64] == [a["outlier"] for a in rows]
+    wr, wj = _pf_ratios(rows, [(a["r"], [J for _, J in a["blocks"]]) for a in r64])
+    print("HPREF pose-factor rows fp64", name, f"rows={len(rows)} r_over_bar={wr:.3g} J_over_bar={wj:.3g}")
+    assert wr <= 1.0 and wj <= 1.0, (name, wr, wj)
+
+
+def _dev_so3_log(R):
+    axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = 0.5 * np.sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2])
+    c = 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)
+    angle = np.arctan2(s, c)
+    if abs(angle) <= 2.0 ** -52:
+        return 0.5 * axis
+    return 0.5 * angle * axis / s
+
+
+def _dev_inv_right_jacobian(phi, mut=""):
+    th2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]
+    th = np.sqrt(th2)
+    W = npr.wedge(phi)
+    if mut == "series_everywhere":
+        c = 1.0 / 12.0 + th2 / 720.0
+    else:
+        c = 1.0 / 12.0 + th2 / 720.0 if th < 1e-5 else 1.0 / th2 - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th))
+    return np.eye(3) + 0.5 * W + c * (W @ W)
+
+
+def _device_pose_factor(f, poses, mut=""):
+    """The arithmetic of pf_prior / pf_sun / pf_rel and the corrector of pf_evaluate in fp64 (closed-form Jacobians), written
+    out on the host; `mut`: a plausible kernel error."""
+    S = np.asarray(f["stiffness"], np.float64)
+    d = np.asarray(f["data"], np.float64)
+    T = poses[f["pose"]]
+    if f["type"] == 1:
+        S = S.reshape(2, 2)
+        oc, eg = d[:3] / np.sqrt(d[:3] @ d[:3]), d[3:6] / np.sqrt(d[3:6] @ d[3:6])
+        sc = T[3:].reshape(3, 3) @ eg
+        raz, rzen = np.arctan2(sc[0], sc[2]) - np.arctan2(oc[0], oc[2]), np.arccos(-sc[1]) - np.arccos(-oc[1])
+        if raz > np.pi:
+            raz -= 2 * np.pi
+        elif raz < -np.pi:
+            raz += 2 * np.pi
+        kaz, kzen = not abs(raz) > d[6], not abs(rzen) > d[7]
+        raz, rzen = raz * kaz, rzen * kzen
+        r = S @ np.array([raz, rzen])
+        x, y, z = sc
+        d2 = x * x + z * z
+        gaz, gzen = np.array([z / d2, 0.0, -x / d2]), np.array([0.0, 1.0 / np.sqrt(1.0 - y * y), 0.0])
+        jaz, jzen = -np.cross(gaz, sc) * kaz, -np.cross(gzen, sc) * (kzen or mut == "threshold_keeps_gradient")
+        Js = [np.concatenate([np.zeros((2, 3)), S @ np.stack([jaz, jzen])], 1)]
+    elif f["type"] == 0:
+        S = S.reshape(6, 6)
+        Rres = d[3:12].reshape(3, 3) @ T[3:].reshape(3, 3).T
+        e = np.concatenate([d[:3] - Rres @ T[:3], _dev_so3_log(Rres)])
+        r = S @ e
+        Jr = _dev_inv_right_jacobian(e[3:], mut)
+        Js = [-S @ np.block([[Rres, np.zeros((3, 3))], [np.zeros((3, 3)), Jr]])]
+    else:
+        S = S.reshape(6, 6)
+        T2, Rr = poses[f["pose2"]], d[3:12].reshape(3, 3)
+        R12 = T[3:].reshape(3, 3) @ T2[3:].reshape(3, 3).T
+        v = T[:3] - R12 @ T2[:3]
+        Rres = Rr @ R12
+        e = np.concatenate([Rr @ v + d[:3], _dev_so3_log(Rres)])
+        r = S @ e
+        Jr = _dev_inv_right_jacobian(e[3:], mut)
+        Z = np.zeros((3, 3))
+        Js = [S @ np.block([[Rr, -Rr @ npr.wedge(v)], [Z, (Jr if mut == "left_is_right" else Jr.T) @ Rr]]), -S @ np.block([[Rres, Z], [Z, Jr]])]
+    sq, a = r @ r, f.get("huber", 0.0)
+    if a > 0 and sq > a * a:
+        w = np.sqrt(a / np.sqrt(sq))
+        r = r * w
+        Js = [J * (1.0 if (mut == "huber_on_first_only" and i == 1) else w) for i, J in enumerate(Js)]
+    return r, Js
+
+
+@pytest.mark.parametrize("name", PF_BATCHES)
+def test_device_closed_forms_meet_the_pose_factor_row_bar_and_plausible_errors_do_not(name):
+    """The kernels' closed forms (inverse right Jacobian with its series branch, the angle gradients of the sun block) on the
+    host in fp64, against the long-double complex-step rows at the same bar -- and four plausible errors that must not pass
+    it: the series coefficient used beyond its branch, Jr^-1 in place of Jl^-1 for the first pose of a relative block, the
+    Huber scale on J_1 but not on J_2, a zeroed zenith residual that keeps its gradient."""
+    poses, factors = pfe.batches()[name]
+    rows = pfe.truth(name)
+    wr, wj = _pf_ratios(rows, [_device_pose_factor(f, poses) for f in factors])
+    print("HPREF pose-factor rows closed-form", name, f"r_over_bar={wr:.3g} J_over_bar={wj:.3g}")
+    assert wr <= 1.0 and wj <= 1.0, (name, wr, wj)
+    muts = {"prior": ["series_everywhere"], "sun": ["threshold_keeps_gradient"], "relative_a": [], "relative_b": ["series_everywhere", "left_is_right"],
+            "relative_huber": ["huber_on_first_only", "left_is_right"]}[name]
+    for mut in muts:
+        _, mj = _pf_ratios(rows, [_device_pose_factor(f, poses, mut) for f in factors])
+        assert mj > 1e3, (name, mut, mj)
+
+
+def test_long_double_pose_factor_jacobians_match_central_differences():
+    """On the generic rows (angles 1e-3 and 1, no Huber, nothing zeroed) the complex-step Jacobians against a long-double
+    central difference of the long-double residual through hp.se3_plus: step 2^-20, so the truncation is ~2^-40 |J| and the
+    rounding 2^-64 2^20 mag."""
+    h = hp.LD(2.0) ** -20
+    for name in ("prior", "sun", "relative_b"):
+        poses, factors = pfe.batches()[name]
+        pick = [i for i, f in enumerate(factors) if f["edge"] and (f["edge"][0] == "generic" or f["edge"][:2] in (("angle", "1e-3"), ("angle", "1")))]
+        assert len(pick) >= 4
+        fs = [dict(factors[i], huber=0.0) for i in pick]
+        rows = hp.pose_factor_rows(poses, fs, mags=False)
+        for which in range(2 if name == "relative_b" else 1):
+            touched = sorted({f["pose2" if which else "pose"] for f in fs})
+            for c in range(6):
+                res = []
+                for sgn in (1, -1):
+                    eps = np.zeros((len(touched), 6), hp.LD)
+                    eps[:, c] = sgn * h
+                    P = np.asarray(poses, hp.LD).copy()
+                    P[touched] = hp.se3_plus(poses[touched], eps)[0]
+                    res.append([a["r"] for a in _pf_rows_ld(P, fs)])
+                for a, rp, rm in zip(rows, *res):
+                    J = a["blocks"][which][1]
+                    fd = (rp - rm) / (2 * h)
+                    assert float(np.abs(fd - J[:, c]).max()) <= 1e-9 * max(float(np.abs(J).max()), 1e-300)
+
+
+def _pf_rows_ld(P, fs):
+    """pose_factor_rows at long-double poses (the central difference moves them off the fp64 grid)."""
+    out = []
+    for f in fs:
+        d = np.asarray(f["data"], hp.LD)
+        m = 2 if f["type"] == 1 else 6
+        S = np.asarray(f["stiffness"], hp.LD).reshape(m, m)
+        c = lambda v: np.asarray(v, np.clongdouble)[None]
+        if f["type"] == 0:
+            r = npr.pose_prior_residual(c(P[f["pose"]]), c(d[:12]), c(S))
+        elif f["type"] == 1:
+            r = npr.sun_sensor_residual(c(P[f["pose"]]), c(d[:3]), c(d[3:6]), c(S), c(d[6])[0], c(d[7])[0])
+        else:
+            r = npr.relative_pose_residual(c(P[f["pose"]]), c(P[f["pose2"]]), c(d[:12]), c(S))
+        out.append(dict(r=r[0].real))
+    return out
+
+
+def test_huber_corrector_and_zeroed_sun_rows_behave_as_documented():
+    for name in ("prior", "sun", "relative_huber"):
+        poses, factors = pfe.batches()[name]
+        rows = pfe.truth(name)
+        raw = hp.pose_factor_rows(poses, [dict(f, huber=0.0) for f in factors], mags=False)
+        n_out = 0
+        for f, a, b in zip(factors, rows, raw):
+            a_h = hp.LD(f.get("huber", 0.0))
+            assert a["sq"] == b["sq"] and np.array_equal(b["r"] * b["r"], b["r"] ** 2) and not b["outlier"]
+            assert a["outlier"] == bool(a_h > 0 and a["sq"] > a_h * a_h)
+            w = np.sqrt(a_h / np.sqrt(a["sq"])) if a["outlier"] else hp.LD(1)
+            tol = hp.LD(2.0) ** -60
+            assert np.all(np.abs(a["r"] - w * b["r"]) <= tol * np.abs(b["r"]))
+            for (_, Ja), (_, Jb) in zip(a["blocks"], b["blocks"]):
+                assert np.all(np.abs(Ja - w * Jb) <= tol * np.abs(Jb))
+            rho = 2 * a_h * np.sqrt(a["sq"]) - a_h * a_h if a["outlier"] else a["sq"]
+            assert abs(a["cost"] - rho / 2) <= tol * rho
+            if f["edge"] and f["edge"][0] == "huber":       # the corrected row is continuous across the switch
+                assert abs(float(w) - 1) <= f["edge"][1]
+            n_out += a["outlier"]
+        assert n_out >= 4
+    poses, factors = pfe.batches()["sun"]
+    for f, a in zip(factors, pfe.truth("sun")):
+        if not (f["edge"] and f["edge"][0] == "threshold"):
+            continue
+        S = np.asarray(f["stiffness"], hp.LD).reshape(2, 2)
+        J = a["blocks"][0][1]
+        zero_az, zero_zen = f["edge"][1], f["edge"][2]
+        if zero_az and zero_zen:     # both angles zeroed: the row, its Jacobian and their bars are exact zeros
+            assert not a["r"].any() and not J.any() and not a["mag_r"].any() and not a["mag_blocks"][0][1].any()
+        elif zero_az or zero_zen:    # one angle left: r and every column of J are multiples of that angle's column of S
+            col = S[:, 1 if zero_az else 0]
+            assert a["r"].any() and J[:, 3:].any() and not J[:, :3].any()
+            for v in [a["r"]] + [J[:, c] for c in range(3, 6)]:
+                assert abs(v[0] * col[1] - v[1] * col[0]) <= hp.LD(2.0) ** -60 * abs(v[0] * col[1])
+        else:
+            assert abs(np.linalg.det(np.asarray(J[:, 3:] @ J[:, 3:].T, np.float64))) > 0
+
+
+def test_fp64_pose_factor_rows_agree_with_unary_rows():
+    """unary_rows (the fp64 rows the dogleg and candidate references were built on) and pose_factor_rows at np.float64 are two
+    fp64 evaluations of the same formulas: both within the row bar of the long-double rows."""
+    from test_oracle_pose_factors import _odometry_factors, _sun_problem
+    prob, factors = _sun_problem(huber=0.5)
+    factors = factors + _odometry_factors(prob, huber=0.05)[1:]
+    rows = hp.pose_factor_rows(prob.poses_init, factors)
+    for got in (hp.unary_rows(prob.poses_init, factors), hp.pose_factor_rows(prob.poses_init, factors, dtype=np.float64, mags=False)):
+        wr, wj = _pf_ratios(rows, [(a["r"], [J for _, J in a["blocks"]]) for a in got])
+        assert wr <= 1.0 and wj <= 1.0, (wr, wj)
+
+
+@pytest.mark.parametrize("huber", [0.0, 0.05])
+def test_oracle_system_with_odometry_blocks_is_within_the_assembly_bound_and_plausible_errors_are_not(huber):
+    """SchurSystem with the long-double factor blocks (PoseFactorSums) on a chain whose last states are free through odometry
+    alone: the oracle's fp64 system and step meet E; a cross block stored transposed, or one whose Huber scale reached J_1 but
+    not J_2, does not."""
+    import dataclasses
+    from test_oracle_pose_factors import _odometry_factors
+    prob = synth.make_problem(9, 300, track_len=5, seed=6)
+    keep = prob.obs_pose <= 4
+    prob = dataclasses.replace(prob, obs_pose=prob.obs_pose[keep], obs_point=prob.obs_point[keep], obs_uvd=prob.obs_uvd[keep])
+    const = np.zeros(9, np.uint8)
+    factors = _odometry_factors(prob, loop=False, huber=huber)
+    rows = hp.stereo_rows(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness())
+    assert (hp.free_index(9, prob.obs_pose, const) >= 0).sum() == 5
+    fidx = hp.free_index(9, prob.obs_pose, const, hp.factor_poses(factors))
+    assert np.array_equal(fidx, np.arange(9))
+    pr = hp.pose_factor_rows(prob.poses_init, factors)
+    assert huber == 0 or sum(a["outlier"] for a in pr) >= 1
+    sy = hp.SchurSystem(rows, prob.obs_pose, prob.obs_point, fidx, prob.num_points, 20.0, factor_sums=hp.PoseFactorSums(9, factors, pr))
+    op = orc.OracleProblem(prob.camera, prob.poses_init, prob.points_init, prob.obs_pose, prob.obs_point, prob.obs_uvd, prob.stiffness(),
+                           pose_const=const, pose_factors=factors)
+    S, rhs, _ = op.reduced_system(20.0)
+    dp, dl, mcc = op.lm_step(20.0)
+    ex = sy.assembly_excess(S, rhs)
+    assert max(ex) <= 1.0, ex
+    mref, mag, nt = sy.model_cost_change(dp.ravel(), dl[sy.lm])
+    assert abs(mcc - float(mref)) <= (nt + hp.C_TERMS) * hp.U * mag
+    blk = lambda a, b: (slice(6 * a, 6 * a + 6), slice(6 * b, 6 * b + 6))
+    bad = S.copy()
+    bad[blk(6, 7)] = S[blk(6, 7)].T
+    assert sy.assembly_excess(bad, rhs)[0] > 1e3
+    out = [i for i, a in enumerate(pr) if a["outlier"] and factors[i]["type"] == 2]
+    if out:
+        i = out[-1]
+        (k1, J1), (k2, J2) = pr[i]["blocks"]
+        w = float(np.sqrt(hp.LD(huber) / np.sqrt(pr[i]["sq"])))
+        bad = S.copy()
+        bad[blk(k1, k2)] += np.asarray(J1.T @ J2, np.float64) * (1 / w - 1)
+        assert sy.assembly_excess(bad, rhs)[0] > 1e3

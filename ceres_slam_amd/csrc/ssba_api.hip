@@ -1094,12 +1094,12 @@ int ssba_finalize(ssba_problem *p) {
     };
     auto make_fused = [&](PcrFused &F, size_t n, bool pins) -> int {      // one launch per step (PcrFused): ping-pong buffers of the assembled blocks and the Gram products
         for (int q = 0; q < 2; ++q) {
-            TRY(dzero(p, &F.Dpp[q], n * blk)); TRY(dzero(p, &F.rpp[q], n * BD));
-            TRY(dzero(p, &F.GLL[q], n * blk)); TRY(dzero(p, &F.GUU[q], n * blk));
-            TRY(dzero(p, &F.GUL[q], n * blk)); TRY(dzero(p, &F.GULT[q], n * blk));
-            TRY(dzero(p, &F.gL[q], n * BD)); TRY(dzero(p, &F.gU[q], n * BD));
+            // tile images (ssba_types.h): the symmetric ones hold 15 tiles per block, the couplings 25 of the padded block
+            TRY(dzero(p, &F.Dpp[q], n * PCR_IMG_SYM));
+            TRY(dzero(p, &F.GLL[q], n * PCR_IMG_SYM)); TRY(dzero(p, &F.GUU[q], n * PCR_IMG_SYM));
+            TRY(dzero(p, &F.GUL[q], n * PCR_IMG_FULL)); TRY(dzero(p, &F.GULT[q], n * PCR_IMG_FULL));
         }
-        if (pins) { TRY(dzero(p, &F.Lkeep, n * blk)); TRY(dzero(p, &F.Ukeep, n * blk)); }
+        if (pins) { TRY(dzero(p, &F.Lkeep, n * PCR_IMG_FULL)); TRY(dzero(p, &F.Ukeep, n * PCR_IMG_FULL)); }
         F.on = 1;
         return SSBA_OK;
     };

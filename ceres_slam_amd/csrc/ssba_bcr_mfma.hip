@@ -55,8 +55,12 @@ static __device__ __forceinline__ double mf_rsqrt(double a) {
 }
 
 #ifdef SSBA_STAMPS
-#define MF_STAMP(i) do { if (bx == 3 && by == 0 && (threadIdx.x & 63) == 0) d.dbg[(threadIdx.x >> 6) * 64 + (i)] = clock64(); } while (0)
-// phases of EVERY workgroup (its thread 0) on the chip-wide 100 MHz clock: 0 entry, 1 loaded, 2 factored, 3 staged, 4 done
+#ifndef SSBA_STAMP_BX
+#define SSBA_STAMP_BX 3         // the block whose waves are stamped (tools/bcr_bench.hip: -DSSBA_STAMP_BX=40 is a middle block of step 3 at n = 84)
+#endif
+#define MF_STAMP(i) do { if (bx == SSBA_STAMP_BX && by == 0 && (threadIdx.x & 63) == 0) d.dbg[(threadIdx.x >> 6) * 64 + (i)] = clock64(); } while (0)
+// phases of EVERY workgroup (its thread 0) on the chip-wide 100 MHz clock: 0 entry, 1 loaded, 2 factored, 3 staged, 4 done,
+// 6 through the prologue (operands resolved, hand-off words initialised: the first load is issued next)
 #define MF_WG_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 500) d.dbg[4096 + 8 * (int)blockIdx.x + (k)] = wall_clock64(); } while (0)
 #else
 #define MF_STAMP(i) do { } while (0)
@@ -96,11 +100,13 @@ struct FactorOps {
     double *oD, *oYL, *oYU, *orr, *saveU, *oYB, *xsol;
     int f0;                                 // first free pose of the block (solve + pose update)
     bool hasL, hasU, trL, trU;
-    // fused steps (PcrFused): D = Dg - GA - GB, r = rin - ga - gb (null: nothing to subtract), couplings = sgn x [Lg | Ug];
-    // nD / nr: where the assembled D (upper tiles) / r go for the next step; the Gram products of this block
-    const double *GA, *GB, *ga, *gb;
+    // fused steps (PcrFused): [D | r] = Dg - GA - GB (null: nothing to subtract), couplings = sgn x [Lg | Ug];
+    // nD (nr): where the assembled [D | r] goes for the next step; the Gram products of this block.  GA, GB, the Gram products
+    // and nD of a fused step are tile images (ssba_types.h); imgD / imgR: so are Dg (with r in column 72) / Lg and Ug
+    const double *GA, *GB;
     double sgnL, sgnU;
-    double *nD, *nr, *oGLL, *oGUU, *oGUL, *oGULT, *ogL, *ogU;
+    double *nD, *nr, *oGLL, *oGUU, *oGUL, *oGULT;
+    bool imgD, imgR;
     // chains with pinned ends: saveL (like saveU) keeps a coupling that will not be folded again; a pinned block is only
     // assembled (and, the last one, tracks its coupling to the first); which Gram products somebody will read
     double *saveL;
@@ -118,7 +124,7 @@ static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top
     o.trL = o.trU = false;
     o.saveU = nullptr;
     o.Bg = nullptr; o.oYB = nullptr; o.xsol = nullptr;
-    o.GA = o.GB = o.ga = o.gb = nullptr; o.sgnL = o.sgnU = 1.0; o.nD = o.nr = nullptr;
+    o.GA = o.GB = nullptr; o.sgnL = o.sgnU = 1.0; o.nD = o.nr = nullptr; o.imgD = o.imgR = false;
     o.saveL = nullptr; o.pinned = false; o.gLL = o.gUU = o.gUL = false;
     if (which >= 2) {
         const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
@@ -183,13 +189,14 @@ static __device__ __forceinline__ void fused_ops(const Dev &d, int which, int le
     const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
     const PcrFused &F = which == 3 ? d.spcrf : d.pcrf;
     const BcrLevel &B = which == 3 ? d.slev[0] : d.lev[P.level];
-    const size_t blk = (size_t)BD * BD;
+    const size_t blk = (size_t)BD * BD, isym = PCR_IMG_SYM, ifull = PCR_IMG_FULL;     // row-major blocks; tile images of the plan's own buffers
     const int s = 1 << lev, h = s >> 1, last = B.n - 1, e = bx;
     const int lo = P.pin0 ? 1 : 0, hi = P.pin1 ? last - 1 : last;          // the blocks that are factored (and folded by others)
     o.saveU = o.saveL = nullptr; o.Bg = nullptr; o.oYB = nullptr; o.xsol = nullptr;
     o.oYL = o.oYU = nullptr;
-    o.GA = o.GB = o.ga = o.gb = nullptr;
+    o.GA = o.GB = nullptr;
     o.nD = o.nr = nullptr;
+    o.imgD = lev >= 2; o.imgR = lev >= 1;
     o.pinned = e < lo || e > hi;
     const bool pinned_chain = P.pin0 || P.pin1;
     // couplings of this block at this stride: to e -/+ s, or the kept one to the pinned end; the decoupled last step of a
@@ -210,20 +217,21 @@ static __device__ __forceinline__ void fused_ops(const Dev &d, int which, int le
         o.trL = o.trU = (e & 1) == 0;       // even coupling blocks of a level are stored transposed (ssba_bcr.hip)
     } else {
         const int set = (lev - 1) & 1, prev = e - h, next = e + h;
-        o.Dg = lev == 1 ? B.D + e * blk : F.Dpp[(lev - 1) & 1] + e * blk;
-        o.rin = lev == 1 ? B.r + (size_t)e * BD : F.rpp[(lev - 1) & 1] + (size_t)e * BD;
-        if (prev >= lo) { o.GA = F.GUU[set] + prev * blk; o.ga = F.gU[set] + (size_t)prev * BD; }
-        if (next <= hi) { o.GB = F.GLL[set] + next * blk; o.gb = F.gL[set] + (size_t)next * BD; }
+        o.Lg = o.Ug = F.GUL[set] + e * ifull;           // (an absent coupling's lanes still read: somewhere an image's extent is valid)
+        o.Dg = lev == 1 ? B.D + e * blk : F.Dpp[(lev - 1) & 1] + e * isym;       // (an image carries its r in column 72)
+        o.rin = B.r + (size_t)e * BD;
+        if (prev >= lo) o.GA = F.GUU[set] + prev * isym;
+        if (next <= hi) o.GB = F.GLL[set] + next * isym;
         // the coupling was renewed by the last step iff the neighbour at half the stride was folded; else it is a kept one
-        if (o.hasL) { if (prev >= lo) { o.Lg = F.GUL[set] + prev * blk; o.sgnL = -1.0; } else o.Lg = F.Lkeep + e * blk; }
-        if (o.hasU) { if (next <= hi) { o.Ug = F.GULT[set] + next * blk; o.sgnU = -1.0; } else o.Ug = F.Ukeep + e * blk; }
-        if (!top) { o.nD = F.Dpp[lev & 1] + e * blk; o.nr = F.rpp[lev & 1] + (size_t)e * BD; }
+        if (o.hasL) { if (prev >= lo) { o.Lg = F.GUL[set] + prev * ifull; o.sgnL = -1.0; } else o.Lg = F.Lkeep + e * ifull; }
+        if (o.hasU) { if (next <= hi) { o.Ug = F.GULT[set] + next * ifull; o.sgnU = -1.0; } else o.Ug = F.Ukeep + e * ifull; }
+        if (!top) o.nD = F.Dpp[lev & 1] + e * isym;
     }
     if (pinned_chain && !top) {
         // save a coupling when the NEXT step will find it kept (its half-stride neighbour, e -/+ s, pinned or outside) and this
         // step did not read it from the keep buffer already
-        if (o.hasL && e - s < lo && o.Lg != F.Lkeep + e * blk) o.saveL = F.Lkeep + e * blk;
-        if (o.hasU && e + s > hi && o.Ug != F.Ukeep + e * blk) o.saveU = F.Ukeep + e * blk;
+        if (o.hasL && e - s < lo && o.Lg != F.Lkeep + e * ifull) o.saveL = F.Lkeep + e * ifull;
+        if (o.hasU && e + s > hi && o.Ug != F.Ukeep + e * ifull) o.saveU = F.Ukeep + e * ifull;
     }
     // the Gram products somebody reads: the next step's block e - s / e + s assembles from them (a kept coupling feeds nobody's D)
     o.gLL = o.hasL && e - s >= 0 && !top;
@@ -244,10 +252,23 @@ static __device__ __forceinline__ void fused_ops(const Dev &d, int which, int le
         }
     }
     const int oset = lev & 1;
-    o.oGLL = F.GLL[oset] + e * blk; o.oGUU = F.GUU[oset] + e * blk;
-    o.oGUL = F.GUL[oset] + e * blk; o.oGULT = F.GULT[oset] + e * blk;
-    o.ogL = F.gL[oset] + (size_t)e * BD; o.ogU = F.gU[oset] + (size_t)e * BD;
+    o.oGLL = F.GLL[oset] + e * isym; o.oGUU = F.GUU[oset] + e * isym;
+    o.oGUL = F.GUL[oset] + e * ifull; o.oGULT = F.GULT[oset] + e * ifull;
 }
+
+// One tile image (ssba_types.h) <-> the accumulator registers of a wave: two 16-byte accesses per lane.
+static __device__ __forceinline__ mf_d4 img_load(const double *base, int tile, int lane) {
+    const double2 *p = reinterpret_cast<const double2 *>(base) + tile * (PCR_IMG_TILE / 2) + lane;
+    const double2 a = p[0], b = p[64];
+    return mf_d4{a.x, a.y, b.x, b.y};
+}
+static __device__ __forceinline__ void img_store(double *base, int tile, int lane, const mf_d4 &v) {
+    double2 *p = reinterpret_cast<double2 *>(base) + tile * (PCR_IMG_TILE / 2) + lane;
+    p[0] = make_double2(v[0], v[1]);
+    p[64] = make_double2(v[2], v[3]);
+}
+// tile (ti, tj), ti <= tj, of the 15 upper tiles
+static __device__ __forceinline__ int img_sym_tile(int ti, int tj) { return (ti == 4 ? 14 : ti == 3 ? 12 : ti == 2 ? 9 : ti == 1 ? 5 : 0) + tj - ti; }
 
 struct FactorLds {
     // every block row has its own slots: nothing is overwritten during a factorisation, so the hand-offs below need
@@ -304,6 +325,8 @@ struct FactorLds {
 //         [YU | yr] go to LDS block row by block row AS THEY BECOME FINAL, and every wave but the first adds the contribution of
 //         a finished block row to its share of the 55 Gram tiles (16 rows = four instructions per tile) in the time it would
 //         otherwise spend waiting for the pivot chain: when the last block row is done, so are the products.
+// The buffers only MODE 1 / 2 read and write (PcrFused: assembled blocks, Gram products, kept couplings) are tile images
+// (ssba_types.h): half a tile per 16-byte access and lane, no row predicates.  What other kernels read stays row-major.
 static __device__ __forceinline__ void gram_tile(int u, int &kind, int &ti, int &tj);
 static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], double *scr, int lane);
 constexpr int MF_THREADS2 = 512;
@@ -350,6 +373,7 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
     // other waves' right-hand-side tiles.
     __syncthreads();
     MF_STAMP(0);
+    MF_WG_STAMP(6);
 
     // ---- load: straight into the accumulator layout (128-byte row segments): one per-lane base pointer per column
     //      tile, compile-time row offsets, every load issued before the first is waited for ----------------------
@@ -372,30 +396,44 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
                 }
         }
         if (HAS_D && MODE) {
-            // fused plan: [D | r] = [Dg - GA - GB | rin - ga - gb], the three reads of an entry issued together.  A lane of
-            // column 72 (wave 0's tile column 4) reads the right-hand-side vectors instead of the blocks -- same loop, its own
-            // base pointers and row stride -- and the lanes beyond it read nothing: no separate arrays for r.
+            // fused plan: [D | r] = Dg - GA - GB, the three reads of a tile issued together.  GA and GB are tile images with
+            // their right-hand sides in column 72, and so is Dg from the second step on (o.imgD): half a tile per 16-byte
+            // load, no row predicates (the images hold zeros in rows 72..79 and beyond column 72).  Before that Dg is the
+            // level's row-major block: a lane of column 72 (wave 0's tile column 4) reads the right-hand-side vector instead
+            // -- same loop, its own base pointer and row stride -- and the lanes beyond it read nothing.
             const bool isD = colD < BD, isR = colD == BD;
             const long rstride = isD ? BD : 1, off0 = isD ? offD : g;
-            const double *b0 = isD ? o.Dg : o.rin, *b1 = isD ? o.GA : o.ga, *b2 = isD ? o.GB : o.gb;
+            const double *b0 = isD ? o.Dg : o.rin;
             const bool act = isD || isR;
-            mf_d4 x1[NDT], x2[NDT], y1, y2;
+            const mf_d4 zero4 = mf_d4{0.0, 0.0, 0.0, 0.0};
+            mf_d4 x1[NDT], x2[NDT], y1 = zero4, y2 = zero4;
+            d00 = zero4;
+            if (w == 0) {
+                if (o.imgD) d00 = img_load(o.Dg, 0, lane);
+                else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                d00[q] = (w == 0) ? o.Dg[(4 * q + g) * BD + j] : 0.0;
-                y1[q] = (w == 0 && o.GA) ? o.GA[(4 * q + g) * BD + j] : 0.0;
-                y2[q] = (w == 0 && o.GB) ? o.GB[(4 * q + g) * BD + j] : 0.0;
+                    for (int q = 0; q < 4; ++q) d00[q] = o.Dg[(4 * q + g) * BD + j];
+                }
+                if (o.GA) y1 = img_load(o.GA, 0, lane);
+                if (o.GB) y2 = img_load(o.GB, 0, lane);
             }
 #pragma unroll
-            for (int k = 0; k < NDT; ++k)
+            for (int k = 0; k < NDT; ++k) {
+                const bool have = k <= dj;
+                const int tile = img_sym_tile(k, max(dj, k));
+                dt[k] = x1[k] = x2[k] = zero4;
+                if (o.imgD) {
+                    if (have) dt[k] = img_load(o.Dg, tile, lane);
+                } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool in = (k < 4 || q < 2) && k <= dj && act;
-                    const long off = off0 + (16 * k + 4 * q) * rstride;
-                    dt[k][q] = in ? b0[off] : 0.0;
-                    x1[k][q] = (in && b1) ? b1[off] : 0.0;
-                    x2[k][q] = (in && b2) ? b2[off] : 0.0;
+                    for (int q = 0; q < 4; ++q) {
+                        const bool in = (k < 4 || q < 2) && have && act;
+                        dt[k][q] = in ? b0[off0 + (16 * k + 4 * q) * rstride] : 0.0;
+                    }
                 }
+                if (have && o.GA) x1[k] = img_load(o.GA, tile, lane);
+                if (have && o.GB) x2[k] = img_load(o.GB, tile, lane);
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) d00[q] = d00[q] - y1[q] - y2[q];
 #pragma unroll
@@ -426,6 +464,14 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
                 for (int k = 0; k < NDT; ++k)
 #pragma unroll
                     for (int qq = 0; qq < 4; ++qq) rt[q][k][qq] = (k < 4 || qq < 2) ? pp[(16 * k + 4 * qq) * NBP] : 0.0;
+            } else if (MODE && o.imgR) {                 // a tile image: U^T starts in the middle of column tile 4, so a lane picks its tile
+                const double *pp = base + (cc >> 4) * PCR_IMG_TILE + 2 * (16 * g + (cc & 15));
+#pragma unroll
+                for (int k = 0; k < NDT; ++k) {
+                    const double2 a = *reinterpret_cast<const double2 *>(pp + 5 * k * PCR_IMG_TILE);
+                    const double2 b = *reinterpret_cast<const double2 *>(pp + 5 * k * PCR_IMG_TILE + PCR_IMG_TILE / 2);
+                    rt[q][k] = mf_d4{a.x, a.y, b.x, b.y};
+                }
             } else if (tr) {
                 const double *pp = base + cc * BD + g;
 #pragma unroll
@@ -448,7 +494,13 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dt[k][q] = colD < BD ? dt[k][q] : colD == BD ? rv[k][q] : 0.0;
         }
-        if (HAS_D && MODE && o.nD && by == 0) {      // the assembled block (upper tiles) and right-hand side, for the next step
+        if (HAS_D && MODE == 2 && o.nD && by == 0) {     // the assembled [D | r] (upper tiles, as images) for the next step
+#pragma unroll
+            for (int k = 0; k < NDT; ++k)
+                if (k <= dj) img_store(o.nD, img_sym_tile(k, max(dj, k)), lane, dt[k]);
+            if (w == 0) img_store(o.nD, 0, lane, d00);
+        }
+        if (HAS_D && MODE == 1 && o.nD && by == 0) {     // a pinned block of a partitioned chain in its final form, row-major
 #pragma unroll
             for (int k = 0; k < NDT; ++k)
 #pragma unroll
@@ -486,6 +538,19 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
             }
             const int col = 16 * rcol[q] + j;
             const bool saver = MODE != 2 || by == 0;       // (the workgroups of a fused step all hold every tile)
+            if (MODE == 2) {        // kept couplings of a fused step: tile images, rows 72..79 zero
+                double *sv = (col >= BD ? o.saveU : o.saveL);
+                if (sv && rok[q] && rcol[q] < NRT && saver) {
+                    const int cc = col < BD ? col : col - BD;
+                    double *ps = sv + (cc >> 4) * PCR_IMG_TILE + 2 * (16 * g + (cc & 15));
+#pragma unroll
+                    for (int k = 0; k < NDT; ++k) {
+                        *reinterpret_cast<double2 *>(ps + 5 * k * PCR_IMG_TILE) = make_double2(rt[q][k][0], rt[q][k][1]);
+                        *reinterpret_cast<double2 *>(ps + 5 * k * PCR_IMG_TILE + PCR_IMG_TILE / 2) = k < 4 ? make_double2(rt[q][k][2], rt[q][k][3]) : make_double2(0.0, 0.0);
+                    }
+                }
+                continue;
+            }
             if (o.saveU && rok[q] && col >= BD && rcol[q] < NRT && saver) {
                 double *ps = o.saveU + g * BD + col - BD;
 #pragma unroll
@@ -1034,27 +1099,18 @@ static __device__ __forceinline__ void gram_tile(int u, int &kind, int &ti, int 
     }
 }
 static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], double *scr, int lane) {
+    // tile images (ssba_types.h): the whole accumulator leaves in two 16-byte stores per lane.  Rows 72..79 (registers 2, 3
+    // of tile row 4) would hold the products with the right-hand-side column: they are stored as zeros, which is what the
+    // loader's row predicates used to supply
     const int g = lane >> 4, j = lane & 15;
-    const int r0 = 16 * ti + g, c0 = 16 * tj + j;
+    const bool rows = ti < 4;
     if (kind < 2) {
-        double *dst = kind == 0 ? o.oGLL : o.oGUU, *gv = kind == 0 ? o.ogL : o.ogU;
-        if (c0 < BD) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (r0 + 4 * q < BD) dst[(r0 + 4 * q) * BD + c0] = v[q];
-        } else if (c0 == BD) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (r0 + 4 * q < BD) gv[r0 + 4 * q] = v[q];
-        }
+        img_store(kind == 0 ? o.oGLL : o.oGUU, img_sym_tile(ti, tj), lane, mf_d4{v[0], v[1], rows ? v[2] : 0.0, rows ? v[3] : 0.0});
         return;
     }
-    if (c0 < BD) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (r0 + 4 * q < BD) o.oGUL[(r0 + 4 * q) * BD + c0] = v[q];
-    }
-    // the transposed copy leaves through a per-wave LDS tile, as full row segments
+    const bool cols = tj < 4 || j < 8;          // columns 72..79 of a coupling are never read: zeros, to keep the image clean
+    img_store(o.oGUL, 5 * ti + tj, lane, mf_d4{cols ? v[0] : 0.0, cols ? v[1] : 0.0, (cols && rows) ? v[2] : 0.0, (cols && rows) ? v[3] : 0.0});
+    // the transposed copy goes through a per-wave LDS tile and leaves as the image of tile (tj, ti)
 #pragma unroll
     for (int q = 0; q < 4; ++q) scr[j * 17 + 4 * q + g] = v[q];
     MF_FENCE();
@@ -1062,12 +1118,8 @@ static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) r[q] = scr[(4 * q + g) * 17 + j];
     MF_FENCE();
-    const int r1 = 16 * tj + g, c1 = 16 * ti + j;
-    if (c1 < BD) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (r1 + 4 * q < BD) o.oGULT[(r1 + 4 * q) * BD + c1] = r[q];
-    }
+    const bool rowsT = tj < 4, colsT = ti < 4 || j < 8;
+    img_store(o.oGULT, 5 * tj + ti, lane, mf_d4{colsT ? r[0] : 0.0, colsT ? r[1] : 0.0, (colsT && rowsT) ? r[2] : 0.0, (colsT && rowsT) ? r[3] : 0.0});
 }
 
 // One block's reduction as a job of three staged operands -- A0 = YU(prev) | yr(prev), A1 = YL(next) | yr(next),

@@ -136,14 +136,24 @@ constexpr int PCR_MAX_BLOCKS = 128;
 // so the block that has just factored itself forms them from LDS (no reduce launch, no staging of three neighbours'
 // operands from HBM) and the NEXT step's load phase assembles  D(e) - GUU(e - s) - GLL(e + s)  on the way into the
 // registers.  Everything ping-pongs by step parity (a step reads what the previous one wrote).
+// These buffers are written and read by that kernel family only, so they are not row-major: a block is a sequence of TILE
+// IMAGES.  The image of a 16 x 16 tile of the block padded to 80 x 80 is what the accumulator of v_mfma_f64_16x16x4_f64
+// holds for it (lane l = 16 g + j, register q: row 4 q + g, column j), 2 KB in two halves of 1 KB: half h is the double2
+// {register 2 h, register 2 h + 1} of lane l at index l.  A wave reads or writes half a tile with ONE 16-byte access per
+// lane over one contiguous, 128-byte aligned KB.  Rows 72..79 of an image are zero.  Column 72 (tile column 4) of the
+// symmetric ones carries the right-hand side: r in Dpp, YL^T yr in GLL, YU^T yr in GUU, so  r - gU - gL  falls out of the
+// same three-source subtraction as D; columns 73..79 are zero.
+constexpr int PCR_IMG_TILE = 256;                   // doubles of a tile image
+constexpr int PCR_IMG_SYM = 15 * PCR_IMG_TILE;      // the 15 upper tiles (ti <= tj), tile rows starting at 0, 5, 9, 12, 14
+constexpr int PCR_IMG_FULL = 25 * PCR_IMG_TILE;     // all 25 tiles, tile (ti, tj) at 5 ti + tj
 struct PcrFused {
     int on;
-    double *Dpp[2], *rpp[2];                    // assembled D (upper tiles) and r of a step: n x BD x BD, n x BD
-    double *GLL[2], *GUU[2], *GUL[2], *GULT[2]; // n x BD x BD each (GLL / GUU: upper tiles)
-    double *gL[2], *gU[2];                      // YL^T yr, YU^T yr: n x BD
+    double *Dpp[2];                             // assembled [D | r] of a step: n x PCR_IMG_SYM
+    double *GLL[2], *GUU[2];                    // [YL | yr]^T [YL | yr], the same for YU: n x PCR_IMG_SYM each
+    double *GUL[2], *GULT[2];                   // YU^T YL and its transpose: n x PCR_IMG_FULL each (columns 72..79 are never read)
     // chains with pinned ends (partitioned solve): a coupling that points at a pinned block is never folded again; the
     // block that holds it saves it once (canonical orientation: rows of the block) and reads it back in every later step
-    double *Lkeep, *Ukeep;                      // n x BD x BD each, or null
+    double *Lkeep, *Ukeep;                      // n x PCR_IMG_FULL each, or null
 };
 
 // Long tracks on block-cyclic machinery (ssba_wide.hip): landmarks with 13 .. WSP observations (free poses within a span of

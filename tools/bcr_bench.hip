@@ -211,10 +211,9 @@ int main(int argc, char **argv) {
         std::vector<double> cL(n * blk);
         for (auto &v : cL) v = cpl * nd(rng);
         for (int q = 0; q < 2; ++q) {
-            d.pcrf.Dpp[q] = dalloc<double>(n * blk); d.pcrf.rpp[q] = dalloc<double>(n * BD);
-            d.pcrf.GLL[q] = dalloc<double>(n * blk); d.pcrf.GUU[q] = dalloc<double>(n * blk);
-            d.pcrf.GUL[q] = dalloc<double>(n * blk); d.pcrf.GULT[q] = dalloc<double>(n * blk);
-            d.pcrf.gL[q] = dalloc<double>(n * BD); d.pcrf.gU[q] = dalloc<double>(n * BD);
+            d.pcrf.Dpp[q] = dalloc<double>((size_t)n * PCR_IMG_SYM);
+            d.pcrf.GLL[q] = dalloc<double>((size_t)n * PCR_IMG_SYM); d.pcrf.GUU[q] = dalloc<double>((size_t)n * PCR_IMG_SYM);
+            d.pcrf.GUL[q] = dalloc<double>((size_t)n * PCR_IMG_FULL); d.pcrf.GULT[q] = dalloc<double>((size_t)n * PCR_IMG_FULL);
         }
         d.pcrf.on = 1;
         auto upload2 = [&] {
@@ -380,6 +379,43 @@ int main(int argc, char **argv) {
                     const int g = order[i].second;
                     printf("  wg %3d (id %% 8 = %d, XCC_ID %d):", g, g & 7, (int)(stp[4096 + 8 * g + 5] - 1000));
                     for (int k = 0; k < 5; ++k) printf(" %6.2f", (double)(long long)(stp[4096 + 8 * g + k] - lo) / 100.0);
+                    printf("\n");
+                }
+            }
+            {   // the same phases as intervals, averaged over the blocks with both couplings at stride 8 and over the end blocks
+                const int ny = n <= 85 ? 3 : 2, nwg = n * ny;
+                double sum[2][5] = {{0}};
+                int cnt[2] = {0, 0};
+                auto host_map2 = [&](int id, int &e, int &y) {
+                    const int N = n * ny, c = id & 7, q = (N + 7) >> 3, r = (N + 7) & 7;
+                    int idx = (id >> 3) + c * q - std::max(0, c - (r + 1));
+                    e = 0; y = 0;
+                    for (int k = 0; k < 8; ++k) {
+                        const int sk = ((n - k + 7) >> 3) * ny;
+                        if (idx < sk) { const int bq = idx / ny; y = idx - bq * ny; e = k + 8 * bq; return; }
+                        idx -= sk;
+                    }
+                };
+                printf("fused step 3, intervals in us: entry->prologue prologue->loaded loaded->factored factored->staged staged->done\n");
+                for (int g = 0; g < nwg && g < 500; ++g) {
+                    int e, y;
+                    host_map2(g, e, y);
+                    const bool hasL = e - 8 >= 0, hasU = e + 8 <= n - 1;
+                    const unsigned long long *s = &stp[4096 + 8 * g];
+                    const double iv[5] = {(double)(long long)(s[6] - s[0]) / 100.0, (double)(long long)(s[1] - s[6]) / 100.0, (double)(long long)(s[2] - s[1]) / 100.0,
+                                          (double)(long long)(s[3] - s[2]) / 100.0, (double)(long long)(s[4] - s[3]) / 100.0};
+                    if (hasL != hasU || (hasL && hasU)) {
+                        const int c = (hasL && hasU) ? 0 : 1;
+                        ++cnt[c];
+                        for (int k = 0; k < 5; ++k) sum[c][k] += iv[k];
+                    }
+#ifdef SSBA_STAMP_BX
+                    if (e == SSBA_STAMP_BX) printf("  block %d part %d (wg %d): %.2f %.2f %.2f %.2f %.2f\n", e, y, g, iv[0], iv[1], iv[2], iv[3], iv[4]);
+#endif
+                }
+                for (int c = 0; c < 2; ++c) {
+                    printf("  mean of %3d workgroups of %s:", cnt[c], c == 0 ? "middle blocks (both couplings)" : "end blocks (one coupling)   ");
+                    for (int k = 0; k < 5; ++k) printf(" %.2f", cnt[c] ? sum[c][k] / cnt[c] : 0.0);
                     printf("\n");
                 }
             }

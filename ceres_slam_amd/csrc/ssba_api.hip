@@ -124,6 +124,7 @@ struct ssba_problem {
     int eager_iters = 0;                      // iterations enqueued kernel by kernel since the last graph was dropped (enqueue_iteration)
     // solve bookkeeping
     bool began = false;
+    bool solved_once = false;                 // a solve has begun on this handle (a wide handle then serves covariance requests itself)
     ssba_options opt{};
     int ignore_convergence = 0;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -1636,7 +1637,9 @@ static int reset_solver(ssba_problem *p) {
 // The closure border (loop closures as a dense border of the block-tridiagonal system, LM only) does not cover everything
 // the general-structure path does.  A caller that asks for one of those things on a handle that was finalized with a
 // border gets the other layout: ssba_finalize runs again from the host-side problem graph the handle still holds.
-// The same hand-over for the 144-row super-blocks of long tracks (ssba_wide.hip: no covariance sweep): the blocked Cholesky has one.
+// The same hand-over for the 144-row super-blocks of long tracks, for a covariance request BEFORE the handle's first solve: the
+// blocked Cholesky serves it (and the solves that follow).  Once a solve has begun the handle stays on the wide layout and the
+// request runs on its own reduction (wide_cov_sweep below).
 static int refinalize_without_wide(ssba_problem *p, const char *what) {
     if (p->began) {
         set_error(std::string(what) + ": not available on this handle once a solve has begun (long tracks run on 144-row super-blocks; ask "
@@ -1744,6 +1747,7 @@ int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_converge
     if (rc) return rc;
     HIPCHECK(hipEventRecord(p->ev_begin, s));
     p->began = true;
+    p->solved_once = true;
     return SSBA_OK;
 }
 
@@ -2351,6 +2355,58 @@ int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, doub
     return SSBA_OK;
 }
 
+// device buffers of one covariance call, released on every return
+namespace {
+struct CallBuffers {
+    std::vector<void *> v;
+    ~CallBuffers() { for (void *q : v) (void)hipFree(q); }
+    hipError_t get(void **out, size_t bytes) {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) { v.push_back(q); *out = q; }
+        return e;
+    }
+};
+}  // namespace
+
+// Covariance on a wide handle whose first solve has begun (ssba_wide_covariance.hip).  The panel buffers of the reduction are
+// added by the first request (as d.Spb is on a windowed handle without a border).
+static int wide_panel_ready(ssba_problem *p) {
+    WideSys &w = p->launcher.wide;
+    if (w.Rp) return SSBA_OK;
+    drop_graph(p);
+    int rc;
+    double *Rp = nullptr, *Yp = nullptr;
+    if ((rc = dzero(p, &Rp, (size_t)w.n * WBD * WPC))) return rc;
+    if ((rc = dzero(p, &Yp, (size_t)w.n * WBD * WPC))) return rc;
+    if (configure_wide_panel()) { set_error("hipFuncSetAttribute(k_wdc_factor) failed"); return SSBA_ERR_HIP; }
+    HIPCHECK(hipStreamSynchronize(p->launcher.stream));
+    WideSys wn = w;
+    wn.Rp = Rp; wn.Yp = Yp;
+    HIPCHECK(hipMemcpy(const_cast<WideSys *>(p->d.wide), &wn, sizeof wn, hipMemcpyHostToDevice));
+    w = wn;
+    return SSBA_OK;
+}
+// One sweep: the undamped system assembled at the current parameters (radius -> infinity, as on the other layouts), then the unit
+// columns of nq free poses through the reduction into cols (launch_wide_solve_panel); nq = 0 only checks the system.
+static int wide_cov_sweep(ssba_problem *p, const int *free_pose, int nq, double *cols, long nrow, int col0) {
+    ssba_options o;
+    ssba_default_options(&o);
+    int rc = begin_hook(p, &o, 1e300);
+    if (rc) return rc;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    launch_linearize(L, d);
+    launch_dense_schur(L, d);
+    launch_finish_check(L, d);
+    launch_wide_solve_panel(L, d, free_pose, nq, cols, nrow, col0);
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    if ((rc = fetch_state(p))) return rc;
+    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    return SSBA_OK;
+}
+
 // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block (tests/dataset_vo_sun.cpp:159-183):
 // the pose's 6x6 block of (J^T J)^-1 in local coordinates = the same block of the inverse of the (undamped) reduced
 // camera system.  Six unit right-hand sides go through the block-cyclic-reduction factors of S.
@@ -2362,7 +2418,7 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
         int rc = refinalize_without_closure_border(p, "covariance");
         if (rc) return rc;
     }
-    if (p->d.wide) {
+    if (p->d.wide && !p->solved_once) {
         int rc = refinalize_without_wide(p, "covariance");
         if (rc) return rc;
     }
@@ -2376,6 +2432,21 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     if (f < 0) { set_error("covariance of a constant pose"); return SSBA_ERR_INVALID_ARGUMENT; }
     Dev &d = p->d;
     int rc;
+    if (d.wide) {       // a solved wide handle: one sweep of six unit columns through its own reduction
+        if (p->world_size > 1 || p->xfn) { set_error("covariance: not available on landmark-sharded problems"); return SSBA_ERR_UNSUPPORTED; }
+        if ((rc = wide_panel_ready(p))) return rc;
+        const long nrow = (long)p->launcher.wide.n * WBD;
+        CallBuffers B;
+        double *cols = nullptr;
+        HIPCHECK(B.get((void **)&cols, (size_t)6 * nrow * sizeof(double)));
+        if ((rc = wide_cov_sweep(p, &f, 1, cols, nrow, 0))) return rc;
+        for (int c = 0; c < 6; ++c) {
+            double col[6];
+            HIPCHECK(hipMemcpy(col, cols + (size_t)c * nrow + (size_t)f * 6, sizeof col, hipMemcpyDeviceToHost));
+            for (int r = 0; r < 6; ++r) cov[6 * r + c] = col[r];
+        }
+        return SSBA_OK;
+    }
     if (d.dense) {
         // general layout: the six unit vectors go into rows 0..5 of the right-hand-side block row, the blocked
         // Cholesky forward-solves them with the factorisation, then one back-substitution sweep per row
@@ -2440,24 +2511,11 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     return SSBA_OK;
 }
 
-// device buffers of one ssba_covariance_blocks call, released on every return
-namespace {
-struct CallBuffers {
-    std::vector<void *> v;
-    ~CallBuffers() { for (void *q : v) (void)hipFree(q); }
-    hipError_t get(void **out, size_t bytes) {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 8));
-        if (e == hipSuccess) { v.push_back(q); *out = q; }
-        return e;
-    }
-};
-}  // namespace
-
 // ceres::Covariance for any (pose | point, pose | point) pairs (include/ssba.h).  Windowed layout: the band of Sigma from one
 // selected inversion of the kept factors (ssba_covariance.hip), columns of Sigma from multi-right-hand-side sweeps for the
 // poses whose blocks lie outside it; general layout: columns of Sigma for every pose the request touches, DN_BS / 6 poses
-// per blocked Cholesky solve.  The landmark blocks follow from those in one launch.
+// per blocked Cholesky solve; a wide handle that has been solved: the same columns, 8 poses per sweep of its parallel cyclic
+// reduction (ssba_wide_covariance.hip).  The landmark blocks follow from those in one launch.
 int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
     ApiTimer api_timer("ssba_covariance_blocks");
     if (!p || (num && (!blocks || !out))) return SSBA_ERR_INVALID_ARGUMENT;
@@ -2496,7 +2554,7 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
     }
     int rc;
     if (p->d.cb && (rc = refinalize_without_closure_border(p, "covariance"))) return rc;
-    if (p->d.wide && (rc = refinalize_without_wide(p, "covariance"))) return rc;
+    if (p->d.wide && !p->solved_once && (rc = refinalize_without_wide(p, "covariance"))) return rc;
     Dev &d = p->d;
     Launcher &L = p->launcher;
     const bool dense = d.dense;
@@ -2624,6 +2682,16 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
         src.sc0 = si.sc;
         src.nrow = nrow;
         // the factors and the band must be complete before the buffers they came from are released (hipFree synchronises)
+    } else if (d.wide) {       // a solved wide handle: WPC / 6 = 8 poses per sweep of its own reduction
+        if ((rc = wide_panel_ready(p))) return rc;
+        const long nrow = (long)L.wide.n * WBD;
+        HIPCHECK(B.get((void **)&cols, ((size_t)std::max(nslots, 1) * 6 * nrow) * sizeof(double)));
+        constexpr int PER = WPC / 6;
+        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {     // (no column needed: one sweep still checks the system)
+            const int nq = std::max(0, std::min(PER, nslots - s0));
+            if ((rc = wide_cov_sweep(p, slot_pose.data() + s0, nq, cols, nrow, 6 * s0))) return rc;
+        }
+        src.nrow = nrow;
     } else {
         const size_t lda = (size_t)d.dn_pad;
         HIPCHECK(B.get((void **)&cols, ((size_t)std::max(nslots, 1) * 6 * lda) * sizeof(double)));

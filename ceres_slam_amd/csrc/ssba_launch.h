@@ -161,6 +161,10 @@ void launch_wide_schur(Launcher &L, const Dev &d, bool fuse_finish);
 void launch_wide_finish(Launcher &L, const Dev &d, bool fused);
 bool launch_ctrl_fusable(const Dev &d);       // ssba_kernels.hip: k_check forms the linearisation sums itself on this layout
 void launch_wide_solve(Launcher &L, const Dev &d);
+// covariance on a solved wide handle (ssba_wide_covariance.hip): the unit columns of nq <= WPC / 6 free poses through the reduction
+// of the assembled system (WideSys::Rp, Yp allocated); column 6 q + c goes to cols + (col0 + 6 q + c) * nrow
+int configure_wide_panel();
+void launch_wide_solve_panel(Launcher &L, const Dev &d, const int *free_pose, int nq, double *cols, long nrow, int col0);
 
 // covariance blocks (ssba_covariance.hip, ssba_covariance_blocks)
 struct SelInv {                  // selected inversion of the block-tridiagonal S on its pattern

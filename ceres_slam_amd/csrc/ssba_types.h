@@ -167,6 +167,8 @@ constexpr int WBD = 6 * WSP;            // 144 = 9 tiles of 16
 constexpr int WNT = WBD / 16;           // 9
 constexpr int WSLAB_TILES = WNT * (WNT + 1) / 2 + WNT;      // 45 upper tiles + 9 tiles of the gradient column
 constexpr int WSLAB_DOUBLES = WSLAB_TILES * 256;
+constexpr int WPT = 3;                  // column tiles of a right-hand-side panel: the slots the tile deal of k_wd_factor leaves (21 for 19)
+constexpr int WPC = 16 * WPT;           // 48 columns = the unit columns of 8 poses per sweep
 struct WideSys {
     int n, steps, n_items, n_blk;       // super-blocks, PCR steps = ceil(log2 n), Schur items, non-zero 6x6 blocks (a <= b)
     // exchange vector of the wide system: [D (n x WBD x WBD, row-major) | L (n: L[I] = S[I, I-1]) | rhs (n x WBD)]
@@ -182,6 +184,9 @@ struct WideSys {
     // parallel cyclic reduction
     double *U;                          // n blocks: U[e] = S[e, e + stride] from the second step on
     double *YL, *YU, *yr;               // G^-1 [L | U | r] of the current step
+    // covariance after a solve (ssba_wide_covariance.hip): a panel of WPC right-hand-side columns through the same reduction,
+    // allocated by the first call that needs it (null until then)
+    double *Rp, *Yp;                    // n x WBD x WPC row-major: the panel R of the current step, Yr = G^-1 R
 };
 
 struct Dev {

@@ -2,7 +2,9 @@
 // include/ceres_slam_amd/ceres_shim.hpp: a synthetic stereo window (cameras along a line, the first one held constant)
 // is solved, then one Covariance::Compute asks for every pose marginal, one landmark marginal and one pose-landmark block.
 //
-// usage: covariance_blocks_gpu [num_poses [num_points]]
+// usage: covariance_blocks_gpu [num_poses [num_points [reach]]]
+//   reach (2.5): a camera sees the points within `reach` of it along the line; cameras are 0.5 apart, so 2.5 gives tracks of
+//   up to 11 observations (windowed layout) and 4.0 tracks of 16 (the 144-row super-blocks of long tracks)
 // Output (17 significant digits), so that a test can rebuild the problem at the solution and check the blocks:
 //   "problem P L N", "pose k <12>" and "point j <3>" (the solution), "obs k j u v d" (the observations),
 //   "cov_pose k <36>", "cov_point j <9>", "cov_pose_point k j <18>" (row-major blocks in the tangent space).
@@ -17,9 +19,9 @@
 int main(int argc, char **argv) {
     const int P = argc > 1 ? std::atoi(argv[1]) : 16;
     const int L = argc > 2 ? std::atoi(argv[2]) : 200;
-    if (P < 2 || L < 1) { std::cerr << "usage: covariance_blocks_gpu [num_poses >= 2 [num_points >= 1]]" << std::endl; return EXIT_FAILURE; }
+    if (P < 2 || L < 1) { std::cerr << "usage: covariance_blocks_gpu [num_poses >= 2 [num_points >= 1 [reach]]]" << std::endl; return EXIT_FAILURE; }
     std::shared_ptr<const ceres_slam::StereoCamera> camera = std::make_shared<ceres_slam::StereoCamera>(400.0, 400.0, 320.0, 240.0, 0.24);
-    const double spacing = 0.5, reach = 2.5;          // camera k sits at x = k spacing and sees the points within `reach` of it
+    const double spacing = 0.5, reach = argc > 3 ? std::atof(argv[3]) : 2.5;          // camera k sits at x = k spacing and sees the points within `reach` of it
     std::vector<double> poses(12 * (size_t)P, 0.0), points(3 * (size_t)L), truth(3 * (size_t)L);
     for (int k = 0; k < P; ++k) {
         double *T = &poses[12 * (size_t)k];        // [t | R row-major]: q = R p + t

@@ -25,6 +25,7 @@
 #include "ceres_slam_amd/dataset_problem_sun.hpp"
 
 // SSBA_DRIVER_TIMING=1: wall time spent in the three stages of a window, printed at exit
+// SSBA_DRIVER_COVARS=1: the covariance block of state k1+1 that every window hands to the next one's prior, one line each on stderr
 static double g_time[3] = {0, 0, 0};
 struct StageTimer {
     int stage;
@@ -90,6 +91,12 @@ static void solveWindow(ceres_slam::DatasetProblemSun &dataset, ceres_slam::uint
         dataset.pose_covars[k1 + 1] = dataset.pose_covars[k1];
     } else {
         covariance.GetCovarianceBlockInTangentSpace(dataset.poses[k1 + 1].data(), dataset.poses[k1 + 1].data(), dataset.pose_covars[k1 + 1].data());
+        if (std::getenv("SSBA_DRIVER_COVARS")) {      // the block the next window's prior is built from, on a line of its own
+            std::cerr.precision(17);
+            std::cerr << "\npose covariance " << k1 + 1 << ":";
+            for (double v : dataset.pose_covars[k1 + 1]) std::cerr << " " << v;
+            std::cerr << std::endl;
+        }
     }
 }
 

@@ -427,7 +427,14 @@ SSBA_API int ssba_add_sun_observation(ssba_problem *p, uint32_t pose, const doub
 /* ssba_pose_covariance replaces ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block
  * (tests/dataset_vo_sun.cpp:159-183): cov (6x6 row-major) = that pose's block of (J^T J)^-1 in local (tangent)
  * coordinates at the caller's current parameters, i.e. of the inverse of the undamped reduced camera system.
- * SSBA_ERR_NUMERICAL_FAILURE when the system is rank deficient (Ceres: "Covariance computation failed"). */
+ * SSBA_ERR_NUMERICAL_FAILURE when the system is rank deficient (Ceres: "Covariance computation failed").
+ * Long tracks (a wide handle, ssba_stats.wide_superblocks > 0): once a solve has begun on the handle, the call runs on the
+ * handle's own 144-row reduction, between solves or after ssba_solve_end as on a windowed handle; the handle stays on the
+ * wide layout and a later ssba_solve runs exactly as if the call had not been made.  BEFORE the handle's first solve the call
+ * still finalizes it again onto the general layout (blocked Cholesky), where the solves that follow then run.  A closure-border
+ * handle is finalized again the same way, which is only possible before its first solve begins (afterwards SSBA_ERR_STATE; ask
+ * before solving, or set SSBA_NO_CLOSURE_BORDER=1).  Landmark-sharded or partitioned handles and lighting terms:
+ * SSBA_ERR_UNSUPPORTED. */
 SSBA_API int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]);
 
 /* ssba_covariance_blocks replaces ceres::Covariance::Compute + GetCovarianceBlock(InTangentSpace) for any list of
@@ -443,10 +450,12 @@ SSBA_API int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]
  * Windowed layout: one selected inversion of the block-tridiagonal reduced system (its diagonal and sub-diagonal super-blocks)
  * plus one multi-right-hand-side sweep per 5 poses whose blocks lie outside that band.  General layout: one blocked
  * Cholesky solve per 10 poses the request touches (requested poses and the observing poses of requested points).
- * State rules, closure border and long tracks as ssba_pose_covariance: a closure-border or a wide (13..24 observation) handle
- * is finalized again onto the general layout the first time, which is only possible before its first solve begins
- * (afterwards SSBA_ERR_STATE; ask before solving, or set SSBA_NO_CLOSURE_BORDER=1 / SSBA_NO_WIDE=1).  A later ssba_solve
- * runs exactly as if the call had not been made. */
+ * State rules, closure border and long tracks as ssba_pose_covariance.  A wide (13..24 observation) handle on which a solve
+ * has begun serves the request itself: the columns of Sigma for every pose the request touches (the general layout's rule),
+ * 8 poses per sweep of its parallel cyclic reduction; it stays on the wide layout.  Before its first solve it is finalized
+ * again onto the general layout, as a closure-border handle is -- for the closure border only possible before its first solve
+ * begins (afterwards SSBA_ERR_STATE; ask before solving, or set SSBA_NO_CLOSURE_BORDER=1).  A later ssba_solve runs exactly
+ * as if the call had not been made. */
 #define SSBA_COV_POSE 0
 #define SSBA_COV_POINT 1
 typedef struct { uint32_t kind_a, index_a, kind_b, index_b; } ssba_cov_block;

@@ -39,15 +39,10 @@ def landmark_ranges(obs_point: np.ndarray, num_points: int, world: int):
     return [(int(cuts[r]), int(cuts[r + 1])) for r in range(world)]
 
 
-def aligned_partition(obs_pose: np.ndarray, obs_point: np.ndarray, num_poses: int, num_points: int, world: int, pose_const=None,
-                      sbp: int = 12):
-    """Landmark ranges cut where the co-visibility band crosses a super-block boundary, for the partitioned
-    reduced solve (ssba_set_partition).  Landmarks must be ordered along the trajectory (as the reference's
-    datasets and synth.py are: by first observing state).  Returns (ranges, separator_superblocks) or None if no
-    such cut exists near the balanced one (the caller then uses the plain all-reduce path).
-
-    Free-pose index f = rank of the pose among the non-constant poses; super-block = f // sbp.  Rank r may only
-    touch super-blocks [sep[r], sep[r+1]] and neighbours share exactly the super-block sep[r+1]."""
+def _superblock_envelopes(obs_pose, obs_point, num_poses, num_points, pose_const=None, sbp: int = 12):
+    """(number of super-blocks, hi_prefix, lo_suffix): the highest super-block touched by the landmarks up to c, and the
+    lowest touched by the landmarks from c on.  Free-pose index f = rank of the pose among the non-constant poses;
+    super-block = f // sbp."""
     if pose_const is None:
         pose_const = np.zeros(num_poses, dtype=bool)
         pose_const[0] = True
@@ -65,6 +60,19 @@ def aligned_partition(obs_pose: np.ndarray, obs_point: np.ndarray, num_poses: in
     # super-blocks <= s and every landmark >= c stays in super-blocks >= s
     hi_prefix = np.maximum.accumulate(np.where(seen, hi, -1))
     lo_suffix = np.minimum.accumulate(np.where(seen, lo, np.iinfo(np.int64).max)[::-1])[::-1]
+    return nsb, hi_prefix, lo_suffix
+
+
+def aligned_partition(obs_pose: np.ndarray, obs_point: np.ndarray, num_poses: int, num_points: int, world: int, pose_const=None,
+                      sbp: int = 12):
+    """Landmark ranges cut where the co-visibility band crosses a super-block boundary, for the partitioned
+    reduced solve (ssba_set_partition).  Landmarks must be ordered along the trajectory (as the reference's
+    datasets and synth.py are: by first observing state).  Returns (ranges, separator_superblocks) or None if no
+    such cut exists near the balanced one (the caller then uses the plain all-reduce path).
+
+    Free-pose index f = rank of the pose among the non-constant poses; super-block = f // sbp.  Rank r may only
+    touch super-blocks [sep[r], sep[r+1]] and neighbours share exactly the super-block sep[r+1]."""
+    nsb, hi_prefix, lo_suffix = _superblock_envelopes(obs_pose, obs_point, num_poses, num_points, pose_const, sbp)
     balanced = landmark_ranges(obs_point, num_points, world)
     cuts, seps = [0], [0]
     for r in range(1, world):
@@ -84,6 +92,25 @@ def aligned_partition(obs_pose: np.ndarray, obs_point: np.ndarray, num_poses: in
     if seps[-1] <= seps[-2]:
         return None
     return [(cuts[r], cuts[r + 1]) for r in range(world)], np.asarray(seps, dtype=np.uint32)
+
+
+def ranges_for_separators(obs_pose, obs_point, num_poses, num_points, seps, pose_const=None, sbp: int = 12):
+    """Landmark ranges for an explicit list of separator super-blocks (seps[0] = 0, ..., seps[-1] = the last super-block):
+    the cut for an interior separator s is the first landmark from which on every landmark stays in super-blocks >= s, and
+    it must leave every landmark before it in super-blocks <= s -- the envelopes of aligned_partition.  Raises ValueError
+    where the co-visibility band admits no such cut."""
+    nsb, hi_prefix, lo_suffix = _superblock_envelopes(obs_pose, obs_point, num_poses, num_points, pose_const, sbp)
+    seps = [int(s) for s in seps]
+    if len(seps) < 2 or seps[0] != 0 or seps[-1] != nsb - 1 or any(b <= a for a, b in zip(seps, seps[1:])):
+        raise ValueError(f"separators {seps} must rise from 0 to the last super-block {nsb - 1}")
+    cuts = [0]
+    for s in seps[1:-1]:
+        c = int(np.argmax(lo_suffix >= s))
+        if not (lo_suffix[c] >= s and c > cuts[-1] and hi_prefix[c - 1] <= s):
+            raise ValueError(f"no landmark cut at separator super-block {s}")
+        cuts.append(c)
+    cuts.append(num_points)
+    return [(cuts[r], cuts[r + 1]) for r in range(len(seps) - 1)]
 
 
 def whole(prob) -> Shard:

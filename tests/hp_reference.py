@@ -1467,6 +1467,38 @@ def se3_plus(T, eps, dtype=LD):
     return out, bar
 
 
+def se3_minus(T_new, T, dtype=LD):
+    """The inverse of se3_plus: eps with Plus(T, eps) = T_new.  E = R_new R^T, eps_r = so3 log(E) = a v / |v| with
+    v = vee(E - E^T) / 2 = sin(a) n and a = atan2(|v|, (tr E - 1) / 2) (accurate for small angles, where acos(cos a) loses half
+    the digits, and up to pi; for a <= DBL_EPSILON it returns v, the first-order branch of se3_plus, to 1e-32 relative),
+    eps_t = t_new - E t.  T_new, T (..., 12) = [t | R row-major].  Returns (eps (N, 6) = [translation | rotation], bar (N, 6)).
+
+    The bar is for T_new an fp64 evaluation of Plus(T, eps): its entrywise se3_plus bar b = (b_t, b_R) carried through the log
+    to first order.  dE = dR_new R^T, so |dE| <= b_R |R|^T entrywise, plus |E| |R R^T - I|: an fp64 R is orthonormal only to
+    rounding and E inherits the defect.  d eps_r = J_l^-1(eps_r) vee(skew(dE E^T)): |vee(skew M)|_2 <= |M|_F / sqrt 2, and the
+    largest singular value of J_l^-1 is (a / 2) / sin(a / 2) (1 at a = 0, 1.043 at a = 1, pi / 2 at pi), so every entry of eps_r
+    is within (a / 2) / sin(a / 2) |dE|_F / sqrt 2.  d eps_t = d t_new - dE t: b_t + |dE| |t|."""
+    T_new = np.asarray(T_new, dtype).reshape(-1, 12)
+    T = np.asarray(T, dtype).reshape(-1, 12)
+    n = T.shape[0]
+    t, R = T[:, :3], T[:, 3:].reshape(n, 3, 3)
+    E = np.einsum("nij,nkj->nik", T_new[:, 3:].reshape(n, 3, 3), R)
+    v = np.stack([E[:, 2, 1] - E[:, 1, 2], E[:, 0, 2] - E[:, 2, 0], E[:, 1, 0] - E[:, 0, 1]], 1) / 2
+    vn = np.sqrt((v * v).sum(1))
+    ang = np.arctan2(vn, (E[:, 0, 0] + E[:, 1, 1] + E[:, 2, 2] - 1) / 2)
+    eps_r = v * np.where(vn > 0, ang / np.where(vn > 0, vn, dtype(1)), dtype(1))[:, None]
+    eps = np.concatenate([T_new[:, :3] - np.einsum("nij,nj->ni", E, t), eps_r], 1)
+    f = lambda x: np.abs(np.asarray(x, np.float64))
+    b = se3_plus(T, eps, dtype)[1]
+    defect = f(np.einsum("nij,nkj->nik", R, R) - np.eye(3, dtype=dtype))
+    dE = np.einsum("nij,nkj->nik", b[:, 3:].reshape(n, 3, 3), f(R)) + np.einsum("nij,njk->nik", f(E), defect)
+    a64 = np.asarray(ang, np.float64)
+    k = np.where(a64 > 1e-8, 0.5 * a64 / np.sin(0.5 * np.maximum(a64, 1e-8)), 1.0)
+    bar_r = k * np.sqrt((dE * dE).sum((1, 2)) / 2)
+    bar = np.concatenate([b[:, :3] + np.einsum("nij,nj->ni", dE, f(t)), np.repeat(bar_r[:, None], 3, 1)], 1)
+    return eps, bar
+
+
 def unit_plus(x, d, dtype=LD):
     """UnitVectorPerturbation: Plus(x, d) = y / |y|, y = x + d - (d.x / x.x) x.  x, d (..., 3).  Returns (Plus, bar), (N, 3).
 

@@ -228,13 +228,8 @@ def _check_against_truth(tag, sy, S, rhs, dp, dl, mcc, fidx, prob_points):
     _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points)
 
 
-def _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points, db=None):
-    x = dp[fidx >= 0].ravel()
-    # delta_l from the device's own delta_p, per landmark within (t_j + c) u kappa(V_j) |V^-1| (|J_l|^T |r| + |J_l|^T |J_p| |delta_p|)
-    # -- the device forms W^T delta_p as J_l^T (J_p delta_p) from re-linearised rows (k_backsub_eval), so the magnitudes are those
-    # of the rows (Jla, Jpa, rabs: hp_reference.stereo_rows), not of |W| -- plus 2 u (|p_j| + |delta_l,j|): the hook reports
-    # delta_l as fl(p + delta_l) - p (candidate minus current point)
-    dl_ref = sy.back_substitute(x, db)
+def _back_substitution_bound(sy, x, dl_ref, prob_points, db=None):
+    """Per landmark present: (t_j + c) u kappa(V_j) |V^-1| (|J_l|^T |r| + |J_l|^T |J_p| |delta_p|) + 2 u (|p_j| + |delta_l,j|)."""
     rows, fr, so = sy.rows, sy._f >= 0, sy.slot_of_obs
     gla = np.zeros((sy.lm.shape[0], sy.d))
     np.add.at(gla, so, np.einsum("nai,na->ni", rows["Jla"], rows["rabs"]))
@@ -245,7 +240,17 @@ def _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points, db=None):
     mag = np.einsum("nij,nj->ni", np.abs(np.asarray(sy.Vinv, np.float64)), gla).max(1)
     t = np.bincount(sy.slot_of_obs, minlength=sy.lm.shape[0])
     pts = np.abs(prob_points[sy.lm]).max(1)
-    bound = (t + hp.C_TERMS) * hp.U * sy.kappa_V * mag + 2 * hp.U * (pts + np.abs(np.asarray(dl_ref, np.float64)).max(1))
+    return (t + hp.C_TERMS) * hp.U * sy.kappa_V * mag + 2 * hp.U * (pts + np.abs(np.asarray(dl_ref, np.float64)).max(1))
+
+
+def _check_back_substitution(tag, sy, dp, dl, mcc, fidx, prob_points, db=None):
+    x = dp[fidx >= 0].ravel()
+    # delta_l from the device's own delta_p, per landmark within (t_j + c) u kappa(V_j) |V^-1| (|J_l|^T |r| + |J_l|^T |J_p| |delta_p|)
+    # -- the device forms W^T delta_p as J_l^T (J_p delta_p) from re-linearised rows (k_backsub_eval), so the magnitudes are those
+    # of the rows (Jla, Jpa, rabs: hp_reference.stereo_rows), not of |W| -- plus 2 u (|p_j| + |delta_l,j|): the hook reports
+    # delta_l as fl(p + delta_l) - p (candidate minus current point)
+    dl_ref = sy.back_substitute(x, db)
+    bound = _back_substitution_bound(sy, x, dl_ref, prob_points, db)
     err = np.abs(np.asarray(np.asarray(dl[sy.lm], hp.LD) - dl_ref, np.float64)).max(1)
     _report(tag + " back-substitution", worst_over_bound=float((err / bound).max()))
     assert np.all(err <= bound), (tag, float((err / bound).max()))

@@ -1377,3 +1377,38 @@ def test_oracle_system_with_odometry_blocks_is_within_the_assembly_bound_and_pla
         bad = S.copy()
         bad[blk(k1, k2)] += np.asarray(J1.T @ J2, np.float64) * (1 / w - 1)
         assert sy.assembly_excess(bad, rhs)[0] > 1e3
+
+
+# ------------------------------------------------------------------------------------------------- se3_minus and the recovered step
+def test_se3_minus_inverts_se3_plus_within_its_bar():
+    """se3_minus(se3_plus(T, eps), T) == eps for steps from 1e-9 to 1 and on the first-order branch of se3_plus (|eps_r| <=
+    DBL_EPSILON, zero included) -- with the candidate kept in long double, and rounded to fp64 as a device writes it back, which
+    is the error the bar is made for: an fp64 entry of Plus is within its se3_plus bar of the truth."""
+    rng = np.random.default_rng(11)
+    scales = [1e-9, 1e-7, 1e-5, 1e-3, 1e-2, 0.1, 0.5, 1.0, 1e-17, 0.0]
+    T = np.stack([_rand_pose(rng) for _ in range(8 * len(scales))])
+    eps = rng.standard_normal((T.shape[0], 6)) * np.repeat(scales, 8)[:, None]
+    eps[-16:, :3] = rng.standard_normal((16, 3)) * 1e-3                    # first-order rotations with an ordinary translation
+    ang = np.sqrt((eps[:, 3:] ** 2).sum(1))
+    assert (ang <= hp.DBL_EPSILON).sum() == 16 and ang.max() > 0.5
+    Tn, pb = hp.se3_plus(T, eps)
+    for cand in (Tn, np.asarray(Tn, np.float64)):
+        back, bar = hp.se3_minus(cand, T)
+        err = np.abs(np.asarray(back - np.asarray(eps, hp.LD), np.float64))
+        assert np.all(err <= bar), float((err / bar).max())
+    # the rounded candidate does use the bar (the check is not vacuous), and a rotation entry off by 1e-10 leaves it
+    assert (err / bar).max() > 1e-3
+    bad = np.asarray(Tn, np.float64)
+    bad[:, 4] += 1e-10
+    back, bar = hp.se3_minus(bad, T)
+    assert np.all((np.abs(np.asarray(back - np.asarray(eps, hp.LD), np.float64)) / bar).max(1) > 1)
+
+
+@pytest.mark.parametrize("huber,strategy,dogleg_type,radius", [(0.0, 0, 0, 1e4), (1.345, 0, 0, 30.0), (0.0, 1, 0, 3.0)])
+def test_recovered_step_comparison_holds_with_the_oracle_as_the_ranks(huber, strategy, dogleg_type, radius):
+    """The whole comparison of tests/test_gpu_hp_sharded.py with one iteration of the CPU oracle in place of the ranks: the
+    precondition, the recovery of the step from the written-back point, every bar."""
+    import test_gpu_hp_sharded as sh
+    T = sh.truth((61, 2400, 8), huber, strategy, dogleg_type, radius)
+    out = sh.compare(f"oracle {T['tag']}", T, [sh.oracle_as_rank(T)])
+    assert out["fe"] < 1e-11 and out["r_fe"] < 1e-2                       # the recovery costs nothing against the bar

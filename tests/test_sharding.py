@@ -192,6 +192,24 @@ def test_aligned_partition_cuts_at_superblock_boundaries():
     assert sharding.aligned_partition(op, ol, 60, 200, 2) is None
 
 
+def test_ranges_for_separators_keep_every_rank_inside_its_chain():
+    """Explicit separator lists (tests/test_gpu_hp_sharded.py): with tracks of 8 every interior super-block has a landmark cut."""
+    for size, seps in (((61, 2400, 8), [0, 2, 4]), ((61, 2400, 8), [0, 1, 2, 4]), ((58, 2300, 8), [0, 1, 2, 3, 4]),
+                       ((85, 3400, 8), [0, 2, 3, 4, 5, 6]), ((133, 5300, 8), [0, 6, 10])):
+        prob = synth.make_problem(size[0], size[1], track_len=size[2], seed=21)
+        ranges = sharding.ranges_for_separators(prob.obs_pose, prob.obs_point, prob.num_poses, prob.num_points, seps)
+        assert ranges[0][0] == 0 and ranges[-1][1] == size[1] and all(ranges[r][1] == ranges[r + 1][0] for r in range(len(seps) - 2))
+        f = prob.obs_pose.astype(int) - 1          # pose 0 is constant
+        for r, (b, e) in enumerate(ranges):
+            sb = f[(prob.obs_point >= b) & (prob.obs_point < e) & (f >= 0)] // 12
+            assert sb.min() >= seps[r] and sb.max() <= seps[r + 1]
+    with pytest.raises(ValueError):               # the list must end at the last super-block
+        sharding.ranges_for_separators(prob.obs_pose, prob.obs_point, prob.num_poses, prob.num_points, [0, 6, 9])
+    prob = synth.make_problem(60, 2400, track_len=20, seed=21)      # tracks of 20 span three super-blocks: no cut at 2
+    with pytest.raises(ValueError):
+        sharding.ranges_for_separators(prob.obs_pose, prob.obs_point, prob.num_poses, prob.num_points, [0, 2, 4])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,size,pcr_max,maxit", [(2, (40, 1600, 12), None, 0), (3, (100, 4000, 12), None, 30), (2, (300, 9000, 12), None, 30),
                                                       (4, (300, 9000, 12), None, 0), (2, (300, 9000, 12), 4, 30), (4, (300, 9000, 12), 3, 30),

@@ -32,7 +32,7 @@ SYMBOLS = [
     "ssba_default_options", "ssba_solve", "ssba_brief_report", "ssba_solve_begin", "ssba_solve_step",
     "ssba_solve_end", "ssba_solve_restart", "ssba_synchronize", "ssba_iteration_log", "ssba_set_stream",
     "ssba_set_exchange", "ssba_set_distributed", "ssba_exchange_size", "ssba_set_kernel_timing", "ssba_kernel_times",
-    "ssba_get_stats", "ssba_evaluate", "ssba_lm_step", "ssba_dogleg_step", "ssba_phong_evaluate", "ssba_status_string", "ssba_last_error",
+    "ssba_get_stats", "ssba_evaluate", "ssba_lm_step", "ssba_dogleg_step", "ssba_line_search_probe", "ssba_phong_evaluate", "ssba_status_string", "ssba_last_error",
     "ssba_add_normal_blocks", "ssba_add_material_blocks", "ssba_add_light_block", "ssba_set_shared_block_constant",
     "ssba_add_lighting_observations", "ssba_border_system", "ssba_set_shared_block_bounds", "ssba_set_point_blocks_constant", "ssba_release_cached_memory",
     "ssba_set_partition", "ssba_ransac_samples", "ssba_frontend_ransac", "ssba_add_pose_prior", "ssba_add_sun_observation", "ssba_add_relative_pose",
@@ -147,7 +147,8 @@ def load():
     L.ssba_evaluate.argtypes = [H, _dp, _dp, _dp, _dp, _dp]
     L.ssba_lm_step.argtypes = [H, C.POINTER(Options), C.c_double, _dp, _dp, _dp, _dp, _dp]
     L.ssba_dogleg_step.argtypes = [H, C.POINTER(Options), C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
-    L.ssba_armijo_trace.argtypes = [_dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, _dp, C.c_int32, C.c_int32]
+    L.ssba_line_search_probe.argtypes = [H, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.ssba_armijo_trace.argtypes =[_dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, _dp, C.c_int32, C.c_int32]
     L.ssba_phong_evaluate.argtypes = [C.c_int, C.c_int, C.c_uint64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp,
                                       _dp, _dp, _dp, _dp, _dp]
     L.ssba_add_normal_blocks.argtypes = [H, _dp, C.c_uint32]

@@ -124,6 +124,7 @@ struct ssba_problem {
     int eager_iters = 0;                      // iterations enqueued kernel by kernel since the last graph was dropped (enqueue_iteration)
     // solve bookkeeping
     bool began = false;
+    bool step_hook_done = false;              // the device holds the step of ssba_lm_step / ssba_dogleg_step (ssba_line_search_probe)
     bool solved_once = false;                 // a solve has begun on this handle (a wide handle then serves covariance requests itself)
     ssba_options opt{};
     int ignore_convergence = 0;
@@ -1701,6 +1702,7 @@ int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_converge
         return SSBA_ERR_UNSUPPORTED;
     }
     if (o->dogleg_type != 0 && o->dogleg_type != 1) return SSBA_ERR_INVALID_ARGUMENT;
+    p->step_hook_done = false;
     if (o->trust_region_strategy_type == 1 && p->d.cb) {
         // DOGLEG is not implemented on the closure border: the symbolic phase runs again and puts the problem on the
         // general-structure path, which has it (once per handle; the caller's blocks and pointers are unchanged)
@@ -2040,6 +2042,7 @@ static int begin_hook(ssba_problem *p, const ssba_options *o, double radius) {
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
     if (p->d.part) { set_error("test hooks are not available on a partitioned problem"); return SSBA_ERR_UNSUPPORTED; }
     if (p->began) return SSBA_ERR_STATE;
+    p->step_hook_done = false;
     HIPCHECK(hipSetDevice(p->device));
     ssba_options opt;
     if (o) opt = *o; else ssba_default_options(&opt);
@@ -2280,6 +2283,7 @@ int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius, double *
             for (int c = 0; c < 3; ++c) delta_l[3 * (size_t)j + c] = a[c * Lp + l] - b[c * Lp + l];
         }
     }
+    p->step_hook_done = true;
     return SSBA_OK;
 }
 
@@ -2351,6 +2355,55 @@ int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, doub
             st.sub_e[0][0], st.sub_e[0][1], st.sub_e[1][0], st.sub_e[1][1], st.sub_g[0], st.sub_g[1],
             st.sub_B[0], st.sub_B[1], st.sub_B[2]};
         memcpy(scalars, s, sizeof s);
+    }
+    p->step_hook_done = true;
+    return SSBA_OK;
+}
+
+// One evaluation of the line-search function at step `alpha` along the step the last ssba_lm_step / ssba_dogleg_step left on the
+// device: what finish_pending_search enqueues per evaluation, then the sums and the trial point copied out.
+int ssba_line_search_probe(ssba_problem *p, double alpha, double *ls_out, double *cand_poses, double *cand_points, double *cand_normals,
+                           double *cand_light, double *cand_phong, double *cand_texture) {
+    if (!p || !(alpha >= 0.0) || !ls_finite(alpha)) return SSBA_ERR_INVALID_ARGUMENT;
+    if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    if (!p->d.phong || !p->step_hook_done || p->began) {
+        set_error("ssba_line_search_probe: lighting terms and a step from ssba_lm_step / ssba_dogleg_step on this handle are needed");
+        return SSBA_ERR_STATE;
+    }
+    if (p->xfn) { set_error("ssba_line_search_probe is not available with landmark sharding"); return SSBA_ERR_UNSUPPORTED; }
+    HIPCHECK(hipSetDevice(p->device));
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    launch_ph_ls_probe(L, d, alpha, 1);
+    HIPCHECK(hipMemcpyAsync(p->h_ls, d.ls_out, NLS_OUT * sizeof(double), hipMemcpyDeviceToHost, L.stream));
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    int rc = fetch_state(p);
+    if (rc) return rc;
+    if (p->h_state->terminated) { p->step_hook_done = false; set_error("ssba_line_search_probe: the solver state is terminated"); return SSBA_ERR_STATE; }
+    if (ls_out) memcpy(ls_out, p->h_ls, NLS_OUT * sizeof(double));
+    if (cand_poses && p->P) HIPCHECK(hipMemcpy(cand_poses, d.cand_poses, (size_t)p->P * 12 * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t Lp = (size_t)d.Lpad;
+    for (int which = 0; which < 2; ++which) {
+        double *out = which ? cand_normals : cand_points;
+        if (!out) continue;
+        const double *user = which ? p->user_normals : p->user_points;
+        std::vector<double> a(Lp * 3);
+        HIPCHECK(hipMemcpy(a.data(), which ? d.cand_nrm : d.cand_pts, a.size() * sizeof(double), hipMemcpyDeviceToHost));
+        memcpy(out, user, (size_t)p->L * 3 * sizeof(double));        // landmarks the device does not hold stay where they are
+        for (size_t l = 0; l < Lp; ++l) {
+            const uint32_t j = p->user_of_dev[l];
+            if (j == 0xFFFFFFFFu) continue;
+            for (int c = 0; c < 3; ++c) out[3 * (size_t)j + c] = a[c * Lp + l];
+        }
+    }
+    if (cand_light || cand_phong || cand_texture) {
+        const size_t M = p->M;
+        std::vector<double> sh((size_t)d.nsh);
+        HIPCHECK(hipMemcpy(sh.data(), d.cand_sh, sh.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (cand_light) memcpy(cand_light, sh.data(), 3 * sizeof(double));
+        if (cand_phong) memcpy(cand_phong, sh.data() + 3, 3 * M * sizeof(double));
+        if (cand_texture) memcpy(cand_texture, sh.data() + 3 + 3 * M, M * sizeof(double));
     }
     return SSBA_OK;
 }

@@ -349,3 +349,15 @@ class StereoBA:
         return DoglegStep(gn_p=gp, gn_l=gl, gn_b=gb[:nb], v_p=vp, v_l=vl, v_b=vb[:nb], sums=sc[0:6], alpha=sc[6], beta=sc[7],
                           gamma=sc[8], step_norm=sc[9], mcc=sc[10], one_dim=bool(sc[11]), sub_e=sc[12:16].reshape(2, 2),
                           sub_g=sc[16:18], sub_B=sc[18:21])
+
+    def line_search_probe(self, alpha: float):
+        """One evaluation of the projected line search's function along the step of the last lm_step / dogleg_step
+        (ssba_line_search_probe): (ls_out (8), the trial point as a dict of poses, points, normals, light, phong, texture)."""
+        out = np.zeros(8)
+        if self.normals is None:      # no lighting terms: the call reports SSBA_ERR_STATE
+            capi.check(self.lib.ssba_line_search_probe(self.h, float(alpha), capi.dptr(out), *([None] * 6)), "ssba_line_search_probe")
+        c = dict(poses=np.zeros_like(self.poses), points=np.zeros_like(self.points), normals=np.zeros_like(self.normals),
+                 light=np.zeros_like(self.light), phong=np.zeros_like(self.phong), texture=np.zeros_like(self.texture))
+        capi.check(self.lib.ssba_line_search_probe(self.h, float(alpha), capi.dptr(out), *[capi.dptr(c[k]) for k in (
+            "poses", "points", "normals", "light", "phong", "texture")]), "ssba_line_search_probe")
+        return out, c

@@ -293,6 +293,16 @@ SSBA_API int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius,
 #define SSBA_DOGLEG_NUM_SCALARS 21
 SSBA_API int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, double mu, double *gn_p,
                      double *gn_l, double *gn_b, double *v_p, double *v_l, double *v_b, double *scalars);
+/* One evaluation of the line-search function of the projected Armijo search along the step delta the last ssba_lm_step /
+ * ssba_dogleg_step left on the device (a handle with lighting observations, bounds or not; SSBA_ERR_STATE otherwise, or once
+ * another call has touched the solver state): phi(alpha) = cost(Plus(x, alpha delta)), phi'(alpha) = delta . gradient there.
+ * It enqueues what the solver enqueues for one evaluation of a search the host drives, and no other kernel.
+ *   ls_out (8): phi, phi', |dx_l|^2 of the landmark blocks, non-finite flag, max |delta|, g(x) . delta (= phi'(0), from the
+ *               gradient of the linearisation), step validity, cost at x;
+ *   the trial point in user index order: cand_poses (P*12), cand_points (L*3), cand_normals (L*3), cand_light (3),
+ *   cand_phong (3M), cand_texture (M).  Any output may be NULL.  May be called again with another alpha. */
+SSBA_API int ssba_line_search_probe(ssba_problem *p, double alpha, double *ls_out, double *cand_poses, double *cand_points,
+                           double *cand_normals, double *cand_light, double *cand_phong, double *cand_texture);
 /* The scalar state machine of the projected line search [Ceres 1.x line_search.cc ArmijoLineSearch::DoSearch, CUBIC
  * interpolation; bounds: tests/dataset_ba_phong.cpp:143-181] replayed on a given sequence of evaluations: phi(0),
  * phi'(0), max |direction|, then values[k] / gradients[k] = phi, phi' at the k-th step it asks for (steps_out[k], capacity

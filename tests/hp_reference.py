@@ -1588,11 +1588,12 @@ def _unary_magnitudes(poses, factors):
 
 
 def cost_at(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a=0.0, factors=None, lighting=None,
-            normals=None, jacobians=True):
+            normals=None, jacobians=True, rows=None):
     """1/2 sum rho(|r|^2) over all residual blocks at (poses, points[, normals, the shared blocks in `lighting`]) in long
     double: the stereo blocks with the Huber loss (stereo_rows), the intensity and normal blocks (phong_observation_rows; a
     NULL loss), the unary and relative pose blocks (unary_rows: fp64 values, each with its own Huber loss).  Returns a dict:
     cost, bar, rows (the stereo / lighting rows, for reuse; jacobians=False: stereo residuals and magnitudes only), n_terms.
+    rows: the rows of this very point when the caller has them already (stereo_rows / phong_observation_rows).
 
     The bar on an fp64 evaluation, in any summation order, has two parts.
     (1) The rounding of each term.  A row value r carries c u rabs (rabs of stereo_rows: pred - z cancels; the C_ROW magnitudes
@@ -1604,13 +1605,15 @@ def cost_at(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a
     if lighting is not None:
         lt = dict(lighting)
         nrm = lt["normals"] if normals is None else normals
-        rows = phong_observation_rows(cam, poses, points, nrm, obs_pose, obs_point, obs_uvd, stiffness, lt, huber_a, 0)
+        if rows is None:
+            rows = phong_observation_rows(cam, poses, points, nrm, obs_pose, obs_point, obs_uvd, stiffness, lt, huber_a, 0)
         N = rows["r"].shape[0]
         st_cost = rows["cost"] - LD(0.5) * (rows["r"][:, 3:] ** 2).sum()
         terms = [np.asarray(LD(0.5) * (rows["r"][:, 3] ** 2), LD), np.asarray(LD(0.5) * (rows["r"][:, 4:] ** 2).sum(1), LD)]
         n_terms = 3 * N
     else:
-        rows = stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a, jacobians=jacobians)
+        if rows is None:
+            rows = stereo_rows(cam, poses, points, obs_pose, obs_point, obs_uvd, stiffness, huber_a, jacobians=jacobians)
         N = rows["r"].shape[0]
         st_cost = rows["cost"]
         terms = []
@@ -1869,4 +1872,237 @@ def trust_region_decision(x_cost, candidate_cost, mcc, step_norm, x_norm, state,
         else:
             st["radius"], st["decrease_factor"] = st["radius"] / st["decrease_factor"], st["decrease_factor"] * 2
     out.update(radius=st["radius"], state=st)
+    return out
+
+
+# ------------------------------------------------------------------------------------------- the projected line search
+# [Ceres 1.x TrustRegionMinimizer::DoLineSearch -> ArmijoLineSearch::DoSearch, polynomial.cc] phi(a) = cost(Plus(x, a delta)),
+# phi'(a) = delta . gradient(Plus(x, a delta)): the gradient J^T r of the rows AT the trial point, in the tangent space of the
+# trial point (the plus-Jacobians of SE3Perturbation / UnitVectorPerturbation are inside the rows' J), against the UNSCALED
+# delta with every entry in full -- also the entries whose trial value the projection put on a bound (LineSearchFunction
+# knows nothing of the projection).
+class RowGradient:
+    """g = J^T r, its rounding magnitude ga = |J|^T |r| (from the rows' magnitudes) and the row count m per column, over the
+    parameter vector of DoglegReference -- [free poses (6 nf) | landmarks present (d each, index order) | free shared blocks
+    (nb)] -- straight from the rows (stereo_rows / phong_observation_rows): no Schur system is formed, so it scales to
+    thousands of poses."""
+
+    def __init__(self, rows, obs_pose, obs_point, fidx):
+        fidx = np.asarray(fidx, np.int64)
+        k, j = np.asarray(obs_pose, np.int64), np.asarray(obs_point, np.int64)
+        self.lm = np.unique(j)
+        slot = np.searchsorted(self.lm, j)
+        self.nf, self.d, self.Lp = int((fidx >= 0).sum()), rows["Jl"].shape[2], self.lm.shape[0]
+        self.nb = rows["Jb"].shape[2] if "Jb" in rows else 0
+        self.o_l = 6 * self.nf
+        self.o_b = self.o_l + self.d * self.Lp
+        self.N = self.o_b + self.nb
+        f = fidx[k]
+        cp = np.where(f[:, None] >= 0, 6 * f[:, None] + np.arange(6), self.N)        # constant poses: the sink column N
+        cl = self.o_l + self.d * slot[:, None] + np.arange(self.d)
+        self.blocks = [(rows["Jp"], rows["Jpa"], cp), (rows["Jl"], rows["Jla"], cl)]
+        if self.nb:
+            self.blocks.append((rows["Jb"], rows["Jba"], np.broadcast_to(self.o_b + np.arange(self.nb), (cl.shape[0], self.nb))))
+        self.r, self.rabs = rows["r"], rows["rabs"]
+        self.r64 = np.abs(np.asarray(self.r, np.float64))
+        g, ga, m = np.zeros(self.N + 1, LD), np.zeros(self.N + 1), np.zeros(self.N + 1)
+        for J, Ja, col in self.blocks:
+            np.add.at(g, col, np.einsum("nmw,nm->nw", J, self.r))
+            np.add.at(ga, col, np.einsum("nmw,nm->nw", Ja, self.rabs))
+            np.add.at(m, col, np.full(col.shape, float(self.r.shape[1])))
+        self.g, self.ga, self.m = g[:-1], ga[:-1], m[:-1]
+        self.t_max = int(np.bincount(slot).max()) if slot.size else 0
+
+    def jx(self, x):
+        xe = np.concatenate([np.asarray(x, LD), [LD(0)]])
+        return sum(np.einsum("nmw,nw->nm", J, xe[col]) for J, _, col in self.blocks)
+
+    def jx_mag(self, x):
+        xe = np.concatenate([np.abs(np.asarray(x, np.float64)), [0.0]])
+        return sum(np.einsum("nmw,nw->nm", Ja, xe[col]) for _, Ja, col in self.blocks)
+
+    def g_bar(self):
+        """Entrywise bar of an fp64 gradient: (m + C_TERMS) u |J|^T |r| (m rows summed into the entry, in any order)."""
+        return (self.m + C_TERMS) * U * self.ga
+
+    def directional(self, delta):
+        """phi' = delta . g = sum_rows r (J delta) and the bars of its two fp64 evaluations.
+
+        Row pass (k_ph_ls_probe: sum over the rows of r times the row's J delta): every term r_i J_ic delta_c is bounded by
+        T = |delta|^T |J|^T |r|.  One lane adds the 7 rows of its landmark's t_max observations in sequence, each row's dot
+        product has at most 19 terms (6 pose + 6 landmark + 7 border entries), two 256-lane trees (8 levels each) and
+        the final pass over the work-group partials (one per 256 landmarks, 1 024 lanes) follow: m = 7 t_max + 19 + 16 +
+        ceil(parts / 1024), and (m + C_TERMS) u T bounds summation and products.  The rounding of r and J themselves
+        (C_ROW u of the rows' magnitudes rabs, Ja) is carried through |J delta|: C_ROW u (rabs . |J delta| + |r| . Ja |delta|).
+
+        Column pass (g . delta from the gradient of the linearisation, ls_out[5]): the gradient's own bar carried through
+        |delta|, plus (n + C_TERMS) u sum |g| |delta| for the dot product over the n parameters in any order."""
+        d = np.asarray(delta, LD)
+        d64 = np.abs(np.asarray(delta, np.float64))
+        jd = self.jx(d)
+        val = (self.r * jd).sum()
+        T = float((self.r64 * self.jx_mag(d64)).sum())
+        parts = (self.Lp + 255) // 256
+        m_row = 7 * self.t_max + 19 + 16 + (parts + 1023) // 1024
+        row_bar = (m_row + C_TERMS) * U * T + C_ROW * U * float((self.rabs * np.abs(np.asarray(jd, np.float64))).sum() + T)
+        g64 = np.abs(np.asarray(self.g, np.float64))
+        col_bar = float((self.g_bar() * d64).sum()) + (self.N + C_TERMS) * U * float((g64 * d64).sum())
+        return dict(value=val, row_bar=row_bar, col_bar=col_bar, via_g=(self.g * d).sum(), T=T, m_row=m_row)
+
+
+def line_search_function(problem, x, ref, delta, alpha, trial=None):
+    """phi*(alpha) and phi'*(alpha) of the projected line search from x along delta (a vector over ref's parameters), in long
+    double.  problem: an object with rows(x) -> the rows at x, cost(x, rows=) -> cost_at dict and plus(x, ref, delta) -> (point,
+    bars), with obs = (obs_pose, obs_point, ...) and fidx (the Spec of the GPU tests); ref: a DoglegReference / RowGradient at x (only
+    its split of the parameter vector is used).  trial: the trial point to evaluate at -- an fp64 side's own Plus(x, alpha
+    delta) -- or None for the long-double Plus.  phi* carries the cost bar of cost_at; phi'* the bars of RowGradient.directional.
+    Returns a dict: alpha, trial, phi, phi_bar, dphi, dphi_bar (row pass), dphi_col_bar (column pass), grad (the RowGradient)."""
+    if trial is None:
+        trial = problem.plus(x, ref, LD(alpha) * np.asarray(delta, LD))[0]
+    rows = problem.rows(trial)
+    c = problem.cost(trial, rows=rows)
+    grad = RowGradient(rows, problem.obs[0], problem.obs[1], problem.fidx)
+    assert grad.N == np.asarray(delta).shape[0], (grad.N, np.asarray(delta).shape)
+    dd = grad.directional(delta)
+    return dict(alpha=alpha, trial=trial, phi=c["cost"], phi_bar=c["bar"], dphi=dd["value"], dphi_bar=dd["row_bar"],
+                dphi_col_bar=dd["col_bar"], dphi_via_g=dd["via_g"], grad=grad)
+
+
+ARMIJO = dict(sufficient_decrease=1e-4, max_step_contraction=1e-3, min_step_contraction=0.6, min_step_size=1e-9, max_num_iterations=20)
+# c of the elimination term c u kappa_inf(A) |alpha| of an interior step: four times the worst |alpha_fp64 - alpha_mpmath| /
+# (u kappa_inf(A) |alpha|) measured over the 40 synthetic searches of tests/test_oracle_bounds.py for the numpy restatement
+# and the C oracle (tests/test_hp_reference.py: test_armijo_elimination_constant), two bits for another pivoting order and
+# root finder
+ARMIJO_C = 5.61           # measured: 1.4006
+MP_DIGITS = 50
+
+
+def interpolation_minimum(samples, lo, hi, bars=None):
+    """FindInterpolatingPolynomial + MinimizeInterpolatingPolynomial at MP_DIGITS digits (mpmath).  samples: (x, value,
+    gradient) triples -- the polynomial of degree 2 len(samples) - 1 through all of them -- and the candidates in Ceres' order:
+    the midpoint of [lo, hi], lo, hi, the real parts of ALL roots of the derivative that fall inside [lo, hi], then the samples
+    inside it with their own values; the first strictly smallest value wins.
+
+    Returns a dict: x (float), kind ("mid" / "lo" / "hi" / "root" / "sample"), interior (kind == "root"), kappa (kappa_inf of the
+    interpolation system A), and with bars (one (value bar, gradient bar) pair per sample): x_bar -- the bars carried through
+    the minimiser by central differences --, rank_margin (smallest |p(other) - p(best)| over its propagated bar) and
+    edge_margin (smallest distance of a root's real part from lo / hi over its propagated bar); inf where nothing competes."""
+    import mpmath as mp
+    with mp.workdps(MP_DIGITS):
+        lo_, hi_ = mp.mpf(float(lo)), mp.mpf(float(hi))
+        xs = [mp.mpf(float(s[0])) for s in samples]
+        n = 2 * len(samples)
+
+        def solve(vals):
+            A, b = mp.zeros(n, n), mp.zeros(n, 1)
+            for i, x in enumerate(xs):
+                for jc in range(n):
+                    A[2 * i, jc] = x ** (n - 1 - jc)
+                    A[2 * i + 1, jc] = (n - 1 - jc) * x ** (n - 2 - jc) if jc < n - 1 else mp.mpf(0)
+                b[2 * i], b[2 * i + 1] = vals[2 * i], vals[2 * i + 1]
+            coef = [c for c in mp.lu_solve(A, b)]
+            der = [(n - 1 - i) * coef[i] for i in range(n - 1)]
+            while len(der) > 1 and der[0] == 0:
+                der = der[1:]
+            roots = sorted((mp.re(z) for z in mp.polyroots(der, maxsteps=500, extraprec=4 * MP_DIGITS)), key=float) if len(der) > 1 else []
+            return A, coef, roots
+
+        base = [mp.mpf(float(v)) for s in samples for v in (s[1], s[2])]
+        A, coef, roots = solve(base)
+        kappa = float(mp.norm(A, mp.inf) * mp.norm(mp.inverse(A), mp.inf))
+        cands = [("mid", (lo_ + hi_) / 2, None), ("lo", lo_, None), ("hi", hi_, None)]
+        cands += [("root", z, i) for i, z in enumerate(roots) if lo_ <= z <= hi_]
+        vals = [mp.polyval(coef, x) for _, x, _ in cands]
+        cands += [("sample", xs[i], i) for i in range(len(xs)) if lo_ <= xs[i] <= hi_]
+        vals += [base[2 * i] for i in range(len(xs)) if lo_ <= xs[i] <= hi_]
+        best = 0
+        for i in range(1, len(cands)):
+            if vals[i] < vals[best]:
+                best = i
+        out = dict(x=float(cands[best][1]), kind=cands[best][0], interior=cands[best][0] == "root", kappa=kappa,
+                   x_bar=0.0, rank_margin=float("inf"), edge_margin=float("inf"))
+        if bars is None:
+            return out
+        flat = [float(b) for pair in bars for b in pair]
+
+        def observe(v):
+            _, cf, rt = solve(v)
+            assert len(rt) == len(roots)
+            loc = lambda c: rt[c[2]] if c[0] == "root" else c[1]
+            val = lambda c, v=v: v[2 * c[2]] if c[0] == "sample" else mp.polyval(cf, loc(c))
+            o = {"x": loc(cands[best])}
+            for i, c in enumerate(cands):
+                if i != best:
+                    o[f"rank{i}"] = val(c) - val(cands[best])
+            for i, z in enumerate(rt):
+                o[f"root{i}"] = z
+            return o
+
+        obs0, acc = observe(base), {}
+        for i in range(len(base)):
+            h = max(abs(base[i]), mp.mpf(1)) * mp.mpf(2) ** -60
+            up, dn = list(base), list(base)
+            up[i], dn[i] = base[i] + h, base[i] - h
+            ou, od = observe(up), observe(dn)
+            for k in obs0:
+                acc[k] = acc.get(k, 0.0) + float(abs((ou[k] - od[k]) / (2 * h))) * flat[i]
+        ratio = lambda dist, bar: float("inf") if bar == 0 else abs(float(dist)) / bar
+        out["x_bar"] = acc["x"]
+        ranks = [ratio(obs0[k], acc[k]) for k in obs0 if k.startswith("rank")]
+        edges = [ratio(z - e, acc[f"root{i}"]) for i, z in enumerate(roots) for e in (lo_, hi_)]
+        out["rank_margin"] = min(ranks) if ranks else float("inf")
+        out["edge_margin"] = min(edges) if edges else float("inf")
+        return out
+
+
+def armijo_search(phi, dphi, dir_max_norm=1.0, initial=None):
+    """ArmijoLineSearch::DoSearch with the defaults quoted at the top of csrc/ssba_linesearch.h (ARMIJO): CUBIC interpolation
+    through (0, previous, current), step contraction into [1e-3, 0.6] of the current step, at most 20 iterations, minimum step
+    size 1e-9 / |direction|_inf.  phi(a), dphi(a) return a value or (value, bar).  initial: ((phi(0), bar), (phi'(0), bar)) when
+    they are known already.  The decisions are made on the values; the interpolating polynomial and its minimiser at
+    MP_DIGITS digits (interpolation_minimum).
+
+    Returns a dict: alphas (every step evaluated, the first is 1), kinds (None for the first, then the kind of each choice),
+    interior, x_bars and kappas per chosen step, armijo_margins (|phi(a) - phi(0) - 1e-4 phi'(0) a| over its bar, per sample),
+    choice_margins (min of rank and edge margin per choice), success, optimal (the accepted step or None), count (evaluations),
+    samples ((a, phi, phi')), margin (the smallest of all margins)."""
+    pair = lambda v: (v[0], float(v[1])) if isinstance(v, tuple) else (v, 0.0)
+    o = ARMIJO
+    (f0, f0b), (g0, g0b) = (pair(phi(0.0)), pair(dphi(0.0))) if initial is None else (pair(initial[0]), pair(initial[1]))
+    init = (0.0, f0, g0)
+    init_b = (f0b, g0b)
+    prev = prev_b = None
+    x = 1.0
+    out = dict(alphas=[], kinds=[None], interior=[False], x_bars=[0.0], kappas=[0.0], armijo_margins=[], choice_margins=[], samples=[],
+               success=False, optimal=None)
+    it = 0
+    ratio = lambda dist, bar: float("inf") if bar == 0 else abs(float(dist)) / bar
+    while True:
+        (v, vb), (g, gb) = pair(phi(x)), pair(dphi(x))
+        out["alphas"].append(x)
+        out["samples"].append((x, v, g))
+        thr = LD(f0) + LD(o["sufficient_decrease"]) * LD(g0) * LD(x)
+        out["armijo_margins"].append(ratio(LD(v) - thr, vb + f0b + o["sufficient_decrease"] * x * g0b))
+        if not LD(v) > thr:
+            out.update(success=True, optimal=x)
+            break
+        it += 1
+        if it >= o["max_num_iterations"]:
+            break
+        lo, hi = o["max_step_contraction"] * x, o["min_step_contraction"] * x
+        smp, sb = [init, (x, v, g)], [init_b, (vb, gb)]
+        if prev is not None:
+            smp.append(prev)
+            sb.append(prev_b)
+        m = interpolation_minimum(smp, lo, hi, sb)
+        if m["x"] * dir_max_norm < o["min_step_size"]:
+            break
+        out["kinds"].append(m["kind"])
+        out["interior"].append(m["interior"])
+        out["x_bars"].append(m["x_bar"])
+        out["kappas"].append(m["kappa"])
+        out["choice_margins"].append(min(m["rank_margin"], m["edge_margin"]))
+        prev, prev_b, x = (x, v, g), (vb, gb), m["x"]
+    out["count"] = len(out["alphas"])
+    out["margin"] = min(out["armijo_margins"] + out["choice_margins"])
     return out

@@ -36,8 +36,9 @@ Further cases: bounds on the Phong and texture blocks with the full step passing
 one entry projected onto its bound; a pose-graph-only problem with a prior exactly on its pose (the first-order branch of
 se3_plus); one C2-sized LM iteration, rejected and accepted.
 
-Not compared here: a projected line search that contracts; LM landmark steps other than through the cost
-and rho (see 2.)."""
+A projected line search that contracts is in tests/test_gpu_hp_linesearch.py, which drives candidate_case with the step the
+search accepted (line_search=).  Not compared here: LM landmark steps other than through the cost and rho
+(see 2.)."""
 import numpy as np
 import pytest
 
@@ -121,9 +122,26 @@ class Spec:
             x.update(normals=ba.normals.copy(), light=ba.light.copy(), phong=ba.phong.copy(), texture=ba.texture.copy())
         return x
 
-    def cost(self, x, jacobians=True):
+    def remember(self, x):
+        """cost(x) and reference(x, mu) of this very object are computed once from now on (the start of a case that several
+        comparisons share; the point must not be modified)."""
+        self._at, self._memo = x, {}
+
+    def _remembered(self, x, key, make):
+        if getattr(self, "_at", None) is not x:
+            return make()
+        if key not in self._memo:
+            self._memo[key] = make()
+        return self._memo[key]
+
+    def cost(self, x, jacobians=True, rows=None):
+        if rows is None:
+            return self._remembered(x, ("cost", jacobians), lambda: self._cost(x, jacobians, None))
+        return self._cost(x, jacobians, rows)
+
+    def _cost(self, x, jacobians, rows):
         return hp.cost_at(self.cam, x["poses"], x["points"], *self.obs, self.S, huber_a=self.huber, factors=self.factors,
-                          lighting=self.lighting_at(x), jacobians=jacobians)
+                          lighting=self.lighting_at(x), jacobians=jacobians, rows=rows)
 
     def shared(self, x):
         if not self.shared_free:
@@ -131,7 +149,18 @@ class Spec:
         return dict(light_type=self.lighting["light_type"], light=x["light"], phong=x["phong"], texture=x["texture"],
                     shared_free=self.shared_free, bounds=self.bounds)
 
+    def rows(self, x, reuse=None):
+        """The long-double rows at x (with the border columns of the free shared blocks).  reuse: rows of the same point
+        (cost(x)["rows"]), whose lighting part is taken over."""
+        if self.lighting is not None:
+            return hp.phong_observation_rows(self.cam, x["poses"], x["points"], x["normals"], *self.obs, self.S, self.lighting_at(x),
+                                             self.huber, self.shared_free, phong=None if reuse is None else reuse["phong"])
+        return hp.stereo_rows(self.cam, x["poses"], x["points"], *self.obs, self.S, self.huber)
+
     def reference(self, x, mu, rows=None):
+        return self._remembered(x, ("reference", mu), lambda: self._reference(x, mu, rows))
+
+    def _reference(self, x, mu, rows=None):
         """DoglegReference at x (its gradient, and the step of the system damped at radius 1 / mu)."""
         if self.lighting is not None:
             rows = hp.phong_observation_rows(self.cam, x["poses"], x["points"], x["normals"], *self.obs, self.S, self.lighting_at(x),
@@ -278,7 +307,14 @@ def _reference_step(spec, x, ref, rows, strategy, dogleg_type, radius):
     return delta, mcc, mag, dl_norm
 
 
-def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, second=False, expect=None, **okw):
+def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, second=False, expect=None, line_search=None, **okw):
+    """line_search (bounds; tests/test_gpu_hp_linesearch.py): dict(alpha_ref, alpha, count) of a projected line search that
+    contracts -- the step the reference's own search accepts along the reference's step, the one the device's search accepts
+    along its own, and the number of evaluations.  The candidate is then Plus(x, alpha delta) (one more rounding, alpha *
+    delta, on top of the step's own), while rho keeps the model cost change of the unscaled delta [DoLineSearch only rescales
+    delta]; a failed search comes here with alpha = 1."""
+    ls = line_search
+    a_ref, a_dev = (LD(ls["alpha_ref"]), LD(ls["alpha"])) if ls else (LD(1), LD(1))
     o = _options(strategy, dogleg_type, radius, **okw)
     ho = _hp_options(o)
     ref, rows = spec.reference(x, 1e-8)
@@ -291,7 +327,7 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
 
     # ---- the decision from the reference's own step: every comparison more than 4 bars from its threshold
     d_ref, mcc_ref, mag_ref, dl_ref = _reference_step(spec, x, ref, rows, strategy, dogleg_type, radius)
-    cand_ref, pb_ref = spec.plus(x, ref, d_ref)
+    cand_ref, pb_ref = spec.plus(x, ref, a_ref * d_ref)
     cc_ref = spec.cost(cand_ref)
     sn_ref, sn_ref_bar = spec.norms(x, cand_ref)
     pre = hp.trust_region_decision(c0["cost"], cc_ref["cost"], mcc_ref, sn_ref, xn, state0, ho, dl_norm=dl_ref,
@@ -302,7 +338,7 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
     assert pre["termination"] is None and pre["valid"], (tag, pre["termination"])
     if expect is not None:
         assert pre["accepted"] == (expect == "accepted"), (tag, pre["rho"])
-    if spec.bounds is not None:
+    if spec.bounds is not None and ls is None:
         # the projected Armijo search takes the full step: cost(Plus(x, delta)) <= cost + 1e-4 g . delta, by more than the bars
         g_delta = float((ref.g * d_ref).sum())
         assert g_delta < 0 and float(cc_ref["cost"] - c0["cost"]) + 4 * (cc_ref["bar"] + c0["bar"]) < 0.5e-4 * g_delta, (tag, g_delta)
@@ -316,7 +352,9 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
     cost_eval = ba_h.evaluate()[0]
     ba, s, log = _solve(spec, x, o, 2)
     out = dict(margin=margin)
-    if spec.bounds is not None:
+    if ls is not None:
+        assert s.num_line_search_steps == ls["count"], (tag, s.num_line_search_steps, ls["count"])
+    elif spec.bounds is not None:
         assert s.num_line_search_steps == 1, (tag, s.num_line_search_steps)            # one evaluation, at alpha = 1, for the one iteration
         crossed = _crossings(spec, x, ref.split(delta)[2])
         assert crossed.any() and np.array_equal(crossed, out_of_box), (tag, crossed, out_of_box)
@@ -326,7 +364,7 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
     out["r_gmax"] = abs(float(LD(log["gradient_max_norm"][0]) - gmax)) / gmax_bar
     accepted = bool(log["step_is_successful"][1])
     assert accepted == pre["accepted"], (tag, accepted, pre["rho"], log["relative_decrease"][1])
-    cand, pb = spec.plus(x, ref, delta, combo)
+    cand, pb = spec.plus(x, ref, a_dev * delta, combo + (2.0 if ls else 0.0))
     xw = spec.written_back(ba)
     keys = ["poses", "points"] + (["normals", "light", "phong", "texture"] if spec.lighting is not None else [])
     if accepted:
@@ -344,6 +382,14 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
         ob = ortho(f64(x["poses"])[free]) + 6 * pb["poses"][free, 3:].max(1) + 8 * U
         out["r_ortho"] = float((ortho(xw["poses"][free]) / ob).max())
         cc = spec.cost(xw)
+        cc_bar = cc["bar"]
+        out["r_cost1"] = abs(float(LD(log["cost"][1]) - cc["cost"])) / cc_bar
+    elif ls is not None:
+        # a rejected candidate is never written back; the line-search hook hands out the fp64 trial point the same kernels form
+        # (ls["trial"]), so its cost needs no propagated Plus bar
+        for k in keys:
+            assert np.array_equal(f64(xw[k]), f64(x[k])), (tag, k)
+        cc = spec.cost(ls["trial"])
         cc_bar = cc["bar"]
         out["r_cost1"] = abs(float(LD(log["cost"][1]) - cc["cost"])) / cc_bar
     else:
@@ -387,6 +433,7 @@ def candidate_case(tag, spec, x, strategy, dogleg_type, radius, layout=None, sec
     for k, v in out.items():
         if k.startswith("r_"):
             assert v <= 1.0, (tag, k, v, out)
+    out.update(written_back=xw, log=log, delta=delta)
     return out
 
 

@@ -255,8 +255,8 @@ class Problem:
 
     def SetParameterBlockConstant(self, block):
         a = _addr(block)
-        if a not in self._pose_blocks:
-            raise KeyError("parameter block not found (only pose blocks can be held constant)")
+        if a not in self._pose_blocks and a not in self._point_blocks:
+            raise KeyError("parameter block not found in the problem")   # Ceres aborts here
         self._constant.add(a)
 
     def SetParameterBlockVariable(self, block):
@@ -291,11 +291,15 @@ def _lower(problem: Problem, device: int = -1):
     stiffness = shared if all(np.array_equal(x, shared) for x in per_block) else np.array(per_block)
     cam = problem._camera or StereoCamera(1.0, 1.0, 0.0, 0.0, 1.0)
     const = np.zeros(P, dtype=np.uint8)
+    point_const = np.zeros(L, dtype=bool)
     for a in problem._constant:
-        const[problem._pose_blocks[a][0]] = 1
+        if a in problem._pose_blocks:
+            const[problem._pose_blocks[a][0]] = 1
+        else:
+            point_const[problem._point_blocks[a][0]] = True
     ba = StereoBA(dict(fu=cam.fu, fv=cam.fv, cu=cam.cu, cv=cam.cv, b=cam.b), poses, points, op, ol, uv, stiffness, pose_const=const,
                   huber_a=0.0 if problem._loss in ("unset", None) else problem._loss, device=device,
-                  pose_factors=problem._pose_factors or None)
+                  pose_factors=problem._pose_factors or None, point_const=point_const if point_const.any() else None)
     return ba
 
 

@@ -58,9 +58,12 @@ struct ssba_problem {
     double S[9] = {0};
     bool have_S = false, per_obs_S = false, points_const = false;
     bool no_closure_border = false;     // a caller asked for something the closure border does not cover (DOGLEG, covariance): general path
+    bool no_pose_only = false;          // ... or something the pose-only layout does not cover (DOGLEG, the test hooks): windowed layout with constant points
     bool no_wide = false;               // ... or something the 144-row super-blocks of ssba_wide.hip do not cover (covariance): blocked Cholesky
     std::vector<double> obs_S;          // 9 per observation once two stereo blocks differ in stiffness
     std::vector<uint8_t> pose_const;
+    std::vector<uint8_t> point_const;   // L flags (ssba_set_point_constant), empty until the first call
+    bool point_is_const(uint32_t j) const { return points_const || (!point_const.empty() && point_const[j]); }
     double huber_a = 0.0;
     bool finalized = false;
     // config 3: lighting terms
@@ -423,6 +426,7 @@ int ssba_add_point_blocks(ssba_problem *p, double *points, uint32_t num) {
     if (p->finalized) return SSBA_ERR_STATE;
     p->user_points = points;
     p->L = num;
+    p->point_const.clear();
     return SSBA_OK;
 }
 
@@ -578,6 +582,16 @@ int ssba_set_point_blocks_constant(ssba_problem *p, int is_constant) {
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->points_const = is_constant != 0;
+    return SSBA_OK;
+}
+
+int ssba_set_point_constant(ssba_problem *p, const uint32_t *points, uint64_t num, int is_constant) {
+    if (!p || (num && !points)) return SSBA_ERR_INVALID_ARGUMENT;
+    if (p->finalized) return SSBA_ERR_STATE;   // the flags live in the layout's landmark masks
+    for (uint64_t i = 0; i < num; ++i)
+        if (points[i] >= p->L) { set_error("ssba_set_point_constant: point index out of range"); return SSBA_ERR_INVALID_ARGUMENT; }
+    if (p->point_const.empty()) p->point_const.assign(p->L, 0);
+    for (uint64_t i = 0; i < num; ++i) p->point_const[points[i]] = is_constant ? 1 : 0;
     return SSBA_OK;
 }
 
@@ -873,7 +887,7 @@ int ssba_finalize(ssba_problem *p) {
     {
         const LayoutInput in{P, L, p->obs_pose, p->obs_point, p->obs_uvd, p->pose_const, p->per_obs_S, p->obs_S, ph, p->M, p->ph_mat_of_point,
                              p->ph_intensity, p->ph_nobs, p->points_const, p->pose_factors, p->rel_factors, p->world_size, p->sep_sb.size() > 2,
-                             p->no_closure_border, p->no_wide};
+                             p->no_closure_border, p->no_wide, &p->point_const, p->no_pose_only};
         std::string err;
         const int lrc = build_layout(in, lay, err, [&](const char *what) { phase.mark(what); });
         if (lrc) { set_error(err); return lrc; }
@@ -883,6 +897,7 @@ int ssba_finalize(ssba_problem *p) {
     p->user_of_dev = std::move(lay.user_of_dev);
     const int nfree = lay.nfree, nchain = lay.nchain, nborder = lay.nborder;
     const bool dense = lay.dense, wide_sys = lay.wide_sys;
+    const bool po = lay.pose_only;      // every observed point constant: pose-major records only, none of the windowed / general structures
     const uint32_t Lact = lay.Lact, Lpad = lay.Lpad, n_groups = lay.n_groups, n_windows = lay.n_windows, n_slabs = lay.n_slabs, n_sblk = lay.n_sblk;
     const uint32_t bandwidth = lay.bandwidth;
     auto &pfs = lay.pfs;
@@ -908,6 +923,8 @@ int ssba_finalize(ssba_problem *p) {
     memcpy(d.S, p->S, sizeof d.S);
     d.huber_a = p->huber_a;
     d.P = (int)P; d.nfree = nfree; d.nchain = nchain;
+    d.lm_const = lay.lm_const ? 1 : 0;
+    d.pose_only = po ? 1 : 0;
     d.Nsb = std::max(1, (nfree + SBP - 1) / SBP);
     d.nf_pad = d.Nsb * SBP;
     d.Lpad = (int)Lpad; d.n_groups = (int)n_groups; d.n_windows = (int)n_windows;
@@ -925,6 +942,7 @@ int ssba_finalize(ssba_problem *p) {
     TRY(dzero(p, &d.best_pts, (size_t)Lpad * 3)); TRY(dzero(p, &d.init_pts, (size_t)Lpad * 3));
     TRY(dupload(p, &d.pose_free, p->pose_free));
     TRY(dupload(p, &d.free_pose, p->free_pose));
+    if (!po) {
     TRY(dupload(p, &d.ou, ou)); TRY(dupload(p, &d.ov, ov)); TRY(dupload(p, &d.od, od));
     TRY(dupload(p, &d.lm_mask, lm_mask)); TRY(dupload(p, &d.lm_win, lm_win));
     if (win_pose.empty()) win_pose.assign(TW, 0xFFFFFFFFu);
@@ -932,6 +950,7 @@ int ssba_finalize(ssba_problem *p) {
     TRY(dupload(p, &d.pose_obs_start, pose_obs_start)); TRY(dupload(p, &d.pose_obs_ref, pose_obs_ref));
     TRY(dzero(p, &d.hll, (size_t)Lpad * (ph ? 21 : 6))); TRY(dzero(p, &d.gl, (size_t)Lpad * (ph ? 6 : 3)));
     TRY(dzero(p, &d.sl, (size_t)Lpad * (ph ? 6 : 3)));
+    }
     if (ph) {
         d.phong = 1;
         d.pos_const = p->points_const ? 1 : 0;
@@ -984,6 +1003,14 @@ int ssba_finalize(ssba_problem *p) {
     }
     TRY(dzero(p, &d.hpp, (size_t)P * 21)); TRY(dzero(p, &d.gp, (size_t)P * 6));
     TRY(dzero(p, &d.sp, (size_t)d.nf_pad * 6));
+    d.pcr.level = -1;
+    if (po) {       // the records, and of the exchange vector only its scalars (k_check's sums)
+        TRY(dupload(p, &d.dn_pose_start, lay.dn_pose_start)); TRY(dupload(p, &d.dn_prec, dn_prec));
+        if (p->per_obs_S) TRY(dupload(p, &d.dn_Sobs, dn_Sobs));
+        d.off_scal = 0;
+        d.xv_count = NSCAL;
+        TRY(dzero(p, &d.xv, d.xv_count));
+    } else {
     TRY(dupload(p, &d.slab_win, slab_win)); TRY(dupload(p, &d.slab_lm_begin, slab_b));
     TRY(dupload(p, &d.slab_lm_end, slab_e));
     TRY(dzero(p, &d.slab, (size_t)n_slabs * SLAB_DOUBLES));
@@ -1140,6 +1167,7 @@ int ssba_finalize(ssba_problem *p) {
         TRY(make_pcr(d.spcr, 0, d.n_sep, 0, 0, 0));
         TRY(make_fused(d.spcrf, (size_t)ns, false));        // one launch per step of the separator solve
     }
+    }       // !po
     std::vector<uint32_t> dn_blk_rf_start, dn_blk_rf;
     if (!pfs.empty()) {
         std::vector<uint32_t> start(P + 1, 0);
@@ -1229,10 +1257,11 @@ int ssba_finalize(ssba_problem *p) {
         TRY(dzero(p, &d.dn_Mg, (size_t)Lpad * (ph ? 6 : 3)));
         TRY(dzero(p, &d.dn_S, (size_t)(d.dn_pad + DN_BS) * std::max(d.dn_pad, DN_BS)));
     }
-    TRY(dzero(p, &d.part_lin, (size_t)d.n_groups * 4));       // one entry per block of 256 landmarks, or per group of 64 (window layout)
-    TRY(dzero(p, &d.part_eval, (size_t)d.n_groups * 4));
+    const size_t n_lm_parts = po ? std::max<size_t>(P, 1) : (size_t)d.n_groups;      // pose-only: one entry per pose
+    TRY(dzero(p, &d.part_lin, n_lm_parts * 4));       // one entry per block of 256 landmarks, or per group of 64 (window layout)
+    TRY(dzero(p, &d.part_eval, n_lm_parts * 4));
     TRY(dzero(p, &d.part_chk, (size_t)std::max<uint32_t>(d.nfree, 1) * 2));
-    TRY(dzero(p, &d.part_pose, (size_t)(std::max(d.n_pose_blocks, d.Nsb) + 1) * NPP));   // + one entry for the border of shared blocks
+    TRY(dzero(p, &d.part_pose, (size_t)(std::max(po ? (int)P : d.n_pose_blocks, d.Nsb) + 1) * NPP));   // + one entry for the border of shared blocks
     TRY(dzero(p, &d.part_dl, (size_t)(d.n_lm_blocks + d.n_pose_blocks + 1) * NDL));
     TRY(dzero(p, &d.scal2, (size_t)NSCAL));
     TRY(dzero(p, &d.scal_dl, (size_t)NSCAL));
@@ -1273,7 +1302,7 @@ int ssba_finalize(ssba_problem *p) {
     p->stats.num_observations = N; p->stats.num_windows = n_windows;
     p->stats.num_superblocks = (uint32_t)d.Nsb; p->stats.num_reduced_blocks = n_sblk;
     p->stats.pose_bandwidth = bandwidth;
-    p->stats.general_structure = dense ? 1u : nborder ? 2u : 0u;      // 2: windowed layout + closure border
+    p->stats.general_structure = po ? 3u : dense ? 1u : nborder ? 2u : 0u;      // 2: windowed layout + closure border, 3: pose-only
     p->stats.pcr_blocks = d.pcr.level >= 0 ? (uint32_t)d.pcr.n : 0u;
     p->stats.pcr_fused = d.pcrf.on ? 1u : 0u;
     p->stats.wide_superblocks = 0;
@@ -1478,6 +1507,12 @@ static bool fuse_all_launches(const ssba_problem *p) {
 }
 
 static int enqueue_kernels(ssba_problem *p) {
+    if (p->d.pose_only) {       // k_po_step . k_po_eval . k_decide . k_best
+        launch_pose_only(p->launcher, p->d);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return SSBA_ERR_HIP; }
+        return SSBA_OK;
+    }
     int rc = enqueue_front(p);
     if (rc) return rc;
     // single GPU, LM: the decision kernel forms the evaluation sums itself (no exchange sits between them)
@@ -1689,6 +1724,30 @@ static int refinalize_without_closure_border(ssba_problem *p, const char *what) 
     return rc;
 }
 
+// The pose-only layout (every observed point constant) runs Levenberg-Marquardt solves and covariance requests.  DOGLEG and the
+// test hooks hand the handle over to the windowed layout with constant points, as above: ssba_finalize runs again before the
+// first solve begins.  A structure that layout does not take (long tracks, per-block stiffness, a closure border) is
+// SSBA_ERR_UNSUPPORTED, and the handle keeps its pose-only layout.
+static int refinalize_without_pose_only(ssba_problem *p, const char *what) {
+    if (p->began) {
+        set_error(std::string(what) + ": not available on the pose-only layout of this handle once a solve has begun (ask before the first "
+                  "solve, or set SSBA_NO_POSE_ONLY=1)");
+        return SSBA_ERR_STATE;
+    }
+    p->no_pose_only = true;
+    p->finalized = false;
+    int rc = ssba_finalize(p);
+    if (rc) {       // the windowed layout does not take this structure: back onto the pose-only layout
+        const std::string why = ssba_last_error();
+        p->no_pose_only = false;
+        p->finalized = false;
+        const int rc2 = ssba_finalize(p);
+        set_error(std::string(what) + ": not available on the pose-only layout, and the windowed layout it would need refuses the problem (" + why + ")");
+        return rc2 ? rc2 : rc;
+    }
+    return rc;
+}
+
 int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_convergence) {
     ApiTimer api_timer("ssba_solve_begin");
     if (!p || !o) return SSBA_ERR_INVALID_ARGUMENT;
@@ -1703,6 +1762,10 @@ int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_converge
     }
     if (o->dogleg_type != 0 && o->dogleg_type != 1) return SSBA_ERR_INVALID_ARGUMENT;
     p->step_hook_done = false;
+    if (o->trust_region_strategy_type == 1 && p->d.pose_only) {
+        int rc = refinalize_without_pose_only(p, "DOGLEG");
+        if (rc) return rc;
+    }
     if (o->trust_region_strategy_type == 1 && p->d.cb) {
         // DOGLEG is not implemented on the closure border: the symbolic phase runs again and puts the problem on the
         // general-structure path, which has it (once per handle; the caller's blocks and pointers are unchanged)
@@ -2042,6 +2105,10 @@ static int begin_hook(ssba_problem *p, const ssba_options *o, double radius) {
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
     if (p->d.part) { set_error("test hooks are not available on a partitioned problem"); return SSBA_ERR_UNSUPPORTED; }
     if (p->began) return SSBA_ERR_STATE;
+    if (p->d.pose_only) {       // the hooks read the windowed structures
+        int rc = refinalize_without_pose_only(p, "test hook");
+        if (rc) return rc;
+    }
     p->step_hook_done = false;
     HIPCHECK(hipSetDevice(p->device));
     ssba_options opt;
@@ -2297,6 +2364,10 @@ int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, doub
     if (o) opt = *o; else ssba_default_options(&opt);
     if (opt.dogleg_type != 0 && opt.dogleg_type != 1) return SSBA_ERR_INVALID_ARGUMENT;
     opt.trust_region_strategy_type = 1;
+    if (p->d.pose_only) {
+        int rc = refinalize_without_pose_only(p, "ssba_dogleg_step");
+        if (rc) return rc;
+    }
     if (p->d.cb) {      // as ssba_solve_begin: DOGLEG runs on the general path
         int rc = refinalize_without_closure_border(p, "DOGLEG");
         if (rc) return rc;
@@ -2467,6 +2538,11 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     ApiTimer api_timer("ssba_pose_covariance");
     if (!p || !cov || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    if (p->d.pose_only) {
+        if (p->pose_free[pose] < 0) { set_error("covariance of a constant pose"); return SSBA_ERR_INVALID_ARGUMENT; }
+        const ssba_cov_block b{SSBA_COV_POSE, pose, SSBA_COV_POSE, pose};
+        return ssba_covariance_blocks(p, &b, 1, cov);
+    }
     if (p->d.cb) {      // the closure border has no covariance sweep: the general path has (symbolic phase again, once)
         int rc = refinalize_without_closure_border(p, "covariance");
         if (rc) return rc;
@@ -2569,6 +2645,63 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
 // poses whose blocks lie outside it; general layout: columns of Sigma for every pose the request touches, DN_BS / 6 poses
 // per blocked Cholesky solve; a wide handle that has been solved: the same columns, 8 poses per sweep of its parallel cyclic
 // reduction (ssba_wide_covariance.hip).  The landmark blocks follow from those in one launch.
+// Pose-only layout: every point is constant, the reduced system is block diagonal.  A (pose, pose) block of one free pose is
+// the inverse of its undamped 6 x 6 block (k_po_step at the current poses leaves H_pp, k_po_cov inverts), every other block is
+// zero.  A block that is not positive definite (a pose with one or two observations): SSBA_ERR_NUMERICAL_FAILURE.
+static int pose_only_covariance(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
+    if (p->began) return SSBA_ERR_STATE;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    std::vector<uint64_t> off(num + 1, 0);
+    for (uint64_t q = 0; q < num; ++q)
+        off[q + 1] = off[q] + (blocks[q].kind_a == SSBA_COV_POINT ? 3 : 6) * (blocks[q].kind_b == SSBA_COV_POINT ? 3 : 6);
+    std::fill(out, out + off[num], 0.0);
+    std::vector<int> poses;
+    std::vector<uint64_t> where;
+    for (uint64_t q = 0; q < num; ++q) {
+        const ssba_cov_block &b = blocks[q];
+        if (b.kind_a != SSBA_COV_POSE || b.kind_b != SSBA_COV_POSE || b.index_a != b.index_b || p->pose_free[b.index_a] < 0) continue;
+        poses.push_back((int)b.index_a);
+        where.push_back(off[q]);
+    }
+    if (poses.empty()) return SSBA_OK;
+    HIPCHECK(hipSetDevice(p->device));
+    ssba_options o;
+    ssba_default_options(&o);
+    p->opt = o;
+    p->ignore_convergence = 1;
+    d.huber_a = p->huber_a;
+    int rc = ensure_log(p, 16);
+    if (rc) return rc;
+    if ((rc = upload_params(p))) return rc;
+    hipStream_t s = L.stream;
+    HIPCHECK(hipMemcpyAsync(d.init_poses, d.poses, (size_t)d.P * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(hipMemcpyAsync(d.init_pts, d.pts, (size_t)d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if ((rc = reset_solver(p))) return rc;
+    launch_pose_only_step(L, d);
+    CallBuffers B;
+    int *d_poses = nullptr, *d_fail = nullptr;
+    double *d_out = nullptr;
+    HIPCHECK(B.get((void **)&d_poses, poses.size() * sizeof(int)));
+    HIPCHECK(B.get((void **)&d_fail, sizeof(int)));
+    HIPCHECK(B.get((void **)&d_out, poses.size() * 36 * sizeof(double)));
+    HIPCHECK(hipMemcpyAsync(d_poses, poses.data(), poses.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), s));
+    HIPCHECK(hipMemsetAsync(d_out, 0, poses.size() * 36 * sizeof(double), s));
+    HIPCHECK(hipStreamSynchronize(s));      // (the index list is pageable memory)
+    launch_pose_only_cov(L, d, d_poses, (int)poses.size(), d_out, d_fail);
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    int fail = 0;
+    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
+    if (fail) { set_error("covariance: the 6 x 6 block of a requested pose is not positive definite (too few observations?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    std::vector<double> h(poses.size() * 36);
+    HIPCHECK(hipMemcpy(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < poses.size(); ++i) memcpy(out + where[i], &h[36 * i], 36 * sizeof(double));
+    drop_graph(p);      // (huber_a / options are kernel arguments of a captured graph)
+    return SSBA_OK;
+}
+
 int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
     ApiTimer api_timer("ssba_covariance_blocks");
     if (!p || (num && (!blocks || !out))) return SSBA_ERR_INVALID_ARGUMENT;
@@ -2606,6 +2739,7 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
         return SSBA_ERR_UNSUPPORTED;
     }
     int rc;
+    if (p->d.pose_only) return pose_only_covariance(p, blocks, num, out);
     if (p->d.cb && (rc = refinalize_without_closure_border(p, "covariance"))) return rc;
     if (p->d.wide && !p->solved_once && (rc = refinalize_without_wide(p, "covariance"))) return rc;
     Dev &d = p->d;
@@ -2634,7 +2768,7 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
         const ssba_cov_block &b = blocks[q];
         const bool pa = b.kind_a == SSBA_COV_POINT, pb = b.kind_b == SSBA_COV_POINT;
         const int fa = pa ? 0 : p->pose_free[b.index_a], fb = pb ? 0 : p->pose_free[b.index_b];
-        if (fa < 0 || fb < 0 || ((pa || pb) && p->points_const)) continue;      // constant block: zeros
+        if (fa < 0 || fb < 0 || (pa && p->point_is_const(b.index_a)) || (pb && p->point_is_const(b.index_b))) continue;      // constant block: zeros
         CovJob J{};
         J.off = (long long)off[q];
         if (!pa && !pb) {

@@ -208,13 +208,16 @@ constexpr int LMW_SPLIT = 2;
 // DN (landmark-major lists of the general layout instead of window slots): the same split, wave w takes the observations
 // w, w + SP, ... of every landmark's list (r04: 235 four-wave work-groups on 256 CUs at 60 000 landmarks left every SIMD
 // with ONE wave of 24 dependent fp64 chains; 940 work-groups of SP = 4 put 3.7 on it).
-template <bool DN, int SP> __device__ __forceinline__ void lin_landmarks_w_body(const Dev &d, const State &st, int grp, const double *__restrict__ PS,
+// CP: the handle has constant point blocks (Dev::lm_const; windowed layout): the instantiations without them are the kernels
+// as they were, the flag bit is never looked at
+template <bool DN, int SP, bool CP = false> __device__ __forceinline__ void lin_landmarks_w_body(const Dev &d, const State &st, int grp, const double *__restrict__ PS,
                                                      const double *__restrict__ PT, bool commit) {
     __shared__ double sm[SP];
     __shared__ double red[SP > 1 ? SP - 1 : 1][10][LMG];
     const int w = threadIdx.x >> 6, li = threadIdx.x & 63;
     const int l = grp * LMG + li;
-    const uint32_t mask = d.lm_mask[l];
+    const uint32_t mraw = d.lm_mask[l], mask = CP ? mraw & LM_SLOTS : mraw;
+    const bool cst = CP && (mraw & LM_CONST) != 0;       // constant point block: its rows count in the cost only (no columns in J)
     const double px = PT[l], py = PT[(size_t)d.Lpad + l], pz = PT[2 * (size_t)d.Lpad + l];
     if (commit && w == 0) { d.pts[l] = px; d.pts[(size_t)d.Lpad + l] = py; d.pts[2 * (size_t)d.Lpad + l] = pz; }
     double h[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, cost = 0.0;
@@ -296,7 +299,12 @@ template <bool DN, int SP> __device__ __forceinline__ void lin_landmarks_w_body(
             for (int c = 0; c < 3; ++c) g[c] += red[q][6 + c][li];
             cost += red[q][9][li];
         }
-        if (mask) {
+        if (cst) {       // not part of x: zero block and gradient, unit scale, no share in |x|^2 or the gradient max norm
+#pragma unroll
+            for (int c = 0; c < 6; ++c) d.hll[(size_t)c * d.Lpad + l] = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { d.gl[(size_t)c * d.Lpad + l] = 0.0; d.sl[(size_t)c * d.Lpad + l] = 1.0; }
+        } else if (mask) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) d.hll[(size_t)c * d.Lpad + l] = h[c];
 #pragma unroll
@@ -322,17 +330,17 @@ template <bool DN, int SP> __device__ __forceinline__ void lin_landmarks_w_body(
         d.part_lin[grp * 4 + 2] = c2;
     }
 }
-template <bool DN, int SP> __global__ __launch_bounds__(64 * SP) void k_linearize_landmarks_w(Dev d, int fuse) {
+template <bool DN, int SP, bool CP = false> __global__ __launch_bounds__(64 * SP) void k_linearize_landmarks_w(Dev d, int fuse) {
     const State &st = *d.st;
     if (st.terminated || !st.need_linearize) return;
     const bool commit = fuse && st.accepted;
-    lin_landmarks_w_body<DN, SP>(d, st, (int)blockIdx.x, commit ? d.cand_poses : d.poses, commit ? d.cand_pts : d.pts, commit);
+    lin_landmarks_w_body<DN, SP, CP>(d, st, (int)blockIdx.x, commit ? d.cand_poses : d.poses, commit ? d.cand_pts : d.pts, commit);
 }
 // Both linearisation passes of the window layout in ONE launch: the first n_groups work-groups are lin_landmarks_w_body<false,
 // LMW_SPLIT>'s, the others k_linearize_poses<false, 128, 5>'s -- same block shape, neither reads what the other writes (with the
 // commit folded in both read the candidate buffers and write x).  The second pass's ramp fills the first one's tail: 31.1 -> 28.4 us
 // at C2 (0.3458 -> 0.3431 ms per iteration, same bits).
-__global__ __launch_bounds__(LP_THREADS) void k_linearize_both(Dev d, int fuse, int n_groups) {
+template <bool CP> __global__ __launch_bounds__(LP_THREADS) void k_linearize_both(Dev d, int fuse, int n_groups) {
     static_assert(LP_THREADS == 64 * LMW_SPLIT, "one block shape for both passes");
     const State &st = *d.st;
     if (st.terminated || !st.need_linearize) return;
@@ -340,7 +348,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_linearize_both(Dev d, int fuse, 
     const double *PS = commit ? d.cand_poses : d.poses, *PT = commit ? d.cand_pts : d.pts;
     // (the landmark groups first: with the pose work-groups -- the longer ones -- in front the launch measured 10 us SLOWER at C2)
     if ((int)blockIdx.x < n_groups) {
-        lin_landmarks_w_body<false, LMW_SPLIT>(d, st, (int)blockIdx.x, PS, PT, commit);
+        lin_landmarks_w_body<false, LMW_SPLIT, CP>(d, st, (int)blockIdx.x, PS, PT, commit);
         return;
     }
     const int k = xcd_contiguous_item((int)blockIdx.x - n_groups, d.P);
@@ -384,7 +392,7 @@ typedef double schur_d4 __attribute__((ext_vector_type(4)));
 // the Schur items (radius, options and the termination flag apart -- a stale 0 there costs one wasted pass), so the
 // 10 us dependent launch disappears inside this 75 us one.  k_assemble_reduced, which now runs AFTER the iteration
 // counter was advanced, is told so (its `it0`).
-__global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_windows(Dev d, int n_zero, int check_parts) {
+template <bool CP> __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_windows(Dev d, int n_zero, int check_parts) {
     // (r04: the FIRST work-group of the grid, not the last -- at C4 its sums over 15 625 partial entries and 10 000 poses take
     // longer than a Schur item, and as the last work-group it was the launch's tail: +80 us)
     if (check_parts > 0 && blockIdx.x == 0) { check_body(d, check_parts, true); return; }
@@ -460,8 +468,10 @@ __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_windows(Dev d, int n
     // a landmark in every batch -- a quarter of the producer's fp64 instructions, on the pipe the matrix instructions need)
     double lh[6], lsc[3], lg[3];
     const bool lm_lane = t < le - lb;
+    bool lm_cst = false;
     if (lm_lane) {
         const int l = lb + t;
+        if (CP) lm_cst = (d.lm_mask[l] & LM_CONST) != 0;
 #pragma unroll
         for (int c = 0; c < 6; ++c) lh[c] = d.hll[(size_t)c * d.Lpad + l];
 #pragma unroll
@@ -476,7 +486,10 @@ __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_windows(Dev d, int n
             const double s2 = lsc[c] * lsc[c];
             dmp[c] = fmin(fmax(hd[c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag) * fast_rcp(damp_radius(st) * s2);
         }
-        if (!chol3_inv_fast(lh, dmp, m)) {
+        if (CP && lm_cst) {        // constant point block: M = 0, so its Z and M g_l are zero and H_pp keeps its J_p^T J_p (no factorisation: not a failure)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) m[c] = 0.0;
+        } else if (!chol3_inv_fast(lh, dmp, m)) {
             d.st->step_failed = 1;
 #pragma unroll
             for (int c = 0; c < 6; ++c) m[c] = 0.0;
@@ -1028,14 +1041,15 @@ __global__ __launch_bounds__(256) void k_decide(Dev d, int n_eval_parts, int n_p
 // delta_l itself (fixed order, so the SP lanes of a landmark hold identical candidates) and evaluates the candidate
 // cost of its own slots.
 // fuse_best: also does k_best's share for the points (see k_pose_update)
-template <bool DN, int SP> __global__ __launch_bounds__(64 * SP) void k_backsub_eval_w(Dev d, int fuse_best) {
+template <bool DN, int SP, bool CP = false> __global__ __launch_bounds__(64 * SP) void k_backsub_eval_w(Dev d, int fuse_best) {
     const State &st = *d.st;
     __shared__ double sm4[4 * SP];
     __shared__ double red[SP][5][LMG];
     const int w = threadIdx.x >> 6, li = threadIdx.x & 63;
     const int l = blockIdx.x * LMG + li;
     // operand reads first, the solver state (a cold read: see k_schur_windows) is tested with them in flight
-    const uint32_t mask = d.lm_mask[l];
+    const uint32_t mraw = d.lm_mask[l], mask = CP ? mraw & LM_SLOTS : mraw;
+    const bool cst = CP && (mraw & LM_CONST) != 0;       // constant point block: delta_l = 0, the candidate is the point itself
     const double px = d.pts[l], py = d.pts[(size_t)d.Lpad + l], pz = d.pts[2 * (size_t)d.Lpad + l];
     if (fuse_best && st.copy_best == st.check_count) {
         if (w == 0) { d.best_pts[l] = px; d.best_pts[(size_t)d.Lpad + l] = py; d.best_pts[2 * (size_t)d.Lpad + l] = pz; }
@@ -1137,17 +1151,21 @@ template <bool DN, int SP> __global__ __launch_bounds__(64 * SP) void k_backsub_
         double h[6], dmp[3], Ci[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) h[c] = d.hll[(size_t)c * d.Lpad + l];
-        landmark_damping(d, st, l, h, dmp);
         double dl[3] = {0, 0, 0};
-        if (inv3_spd(h, dmp, Ci)) {
-            dl[0] = -(Ci[0] * tt[0] + Ci[1] * tt[1] + Ci[2] * tt[2]);
-            dl[1] = -(Ci[1] * tt[0] + Ci[3] * tt[1] + Ci[4] * tt[2]);
-            dl[2] = -(Ci[2] * tt[0] + Ci[4] * tt[1] + Ci[5] * tt[2]);
-        } else if (w == 0) {
-            nonfinite = 1.0;
+        if (cst) {
+            // (h and g_l are zero: the model cost change below comes out as -er - ee / 2, the rows of the free poses alone)
+        } else {
+            landmark_damping(d, st, l, h, dmp);
+            if (inv3_spd(h, dmp, Ci)) {
+                dl[0] = -(Ci[0] * tt[0] + Ci[1] * tt[1] + Ci[2] * tt[2]);
+                dl[1] = -(Ci[1] * tt[0] + Ci[3] * tt[1] + Ci[4] * tt[2]);
+                dl[2] = -(Ci[2] * tt[0] + Ci[4] * tt[1] + Ci[5] * tt[2]);
+            } else if (w == 0) {
+                nonfinite = 1.0;
+            }
+            if (w == 0 && (!isfinite(dl[0]) || !isfinite(dl[1]) || !isfinite(dl[2]))) nonfinite = 1.0;
+            nx = px + dl[0]; ny = py + dl[1]; nz = pz + dl[2];
         }
-        if (w == 0 && (!isfinite(dl[0]) || !isfinite(dl[1]) || !isfinite(dl[2]))) nonfinite = 1.0;
-        nx = px + dl[0]; ny = py + dl[1]; nz = pz + dl[2];
         if (w == 0) {
             dn = dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2];
             const double hd0 = h[0] * dl[0] + h[1] * dl[1] + h[2] * dl[2], hd1 = h[1] * dl[0] + h[3] * dl[1] + h[4] * dl[2],
@@ -1268,12 +1286,13 @@ __global__ __launch_bounds__(256) void k_dogleg_vec(Dev d) {
 
 // per landmark: Gauss-Newton back-substitution delta_l = -C^-1 (g_l + sum W^T delta_p), v_l, the
 // landmark parts of the norms, and |J v|^2 over the landmark's observations
-template <bool DN> __global__ __launch_bounds__(256) void k_dogleg_gn(Dev d) {
+template <bool DN, bool CP = false> __global__ __launch_bounds__(256) void k_dogleg_gn(Dev d) {
     const State &st = *d.st;
     if (st.terminated || st.dl_reuse) return;
     __shared__ double sm[4];
     const int l = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t mask = d.lm_mask[l];
+    const uint32_t mraw = d.lm_mask[l], mask = CP ? mraw & LM_SLOTS : mraw;
+    const bool cst = CP && (mraw & LM_CONST) != 0;       // constant point block: no entries in gradient_, gn or v; its rows reach |J .|^2 through the poses
     double gsq = 0.0, nsq = 0.0, dot = 0.0, jv2 = 0.0, jg2 = 0.0, jvg = 0.0;
     double dl[3] = {0, 0, 0}, vl[3] = {0, 0, 0};
     if (mask && !st.step_failed) {
@@ -1318,17 +1337,21 @@ template <bool DN> __global__ __launch_bounds__(256) void k_dogleg_gn(Dev d) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) h[c] = d.hll[(size_t)c * d.Lpad + l];
         const double H[6] = {h[0], h[1], h[2], h[3], h[4], h[5]};       // (undamped: inv3_spd may work on h in place)
-        landmark_damping(d, st, l, h, dmp);
-        if (inv3_spd(h, dmp, Ci)) {
-            dl[0] = -(Ci[0] * tt[0] + Ci[1] * tt[1] + Ci[2] * tt[2]);
-            dl[1] = -(Ci[1] * tt[0] + Ci[3] * tt[1] + Ci[4] * tt[2]);
-            dl[2] = -(Ci[2] * tt[0] + Ci[4] * tt[1] + Ci[5] * tt[2]);
-        } else {
-            d.st->step_failed = 1;
+        if (!cst) {
+            landmark_damping(d, st, l, h, dmp);
+            if (inv3_spd(h, dmp, Ci)) {
+                dl[0] = -(Ci[0] * tt[0] + Ci[1] * tt[1] + Ci[2] * tt[2]);
+                dl[1] = -(Ci[1] * tt[0] + Ci[3] * tt[1] + Ci[4] * tt[2]);
+                dl[2] = -(Ci[2] * tt[0] + Ci[4] * tt[1] + Ci[5] * tt[2]);
+            } else {
+                d.st->step_failed = 1;
+            }
         }
         const double hd[3] = {H[0], H[3], H[5]};
+        // (a constant block: dl = vl = 0 and H = 0 leave jv2 = svv, jg2 = see, jvg = sev below; D^2 would clamp to min_lm_diag, not to 0)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
+            if (cst) continue;
             const double s = d.sl[(size_t)c * d.Lpad + l], s2 = s * s;
             const double D2 = fmin(fmax(hd[c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag);
             vl[c] = s2 * gl[c] / D2;
@@ -1535,23 +1558,26 @@ __global__ __launch_bounds__(256) void k_dogleg_interp(Dev d, int from_scal) {
 }
 
 // per landmark: delta_l = beta * gn + gamma * v, candidate point, model cost change, candidate cost
-template <bool DN> __global__ __launch_bounds__(256) void k_dogleg_eval(Dev d) {
+template <bool DN, bool CP = false> __global__ __launch_bounds__(256) void k_dogleg_eval(Dev d) {
     const State &st = *d.st;
     if (st.terminated) return;
     __shared__ double sm[4];
     const int l = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t mask = d.lm_mask[l];
+    const uint32_t mraw = d.lm_mask[l], mask = CP ? mraw & LM_SLOTS : mraw;
+    const bool cst = CP && (mraw & LM_CONST) != 0;       // constant point block: the candidate is the point itself, bit for bit
     double ccost = 0.0, mcc = 0.0, dn = 0.0, nonfinite = 0.0;
     const double px = d.pts[l], py = d.pts[(size_t)d.Lpad + l], pz = d.pts[2 * (size_t)d.Lpad + l];
     double nx = px, ny = py, nz = pz;
     if (mask && !st.step_failed) {
         const LmObs<DN> ob(d, l, mask);
-        double dl[3];
+        if (!cst) {
+            double dl[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) dl[c] = st.beta * d.dl_gn[(size_t)c * d.Lpad + l] + st.gamma * d.vl[(size_t)c * d.Lpad + l];
-        if (!isfinite(dl[0]) || !isfinite(dl[1]) || !isfinite(dl[2])) nonfinite = 1.0;
-        nx = px + dl[0]; ny = py + dl[1]; nz = pz + dl[2];
-        dn = dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2];
+            for (int c = 0; c < 3; ++c) dl[c] = st.beta * d.dl_gn[(size_t)c * d.Lpad + l] + st.gamma * d.vl[(size_t)c * d.Lpad + l];
+            if (!isfinite(dl[0]) || !isfinite(dl[1]) || !isfinite(dl[2])) nonfinite = 1.0;
+            nx = px + dl[0]; ny = py + dl[1]; nz = pz + dl[2];
+            dn = dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2];
+        }
         for (int s = 0; s < ob.count(); ++s) {
             if (!ob.has(s)) continue;
             const uint32_t k = ob.pose(d, s);
@@ -1811,9 +1837,272 @@ void launch_zero_ranges(hipStream_t stream, const ZeroRange *ranges, int n) {
     if (n > 0) hipLaunchKernelGGL(k_zero_ranges, dim3(n), dim3(256), 0, stream, ranges);
 }
 
+// ------------------------------------------------------------------- pose-only ---
+// Every observed point block constant (Dev::pose_only; ssba_finalize): the reduced camera system is block diagonal, one 6 x 6
+// block per free pose, so an LM iteration is k_po_step (linearise + solve + candidate, one work-group per pose) . k_po_eval
+// (candidate cost; its first work-group does k_check's work) . k_decide . k_best.  The layout is the pose-major records
+// (u, v, d, landmark) of Dev::dn_prec with Dev::dn_pose_start, the per-observation stiffness in the same order (POS), and the
+// per-pose lists of unary blocks.  All partials are indexed by POSE (part_lin, part_eval, part_pose: 4 doubles each), sums in
+// fixed order, no atomics.
+constexpr int PO_THREADS = 128, PO_CHUNK = 5;
+
+// the 27 sums of lin_pose_body plus the cost (acc[27]) over the observation records [b, e) of pose block T
+template <bool POS> __device__ __forceinline__ void po_accumulate(const Dev &d, const double *T, uint32_t b, uint32_t e, double acc[28]) {
+    double Sk[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Sk[c] = d.S[c];
+    const double *__restrict__ PT = d.pts;
+    for (uint32_t i0 = b + threadIdx.x; i0 < e; i0 += PO_THREADS * PO_CHUNK) {
+        double4 rec[PO_CHUNK];
+        double pt[PO_CHUNK][3];
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q)
+            if (i0 + PO_THREADS * q < e) rec[q] = reinterpret_cast<const double4 *>(d.dn_prec)[i0 + PO_THREADS * q];
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q) {
+            if (i0 + PO_THREADS * q >= e) continue;
+            const size_t l = (size_t)__double_as_longlong(rec[q].w);
+            pt[q][0] = PT[l]; pt[q][1] = PT[(size_t)d.Lpad + l]; pt[q][2] = PT[2 * (size_t)d.Lpad + l];
+        }
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q) {
+            if (i0 + PO_THREADS * q >= e) continue;
+            if (POS) {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) Sk[c] = d.dn_Sobs[(size_t)(i0 + PO_THREADS * q) * 9 + c];
+            }
+            ObsLin o;
+            obs_linearize_S(d, Sk, T, pt[q][0], pt[q][1], pt[q][2], rec[q].x, rec[q].y, rec[q].z, o);
+            pose_normal_terms(o, acc);
+            acc[27] += o.half_rho;
+        }
+    }
+}
+
+// 6 x 6 Cholesky of the packed upper triangle A (tri21 order), then x = -A^-1 g; false on a non-positive or non-finite pivot
+__device__ __forceinline__ bool po_solve6(const double A[21], const double g[6], double x[6]) {
+    double Lw[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double v = A[tri21(j, j)];
+#pragma unroll
+        for (int q = 0; q < j; ++q) v -= Lw[j][q] * Lw[j][q];
+        if (!(v > 0.0) || !isfinite(v)) return false;
+        const double piv = sqrt(v), ip = 1.0 / piv;
+        Lw[j][j] = piv;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double w = A[tri21(j, i)];
+#pragma unroll
+            for (int q = 0; q < j; ++q) w -= Lw[i][q] * Lw[j][q];
+            Lw[i][j] = w * ip;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double v = -g[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) v -= Lw[i][q] * y[q];
+        y[i] = v / Lw[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; ++q) v -= Lw[q][i] * x[q];
+        x[i] = v / Lw[i][i];
+    }
+    return true;
+}
+
+// One work-group per pose (constant poses with residual blocks included: their blocks only add to the cost).  The iterate is
+// read from the candidate buffers when the last decision accepted its step, and this pose is committed on the way (as
+// lin_pose_body does on the windowed path).  The linearisation is repeated after a rejected step (same point, same sums):
+// the step then only differs by the radius.
+// PF: the handle has unary pose blocks (their evaluation indexes its Jacobian dynamically: 304 B of scratch per lane, as in
+// k_linearize_poses; the instantiation without them has none)
+template <bool POS, bool PF> __global__ __launch_bounds__(PO_THREADS) void k_po_step(Dev d) {
+    const State &st = *d.st;
+    const int k = xcd_contiguous_item((int)blockIdx.x, d.P);
+    if (k < 0) return;
+    const uint32_t b = d.dn_pose_start[k], e = d.dn_pose_start[k + 1];
+    const uint32_t f0 = PF ? d.pf_start[k] : 0u, f1 = PF ? d.pf_start[k + 1] : 0u;
+    const int f = d.pose_free[k];
+    if (st.terminated || (b == e && f0 == f1)) return;
+    const bool commit = st.accepted != 0 && f >= 0;
+    const double *PS = commit ? d.cand_poses : d.poses;
+    __shared__ double sm[PO_THREADS / 64][28];
+    __shared__ double tot[28];
+    double T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = PS[(size_t)k * 12 + i];
+    double acc[28];
+#pragma unroll
+    for (int i = 0; i < 28; ++i) acc[i] = 0.0;
+    po_accumulate<POS>(d, T, b, e, acc);
+#pragma unroll
+    for (int i = 0; i < 28; ++i) {
+        const double v = wave_sum(acc[i]);
+        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 28) {
+        double v = 0.0;
+#pragma unroll
+        for (int w = 0; w < PO_THREADS / 64; ++w) v += sm[w][threadIdx.x];
+        // unary residual blocks of this pose (prior, sun sensor, the half of a relative-pose block whose other pose is constant):
+        // every one of the 28 lanes evaluates them and takes its own entry, as in lin_pose_body
+        int a = 0, c = 0;
+        if (threadIdx.x < 21) { int n = threadIdx.x; while (n >= 6 - a) { n -= 6 - a; ++a; } c = a + n; }
+        for (uint32_t q = f0; PF && q < f1; ++q) {
+            double r[6], J[36];
+            int dim;
+            const int other = pf_other_pose(d, (int)q);
+            const double cost = pf_evaluate(d, (int)q, T, other >= 0 ? d.poses + (size_t)other * 12 : nullptr, r, J, &dim);
+            if (threadIdx.x < 21) { for (int m = 0; m < dim; ++m) v += J[6 * m + a] * J[6 * m + c]; }
+            else if (threadIdx.x < 27) { for (int m = 0; m < dim; ++m) v += J[6 * m + (threadIdx.x - 21)] * r[m]; }
+            else if (pf_counts_cost(d, (int)q)) v += cost;
+        }
+        tot[threadIdx.x] = v;
+    }
+    if (commit && threadIdx.x >= 64 && threadIdx.x < 76) d.poses[(size_t)k * 12 + threadIdx.x - 64] = T[threadIdx.x - 64];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    d.part_lin[(size_t)k * 4] = tot[27];        // (entries 1, 2 -- the landmark shares of |x|^2 and of the gradient norm -- stay zero)
+    if (f < 0) return;
+    double H[21], g[6], A[21];
+#pragma unroll
+    for (int i = 0; i < 21; ++i) { H[i] = tot[i]; A[i] = tot[i]; d.hpp[(size_t)k * 21 + i] = tot[i]; }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { g[i] = tot[21 + i]; d.gp[(size_t)k * 6 + i] = tot[21 + i]; }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {       // Jacobi scale at iteration 0, LM damping in unscaled coordinates (as k_assemble_reduced)
+        const double h = H[tri21(c, c)];
+        double sc;
+        if (st.iteration == 0) { sc = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(h)) : 1.0; d.sp[(size_t)f * 6 + c] = sc; }
+        else sc = d.sp[(size_t)f * 6 + c];
+        const double s2 = sc * sc;
+        A[tri21(c, c)] += fmin(fmax(h * s2, st.opt.min_lm_diag), st.opt.max_lm_diag) / (damp_radius(st) * s2);
+    }
+    double dx[6] = {0, 0, 0, 0, 0, 0}, Tn[12], mcc = 0.0, dn = 0.0, nonfinite = 0.0;
+    bool ok = po_solve6(A, g, dx);
+    if (ok) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) if (!isfinite(dx[c])) nonfinite = 1.0;
+        se3_plus(T, dx, Tn);
+        double dg = 0.0, dHd = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            double hd = 0.0;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) hd += H[tri21(r < c ? r : c, r < c ? c : r)] * dx[c];
+            dHd += dx[r] * hd;
+            dg += dx[r] * g[r];
+        }
+        mcc = -dg - 0.5 * dHd;
+#pragma unroll
+        for (int c = 0; c < 12; ++c) { const double df = Tn[c] - T[c]; dn += df * df; }
+    } else {
+        d.st->step_failed = 1;      // LINEAR_SOLVER_FAILURE
+#pragma unroll
+        for (int c = 0; c < 12; ++c) Tn[c] = T[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 12; ++c) d.cand_poses[(size_t)k * 12 + c] = Tn[c];
+    double *pp = d.part_pose + (size_t)k * 4;
+    pp[0] = mcc; pp[1] = dn; pp[2] = nonfinite;
+    // this pose's share of the gradient max norm |x - Plus(x, -g)|_inf and of |x|^2 (check_body's arithmetic)
+    double ng[6], Tg[12], gm = 0.0, xn = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) ng[c] = -g[c];
+    se3_plus(T, ng, Tg);
+#pragma unroll
+    for (int c = 0; c < 12; ++c) { gm = fmax(gm, fabs(T[c] - Tg[c])); xn += T[c] * T[c]; }
+    d.part_chk[2 * f] = gm;
+    d.part_chk[2 * f + 1] = xn;
+}
+
+// Candidate cost, pose-major; work-group 0 does k_check's work (check_body reads what k_po_step left, nothing it writes is read
+// here beyond the termination flag, where a stale 0 costs one wasted pass).  part_eval[k] = (cost, model cost change, |dx|^2,
+// non-finite) of pose k: the shape k_decide reduces.
+template <bool POS> __global__ __launch_bounds__(PO_THREADS) void k_po_eval(Dev d) {
+    if (blockIdx.x == 0) { check_body(d, d.P, false); return; }
+    const State &st = *d.st;
+    const int k = xcd_contiguous_item((int)blockIdx.x - 1, d.P);
+    if (k < 0) return;
+    const uint32_t b = d.dn_pose_start[k], e = d.dn_pose_start[k + 1];
+    const uint32_t f0 = d.n_pf ? d.pf_start[k] : 0u, f1 = d.n_pf ? d.pf_start[k + 1] : 0u;
+    if (st.terminated || (b == e && f0 == f1)) return;
+    __shared__ double sm[PO_THREADS / 64];
+    double T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = d.cand_poses[(size_t)k * 12 + i];
+    double Sk[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Sk[c] = d.S[c];
+    double cc = 0.0;
+    for (uint32_t i0 = b + threadIdx.x; i0 < e; i0 += PO_THREADS * PO_CHUNK) {
+        double4 rec[PO_CHUNK];
+        double pt[PO_CHUNK][3];
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q)
+            if (i0 + PO_THREADS * q < e) rec[q] = reinterpret_cast<const double4 *>(d.dn_prec)[i0 + PO_THREADS * q];
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q) {
+            if (i0 + PO_THREADS * q >= e) continue;
+            const size_t l = (size_t)__double_as_longlong(rec[q].w);
+            pt[q][0] = d.pts[l]; pt[q][1] = d.pts[(size_t)d.Lpad + l]; pt[q][2] = d.pts[2 * (size_t)d.Lpad + l];
+        }
+#pragma unroll
+        for (int q = 0; q < PO_CHUNK; ++q) {
+            if (i0 + PO_THREADS * q >= e) continue;
+            if (POS) {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) Sk[c] = d.dn_Sobs[(size_t)(i0 + PO_THREADS * q) * 9 + c];
+            }
+            cc += obs_cost_S(d, Sk, T, pt[q][0], pt[q][1], pt[q][2], rec[q].x, rec[q].y, rec[q].z);
+        }
+    }
+    cc = wave_sum(cc);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < PO_THREADS / 64; ++w) v += sm[w];
+    for (uint32_t q = f0; q < f1; ++q) {
+        if (!pf_counts_cost(d, (int)q)) continue;
+        double r[6];
+        int dim;
+        const int other = pf_other_pose(d, (int)q);
+        v += pf_evaluate(d, (int)q, T, other >= 0 ? d.cand_poses + (size_t)other * 12 : nullptr, r, nullptr, &dim);
+    }
+    const double *pp = d.part_pose + (size_t)k * 4;
+    const bool fr = d.pose_free[k] >= 0;
+    reinterpret_cast<double4 *>(d.part_eval)[k] = make_double4(v, fr ? pp[0] : 0.0, fr ? pp[1] : 0.0, fr ? pp[2] : 0.0);
+}
+
+// covariance on a pose-only handle: the inverse of the undamped 6 x 6 block of free pose poses[j] (Dev::hpp, left by k_po_step)
+__global__ __launch_bounds__(64) void k_po_cov(Dev d, const int *__restrict__ poses, int n, double *__restrict__ out, int *fail) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    const int k = poses[j];
+    double A[21];
+#pragma unroll
+    for (int i = 0; i < 21; ++i) A[i] = d.hpp[(size_t)k * 21 + i];
+    for (int c = 0; c < 6; ++c) {
+        double g[6] = {0, 0, 0, 0, 0, 0}, x[6];
+        g[c] = -1.0;
+        if (!po_solve6(A, g, x)) { *fail = 1; return; }
+        for (int r = 0; r < 6; ++r) out[(size_t)j * 36 + 6 * r + c] = x[r];
+    }
+}
+
 // ----------------------------------------------------------------- launchers ---
 int configure_schur() {
-    return hipFuncSetAttribute((const void *)k_schur_windows, hipFuncAttributeMaxDynamicSharedMemorySize, SCHUR_LDS_BYTES) == hipSuccess ? 0 : -1;
+    return hipFuncSetAttribute((const void *)k_schur_windows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SCHUR_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute((const void *)k_schur_windows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SCHUR_LDS_BYTES) == hipSuccess ? 0 : -1;
 }
 
 void launch_reset(Launcher &L, const Dev &d, const Options &o) {
@@ -1853,11 +2142,11 @@ void launch_linearize(Launcher &L, const Dev &d, bool fuse_ctrl, bool fuse_all, 
         launch_ph_linearize(L, d);
     } else {
         if (lm_split(d) && lm_sp(d) == LMW_SPLIT) {
-            LAUNCH(KC_LIN_LM, k_linearize_both, dim3(d.n_groups + xcd_contiguous_grid(d.P)), dim3(LP_THREADS), 0, d, fuse_all ? 1 : 0, d.n_groups);
+            LAUNCH(KC_LIN_LM, (d.lm_const ? k_linearize_both<true> : k_linearize_both<false>), dim3(d.n_groups + xcd_contiguous_grid(d.P)), dim3(LP_THREADS), 0, d, fuse_all ? 1 : 0, d.n_groups);
             if (!fuse_ctrl && !skip_reduce) LAUNCH(KC_SMALL, k_reduce_lin, dim3(1), dim3(256), 0, d, lm_parts(d));
             return;
         }
-        if (lm_split(d)) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
+        if (lm_split(d)) LAUNCH(KC_LIN_LM, (d.lm_const ? k_linearize_landmarks_w<false, 1, true> : k_linearize_landmarks_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
         else if (dn_sp(d) == 4) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 4>), dim3(d.n_groups), dim3(256), 0, d, fuse_all ? 1 : 0);
         else if (dn_sp(d) == 2) LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 2>), dim3(d.n_groups), dim3(128), 0, d, fuse_all ? 1 : 0);
         else LAUNCH(KC_LIN_LM, (k_linearize_landmarks_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, fuse_all ? 1 : 0);
@@ -1874,7 +2163,7 @@ void launch_schur(Launcher &L, const Dev &d, bool fuse_ctrl, bool check_in_schur
     // the reduced system is cleared on the way: by 128 extra workgroups of the stereo Schur launch, by k_ph_invert with lighting terms
     const int n_zero = 128;
     if (d.phong) launch_ph_schur(L, d, check_in_schur);
-    else LAUNCH(KC_SCHUR, k_schur_windows, dim3(d.n_slabs + n_zero + (check_in_schur ? 1 : 0)), dim3(SCHUR_THREADS), SCHUR_LDS_BYTES, d, n_zero, check_in_schur ? d.n_groups : 0);
+    else LAUNCH(KC_SCHUR, (d.lm_const ? k_schur_windows<true> : k_schur_windows<false>), dim3(d.n_slabs + n_zero + (check_in_schur ? 1 : 0)), dim3(SCHUR_THREADS), SCHUR_LDS_BYTES, d, n_zero, check_in_schur ? d.n_groups : 0);
     const size_t n = (size_t)d.n_sblk * 36 + (size_t)(fuse_ctrl ? d.nf_pad : d.nfree) * 6 + (fuse_ctrl ? (size_t)d.nfree : 0);
     LAUNCH(KC_ASSEMBLE, k_assemble_reduced, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d, fuse_ctrl ? 1 : 0, check_in_schur ? 1 : 0);
     if (d.cb) LAUNCH(KC_BORDER, k_cb_assemble, dim3((unsigned)(((size_t)d.n_cb * 36 + 255) / 256)), dim3(256), 0, d);
@@ -1903,8 +2192,8 @@ void launch_update_eval(Launcher &L, const Dev &d, bool fuse_reduce, bool fuse_b
     const int fb = fuse_best && best_fusable(d) ? 1 : 0;
     if (!pose_update_done) LAUNCH(KC_SMALL, k_pose_update, dim3(d.n_pose_blocks + border_block(d)), dim3(256), 0, d, fb);
     if (d.phong) launch_ph_backsub_eval(L, d, fb, !pose_update_done);
-    else if (lm_split(d) && lm_sp(d) == LMW_SPLIT) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<false, LMW_SPLIT>), dim3(d.n_groups), dim3(64 * LMW_SPLIT), 0, d, pose_update_done ? 2 : fb);
-    else if (lm_split(d)) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
+    else if (lm_split(d) && lm_sp(d) == LMW_SPLIT) LAUNCH(KC_BACKSUB_EVAL, (d.lm_const ? k_backsub_eval_w<false, LMW_SPLIT, true> : k_backsub_eval_w<false, LMW_SPLIT>), dim3(d.n_groups), dim3(64 * LMW_SPLIT), 0, d, pose_update_done ? 2 : fb);
+    else if (lm_split(d)) LAUNCH(KC_BACKSUB_EVAL, (d.lm_const ? k_backsub_eval_w<false, 1, true> : k_backsub_eval_w<false, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
     else if (dn_sp(d) == 4) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 4>), dim3(d.n_groups), dim3(256), 0, d, pose_update_done ? 2 : fb);
     else if (dn_sp(d) == 2) LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 2>), dim3(d.n_groups), dim3(128), 0, d, pose_update_done ? 2 : fb);
     else LAUNCH(KC_BACKSUB_EVAL, (k_backsub_eval_w<true, 1>), dim3(d.n_groups), dim3(64), 0, d, pose_update_done ? 2 : fb);
@@ -1939,7 +2228,7 @@ void launch_dogleg_eval(Launcher &L, const Dev &d, int stage, int own_poses, boo
     if (stage != 2) {
         LAUNCH(KC_SMALL, k_dogleg_vec, dim3(d.n_pose_blocks + border_block(d)), dim3(256), 0, d);
         if (d.phong) launch_ph_dogleg_gn(L, d);
-        else LAUNCH(KC_DOGLEG, (d.dense ? k_dogleg_gn<true> : k_dogleg_gn<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
+        else LAUNCH(KC_DOGLEG, (d.dense ? k_dogleg_gn<true> : d.lm_const ? k_dogleg_gn<false, true> : k_dogleg_gn<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
     }
     if (stage == 1) {
         LAUNCH(KC_SMALL, k_dogleg_sum, dim3(1), dim3(256), 0, d, own_poses);
@@ -1948,7 +2237,7 @@ void launch_dogleg_eval(Launcher &L, const Dev &d, int stage, int own_poses, boo
     LAUNCH(KC_SMALL, k_dogleg_interp, dim3(1), dim3(256), 0, d, stage == 2 ? 1 : 0);
     LAUNCH(KC_SMALL, k_pose_update, dim3(d.n_pose_blocks + border_block(d)), dim3(256), 0, d, 0);
     if (d.phong) launch_ph_dogleg_eval(L, d);
-    else LAUNCH(KC_DOGLEG, (d.dense ? k_dogleg_eval<true> : k_dogleg_eval<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
+    else LAUNCH(KC_DOGLEG, (d.dense ? k_dogleg_eval<true> : d.lm_const ? k_dogleg_eval<false, true> : k_dogleg_eval<false>), dim3(d.n_lm_blocks), dim3(256), 0, d);
     if (!reduce_later) LAUNCH(KC_SMALL, k_reduce_eval, dim3(1), dim3(256), 0, d, d.n_lm_blocks, 0);
 }
 
@@ -1958,6 +2247,27 @@ void launch_decide_commit(Launcher &L, const Dev &d, bool fuse_reduce, bool fuse
     if (fuse_all) return;       // the next linearisation commits (launch_linearize)
     const size_t n = (size_t)d.P * 12 > (size_t)d.Lpad * 3 ? (size_t)d.P * 12 : (size_t)d.Lpad * 3;
     LAUNCH(KC_COPY, k_commit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d, with_best ? 1 : 0);
+}
+
+// pose-only layout: the four launches of an LM iteration
+void launch_pose_only_step(Launcher &L, const Dev &d);
+void launch_pose_only(Launcher &L, const Dev &d) {
+    const int grid = xcd_contiguous_grid(d.P);
+    launch_pose_only_step(L, d);
+    if (d.dn_Sobs) LAUNCH(KC_BACKSUB_EVAL, k_po_eval<true>, dim3(grid + 1), dim3(PO_THREADS), 0, d);
+    else LAUNCH(KC_BACKSUB_EVAL, k_po_eval<false>, dim3(grid + 1), dim3(PO_THREADS), 0, d);
+    LAUNCH(KC_SMALL, k_decide, dim3(1), dim3(256), 0, d, d.P, 0);
+    const size_t n = (size_t)d.P * 12 > (size_t)d.Lpad * 3 ? (size_t)d.P * 12 : (size_t)d.Lpad * 3;
+    LAUNCH(KC_COPY, k_best, dim3((unsigned)std::min<size_t>((n + 255) / 256, 512)), dim3(256), 0, d);
+}
+// the linearisation alone (covariance: Dev::hpp at the current poses)
+void launch_pose_only_step(Launcher &L, const Dev &d) {
+    const int grid = xcd_contiguous_grid(d.P);
+    if (d.dn_Sobs) LAUNCH(KC_LIN_POSE, (d.n_pf ? k_po_step<true, true> : k_po_step<true, false>), dim3(grid), dim3(PO_THREADS), 0, d);
+    else LAUNCH(KC_LIN_POSE, (d.n_pf ? k_po_step<false, true> : k_po_step<false, false>), dim3(grid), dim3(PO_THREADS), 0, d);
+}
+void launch_pose_only_cov(Launcher &L, const Dev &d, const int *poses, int n, double *out, int *fail) {
+    LAUNCH(KC_SMALL, k_po_cov, dim3((n + 63) / 64), dim3(64), 0, d, poses, n, out, fail);
 }
 
 }  // namespace ssba

@@ -127,6 +127,10 @@ void launch_mask_unowned_poses(Launcher &L, const Dev &d, double *poses);
 int eval_parts(const Dev &d);      // partial sums the evaluation kernel of this layout leaves
 void launch_update_eval(Launcher &L, const Dev &d, bool fuse_reduce = false, bool fuse_best = false, bool pose_update_done = false);
 void launch_dogleg_eval(Launcher &L, const Dev &d, int stage = 0, int own_poses = 1, bool reduce_later = false);     // reduce_later: launch_ph_ls_fast forms the evaluation sums;      // stage: see ssba_kernels.hip (landmark sharding: one more exchange point)
+// pose-only layout (every observed point block constant; ssba_kernels.hip): k_po_step . k_po_eval (+ k_check's work) . k_decide . k_best
+void launch_pose_only(Launcher &L, const Dev &d);
+void launch_pose_only_step(Launcher &L, const Dev &d);
+void launch_pose_only_cov(Launcher &L, const Dev &d, const int *poses, int n, double *out, int *fail);
 void launch_decide_commit(Launcher &L, const Dev &d, bool fuse_reduce = false, bool fuse_all = false, int n_pose_parts = -1, bool with_best = false);
 // config 3 (ssba_phong_solver.hip)
 int upload_phong_tables(hipStream_t s);

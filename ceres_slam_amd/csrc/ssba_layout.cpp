@@ -161,8 +161,52 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
             max_span = std::max(max_span, a.max_span);
         }
     }
-    if (in.points_const && !ph) {
-        set_error("constant position blocks are only available with lighting terms (stage 2 of --multistage)");
+    // Constant point blocks of a stereo problem: a flag per landmark of the windowed layout (LM_CONST in lm_mask).  With lighting
+    // terms only "every position block" exists (Dev::pos_const, stage 2 of --multistage).
+    const bool all_const = in.points_const && !ph;
+    bool any_const = all_const;
+    if (in.point_const && !in.point_const->empty())
+        for (uint32_t j = 0; j < L && !any_const; ++j) any_const = (*in.point_const)[j] != 0 && lm_start[j + 1] > lm_start[j];
+    if (any_const && ph) {
+        set_error("constant point blocks with lighting terms: only all of them (ssba_set_point_blocks_constant), not a subset");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    // Pose-only layout: with every observed point constant the reduced camera system is block diagonal (one 6 x 6 block per free
+    // pose), so track length, co-visibility span, repeated (pose, landmark) pairs and per-block stiffness do not matter and none
+    // of the structures below is needed.  SSBA_NO_POSE_ONLY=1 (A/B) or a hand-over (DOGLEG, test hooks) keeps the layouts below.
+    bool pose_only = any_const && !ph && in.world_size == 1 && !in.partitioned && !in.no_pose_only && N > 0;
+    if (pose_only) { const char *e = getenv("SSBA_NO_POSE_ONLY"); if (e && e[0] == '1') pose_only = false; }
+    for (uint32_t j = 0; j < L && pose_only && !all_const; ++j)
+        if (lm_start[j + 1] > lm_start[j] && !(*in.point_const)[j]) pose_only = false;
+    for (auto &rf : in.rel_factors)
+        if (out.pose_free[rf.pose1] >= 0 && out.pose_free[rf.pose2] >= 0) pose_only = false;
+    if (pose_only) {
+        const uint32_t Lact = (uint32_t)order.size();
+        const uint32_t Lpad = std::max<uint32_t>(256, (Lact + 255) / 256 * 256);
+        out.user_of_dev.assign(Lpad, 0xFFFFFFFFu);
+        std::vector<uint32_t> dev_of(L, 0xFFFFFFFFu);
+        for (uint32_t l = 0; l < Lact; ++l) { out.user_of_dev[l] = order[l].j; dev_of[order[l].j] = l; }
+        out.dn_pose_start.assign(P + 1, 0);
+        for (uint32_t k = 0; k < P; ++k) out.dn_pose_start[k + 1] = out.dn_pose_start[k] + pose_cnt[k];
+        std::vector<uint32_t> at(out.dn_pose_start.begin(), out.dn_pose_start.end() - 1);
+        out.dn_prec.resize(4 * (size_t)N);
+        if (in.per_obs_S) out.dn_Sobs.resize(9 * (size_t)N);
+        for (uint64_t i = 0; i < N; ++i) {
+            const size_t q = at[in.obs_pose[i]]++;
+            const int64_t lm = (int64_t)dev_of[in.obs_point[i]];
+            out.dn_prec[4 * q] = in.obs_uvd[3 * i]; out.dn_prec[4 * q + 1] = in.obs_uvd[3 * i + 1]; out.dn_prec[4 * q + 2] = in.obs_uvd[3 * i + 2];
+            memcpy(&out.dn_prec[4 * q + 3], &lm, 8);
+            if (in.per_obs_S) memcpy(&out.dn_Sobs[9 * q], &in.obs_S[9 * i], 9 * sizeof(double));
+        }
+        out.pfs = std::move(pfs);
+        out.nfree = nfree; out.nchain = nfree; out.nborder = 0;
+        out.pose_only = true;
+        out.Lact = Lact; out.Lpad = Lpad; out.n_groups = Lpad / LMG;
+        phase.mark("finalize: pose-only records");
+        return SSBA_OK;
+    }
+    if (any_const && (in.world_size > 1 || in.partitioned)) {
+        set_error("constant point blocks are not available with landmark sharding or ssba_set_partition");
         return SSBA_ERR_UNSUPPORTED;
     }
     if (const char *e = getenv("SSBA_FORCE_DENSE")) if (e[0] == '1') dense = dense_only = true;
@@ -243,6 +287,15 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
     if (wide_sys && in.partitioned) {
         set_error("ssba_set_partition: the partitioned reduced solve is built for the windowed layout (tracks <= SSBA_MAX_TRACK); long tracks "
                   "shard with the all-reduce of the reduced system (no partition)");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    if (any_const && nborder) {
+        set_error("constant point blocks are not available on a handle with a closure border (a loop closure folded into a border of the chain)");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    if (any_const && dense) {
+        set_error(wide_sys ? "constant point blocks are not available on the wide (long-track) layout: tracks of at most SSBA_MAX_TRACK observations only"
+                           : "constant point blocks are not available on the general (blocked Cholesky) layout: the windowed layout only");
         return SSBA_ERR_UNSUPPORTED;
     }
     if (dense && wide_sys) {
@@ -692,10 +745,13 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
         cb_start.push_back((uint32_t)cb_contrib.size());
     }
 
+    if (any_const)      // (after the block structure above, which compares slot masks)
+        for (uint32_t l = 0; l < Lact; ++l)
+            if (all_const || (*in.point_const)[order[l].j]) lm_mask[l] |= LM_CONST;
     phase.mark("finalize: 6 block structure");
     out.pfs = std::move(pfs);
     out.nfree = nfree; out.nchain = nchain; out.nborder = nborder;
-    out.dense = dense; out.wide_sys = wide_sys;
+    out.dense = dense; out.wide_sys = wide_sys; out.lm_const = any_const;
     out.Lact = Lact; out.Lpad = Lpad; out.n_groups = n_groups; out.n_windows = n_windows; out.n_slabs = n_slabs; out.n_sblk = n_sblk;
     out.bandwidth = bandwidth;
 #define MV(x) out.x = std::move(x)

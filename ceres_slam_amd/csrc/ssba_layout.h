@@ -61,6 +61,10 @@ struct LayoutInput {
     int world_size;
     bool partitioned;                   // ssba_set_partition with more than one rank
     bool no_closure_border, no_wide;
+    // stereo problems: point blocks held constant, one flag per point (null or empty: none); points_const without lighting
+    // terms means every point
+    const std::vector<uint8_t> *point_const = nullptr;
+    bool no_pose_only = false;          // keep a problem whose observed points are all constant off the pose-only layout (hand-over, A/B)
 };
 
 struct Layout {
@@ -69,6 +73,11 @@ struct Layout {
     std::vector<PoseFactor> pfs;                // unary blocks incl. the halves of the relative-pose blocks
     int nfree = 0, nchain = 0, nborder = 0;
     bool dense = false, wide_sys = false;
+    // pose-only layout (every observed point block constant, one GPU, no lighting terms, no relative-pose block between two free
+    // poses): only user_of_dev, the pose-major records dn_pose_start / dn_prec (u, v, d, device landmark as integer bits; the
+    // caller's order inside a pose), dn_Sobs in the same order when the blocks carry their own stiffness, and pfs are built
+    bool pose_only = false;
+    bool lm_const = false;                      // some landmark carries LM_CONST in lm_mask (constant point blocks of a stereo problem)
     uint32_t Lact = 0, Lpad = 0, n_groups = 0, n_windows = 0, n_slabs = 0, n_sblk = 0, bandwidth = 0;
     // windowed layout
     std::vector<uint32_t> win_pose, lm_win, lm_mask, lm_mat, pose_obs_start, pose_mat_start;

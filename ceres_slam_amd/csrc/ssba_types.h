@@ -33,6 +33,9 @@ constexpr int NPAIR = TW * (TW + 1) / 2;  // 78 pose pairs (sa <= sb) per window
 constexpr int SBP = 12;                 // poses per super-block of the reduced system
 constexpr int BD = 6 * SBP;             // 72 rows per super-block
 constexpr int LMG = 64;                 // landmarks per ELL group (= wavefront)
+// Dev::lm_mask of the windowed layout: bits 0..TW-1 mark the occupied slots, bit 31 a point block the caller holds constant
+// (stereo problems: ssba_set_point_constant).  Kernels that branch on "has observations" test the slot bits only.
+constexpr uint32_t LM_CONST = 0x80000000u, LM_SLOTS = 0x7FFFFFFFu;
 constexpr int SLAB_DOUBLES = NPAIR * 36 + TW * 6;   // per Schur work item
 constexpr int MAX_LEVELS = 18;          // plain levels below a parallel top of <= 128 blocks: 2^17 x 128 super-blocks
 constexpr int MAX_SLEVELS = 1;          // the separator system of a partitioned (multi-rank) solve: one level, parallel cyclic reduction
@@ -298,6 +301,8 @@ struct Dev {
     // unary pose residual blocks (pose prior, sun sensor), sorted by pose
     int pf_owner;                                   // landmark sharding: this rank adds the unary blocks to the sums that are exchanged (H_pp, g_p, cost); every rank evaluates them at the candidate
     int n_pf, pos_const;                            // pos_const: every position block constant (--multistage stage 2; lighting problems)
+    int pose_only;                                  // every observed point block constant: pose-major records (dn_pose_start, dn_prec, dn_Sobs in the same order), one 6 x 6 system per pose
+    int lm_const;                                   // stereo problem with constant point blocks: LM_CONST is set in lm_mask (windowed layout), the kernels that look at it run
     const uint32_t *pf_start;                       // P+1
     const int *pf_type;                             // F
     const double *pf_data, *pf_S, *pf_huber;        // F*18, F*36, F

@@ -251,7 +251,7 @@ typedef struct {
     uint32_t num_reduced_blocks;   /* non-zero 6x6 blocks of S (upper incl. diagonal)   */
     uint32_t pose_bandwidth;       /* max free-pose index distance of co-observers      */
     uint64_t device_bytes;         /* device memory held by the handle                  */
-    uint32_t general_structure;    /* 1: tracks > SSBA_MAX_TRACK or span > 12 poses -> dense reduced system; 2: windowed layout + closure border */
+    uint32_t general_structure;    /* 1: tracks > SSBA_MAX_TRACK or span > 12 poses -> dense reduced system; 2: windowed layout + closure border; 3: pose-only layout (every observed point block constant: one 6x6 system per pose, no Schur or reduction launches) */
     uint32_t pcr_blocks;           /* blocks handed to the parallel cyclic reduction (<= 128), 0 = plain BCR */
     uint32_t pcr_fused;            /* 1: one launch per step of that reduction (no border columns, single GPU; SSBA_NO_PCR_FUSED=1 in the environment of a solve keeps factor + reduce launches) */
     uint32_t wide_superblocks;     /* > 0: general layout whose tracks have 13..24 observations (free poses within a span of 24): the reduced system is block tridiagonal over this many super-blocks of 24 poses (144 rows), solved by parallel cyclic reduction (general_structure stays 1; SSBA_NO_WIDE=1 at ssba_finalize keeps the blocked Cholesky) */
@@ -403,9 +403,30 @@ SSBA_API int ssba_phong_evaluate(int device, int light_type, uint64_t n, const d
                         double *J_nrm_n);
 
 /* replaces: problem.SetParameterBlockConstant(map_vertices[j].position().data()) on EVERY position block (stage 2 of
- * --multistage, tests/dataset_ba_phong.cpp:210-228; SetParameterBlockVariable afterwards = 0).  Lighting problems only:
- * the landmark block is then the normal alone.  Before ssba_finalize. */
+ * --multistage, tests/dataset_ba_phong.cpp:210-228; SetParameterBlockVariable afterwards = 0).  With lighting terms the
+ * landmark block is then the normal alone.  On a stereo problem (no lighting terms) it means "every point", as if
+ * ssba_set_point_constant had named them all: localisation against a fixed map.  Before ssba_finalize. */
 SSBA_API int ssba_set_point_blocks_constant(ssba_problem *p, int is_constant);
+
+/* replaces: problem.SetParameterBlockConstant(point) / SetParameterBlockVariable(point) on the listed position blocks of a
+ * stereo problem (anchored or surveyed landmarks, map points of a marginalised window).  As in Ceres a constant point is not
+ * part of x: no Jacobian columns, no Jacobi scale, no damping, no share in the step / parameter norms or the gradient max
+ * norm; its residual blocks still count in the cost (also those on a constant pose); its coordinates come back bit-unchanged;
+ * ssba_lm_step / ssba_dogleg_step report a zero step for it, ssba_evaluate zero H_ll / g_l, ssba_covariance_blocks zeros for
+ * every block that touches it (the pose blocks are those of the inverse of the reduced system, to which a constant point adds
+ * J_p^T J_p only).  Before ssba_finalize; an index >= the number of points: SSBA_ERR_INVALID_ARGUMENT.
+ * Some points constant: windowed layout, one GPU.  ssba_finalize answers SSBA_ERR_UNSUPPORTED (ssba_last_error says which) for
+ * a subset of the points with lighting terms, with landmark sharding or ssba_set_partition, on a handle with a closure border,
+ * and on the wide (long-track) and blocked-Cholesky layouts.
+ * EVERY point that has a residual block constant (one GPU, no lighting terms, no relative-pose block between two free poses):
+ * the handle takes the pose-only layout, ssba_stats.general_structure = 3 -- pose-major observation records, one 6x6 system
+ * per free pose, four launches per Levenberg-Marquardt iteration; track length, co-visibility span, repeated (pose, point)
+ * pairs and per-block stiffness do not matter.  The covariance calls give the inverse of a pose's undamped 6x6 block
+ * (SSBA_ERR_NUMERICAL_FAILURE when it is singular) and zeros elsewhere.  A DOGLEG solve and the test hooks (evaluate, LM
+ * step, dogleg step) run the symbolic phase again onto the windowed layout before the first solve begins:
+ * SSBA_ERR_UNSUPPORTED when the structure does not fit it, SSBA_ERR_STATE once a solve has begun.  SSBA_NO_POSE_ONLY=1 in
+ * the environment of ssba_finalize selects the windowed layout from the start. */
+SSBA_API int ssba_set_point_constant(ssba_problem *p, const uint32_t *points, uint64_t num, int is_constant);
 
 /* ---- unary pose residual blocks (tests/dataset_vo_sun.cpp:80-124) ------- */
 /* ssba_add_pose_prior replaces problem.AddResidualBlock(PoseErrorAutomatic::Create(T_k_0_ref, stiffness), loss,

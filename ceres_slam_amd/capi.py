@@ -38,6 +38,7 @@ SYMBOLS = [
     "ssba_set_partition", "ssba_ransac_samples", "ssba_frontend_ransac", "ssba_add_pose_prior", "ssba_add_sun_observation", "ssba_add_relative_pose",
     "ssba_pose_covariance", "ssba_rccl_unique_id", "ssba_set_rccl", "ssba_frontend_vo",
     "ssba_rccl_describe", "ssba_rccl_ranks", "ssba_armijo_trace", "ssba_debug_stamps", "ssba_covariance_blocks",
+    "ssba_add_image_blocks", "ssba_set_disparity_blocks_constant", "ssba_image_step",
 ]
 
 
@@ -66,6 +67,7 @@ class CovBlock(C.Structure):
 
 
 LEVENBERG_MARQUARDT, DOGLEG = 0, 1
+IMAGE_NEAREST, IMAGE_BILINEAR = 0, 1     # SSBA_IMAGE_NEAREST / SSBA_IMAGE_BILINEAR
 
 
 class Summary(C.Structure):
@@ -165,6 +167,9 @@ def load():
     L.ssba_add_relative_pose.argtypes = [H, C.c_uint32, C.c_uint32, _dp, _dp, C.c_double]
     L.ssba_pose_covariance.argtypes = [H, C.c_uint32, _dp]
     L.ssba_covariance_blocks.argtypes = [H, C.POINTER(CovBlock), C.c_uint64, _dp]
+    L.ssba_add_image_blocks.argtypes = [H, _dp, _dp, _dp, _dp, _dp, _dp, C.c_uint32, C.c_uint32, C.c_int]
+    L.ssba_set_disparity_blocks_constant.argtypes = [H, C.c_int]
+    L.ssba_image_step.argtypes = [H, C.POINTER(Options), C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     L.ssba_ransac_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_int, _u32p]
     L.ssba_frontend_ransac.argtypes = [C.POINTER(Camera), C.c_int, C.c_uint32, _u32p, _dp, _dp, _u32p, C.c_uint32, C.c_double, _dp,
                                        C.POINTER(C.c_uint8), _u32p, _dp]

@@ -88,6 +88,14 @@ struct ssba_problem {
     std::vector<double> ph_intensity, ph_nobs;
     double ph_int_stiff = 0.0, ph_Sn[9] = {0};
     bool lighting() const { return !ph_intensity.empty(); }
+    // dense photometric alignment (ssba_add_image_blocks): one pose (user_poses, P = 1), one ImageError block per pixel of the
+    // caller's disparity map; the four images are read at ssba_finalize
+    bool image = false, disp_const = false;
+    double *user_disp = nullptr;
+    const double *img_ref = nullptr, *img_track = nullptr, *img_gradx = nullptr, *img_grady = nullptr;
+    uint32_t img_rows = 0, img_cols = 0;
+    int img_interp = 0;
+    std::vector<uint32_t> img_blk;         // pixel of every block (ssba_finalize)
     // host structure
     std::vector<int> pose_free, free_pose;
     std::vector<uint32_t> user_of_dev;   // Lpad -> user landmark or 0xFFFFFFFF
@@ -412,7 +420,52 @@ int ssba_release_cached_memory(void) {
     return SSBA_OK;
 }
 
+// An image handle (ssba_add_image_blocks) holds one pose, its disparity blocks and nothing else, on one GPU
+static int refuse_on_image(const ssba_problem *p, const char *what) {
+    if (!p || !p->image) return SSBA_OK;
+    set_error(std::string(what) + ": not available on a handle with image blocks (ssba_add_image_blocks holds one pose, one "
+              "disparity block per pixel and nothing else, on one GPU, Levenberg-Marquardt only)");
+    return SSBA_ERR_UNSUPPORTED;
+}
+
+// replaces the loop of tests/dense_stereo_test.cpp:101-117: ImageError::Create + AddResidualBlock(cost, NULL, pose, &disparity[v][u])
+// for every pixel with a finite positive disparity, and SetParameterization(pose, SE3Perturbation)
+int ssba_add_image_blocks(ssba_problem *p, double *pose, double *disparity, const double *ref_img, const double *track_img,
+                          const double *track_gradx, const double *track_grady, uint32_t rows, uint32_t cols, int interpolation) {
+    if (!p || !pose || !disparity || !ref_img || !track_img || !track_gradx || !track_grady || rows == 0 || cols == 0) return SSBA_ERR_INVALID_ARGUMENT;
+    if (interpolation != SSBA_IMAGE_NEAREST && interpolation != SSBA_IMAGE_BILINEAR) {
+        set_error("ssba_add_image_blocks: unknown interpolation");
+        return SSBA_ERR_INVALID_ARGUMENT;
+    }
+    if (p->finalized) return SSBA_ERR_STATE;
+    if (p->image) { set_error("ssba_add_image_blocks: a second call (one tracked frame per handle)"); return SSBA_ERR_UNSUPPORTED; }
+    if (p->P || p->L || !p->obs_pose.empty() || p->num_normals || p->M || p->user_light || !p->pose_factors.empty() || !p->rel_factors.empty() ||
+        !p->ph_intensity.empty() || p->world_size > 1 || !p->sep_sb.empty() || p->xfn || p->huber_a > 0.0) {
+        set_error("ssba_add_image_blocks: the handle already holds pose, point, stereo, lighting or pose-factor blocks, a loss or a sharding "
+                  "(an image handle holds nothing else, on one GPU)");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    if ((uint64_t)rows * cols >= (1ull << 31)) { set_error("image too large for the 32-bit pixel references of this build"); return SSBA_ERR_UNSUPPORTED; }
+    p->image = true;
+    p->user_poses = pose; p->P = 1;
+    p->pose_const.assign(1, 0);
+    p->user_disp = disparity;
+    p->img_ref = ref_img; p->img_track = track_img; p->img_gradx = track_gradx; p->img_grady = track_grady;
+    p->img_rows = rows; p->img_cols = cols; p->img_interp = interpolation;
+    return SSBA_OK;
+}
+
+// replaces: problem.SetParameterBlockConstant / SetParameterBlockVariable on every disparity block
+int ssba_set_disparity_blocks_constant(ssba_problem *p, int is_constant) {
+    if (!p) return SSBA_ERR_INVALID_ARGUMENT;
+    if (!p->image) { set_error("ssba_set_disparity_blocks_constant: the handle has no image blocks"); return SSBA_ERR_STATE; }
+    if (p->finalized) return SSBA_ERR_STATE;   // the kernels are instantiated per case
+    p->disp_const = is_constant != 0;
+    return SSBA_OK;
+}
+
 int ssba_add_pose_blocks(ssba_problem *p, double *poses, uint32_t num) {
+    if (int irc = refuse_on_image(p, "ssba_add_pose_blocks")) return irc;
     if (!p || (!poses && num)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->user_poses = poses;
@@ -422,6 +475,7 @@ int ssba_add_pose_blocks(ssba_problem *p, double *poses, uint32_t num) {
 }
 
 int ssba_add_point_blocks(ssba_problem *p, double *points, uint32_t num) {
+    if (int irc = refuse_on_image(p, "ssba_add_point_blocks")) return irc;
     if (!p || (!points && num)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->user_points = points;
@@ -432,6 +486,7 @@ int ssba_add_point_blocks(ssba_problem *p, double *points, uint32_t num) {
 
 int ssba_add_stereo_observations(ssba_problem *p, const uint32_t *pose_index, const uint32_t *point_index,
                                  const double *uvd, uint64_t num, const double stiffness[9]) {
+    if (int irc = refuse_on_image(p, "ssba_add_stereo_observations")) return irc;
     if (!p || !stiffness || (num && (!pose_index || !point_index || !uvd))) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     for (int c = 0; c < 9; ++c)
@@ -462,6 +517,7 @@ int ssba_add_stereo_observations(ssba_problem *p, const uint32_t *pose_index, co
 }
 
 int ssba_add_normal_blocks(ssba_problem *p, double *normals, uint32_t num) {
+    if (int irc = refuse_on_image(p, "ssba_add_normal_blocks")) return irc;
     if (!p || (!normals && num)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->user_normals = normals;
@@ -471,6 +527,7 @@ int ssba_add_normal_blocks(ssba_problem *p, double *normals, uint32_t num) {
 
 int ssba_add_material_blocks(ssba_problem *p, double *phong, double *texture, uint32_t num_materials,
                              const uint32_t *material_of_point, uint32_t num_points) {
+    if (int irc = refuse_on_image(p, "ssba_add_material_blocks")) return irc;
     if (!p || !phong || !texture || !material_of_point || num_materials == 0) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     if (num_materials > SSBA_MAX_MATERIALS) {
@@ -487,6 +544,7 @@ int ssba_add_material_blocks(ssba_problem *p, double *phong, double *texture, ui
 }
 
 int ssba_add_light_block(ssba_problem *p, double *light, int light_type) {
+    if (int irc = refuse_on_image(p, "ssba_add_light_block")) return irc;
     if (!p || !light || (light_type != 0 && light_type != 1)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->user_light = light;
@@ -495,6 +553,7 @@ int ssba_add_light_block(ssba_problem *p, double *light, int light_type) {
 }
 
 int ssba_set_shared_block_constant(ssba_problem *p, int which, int is_constant) {
+    if (int irc = refuse_on_image(p, "ssba_set_shared_block_constant")) return irc;
     if (!p || which < 0 || which > 2) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;   // the border of the reduced system depends on it
     if (is_constant) p->shared_const |= (1u << which);
@@ -503,6 +562,7 @@ int ssba_set_shared_block_constant(ssba_problem *p, int which, int is_constant) 
 }
 
 int ssba_add_pose_prior(ssba_problem *p, uint32_t pose, const double T_ref[12], const double stiffness[36], double huber_a) {
+    if (int irc = refuse_on_image(p, "ssba_add_pose_prior")) return irc;
     if (!p || !T_ref || !stiffness || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     PoseFactor f{};
@@ -515,6 +575,7 @@ int ssba_add_pose_prior(ssba_problem *p, uint32_t pose, const double T_ref[12], 
 
 int ssba_add_relative_pose(ssba_problem *p, uint32_t pose1, uint32_t pose2, const double T_2_1_ref[12], const double stiffness[36],
                            double huber_a) {
+    if (int irc = refuse_on_image(p, "ssba_add_relative_pose")) return irc;
     if (!p || !T_2_1_ref || !stiffness || pose1 >= p->P || pose2 >= p->P || pose1 == pose2) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     RelFactor f{};
@@ -527,6 +588,7 @@ int ssba_add_relative_pose(ssba_problem *p, uint32_t pose1, uint32_t pose2, cons
 
 int ssba_add_sun_observation(ssba_problem *p, uint32_t pose, const double observed_dir_c[3], const double expected_dir_g[3],
                              const double stiffness[4], double az_err_thresh, double zen_err_thresh, double huber_a) {
+    if (int irc = refuse_on_image(p, "ssba_add_sun_observation")) return irc;
     if (!p || !observed_dir_c || !expected_dir_g || !stiffness || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     PoseFactor f{};
@@ -540,6 +602,7 @@ int ssba_add_sun_observation(ssba_problem *p, uint32_t pose, const double observ
 }
 
 int ssba_set_shared_block_bounds(ssba_problem *p, int which, int index, double lower, double upper) {
+    if (int irc = refuse_on_image(p, "ssba_set_shared_block_bounds")) return irc;
     if (!p || (which != SSBA_BLOCK_PHONG && which != SSBA_BLOCK_TEXTURE) || !(lower <= upper)) return SSBA_ERR_INVALID_ARGUMENT;
     if ((which == SSBA_BLOCK_PHONG && (index < 0 || index > 2)) || (which == SSBA_BLOCK_TEXTURE && index != 0))
         return SSBA_ERR_INVALID_ARGUMENT;
@@ -552,6 +615,7 @@ int ssba_set_shared_block_bounds(ssba_problem *p, int which, int index, double l
 
 int ssba_add_lighting_observations(ssba_problem *p, const double *intensity, double intensity_stiffness,
                                    const double *normal_obs, const double normal_stiffness[9], uint64_t num) {
+    if (int irc = refuse_on_image(p, "ssba_add_lighting_observations")) return irc;
     if (!p || !normal_stiffness || (num && (!intensity || !normal_obs))) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     if (!p->ph_intensity.empty() &&
@@ -572,6 +636,7 @@ int ssba_add_lighting_observations(ssba_problem *p, const double *intensity, dou
 }
 
 int ssba_set_pose_constant(ssba_problem *p, uint32_t pose, int is_constant) {
+    if (int irc = refuse_on_image(p, "ssba_set_pose_constant")) return irc;
     if (!p || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;   // the reduced-system structure depends on it
     p->pose_const[pose] = is_constant ? 1 : 0;
@@ -579,6 +644,7 @@ int ssba_set_pose_constant(ssba_problem *p, uint32_t pose, int is_constant) {
 }
 
 int ssba_set_point_blocks_constant(ssba_problem *p, int is_constant) {
+    if (int irc = refuse_on_image(p, "ssba_set_point_blocks_constant")) return irc;
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->points_const = is_constant != 0;
@@ -586,6 +652,7 @@ int ssba_set_point_blocks_constant(ssba_problem *p, int is_constant) {
 }
 
 int ssba_set_point_constant(ssba_problem *p, const uint32_t *points, uint64_t num, int is_constant) {
+    if (int irc = refuse_on_image(p, "ssba_set_point_constant")) return irc;
     if (!p || (num && !points)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;   // the flags live in the layout's landmark masks
     for (uint64_t i = 0; i < num; ++i)
@@ -596,6 +663,7 @@ int ssba_set_point_constant(ssba_problem *p, const uint32_t *points, uint64_t nu
 }
 
 int ssba_set_huber_loss(ssba_problem *p, double a) {
+    if (int irc = refuse_on_image(p, "ssba_set_huber_loss")) return irc;
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     p->huber_a = a > 0.0 ? a : 0.0;
     if (p->finalized) { p->d.huber_a = p->huber_a; drop_graph(p); }   // kernel arguments are baked into the graph
@@ -756,6 +824,7 @@ int ssba_rccl_unique_id(void *out, uint64_t size) {
 }
 
 int ssba_set_rccl(ssba_problem *p, const void *unique_id, uint64_t size) {
+    if (int irc = refuse_on_image(p, "ssba_set_rccl")) return irc;
     if (!p || !unique_id || size < sizeof(ncclUniqueId)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->began) return SSBA_ERR_STATE;
     RcclApi *a = rccl_api();
@@ -794,12 +863,14 @@ int ssba_rccl_ranks(ssba_problem *p, int *count) {
 
 int ssba_set_exchange(ssba_problem *p, ssba_exchange_fn fn, void *ctx) {
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
+    if (fn) if (int irc = refuse_on_image(p, "ssba_set_exchange")) return irc;
     p->xfn = fn;
     p->xctx = ctx;
     return SSBA_OK;
 }
 
 int ssba_set_distributed(ssba_problem *p, int world_size, int rank) {
+    if (int irc = refuse_on_image(p, "ssba_set_distributed")) return irc;
     if (!p || world_size < 1 || rank < 0 || rank >= world_size) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     p->world_size = world_size;
@@ -808,6 +879,7 @@ int ssba_set_distributed(ssba_problem *p, int world_size, int rank) {
 }
 
 int ssba_set_partition(ssba_problem *p, const uint32_t *separator_superblocks, uint32_t num) {
+    if (int irc = refuse_on_image(p, "ssba_set_partition")) return irc;
     if (!p || (num && !separator_superblocks)) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_ERR_STATE;
     if (num == 0) { p->sep_sb.clear(); return SSBA_OK; }
@@ -847,10 +919,80 @@ int ssba_get_stats(ssba_problem *p, ssba_stats *st) {
 // ---------------------------------------------------------------------------------
 // symbolic phase
 // ---------------------------------------------------------------------------------
+// Image handle (ssba_add_image_blocks): the compacted list of block pixels, the four images, and of Dev what the control kernels
+// (k_reset_state, check_body, k_decide, k_best) and the stepwise calls use: one free pose, the disparity map in the point
+// buffers (rows * cols <= 3 * Lpad doubles, so k_best and ssba_solve_restart cover it), one evaluation partial per work-group
+// in n_groups, the scalars of the exchange vector.
+static int finalize_image(ssba_problem *p) {
+    HIPCHECK(hipSetDevice(p->device));
+    const size_t npix = (size_t)p->img_rows * p->img_cols;
+    p->img_blk.clear();
+    for (size_t i = 0; i < npix; ++i) {
+        const double dd = p->user_disp[i];
+        if (std::isfinite(dd) && dd > 0.0) p->img_blk.push_back((uint32_t)i);       // dense_stereo_test.cpp:105
+    }
+    if (p->img_blk.empty()) { set_error("ssba_finalize: no pixel of the disparity map is finite and positive (no residual block)"); return SSBA_ERR_INVALID_ARGUMENT; }
+    free_device(p);
+    Dev &d = p->d;
+    d = Dev{};
+    ImageSys &im = p->launcher.image;
+    im = ImageSys{};
+    p->log_capacity = 0;
+    d.fu = p->cam.fu; d.fv = p->cam.fv; d.cu = p->cam.cu; d.cv = p->cam.cv; d.b = p->cam.b;
+    p->pose_free.assign(1, 0);
+    p->free_pose.assign(1, 0);
+    p->user_of_dev.clear();
+    d.P = 1; d.nfree = 1; d.nchain = 1; d.Nsb = 1; d.nf_pad = SBP;
+    const size_t Lpad = (npix + 3 * 256 - 1) / (3 * 256) * 256;       // 3 * Lpad >= rows * cols
+    d.Lpad = (int)Lpad; d.n_lm_blocks = (int)(Lpad / 256); d.n_pose_blocks = 1;
+    im.rows = (int)p->img_rows; im.cols = (int)p->img_cols; im.interp = p->img_interp; im.disp_const = p->disp_const ? 1 : 0;
+    im.n_blk = (uint32_t)p->img_blk.size();
+    im.n_wg = (int)((p->img_blk.size() + IM_THREADS - 1) / IM_THREADS);
+    d.n_groups = im.n_wg;       // what k_decide sums of part_eval (launch_decide_commit)
+    d.n_obs = im.n_blk;
+    d.pcr.level = -1;
+    int rc;
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    p->defer_zero = true;
+    TRY(dzero(p, &d.poses, 12)); TRY(dzero(p, &d.cand_poses, 12)); TRY(dzero(p, &d.best_poses, 12)); TRY(dzero(p, &d.init_poses, 12));
+    TRY(dzero(p, &d.pts, Lpad * 3)); TRY(dzero(p, &d.cand_pts, Lpad * 3)); TRY(dzero(p, &d.best_pts, Lpad * 3)); TRY(dzero(p, &d.init_pts, Lpad * 3));
+    TRY(dupload(p, &d.pose_free, p->pose_free)); TRY(dupload(p, &d.free_pose, p->free_pose));
+    TRY(dzero(p, &d.hpp, 21)); TRY(dzero(p, &d.gp, 6)); TRY(dzero(p, &d.sp, (size_t)d.nf_pad * 6));
+    d.off_scal = 0; d.xv_count = NSCAL;
+    TRY(dzero(p, &d.xv, d.xv_count));
+    TRY(dzero(p, &d.part_lin, (size_t)im.n_wg * 4)); TRY(dzero(p, &d.part_eval, (size_t)im.n_wg * 4));
+    TRY(dzero(p, &d.part_chk, 2)); TRY(dzero(p, &d.part_pose, 2 * NPP));
+    TRY(dzero(p, &d.scal2, (size_t)NSCAL)); TRY(dzero(p, &d.scal_dl, (size_t)NSCAL)); TRY(dzero(p, &d.gmax_l, 1));
+    TRY(dzero(p, &d.st, 1)); TRY(dzero(p, &d.dbg, 8192));
+    TRY(dupload(p, &im.blk_pix, p->img_blk));
+    const double *imgs[4] = {p->img_ref, p->img_track, p->img_gradx, p->img_grady};
+    const double **dst[4] = {&im.ref, &im.track, &im.gradx, &im.grady};
+    for (int q = 0; q < 4; ++q) TRY(dupload(p, dst[q], std::vector<double>(imgs[q], imgs[q] + npix)));
+    TRY(dzero(p, &im.row, (size_t)IM_ROW * im.n_blk)); TRY(dzero(p, &im.sd, (size_t)im.n_blk));
+    TRY(dzero(p, &im.part, (size_t)im.n_wg * IM_REC)); TRY(dzero(p, &im.sys, (size_t)IM_SYS));
+    TRY(dupload(p, &d.image, std::vector<ImageSys>(1, im)));
+    HIPCHECK(pool_host_malloc((void **)&p->h_state, sizeof(State)));
+    HIPCHECK(pool_host_malloc((void **)&p->h_ls, NLS_OUT * sizeof(double)));
+    p->h_stage_count = Lpad * 3;
+    HIPCHECK(pool_host_malloc((void **)&p->h_stage, p->h_stage_count * sizeof(double)));
+    TRY(flush_zero(p));
+#undef TRY
+    stage_release(p);
+    p->stats = ssba_stats{};
+    p->stats.num_poses = 1; p->stats.num_free_poses = 1;
+    p->stats.num_points = (uint32_t)npix; p->stats.num_active_points = im.n_blk;
+    p->stats.num_observations = im.n_blk;
+    p->stats.num_superblocks = 1;
+    p->stats.general_structure = 4;     // image blocks
+    p->finalized = true;
+    return SSBA_OK;
+}
+
 int ssba_finalize(ssba_problem *p) {
     ApiTimer api_timer("ssba_finalize");
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     if (p->finalized) return SSBA_OK;
+    if (p->image) return finalize_image(p);
     if (!p->have_S && !p->obs_pose.empty()) return SSBA_ERR_INVALID_ARGUMENT;
     HIPCHECK(hipSetDevice(p->device));
     const uint32_t P = p->P, L = p->L;
@@ -1325,6 +1467,15 @@ int ssba_finalize(ssba_problem *p) {
 static int upload_params(ssba_problem *p) {
     Dev &d = p->d;
     hipStream_t s = p->launcher.stream;
+    if (p->image) {     // the pose and the whole disparity map (pixels without a block ride along unread)
+        const size_t npix = (size_t)p->img_rows * p->img_cols;
+        memcpy(p->h_stage, p->user_disp, npix * sizeof(double));
+        std::fill(p->h_stage + npix, p->h_stage + p->h_stage_count, 0.0);
+        HIPCHECK(hipMemcpyAsync(d.poses, p->user_poses, 12 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(d.pts, p->h_stage, p->h_stage_count * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        return SSBA_OK;
+    }
     if (p->P) HIPCHECK(hipMemcpyAsync(d.poses, p->user_poses, (size_t)p->P * 12 * sizeof(double), hipMemcpyHostToDevice, s));
     double *st = p->h_stage;
     const size_t Lp = (size_t)d.Lpad;
@@ -1362,6 +1513,14 @@ static int download_params(ssba_problem *p, const double *dev_poses, const doubl
     Dev &d = p->d;
     hipStream_t s = p->launcher.stream;
     const size_t Lp = (size_t)d.Lpad;
+    if (p->image) {     // free disparities of the block pixels only: constant ones and pixels without a block keep the caller's bits
+        HIPCHECK(hipMemcpyAsync(p->h_stage, dev_pts, Lp * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(p->user_poses, dev_poses, 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        if (!p->disp_const)
+            for (uint32_t pix : p->img_blk) p->user_disp[pix] = p->h_stage[pix];
+        return SSBA_OK;
+    }
     HIPCHECK(hipMemcpyAsync(p->h_stage, dev_pts, Lp * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     for (size_t l = 0; l < Lp; ++l) {
@@ -1507,6 +1666,12 @@ static bool fuse_all_launches(const ssba_problem *p) {
 }
 
 static int enqueue_kernels(ssba_problem *p) {
+    if (p->image) {       // k_im_lin . k_im_solve . k_im_eval . k_decide . k_best
+        launch_image(p->launcher, p->d);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return SSBA_ERR_HIP; }
+        return SSBA_OK;
+    }
     if (p->d.pose_only) {       // k_po_step . k_po_eval . k_decide . k_best
         launch_pose_only(p->launcher, p->d);
         hipError_t e = hipGetLastError();
@@ -1761,6 +1926,7 @@ int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_converge
         return SSBA_ERR_UNSUPPORTED;
     }
     if (o->dogleg_type != 0 && o->dogleg_type != 1) return SSBA_ERR_INVALID_ARGUMENT;
+    if (o->trust_region_strategy_type == 1) if (int irc = refuse_on_image(p, "DOGLEG")) return irc;
     p->step_hook_done = false;
     if (o->trust_region_strategy_type == 1 && p->d.pose_only) {
         int rc = refinalize_without_pose_only(p, "DOGLEG");
@@ -2138,6 +2304,7 @@ static int begin_hook(ssba_problem *p, const ssba_options *o, double radius) {
 }
 
 int ssba_evaluate(ssba_problem *p, double *cost, double *g_p, double *g_l, double *H_pp, double *H_ll) {
+    if (int irc = refuse_on_image(p, "ssba_evaluate")) return irc;
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     int rc = begin_hook(p, nullptr, 0.0);
     if (rc) return rc;
@@ -2244,6 +2411,7 @@ int ssba_armijo_trace(const double *values, const double *gradients, int32_t n, 
 
 int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius, double *S, double *rhs,
                  double *delta_p, double *delta_l, double *model_cost_change) {
+    if (int irc = refuse_on_image(p, "ssba_lm_step")) return irc;
     if (!p || !(radius > 0.0)) return SSBA_ERR_INVALID_ARGUMENT;
     int rc = begin_hook(p, o, radius);
     if (rc) return rc;
@@ -2358,6 +2526,7 @@ int ssba_lm_step(ssba_problem *p, const ssba_options *o, double radius, double *
 // radius 1 / mu, reduced solve with the border, launch_dogleg_eval stage 0), then the vectors and the scalar state copied out.
 int ssba_dogleg_step(ssba_problem *p, const ssba_options *o, double radius, double mu, double *gn_p, double *gn_l, double *gn_b,
                      double *v_p, double *v_l, double *v_b, double *scalars) {
+    if (int irc = refuse_on_image(p, "ssba_dogleg_step")) return irc;
     if (!p || !(radius > 0.0) || !(mu > 0.0)) return SSBA_ERR_INVALID_ARGUMENT;
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
     ssba_options opt;
@@ -2534,10 +2703,103 @@ static int wide_cov_sweep(ssba_problem *p, const int *free_pose, int nq, double 
 // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block (tests/dataset_vo_sun.cpp:159-183):
 // the pose's 6x6 block of (J^T J)^-1 in local coordinates = the same block of the inverse of the (undamped) reduced
 // camera system.  Six unit right-hand sides go through the block-cyclic-reduction factors of S.
+// Image handle, one linearisation at the caller's current pose and disparities.  The hook returns what the kernels of an
+// iteration left; the covariance inverts the undamped 6 x 6 sum J^T J (constant disparities only).
+static int image_begin(ssba_problem *p, const ssba_options *o, double radius) {
+    if (p->began) return SSBA_ERR_STATE;
+    HIPCHECK(hipSetDevice(p->device));
+    ssba_options opt;
+    if (o) opt = *o; else ssba_default_options(&opt);
+    if (radius > 0.0) opt.initial_trust_region_radius = radius;
+    opt.trust_region_strategy_type = 0;
+    p->opt = opt;
+    p->ignore_convergence = 1;
+    int rc = ensure_log(p, 16);
+    if (rc) return rc;
+    if ((rc = upload_params(p))) return rc;
+    hipStream_t s = p->launcher.stream;
+    HIPCHECK(hipMemcpyAsync(p->d.init_poses, p->d.poses, 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(hipMemcpyAsync(p->d.init_pts, p->d.pts, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return reset_solver(p);
+}
+
+static int image_pose_covariance(ssba_problem *p, double cov[36]) {
+    if (!p->disp_const) {
+        set_error("covariance with free disparity blocks: the Jacobian has more columns than rows, J^T J is singular (Ceres: covariance computation failed)");
+        return SSBA_ERR_NUMERICAL_FAILURE;
+    }
+    int rc = image_begin(p, nullptr, 0.0);
+    if (rc) return rc;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    launch_image_lin_solve(L, d);
+    CallBuffers B;
+    int *d_pose = nullptr, *d_fail = nullptr;
+    double *d_out = nullptr;
+    HIPCHECK(B.get((void **)&d_pose, sizeof(int)));
+    HIPCHECK(B.get((void **)&d_fail, sizeof(int)));
+    HIPCHECK(B.get((void **)&d_out, 36 * sizeof(double)));
+    HIPCHECK(hipMemsetAsync(d_pose, 0, sizeof(int), L.stream));
+    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), L.stream));
+    HIPCHECK(hipMemsetAsync(d_out, 0, 36 * sizeof(double), L.stream));
+    launch_pose_only_cov(L, d, d_pose, 1, d_out, d_fail);     // inverts Dev::hpp of pose 0
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    int fail = 0;
+    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
+    if (fail) { set_error("covariance: the sum J^T J of the image blocks is not positive definite"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    HIPCHECK(hipMemcpy(cov, d_out, 36 * sizeof(double), hipMemcpyDeviceToHost));
+    return SSBA_OK;
+}
+
+int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose, double *J_disp,
+                    double *S, double *rhs, double *delta_pose, double *delta_disp, double *model_cost_change) {
+    if (!p || !(radius > 0.0)) return SSBA_ERR_INVALID_ARGUMENT;
+    if (!p->image) { set_error("ssba_image_step: the handle has no image blocks"); return SSBA_ERR_UNSUPPORTED; }
+    if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    int rc = image_begin(p, o, radius);
+    if (rc) return rc;
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    const ImageSys &im = L.image;
+    const size_t nb = im.n_blk, npix = (size_t)im.rows * im.cols;
+    CallBuffers B;
+    double *d_dd = nullptr;
+    HIPCHECK(B.get((void **)&d_dd, nb * sizeof(double)));
+    HIPCHECK(hipMemsetAsync(d_dd, 0, nb * sizeof(double), L.stream));
+    launch_image(L, d, d_dd);
+    HIPCHECK(hipStreamSynchronize(L.stream));
+    HIPCHECK(hipGetLastError());
+    rc = fetch_state(p);
+    if (rc) return rc;
+    if (cost) *cost = p->h_state->x_cost;
+    if (model_cost_change) *model_cost_change = p->h_state->model_cost_change;
+    std::vector<double> row((size_t)IM_ROW * nb), dd(nb), sys(IM_SYS);
+    HIPCHECK(hipMemcpy(row.data(), im.row, row.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(dd.data(), d_dd, nb * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(sys.data(), im.sys, sys.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (residuals) std::fill(residuals, residuals + npix, 0.0);
+    if (J_pose) std::fill(J_pose, J_pose + 6 * npix, 0.0);
+    if (J_disp) std::fill(J_disp, J_disp + npix, 0.0);
+    if (delta_disp) std::fill(delta_disp, delta_disp + npix, 0.0);
+    for (size_t i = 0; i < nb; ++i) {
+        const size_t pix = p->img_blk[i];
+        if (residuals) residuals[pix] = row[7 * nb + i];
+        if (J_disp) J_disp[pix] = row[6 * nb + i];
+        if (J_pose) for (int c = 0; c < 6; ++c) J_pose[6 * pix + c] = row[(size_t)c * nb + i];
+        if (delta_disp) delta_disp[pix] = dd[i];
+    }
+    if (S) memcpy(S, sys.data(), 36 * sizeof(double));
+    if (rhs) memcpy(rhs, sys.data() + 36, 6 * sizeof(double));
+    if (delta_pose) memcpy(delta_pose, sys.data() + 42, 6 * sizeof(double));
+    return SSBA_OK;
+}
+
 int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     ApiTimer api_timer("ssba_pose_covariance");
     if (!p || !cov || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
+    if (p->image) return image_pose_covariance(p, cov);
     if (p->d.pose_only) {
         if (p->pose_free[pose] < 0) { set_error("covariance of a constant pose"); return SSBA_ERR_INVALID_ARGUMENT; }
         const ssba_cov_block b{SSBA_COV_POSE, pose, SSBA_COV_POSE, pose};
@@ -2704,6 +2966,7 @@ static int pose_only_covariance(ssba_problem *p, const ssba_cov_block *blocks, u
 
 int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
     ApiTimer api_timer("ssba_covariance_blocks");
+    if (int irc = refuse_on_image(p, "ssba_covariance_blocks")) return irc;
     if (!p || (num && (!blocks || !out))) return SSBA_ERR_INVALID_ARGUMENT;
     if (!p->finalized) return SSBA_ERR_NOT_FINALIZED;
     bool any_point = false;

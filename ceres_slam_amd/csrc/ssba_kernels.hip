@@ -30,6 +30,7 @@
 #include "ssba_device.h"
 #include "ssba_posefactor_device.h"
 #include "ssba_check.h"
+#include "ssba_solve6.h"
 
 namespace ssba {
 
@@ -579,10 +580,6 @@ template <bool CP> __global__ __launch_bounds__(SCHUR_THREADS, 2) void k_schur_w
     store_tile(acc1, ti1, tj1);
     store_tile(acc2, ti2, tj2);
     if (has3) store_tile(acc3, ti3, tj3);
-}
-
-__device__ __forceinline__ int tri21(int r, int c) {   // packed upper index, r <= c
-    return r * 6 - (r * (r - 1)) / 2 + (c - r);
 }
 
 // Gathers the slabs into the block-tridiagonal reduced system (pure stores, fixed
@@ -1879,43 +1876,6 @@ template <bool POS> __device__ __forceinline__ void po_accumulate(const Dev &d, 
     }
 }
 
-// 6 x 6 Cholesky of the packed upper triangle A (tri21 order), then x = -A^-1 g; false on a non-positive or non-finite pivot
-__device__ __forceinline__ bool po_solve6(const double A[21], const double g[6], double x[6]) {
-    double Lw[6][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double v = A[tri21(j, j)];
-#pragma unroll
-        for (int q = 0; q < j; ++q) v -= Lw[j][q] * Lw[j][q];
-        if (!(v > 0.0) || !isfinite(v)) return false;
-        const double piv = sqrt(v), ip = 1.0 / piv;
-        Lw[j][j] = piv;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double w = A[tri21(j, i)];
-#pragma unroll
-            for (int q = 0; q < j; ++q) w -= Lw[i][q] * Lw[j][q];
-            Lw[i][j] = w * ip;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) v -= Lw[i][q] * y[q];
-        y[i] = v / Lw[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 6; ++q) v -= Lw[q][i] * x[q];
-        x[i] = v / Lw[i][i];
-    }
-    return true;
-}
-
 // One work-group per pose (constant poses with residual blocks included: their blocks only add to the cost).  The iterate is
 // read from the candidate buffers when the last decision accepted its step, and this pose is committed on the way (as
 // lin_pose_body does on the windowed path).  The linearisation is repeated after a rejected step (same point, same sums):
@@ -2268,6 +2228,11 @@ void launch_pose_only_step(Launcher &L, const Dev &d) {
 }
 void launch_pose_only_cov(Launcher &L, const Dev &d, const int *poses, int n, double *out, int *fail) {
     LAUNCH(KC_SMALL, k_po_cov, dim3((n + 63) / 64), dim3(64), 0, d, poses, n, out, fail);
+}
+// k_best alone (dense photometric alignment, ssba_image.hip: the launch that closes its iteration)
+void launch_best(Launcher &L, const Dev &d) {
+    const size_t n = (size_t)d.P * 12 > (size_t)d.Lpad * 3 ? (size_t)d.P * 12 : (size_t)d.Lpad * 3;
+    LAUNCH(KC_COPY, k_best, dim3((unsigned)std::min<size_t>((n + 255) / 256, 512)), dim3(256), 0, d);
 }
 
 }  // namespace ssba

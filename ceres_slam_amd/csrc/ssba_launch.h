@@ -40,6 +40,7 @@ struct Launcher {
     bool spb_in_place_ok = false;    // set by the iteration's front part on one GPU (no exchange sums Spb between the Schur launches and the reduced solve)
     bool spb_rides = false;      // launch_ph_schur -> launch_bcr: k_ph_spb_assemble has also written the border columns where they ride (no copy)
     WideSys wide{};              // host copy of the wide system's sizes and pointers (Dev::wide is the device copy), n = 0: none
+    ImageSys image{};            // host copy of the photometric-alignment state (Dev::image is the device copy), n_wg = 0: none
     struct Pending { int cls; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> pool;
@@ -132,6 +133,12 @@ void launch_pose_only(Launcher &L, const Dev &d);
 void launch_pose_only_step(Launcher &L, const Dev &d);
 void launch_pose_only_cov(Launcher &L, const Dev &d, const int *poses, int n, double *out, int *fail);
 void launch_decide_commit(Launcher &L, const Dev &d, bool fuse_reduce = false, bool fuse_all = false, int n_pose_parts = -1, bool with_best = false);
+void launch_best(Launcher &L, const Dev &d);
+// dense photometric alignment (ImageError blocks on one pose; ssba_image.hip): k_im_lin . k_im_solve . k_im_eval (+ k_check's work) .
+// k_decide . k_best.  launch_image_lin_solve: the first two alone (covariance: Dev::hpp at the current pose).  delta_disp: where
+// k_im_eval also leaves the disparity step per block (test hook), or null.
+void launch_image(Launcher &L, const Dev &d, double *delta_disp = nullptr);
+void launch_image_lin_solve(Launcher &L, const Dev &d);
 // config 3 (ssba_phong_solver.hip)
 int upload_phong_tables(hipStream_t s);
 int configure_phong();

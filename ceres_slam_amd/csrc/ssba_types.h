@@ -192,6 +192,28 @@ struct WideSys {
     double *Rp, *Yp;                    // n x WBD x WPC row-major: the panel R of the current step, Yr = G^-1 R
 };
 
+// Dense photometric alignment (ssba_image.hip): ImageError blocks, one per reference pixel with a usable disparity, on ONE pose
+// T_track_ref.  The disparities are 1-D "landmarks" eliminated in closed form, the reduced system is one 6 x 6 block.  The
+// disparity map lives in Dev::pts / cand_pts / best_pts / init_pts (rows * cols doubles, row-major, inside the 3 * Lpad of those
+// buffers), so the copies of k_best and of a restart cover it.  The struct lives in device memory like WideSys; the host keeps
+// a copy for the launch shapes (Launcher::image).
+constexpr int IM_THREADS = 256;         // lanes = residual blocks per work-group of k_im_lin / k_im_eval
+constexpr int IM_REC = 64;              // doubles per partial record of k_im_lin (IM_NSUM used)
+constexpr int IM_NSUM = 39;             // reduced H_pp 21 | reduced g_p 6 | diag H_pp 6 | g_p 6 (the last twelve only with free disparities)
+constexpr int IM_ROW = 8;               // row buffer, component-major over the blocks: J_pose 6 | J_disp | r
+constexpr int IM_SYS = 64;              // k_im_solve's record: damped S 36 | rhs 6 | delta_pose 6 | Jacobi scale of the pose 6
+struct ImageSys {
+    int rows, cols, interp, disp_const; // interp: SSBA_IMAGE_NEAREST / SSBA_IMAGE_BILINEAR
+    uint32_t n_blk;                     // residual blocks = pixels with a finite, positive disparity at ssba_finalize
+    int n_wg;                           // work-groups of IM_THREADS blocks
+    const uint32_t *blk_pix;            // n_blk: pixel v * cols + u of a block, ascending
+    const double *ref, *track, *gradx, *grady;      // rows * cols each
+    double *row;                        // IM_ROW x n_blk, written by k_im_lin, read by k_im_eval
+    double *sd;                         // n_blk: Jacobi scale of a free disparity (iteration 0)
+    double *part;                       // n_wg x IM_REC partial sums of k_im_lin
+    double *sys;                        // IM_SYS (k_im_solve)
+};
+
 struct Dev {
     // camera, stiffness, loss
     double fu, fv, cu, cv, b;
@@ -333,6 +355,8 @@ struct Dev {
                                                     // right-hand side, so the factorisation leaves L^-1 rhs there
     // general layout, banded with tracks of <= WSP observations: block-tridiagonal system of 144-wide blocks (ssba_wide.hip)
     const WideSys *wide;                            // device copy, or null
+    // dense photometric alignment (ssba_image.hip): one pose, one ImageError block per pixel; none of the structures above
+    const ImageSys *image;                          // device copy, or null
 };
 // Every kernel takes Dev by value: explicit kernel arguments are limited to 4 KB, and the hidden arguments of the code
 // object (256 B) and the handful of scalars beside Dev have to fit next to it.

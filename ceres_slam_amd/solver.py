@@ -39,7 +39,6 @@ class StereoBA:
                  stiffness, pose_const=None, huber_a: float = 0.0, device: int = -1, finalize: bool = True,
                  world_size: int = 1, rank: int = 0, lighting: dict = None, shared_free: int = 0, use_bounds: bool = False, points_const: bool = False,
                  partition=None, pose_factors=None, point_const=None):
-        self.lib = capi.load()
         self.poses = np.ascontiguousarray(poses, dtype=np.float64)     # caller-owned blocks, updated in place
         self.points = np.ascontiguousarray(points, dtype=np.float64)
         self._obs_pose = np.ascontiguousarray(obs_pose, dtype=np.uint32)
@@ -52,9 +51,7 @@ class StereoBA:
             assert self._S_obs.shape[0] == self._obs_pose.shape[0]
         else:
             self._S = np.ascontiguousarray(S.reshape(9))
-        self.h = C.c_void_p()
-        cam = capi.Camera(**camera)
-        capi.check(self.lib.ssba_create(C.byref(cam), device, C.byref(self.h)), "ssba_create")
+        self._create(camera, device)
         P, L = self.poses.shape[0], self.points.shape[0]
         capi.check(self.lib.ssba_add_pose_blocks(self.h, capi.dptr(self.poses), P), "ssba_add_pose_blocks")
         capi.check(self.lib.ssba_add_point_blocks(self.h, capi.dptr(self.points), L), "ssba_add_point_blocks")
@@ -92,8 +89,6 @@ class StereoBA:
                 capi.check(self.lib.ssba_add_sun_observation(self.h, int(f["pose"]), capi.dptr(obs), capi.dptr(exp), capi.dptr(S),
                                                              float(dat[6]), float(dat[7]), float(f.get("huber", 0.0))),
                            "ssba_add_sun_observation")
-        self._xcb = None
-        self.normals = None
         self.shared_free = int(shared_free)
         self.use_bounds = bool(use_bounds)
         if lighting is not None:
@@ -113,6 +108,15 @@ class StereoBA:
                 capi.check(self.lib.ssba_set_partition(self.h, sep.ctypes.data_as(capi._u32p), sep.shape[0]), "ssba_set_partition")
         if finalize:
             self.finalize()
+
+    def _create(self, camera: dict, device: int):
+        """The handle and the fields every method of the class reads, whatever blocks the constructor then adds."""
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        self._xcb = None            # keeps the exchange trampoline alive (set_exchange)
+        self.normals = None         # lighting terms (_add_lighting)
+        cam = capi.Camera(**camera)
+        capi.check(self.lib.ssba_create(C.byref(cam), device, C.byref(self.h)), "ssba_create")
 
     def _add_lighting(self, lt: dict):
         """Config-3 terms (include/ssba.h "config 3"); `lt` has the keys of synth.PhongData.as_oracle_dict()."""
@@ -367,3 +371,59 @@ class StereoBA:
         capi.check(self.lib.ssba_line_search_probe(self.h, float(alpha), capi.dptr(out), *[capi.dptr(c[k]) for k in (
             "poses", "points", "normals", "light", "phong", "texture")]), "ssba_line_search_probe")
         return out, c
+
+
+class ImageStep(NamedTuple):
+    """What ssba_image_step returns (include/ssba.h): the rows, the damped reduced 6 x 6 system and the step."""
+    cost: float
+    residuals: np.ndarray       # (rows, cols), zero at pixels without a block
+    J_pose: np.ndarray          # (rows, cols, 6)
+    J_disp: np.ndarray          # (rows, cols)
+    S: np.ndarray               # (6, 6)
+    rhs: np.ndarray             # (6,)
+    delta_pose: np.ndarray      # (6,)
+    delta_disp: np.ndarray      # (rows, cols)
+    mcc: float
+
+
+class ImageAlignment(StereoBA):
+    """Dense photometric alignment (ssba_add_image_blocks): one pose T_track_ref and one disparity block per reference pixel,
+    the reference's ImageError blocks (tests/dense_stereo_test.cpp:94-136).  ``pose`` (12,) and ``disparity`` (rows, cols) are
+    the caller-owned blocks, updated in place by a solve.  Solving, the stepwise calls, the iteration log, streams, kernel
+    timing and stats are StereoBA's."""
+
+    def __init__(self, camera: dict, pose, disparity, ref, track, gradx, grady, interpolation: int = capi.IMAGE_BILINEAR,
+                 disparity_const: bool = False, device: int = -1, finalize: bool = True):
+        self.pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self.poses = self.pose.reshape(1, 12)           # (the view StereoBA's helpers use)
+        self.disparity = np.ascontiguousarray(disparity, dtype=np.float64)
+        rows, cols = self.disparity.shape
+        self._imgs = [np.ascontiguousarray(a, dtype=np.float64) for a in (ref, track, gradx, grady)]
+        for a in self._imgs:
+            if a.shape != (rows, cols):
+                raise ValueError(f"image of shape {a.shape}, expected {(rows, cols)}")
+        self.points = np.zeros((0, 3))
+        self._create(camera, device)
+        capi.check(self.lib.ssba_add_image_blocks(self.h, capi.dptr(self.pose), capi.dptr(self.disparity), *[capi.dptr(a) for a in self._imgs],
+                                                  rows, cols, int(interpolation)), "ssba_add_image_blocks")
+        if disparity_const:
+            capi.check(self.lib.ssba_set_disparity_blocks_constant(self.h, 1), "ssba_set_disparity_blocks_constant")
+        if finalize:
+            self.finalize()
+
+    @classmethod
+    def from_synth(cls, pair, **kw):
+        return cls(pair.camera, pair.pose_init.copy(), pair.disparity.copy(), pair.ref, pair.track, pair.gradx, pair.grady, **kw)
+
+    def solve(self, options: capi.Options = None):
+        return super().solve(options or capi.default_options(use_nonmonotonic_steps=1))      # dense_stereo_test.cpp:120-125
+
+    def image_step(self, radius: float, options: capi.Options = None) -> ImageStep:
+        rows, cols = self.disparity.shape
+        cost, mcc = C.c_double(), C.c_double()
+        r, Jp, Jd, dd = np.zeros((rows, cols)), np.zeros((rows, cols, 6)), np.zeros((rows, cols)), np.zeros((rows, cols))
+        S, rhs, dp = np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+        o = options or capi.default_options()
+        capi.check(self.lib.ssba_image_step(self.h, C.byref(o), float(radius), C.byref(cost), capi.dptr(r), capi.dptr(Jp), capi.dptr(Jd),
+                                            capi.dptr(S), capi.dptr(rhs), capi.dptr(dp), capi.dptr(dd), C.byref(mcc)), "ssba_image_step")
+        return ImageStep(cost.value, r, Jp, Jd, S, rhs, dp, dd, mcc.value)

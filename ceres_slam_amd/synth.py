@@ -554,3 +554,76 @@ def write_reference_phong_csv(prob: StereoBAProblem, ph: PhongData, dataset_path
         f.write(",".join(repr(float(v)) for v in d["light"]) + "\n")
     return dataset_path, poses_path, map_path, light_path
 
+
+
+# ---------------------------------------------------------------- dense photometric alignment ---
+@dataclass
+class ImagePair:
+    """Inputs of the reference's dense driver (tests/dense_stereo_test.cpp:94-136) after its OpenCV pre-processing."""
+
+    camera: dict
+    ref: np.ndarray             # (rows, cols) reference image
+    track: np.ndarray           # (rows, cols) tracked image
+    gradx: np.ndarray           # (rows, cols) Sobel d/du of the tracked image
+    grady: np.ndarray           # (rows, cols) Sobel d/dv of the tracked image
+    disparity: np.ndarray       # (rows, cols) disparity of the reference image; invalid entries are NaN, 0 or negative
+    pose_true: np.ndarray       # (12,) T_track_ref
+    pose_init: np.ndarray       # (12,) the start: a hundredth of a pixel off the identity the driver starts from (:20)
+
+
+def sobel(img: np.ndarray, scale: float = 0.125):
+    """3 x 3 Sobel derivatives with reflected borders (cv::Sobel's default border); scale 1/8 makes them per-pixel slopes."""
+    p = np.pad(np.asarray(img, dtype=np.float64), 1, mode="reflect")
+    gx = (p[:-2, 2:] - p[:-2, :-2]) + 2.0 * (p[1:-1, 2:] - p[1:-1, :-2]) + (p[2:, 2:] - p[2:, :-2])
+    gy = (p[2:, :-2] - p[:-2, :-2]) + 2.0 * (p[2:, 1:-1] - p[:-2, 1:-1]) + (p[2:, 2:] - p[:-2, 2:])
+    return scale * gx, scale * gy
+
+
+def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, slant=(0.25, -0.15), motion: float = 1.0,
+                    invalid_fraction: float = 0.0, min_wavelength_px: float = 10.0) -> ImagePair:
+    """A textured slanted plane rendered exactly (no resampling) from two poses.
+
+    The plane a x + b y + z = depth in the reference camera frame carries a band-limited texture (six sinusoids whose
+    wavelengths on the image are at least min_wavelength_px pixels); the tracked image is the same plane seen from
+    T_track_ref = pose_true, a motion of a fraction of a pixel to about a pixel (scaled by `motion`).  The disparity map is the
+    exact one of the reference view; invalid_fraction of its entries are replaced by NaN, 0 and negative values in turn."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    fu = 0.6 * cols
+    cam = dict(fu=fu, fv=fu, cu=0.5 * (cols - 1), cv=0.5 * (rows - 1), b=0.54)
+    a, b = slant
+    n = np.array([a, b, 1.0])
+    px_on_plane = depth / fu                                        # metres per pixel at the principal point
+    K = 6
+    lam = min_wavelength_px * px_on_plane * (1.0 + 2.0 * rng.random(K))
+    ang = rng.random(K) * 2.0 * np.pi
+    kx, ky = 2.0 * np.pi / lam * np.cos(ang), 2.0 * np.pi / lam * np.sin(ang)
+    phase = rng.random(K) * 2.0 * np.pi
+    amp = 0.5 + rng.random(K)
+    amp *= 0.45 / amp.sum()
+
+    def texture(X):
+        return 0.5 + sum(amp[k] * np.sin(kx[k] * X[..., 0] + ky[k] * X[..., 1] + phase[k]) for k in range(K))
+
+    v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64), indexing="ij")
+    ray = np.stack([(u - cam["cu"]) / cam["fu"], (v - cam["cv"]) / cam["fv"], np.ones_like(u)], axis=-1)
+    # reference view: the ray through a pixel meets the plane at Z ray with Z = depth / (n . ray)
+    Z = depth / (ray @ n)
+    ref = texture(ray * Z[..., None])
+    disparity = cam["fu"] * cam["b"] / Z
+    t = motion * np.array([0.05, -0.03, 0.08]) * (1.0 + 0.2 * rng.standard_normal(3))
+    R = so3_exp(motion * np.array([0.004, -0.006, 0.008]) * (1.0 + 0.2 * rng.standard_normal(3)))
+    # tracked view: X_track = R X_ref + t; its rays in the reference frame start at -R^T t
+    o = -R.T @ t
+    dirs = ray @ R                                                  # rows of R^T ray
+    s = (depth - n @ o) / (dirs @ n)
+    track = texture(o + dirs * s[..., None])
+    gradx, grady = sobel(track)
+    if invalid_fraction > 0.0:
+        idx = rng.choice(rows * cols, size=int(round(invalid_fraction * rows * cols)), replace=False)
+        bad = np.array([np.nan, 0.0, -1.5])
+        disparity.reshape(-1)[idx] = bad[np.arange(idx.shape[0]) % 3]
+    # the start is NOT the identity: with the exact disparity map the identity projects every pixel onto itself, the first row
+    # and column exactly onto the bounds edge u = 0 / v = 0, where the last bit of u decides whether the block is in bounds
+    t0, R0 = np.array([-0.011, 0.013, -0.017]) * px_on_plane, so3_exp(np.array([2e-4, -3e-4, 2.5e-4]))
+    return ImagePair(camera=cam, ref=ref, track=track, gradx=gradx, grady=grady, disparity=disparity,
+                     pose_true=pose_pack(t, R), pose_init=pose_pack(t0, R0))

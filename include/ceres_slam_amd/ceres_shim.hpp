@@ -31,6 +31,11 @@
 //     covariance.Compute(covar_blocks, &problem);
 //     covariance.GetCovarianceBlockInTangentSpace(pose, pose, out36);     // (pose | point, pose | point) pairs
 //
+// and of the dense photometric driver (tests/dense_stereo_test.cpp:94-136), with ceres_slam::Image in place of cv::Mat:
+//
+//     problem.AddResidualBlock(ceres_slam::ImageError::Create(camera, ref, track, gradx, grady, u, v), NULL, pose, &disparity[v * cols + u]);
+//     problem.SetParameterization(pose, se3_perturbation);
+//
 // The shim recognises the typed cost functions of this path and lowers them to observation
 // tables; it does NOT run arbitrary user functors on the GPU -- any other CostFunction is
 // rejected at AddResidualBlock with std::invalid_argument (Ceres would accept it: that is the
@@ -187,6 +192,33 @@ class NormalErrorAutomatic : public ceres::CostFunction {
     double stiffness[9];
 };
 
+// A row-major image of doubles: what the dense driver holds in cv::Mat (CV_64F) after its OpenCV pre-processing
+struct Image {
+    int rows, cols;
+    const double *data;
+    Image(int rows_, int cols_, const double *data_) : rows(rows_), cols(cols_), data(data_) {}
+};
+
+// include/ceres_slam/image_error.hpp:136-144: blocks (pose 12 = T_track_ref, disparity 1) -> 1 residual at reference pixel (u, v).
+// interpolation: SSBA_IMAGE_NEAREST is the functor as it stands (:156-164), SSBA_IMAGE_BILINEAR what its comment announces.
+class ImageError : public ceres::CostFunction {
+ public:
+    static ceres::CostFunction *Create(const std::shared_ptr<const StereoCamera> &camera, const std::shared_ptr<const Image> &ref_img,
+                                       const std::shared_ptr<const Image> &track_img, const std::shared_ptr<const Image> &track_gradx,
+                                       const std::shared_ptr<const Image> &track_grady, double u_ref, double v_ref,
+                                       int interpolation = SSBA_IMAGE_NEAREST) {
+        ImageError *c = new ImageError;
+        c->camera = camera;
+        c->img[0] = ref_img; c->img[1] = track_img; c->img[2] = track_gradx; c->img[3] = track_grady;
+        c->u = u_ref; c->v = v_ref; c->interpolation = interpolation;
+        return c;
+    }
+    std::shared_ptr<const StereoCamera> camera;
+    std::shared_ptr<const Image> img[4];
+    double u, v;
+    int interpolation;
+};
+
 }  // namespace ceres_slam
 
 namespace ceres {
@@ -292,6 +324,11 @@ class Problem {
 
     void AddResidualBlock(CostFunction *cost, LossFunction *loss, double *pose_block, double *point_block) {
         ++version_;
+        if (auto *im = dynamic_cast<ceres_slam::ImageError *>(cost)) {      // (pose, disparity): dense_stereo_test.cpp:106-112
+            add_image_block_(im, loss, pose_block, point_block);
+            owned_costs_.push_back(cost);
+            return;
+        }
         if (auto *rp = dynamic_cast<ceres_slam::RelativePoseErrorAutomatic *>(cost)) {      // (pose 1, pose 2): blowup_test.cpp:70-76
             RelFactor f;
             std::memset(&f, 0, sizeof f);
@@ -375,7 +412,7 @@ class Problem {
     void SetParameterBlockVariable(double *block) { if (constant_.erase(block)) ++version_; }
     void SetParameterLowerBound(double *block, int index, double v) { lower_[block][index] = v; ++version_; }
     void SetParameterUpperBound(double *block, int index, double v) { upper_[block][index] = v; ++version_; }
-    int NumResidualBlocks() const { return (int)obs_pose_.size(); }
+    int NumResidualBlocks() const { return (int)(obs_pose_.size() + image_blocks_.size()); }
 
  private:
     friend void Solve(const Solver::Options &, Problem *, Solver::Summary *);
@@ -423,6 +460,39 @@ class Problem {
         if (huber_a_ > 0 && (*rc = ssba_set_huber_loss(h, huber_a_))) return "ssba_set_huber_loss";
         return nullptr;
     }
+    // ImageError blocks: the back end takes them as one disparity MAP (ssba_add_image_blocks), so all blocks share the camera, the
+    // four images, the interpolation and the pose, and the disparity block of pixel (u, v) is element v * cols + u of one array
+    void add_image_block_(ceres_slam::ImageError *im, LossFunction *loss, double *pose, double *disparity) {
+        if (loss) throw std::invalid_argument("ceres_shim: ImageError residual blocks take a NULL loss");
+        if (!im->camera) throw std::invalid_argument("ceres_shim: ImageError needs a camera");
+        for (int q = 0; q < 4; ++q)
+            if (!im->img[q] || !im->img[q]->data || im->img[q]->rows != im->img[0]->rows || im->img[q]->cols != im->img[0]->cols || im->img[0]->rows <= 0 || im->img[0]->cols <= 0)
+                throw std::invalid_argument("ceres_shim: ImageError needs four images of one size");
+        const int rows = im->img[0]->rows, cols = im->img[0]->cols;
+        const long u = (long)im->u, v = (long)im->v;
+        if ((double)u != im->u || (double)v != im->v || u < 0 || v < 0 || u >= cols || v >= rows)
+            throw std::invalid_argument("ceres_shim: ImageError reference pixel must be an integer position inside the image");
+        double *base = disparity - ((size_t)v * cols + (size_t)u);
+        if (image_blocks_.empty()) {
+            image_first_ = *im;
+            image_pose_ = pose;
+            image_disp_ = base;
+        } else {
+            for (int q = 0; q < 4; ++q)
+                if (im->img[q]->data != image_first_.img[q]->data) throw std::invalid_argument("ceres_shim: all ImageError blocks must share their four images");
+            if (rows != image_first_.img[0]->rows || cols != image_first_.img[0]->cols || im->interpolation != image_first_.interpolation ||
+                std::memcmp(im->camera.get(), image_first_.camera.get(), sizeof(ceres_slam::StereoCamera)) != 0)
+                throw std::invalid_argument("ceres_shim: all ImageError blocks must share image size, camera and interpolation");
+            if (pose != image_pose_) throw std::invalid_argument("ceres_shim: all ImageError blocks must share one pose block");
+            if (base != image_disp_)
+                throw std::invalid_argument("ceres_shim: the disparity block of ImageError pixel (u, v) must be element v * cols + u of one rows * cols array");
+        }
+        block_index(pose_index_, pose_blocks_, pose);
+        image_blocks_.push_back((uint32_t)((size_t)v * cols + (size_t)u));
+    }
+    ceres_slam::ImageError image_first_;
+    double *image_pose_ = nullptr, *image_disp_ = nullptr;
+    std::vector<uint32_t> image_blocks_;         // pixel of every ImageError block
     static uint32_t block_index(std::map<double *, uint32_t> &idx, std::vector<double *> &blocks, double *b) {
         auto it = idx.find(b);
         if (it != idx.end()) return it->second;
@@ -476,6 +546,40 @@ inline const char *shim_prepare(Problem &P, int *rc_out) {
     std::vector<uint32_t> &material_of_point = P.st_material_of_point_;
     double (&light)[3] = P.st_light_;
     const bool lighting = !P.intensity_.empty();
+    if (!P.image_blocks_.empty() && !(P.h_ && P.h_version_ == P.version_)) {
+        // ---- ImageError blocks (tests/dense_stereo_test.cpp:101-117) -> ssba_add_image_blocks on the caller's own pose and map ----
+        if (!P.obs_pose_.empty() || !P.pose_factors_.empty() || !P.rel_factors_.empty() || lighting || !P.normals_.empty() || P.dist_world_ > 0 ||
+            P.pose_blocks_.size() != 1 || !P.point_blocks_.empty())
+            throw std::invalid_argument("ceres_shim: a problem with ImageError blocks holds one pose, its disparity blocks and nothing else");
+        if (P.constant_.count(P.image_pose_)) throw std::invalid_argument("ceres_shim: the pose of ImageError blocks cannot be held constant");
+        const ceres_slam::ImageError &f = P.image_first_;
+        const size_t npix = (size_t)f.img[0]->rows * f.img[0]->cols;
+        // the back end builds a block for every pixel whose disparity is finite and positive (:105): the caller's set must be that one
+        std::vector<unsigned char> has(npix, 0);
+        size_t n_const = 0;
+        for (uint32_t pix : P.image_blocks_) {
+            if (has[pix]) throw std::invalid_argument("ceres_shim: two ImageError blocks on one pixel");
+            has[pix] = 1;
+            n_const += P.constant_.count(P.image_disp_ + pix);
+        }
+        for (size_t i = 0; i < npix; ++i) {
+            const double dd = P.image_disp_[i];
+            if ((dd == dd && dd - dd == 0.0 && dd > 0.0) != (has[i] != 0))
+                throw std::invalid_argument("ceres_shim: ImageError blocks must cover exactly the pixels with a finite positive disparity");
+        }
+        if (n_const != 0 && n_const != P.image_blocks_.size()) throw std::invalid_argument("ceres_shim: hold all disparity blocks constant or none");
+        if (P.h_) { ssba_destroy(P.h_); P.h_ = nullptr; }
+        ssba_camera cam = ssba_camera{f.camera->fu, f.camera->fv, f.camera->cu, f.camera->cv, f.camera->b};
+        if ((rc = ssba_create(&cam, -1, &P.h_))) { P.h_ = nullptr; return "ssba_create"; }
+        const char *where = nullptr;
+        if ((rc = ssba_add_image_blocks(P.h_, P.image_pose_, P.image_disp_, f.img[0]->data, f.img[1]->data, f.img[2]->data, f.img[3]->data,
+                                        (uint32_t)f.img[0]->rows, (uint32_t)f.img[0]->cols, f.interpolation))) where = "ssba_add_image_blocks";
+        else if (n_const && (rc = ssba_set_disparity_blocks_constant(P.h_, 1))) where = "ssba_set_disparity_blocks_constant";
+        else if ((rc = ssba_finalize(P.h_))) where = "ssba_finalize";
+        if (where) { ssba_destroy(P.h_); P.h_ = nullptr; return where; }
+        P.h_version_ = P.version_;
+        return nullptr;
+    }
     if (P.h_ && P.h_version_ == P.version_) {      // same structure: only the values may have moved
         if (lighting) {
             for (size_t j = 0; j < P.point_blocks_.size(); ++j) std::memcpy(&normals[3 * j], normal_blocks[j], 3 * sizeof(double));
@@ -595,7 +699,7 @@ inline const char *shim_prepare(Problem &P, int *rc_out) {
 inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summary *summary) {
     Problem &P = *problem;
     *summary = Solver::Summary();
-    if (P.obs_pose_.empty() && P.pose_factors_.empty() && P.rel_factors_.empty() && P.dist_world_ <= 1) {     // (a shard without blocks still joins the collectives)
+    if (P.obs_pose_.empty() && P.pose_factors_.empty() && P.rel_factors_.empty() && P.image_blocks_.empty() && P.dist_world_ <= 1) {     // (a shard without blocks still joins the collectives)
         summary->termination_type = CONVERGENCE;
         summary->message = "no residual blocks";
         return;
@@ -634,7 +738,7 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
     summary->initial_cost = s.initial_cost;
     summary->final_cost = s.final_cost;
     summary->total_time_in_seconds = s.total_time_s;
-    if (summary->IsSolutionUsable()) {
+    if (summary->IsSolutionUsable() && P.image_blocks_.empty()) {      // (ImageError blocks: the back end wrote the caller's pose and map itself)
         for (size_t i = 0; i < P.pose_blocks_.size(); ++i) std::memcpy(P.pose_blocks_[i], &poses[12 * i], 12 * sizeof(double));
         for (size_t i = 0; i < P.point_blocks_.size(); ++i) std::memcpy(P.point_blocks_[i], &points[3 * i], 3 * sizeof(double));
         if (lighting) {   // every lighting block is written back; constant ones come back unchanged

@@ -492,6 +492,55 @@ SSBA_API int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]
 typedef struct { uint32_t kind_a, index_a, kind_b, index_b; } ssba_cov_block;
 SSBA_API int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out);
 
+/* ---- dense photometric alignment: ImageError blocks (include/ceres_slam/image_error.hpp) ------------------------
+ * ssba_add_image_blocks replaces the loop of tests/dense_stereo_test.cpp:101-117: one ImageError residual block
+ * (SizedCostFunction<1, 12, 1>) per reference pixel, on ONE pose block T_track_ref (12 doubles, SE3Perturbation) and one
+ * disparity block per pixel.  pose, disparity (rows * cols, row-major) are caller-owned and updated in place by a solve; the
+ * four images (rows * cols doubles each: reference image, tracked image and the two gradient images the functor samples) are
+ * copied to the device at ssba_finalize.  A residual block exists for every pixel whose disparity is finite and > 0 at
+ * ssba_finalize (:105); the pose and the disparities are uploaded again when a solve begins.  Pixels without a block and
+ * constant disparities come back bit-unchanged.
+ *
+ * The arithmetic (fp64), for the block at reference pixel (u_r, v_r) with disparity d and pose [t | R]:
+ *     p = triangulate(u_r, v_r, d),  q = R p + t,  (u, v) = project(q)[0:2]       (stereo_camera.hpp:77-144)
+ *     SSBA_IMAGE_NEAREST   I(u, v) = I[floor(v + 1/2)][floor(u + 1/2)]   (image_error.hpp:156-164 as it stands)
+ *     SSBA_IMAGE_BILINEAR  I(u, v) from the four neighbours of (floor u, floor v) (what its comment says it is meant to be)
+ *     in bounds: 0 <= u, 0 <= v and u < cols - 1/2, v < rows - 1/2 (NEAREST) or u < cols - 1, v < rows - 1 (BILINEAR)
+ *     r = track(u, v) - ref[v_r][u_r],   g = [gradx(u, v), grady(u, v)]
+ *     J_pose = g P(q) [I | -q^]   (1 x 6, local coordinates of SE3Perturbation, translation then rotation, as on stereo blocks;
+ *                                  P = the first two rows of the projection Jacobian)
+ *     J_disp = g P(q) R dp/dd     (dp/dd = the third column of the triangulation Jacobian)
+ *     out of bounds: r = 0, J_pose = 0, J_disp = 0 (:102-128).  No loss, no stiffness: cost = 1/2 sum r^2.
+ * Two deliberate differences from the reference's text.  Its bounds test (u < cols, v < rows, :167-172) lets round() pick column
+ * `cols` or row `rows`, one past the end; here a block is in bounds only when every pixel it reads is inside the image, which
+ * differs from the reference exactly where the reference reads past the end of a row.  And :97-99 takes
+ * tri_jac.block(2, 0, 3, 1), which lies outside the 3 x 3 matrix; the column it means (d p / d disparity) is used.
+ * The minimiser is the Levenberg-Marquardt loop of every other layout; free disparities are part of x (norms, step norm,
+ * gradient max norm) and are eliminated per block: V = J_d^2 + D_d, S = H_pp + D_p - sum (J_p^T J_d)(J_d J_p) / V,
+ * rhs = -(g_p - sum J_p^T J_d J_d r / V), delta_d = -(J_d r + J_d J_p delta_p) / V.
+ *
+ * An image handle holds nothing else and lives on one GPU (ssba_stats.general_structure = 4; num_active_points and
+ * num_observations = the block count).  SSBA_ERR_UNSUPPORTED with a message that names the call: pose, point, stereo,
+ * lighting, pose-factor, loss and constant-block calls on it, a second ssba_add_image_blocks, ssba_set_distributed /
+ * ssba_set_partition / an exchange, a DOGLEG solve, ssba_evaluate, ssba_lm_step, ssba_dogleg_step, ssba_covariance_blocks.
+ * rows or cols = 0, a NULL array, an unknown interpolation: SSBA_ERR_INVALID_ARGUMENT (so is a map without a usable disparity,
+ * at ssba_finalize).  ssba_solve, the stepwise calls, ssba_iteration_log, ssba_set_stream, ssba_set_kernel_timing work as on
+ * every handle.  ssba_pose_covariance(p, 0, cov) with constant disparities: the inverse of sum J_pose^T J_pose
+ * (SSBA_ERR_NUMERICAL_FAILURE when singular); with free disparities SSBA_ERR_NUMERICAL_FAILURE (more columns than rows: Ceres
+ * reports a failed covariance computation there too). */
+#define SSBA_IMAGE_NEAREST 0
+#define SSBA_IMAGE_BILINEAR 1
+SSBA_API int ssba_add_image_blocks(ssba_problem *p, double *pose, double *disparity, const double *ref_img, const double *track_img,
+                          const double *track_gradx, const double *track_grady, uint32_t rows, uint32_t cols, int interpolation);
+/* replaces problem.SetParameterBlockConstant / SetParameterBlockVariable on every disparity block (before ssba_finalize) */
+SSBA_API int ssba_set_disparity_blocks_constant(ssba_problem *p, int is_constant);
+/* test hook: one Levenberg-Marquardt step from the caller's current pose and disparities at the given radius.  cost; residuals
+ * (rows * cols), J_pose (rows * cols * 6), J_disp (rows * cols): the rows, zero at pixels without a block; S (36) the damped
+ * reduced 6 x 6 system and rhs (6); delta_pose (6), delta_disp (rows * cols, zero when constant); model_cost_change.  Any
+ * output may be NULL.  Writes nothing back. */
+SSBA_API int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose,
+                    double *J_disp, double *S, double *rhs, double *delta_pose, double *delta_disp, double *model_cost_change);
+
 /* ---- front end: the VO initial guess --------------------------------- */
 /* ssba_frontend_ransac replaces, for `num_pairs` pairs of consecutive states at once,
  *   PointCloudAligner::compute_transformation_and_inliers (src/ceres_slam/point_cloud_aligner.cpp:64-136)

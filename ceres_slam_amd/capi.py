@@ -39,6 +39,7 @@ SYMBOLS = [
     "ssba_pose_covariance", "ssba_rccl_unique_id", "ssba_set_rccl", "ssba_frontend_vo",
     "ssba_rccl_describe", "ssba_rccl_ranks", "ssba_armijo_trace", "ssba_debug_stamps", "ssba_covariance_blocks",
     "ssba_add_image_blocks", "ssba_set_disparity_blocks_constant", "ssba_image_step",
+    "ssba_image_pyramid_create", "ssba_image_pyramid_destroy", "ssba_image_pyramid_level", "ssba_add_image_level", "ssba_image_pyramid_align",
 ]
 
 
@@ -68,6 +69,7 @@ class CovBlock(C.Structure):
 
 LEVENBERG_MARQUARDT, DOGLEG = 0, 1
 IMAGE_NEAREST, IMAGE_BILINEAR = 0, 1     # SSBA_IMAGE_NEAREST / SSBA_IMAGE_BILINEAR
+GRADIENT_OF_REFERENCE, GRADIENT_OF_TRACKED = 0, 1     # SSBA_GRADIENT_OF_REFERENCE / SSBA_GRADIENT_OF_TRACKED
 
 
 class Summary(C.Structure):
@@ -170,6 +172,12 @@ def load():
     L.ssba_add_image_blocks.argtypes = [H, _dp, _dp, _dp, _dp, _dp, _dp, C.c_uint32, C.c_uint32, C.c_int]
     L.ssba_set_disparity_blocks_constant.argtypes = [H, C.c_int]
     L.ssba_image_step.argtypes = [H, C.POINTER(Options), C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    _u8p = C.POINTER(C.c_uint8)
+    L.ssba_image_pyramid_create.argtypes = [_u8p, _u8p, _dp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_double, C.c_int, C.POINTER(H)]
+    L.ssba_image_pyramid_destroy.argtypes = [H]
+    L.ssba_image_pyramid_level.argtypes = [H, C.c_uint32, _u32p, _u32p, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp]
+    L.ssba_add_image_level.argtypes = [H, H, C.c_uint32, _dp, _dp, C.c_int]
+    L.ssba_image_pyramid_align.argtypes = [H, C.POINTER(Camera), _dp, _dp, C.c_uint32, C.c_int, C.c_int, C.POINTER(Options), C.POINTER(Summary)]
     L.ssba_ransac_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_int, _u32p]
     L.ssba_frontend_ransac.argtypes = [C.POINTER(Camera), C.c_int, C.c_uint32, _u32p, _dp, _dp, _u32p, C.c_uint32, C.c_double, _dp,
                                        C.POINTER(C.c_uint8), _u32p, _dp]

@@ -20,6 +20,7 @@
 
 #include "../../include/ssba.h"
 #include "ssba_pool.h"
+#include "ssba_image_pyramid.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -35,6 +36,7 @@ using namespace ssba;
 
 static thread_local std::string g_last_error;
 static void set_error(const std::string &s) { g_last_error = s; }
+namespace ssba { void set_last_error(const std::string &s) { g_last_error = s; } }      // (ssba_image_pyramid.hip)
 
 #define HIPCHECK(expr)                                                                   \
     do {                                                                                 \
@@ -93,6 +95,7 @@ struct ssba_problem {
     bool image = false, disp_const = false;
     double *user_disp = nullptr;
     const double *img_ref = nullptr, *img_track = nullptr, *img_gradx = nullptr, *img_grady = nullptr;
+    bool img_on_device = false;            // ssba_add_image_level: the four pointers are a pyramid level's device images
     uint32_t img_rows = 0, img_cols = 0;
     int img_interp = 0;
     std::vector<uint32_t> img_blk;         // pixel of every block (ssba_finalize)
@@ -430,18 +433,18 @@ static int refuse_on_image(const ssba_problem *p, const char *what) {
 
 // replaces the loop of tests/dense_stereo_test.cpp:101-117: ImageError::Create + AddResidualBlock(cost, NULL, pose, &disparity[v][u])
 // for every pixel with a finite positive disparity, and SetParameterization(pose, SE3Perturbation)
-int ssba_add_image_blocks(ssba_problem *p, double *pose, double *disparity, const double *ref_img, const double *track_img,
-                          const double *track_gradx, const double *track_grady, uint32_t rows, uint32_t cols, int interpolation) {
+static int add_image(ssba_problem *p, const char *call, double *pose, double *disparity, const double *ref_img, const double *track_img,
+                     const double *track_gradx, const double *track_grady, uint32_t rows, uint32_t cols, int interpolation, bool on_device) {
     if (!p || !pose || !disparity || !ref_img || !track_img || !track_gradx || !track_grady || rows == 0 || cols == 0) return SSBA_ERR_INVALID_ARGUMENT;
     if (interpolation != SSBA_IMAGE_NEAREST && interpolation != SSBA_IMAGE_BILINEAR) {
-        set_error("ssba_add_image_blocks: unknown interpolation");
+        set_error(std::string(call) + ": unknown interpolation");
         return SSBA_ERR_INVALID_ARGUMENT;
     }
     if (p->finalized) return SSBA_ERR_STATE;
-    if (p->image) { set_error("ssba_add_image_blocks: a second call (one tracked frame per handle)"); return SSBA_ERR_UNSUPPORTED; }
+    if (p->image) { set_error(std::string(call) + ": a second call (one tracked frame per handle)"); return SSBA_ERR_UNSUPPORTED; }
     if (p->P || p->L || !p->obs_pose.empty() || p->num_normals || p->M || p->user_light || !p->pose_factors.empty() || !p->rel_factors.empty() ||
         !p->ph_intensity.empty() || p->world_size > 1 || !p->sep_sb.empty() || p->xfn || p->huber_a > 0.0) {
-        set_error("ssba_add_image_blocks: the handle already holds pose, point, stereo, lighting or pose-factor blocks, a loss or a sharding "
+        set_error(std::string(call) + ": the handle already holds pose, point, stereo, lighting or pose-factor blocks, a loss or a sharding "
                   "(an image handle holds nothing else, on one GPU)");
         return SSBA_ERR_UNSUPPORTED;
     }
@@ -451,8 +454,28 @@ int ssba_add_image_blocks(ssba_problem *p, double *pose, double *disparity, cons
     p->pose_const.assign(1, 0);
     p->user_disp = disparity;
     p->img_ref = ref_img; p->img_track = track_img; p->img_gradx = track_gradx; p->img_grady = track_grady;
+    p->img_on_device = on_device;
     p->img_rows = rows; p->img_cols = cols; p->img_interp = interpolation;
     return SSBA_OK;
+}
+
+int ssba_add_image_blocks(ssba_problem *p, double *pose, double *disparity, const double *ref_img, const double *track_img,
+                          const double *track_gradx, const double *track_grady, uint32_t rows, uint32_t cols, int interpolation) {
+    return add_image(p, "ssba_add_image_blocks", pose, disparity, ref_img, track_img, track_gradx, track_grady, rows, cols, interpolation, false);
+}
+
+// ssba_add_image_blocks with the four images of a pyramid level: ssba_finalize copies them device to device
+int ssba_add_image_level(ssba_problem *p, ssba_image_pyramid *pyr, uint32_t level, double *pose, double *disparity, int interpolation) {
+    const char *call = "ssba_add_image_level";
+    if (!p || !pyr || !pose || !disparity) { set_error(std::string(call) + ": NULL argument"); return SSBA_ERR_INVALID_ARGUMENT; }
+    if (level >= pyr->lv.size()) { set_error(std::string(call) + ": no such level"); return SSBA_ERR_INVALID_ARGUMENT; }
+    if ((int)level < pyr->disparity_level) {
+        set_error(std::string(call) + ": levels finer than the pyramid's disparity_level have no disparity map and cannot be aligned");
+        return SSBA_ERR_INVALID_ARGUMENT;
+    }
+    if (p->device != pyr->device) { set_error(std::string(call) + ": the handle and the pyramid live on different devices"); return SSBA_ERR_INVALID_ARGUMENT; }
+    const ssba_image_pyramid::Level &L = pyr->lv[level];
+    return add_image(p, call, pose, disparity, L.img[0], L.img[1], L.img[2], L.img[3], (uint32_t)L.rows, (uint32_t)L.cols, interpolation, true);
 }
 
 // replaces: problem.SetParameterBlockConstant / SetParameterBlockVariable on every disparity block
@@ -967,7 +990,13 @@ static int finalize_image(ssba_problem *p) {
     TRY(dupload(p, &im.blk_pix, p->img_blk));
     const double *imgs[4] = {p->img_ref, p->img_track, p->img_gradx, p->img_grady};
     const double **dst[4] = {&im.ref, &im.track, &im.gradx, &im.grady};
-    for (int q = 0; q < 4; ++q) TRY(dupload(p, dst[q], std::vector<double>(imgs[q], imgs[q] + npix)));
+    for (int q = 0; q < 4; ++q) {
+        if (!p->img_on_device) { TRY(dupload(p, dst[q], std::vector<double>(imgs[q], imgs[q] + npix))); continue; }
+        double *copy = nullptr;       // a pyramid level (ssba_add_image_level): complete since ssba_image_pyramid_create returned
+        TRY(dalloc(p, &copy, npix));
+        HIPCHECK(hipMemcpyAsync(copy, imgs[q], npix * sizeof(double), hipMemcpyDeviceToDevice, p->launcher.stream));
+        *dst[q] = copy;
+    }
     TRY(dzero(p, &im.row, (size_t)IM_ROW * im.n_blk)); TRY(dzero(p, &im.sd, (size_t)im.n_blk));
     TRY(dzero(p, &im.part, (size_t)im.n_wg * IM_REC)); TRY(dzero(p, &im.sys, (size_t)IM_SYS));
     TRY(dupload(p, &d.image, std::vector<ImageSys>(1, im)));

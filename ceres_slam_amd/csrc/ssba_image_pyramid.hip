@@ -1,0 +1,283 @@
+// The pre-processing of the reference's dense driver (tests/dense_stereo_test.cpp:52-72) on the device: cv::pyrDown on the 8-bit
+// pair, convertTo(CV_64F, 1./255.), cv::Sobel, and the disparity map carried to the coarser levels; plus the coarse-to-fine
+// solve over the levels (ssba_image_pyramid_align).  The arithmetic is stated in include/ssba.h; tests/pyramid_reference.py
+// restates it in numpy.
+//
+// A pyramid of n levels is 2 n - 1 launches on its own stream:
+//     k_pyr_down    per level > 0, both images (blockIdx.z): a work-group stages the (2 * 32 + 3) x (2 * 8 + 3) source bytes of
+//                   its 32 x 8 destination tile in LDS, border reflected on the way in, and each lane forms its 5 x 5 sum in
+//                   integers:  dst = (sum w_i w_j src + 128) >> 8
+//     k_pyr_finish  per level, one lane per pixel: ref and track as double, the two Sobel images of the chosen source, and above
+//                   disparity_level the disparity d_l[y][x] = d_{l-1}[2 y][2 x] / 2
+// No atomics and no sums across lanes: two builds give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/ssba.h"
+#include "ssba_image_pyramid.h"
+#include "ssba_pool.h"
+
+namespace ssba {
+
+void set_last_error(const std::string &s);      // ssba_api.hip
+
+constexpr int PYR_TW = 32, PYR_TH = 8, PYR_THREADS = PYR_TW * PYR_TH;
+constexpr int PYR_SW = 2 * PYR_TW + 3, PYR_SH = 2 * PYR_TH + 3, PYR_STRIDE = PYR_SW + 1;
+constexpr int PYR_MIN_SIDE = 8;
+
+// BORDER_REFLECT_101: -1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3.  Lanes of a partial tile ask for indices far outside; those
+// values are never used and only have to stay inside the image.
+static __device__ __forceinline__ int pyr_reflect(int i, int n) {
+    if (i < 0) i = -i;
+    if (i >= n) i = 2 * n - 2 - i;
+    return min(max(i, 0), n - 1);
+}
+
+__global__ __launch_bounds__(PYR_THREADS) void k_pyr_down(const uint8_t *__restrict__ src0, const uint8_t *__restrict__ src1,
+                                                          uint8_t *__restrict__ dst0, uint8_t *__restrict__ dst1, int srows, int scols,
+                                                          int drows, int dcols) {
+    __shared__ uint8_t tile[PYR_SH * PYR_STRIDE];
+    const uint8_t *__restrict__ src = blockIdx.z ? src1 : src0;
+    uint8_t *__restrict__ dst = blockIdx.z ? dst1 : dst0;
+    const int x0 = blockIdx.x * PYR_TW, y0 = blockIdx.y * PYR_TH;
+    for (int i = threadIdx.x; i < PYR_SH * PYR_SW; i += PYR_THREADS) {
+        const int r = i / PYR_SW, c = i - r * PYR_SW;
+        const int sy = pyr_reflect(2 * y0 - 2 + r, srows), sx = pyr_reflect(2 * x0 - 2 + c, scols);
+        tile[r * PYR_STRIDE + c] = src[(size_t)sy * scols + sx];
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % PYR_TW, ty = threadIdx.x / PYR_TW;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= dcols || y >= drows) return;
+    const int w[5] = {1, 4, 6, 4, 1};
+    int sum = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const uint8_t *row = tile + (2 * ty + i) * PYR_STRIDE + 2 * tx;
+        sum += w[i] * ((int)row[0] + 4 * (int)row[1] + 6 * (int)row[2] + 4 * (int)row[3] + (int)row[4]);
+    }
+    dst[(size_t)y * dcols + x] = (uint8_t)((sum + 128) >> 8);
+}
+
+// disp_dst = nullptr below and at disparity_level; disp_src is the finer level's map, src_cols wide
+__global__ __launch_bounds__(PYR_THREADS) void k_pyr_finish(const uint8_t *__restrict__ u0, const uint8_t *__restrict__ u1, double *__restrict__ ref,
+                                                            double *__restrict__ track, double *__restrict__ gradx, double *__restrict__ grady, int rows,
+                                                            int cols, int gradient_source, double scale, const double *__restrict__ disp_src,
+                                                            double *__restrict__ disp_dst, int src_cols) {
+#pragma clang fp contract(off)      // the converted image is rounded before it is differenced, as convertTo stores it
+    const int x = blockIdx.x * PYR_TW + threadIdx.x % PYR_TW, y = blockIdx.y * PYR_TH + threadIdx.x / PYR_TW;
+    if (x >= cols || y >= rows) return;
+    const size_t i = (size_t)y * cols + x;
+    const double k = 1.0 / 255.0;
+    ref[i] = (double)u0[i] * k;
+    track[i] = (double)u1[i] * k;
+    const uint8_t *__restrict__ g = gradient_source == SSBA_GRADIENT_OF_TRACKED ? u1 : u0;
+    const int xm = x > 0 ? x - 1 : 1, xp = x + 1 < cols ? x + 1 : cols - 2;
+    const int ym = y > 0 ? y - 1 : 1, yp = y + 1 < rows ? y + 1 : rows - 2;
+    const uint8_t *__restrict__ r0 = g + (size_t)ym * cols, *__restrict__ r1 = g + (size_t)y * cols, *__restrict__ r2 = g + (size_t)yp * cols;
+    const double a00 = (double)r0[xm] * k, a01 = (double)r0[x] * k, a02 = (double)r0[xp] * k;
+    const double a10 = (double)r1[xm] * k, a12 = (double)r1[xp] * k;
+    const double a20 = (double)r2[xm] * k, a21 = (double)r2[x] * k, a22 = (double)r2[xp] * k;
+    // the summation order of synth.sobel: (first row + 2 * middle row) + last row, then the scale
+    gradx[i] = scale * (((a02 - a00) + 2.0 * (a12 - a10)) + (a22 - a20));
+    grady[i] = scale * (((a20 - a00) + 2.0 * (a21 - a01)) + (a22 - a02));
+    if (disp_dst) disp_dst[i] = disp_src[(size_t)(2 * y) * src_cols + 2 * x] / 2.0;
+}
+
+template <class T>
+static hipError_t pyr_alloc(ssba_image_pyramid *pyr, T **out, size_t n) {
+    void *p = nullptr;
+    const hipError_t e = pool_malloc(&p, n * sizeof(T));
+    if (e != hipSuccess) return e;
+    pyr->allocs.push_back(p);
+    *out = (T *)p;
+    return hipSuccess;
+}
+
+static void pyr_free(ssba_image_pyramid *pyr) {
+    hipSetDevice(pyr->device);
+    if (pyr->stream) hipStreamSynchronize(pyr->stream);
+    for (void *a : pyr->allocs) pool_free(a);
+    if (pyr->stream) pool_stream_release(pyr->stream);
+    delete pyr;
+}
+
+#define PYR_HIP(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) {                                                                        \
+            set_last_error(std::string("ssba_image_pyramid: ") + #expr + ": " + hipGetErrorString(_e)); \
+            return SSBA_ERR_HIP;                                                                       \
+        }                                                                                              \
+    } while (0)
+
+static int pyr_build(ssba_image_pyramid *pyr, const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, char *stage) {
+    const int n = (int)pyr->lv.size(), dl = pyr->disparity_level;
+    for (int l = 0; l < n; ++l) {
+        ssba_image_pyramid::Level &L = pyr->lv[l];
+        const size_t npix = (size_t)L.rows * L.cols;
+        for (int q = 0; q < 2; ++q) PYR_HIP(pyr_alloc(pyr, &L.u8[q], npix));
+        for (int q = 0; q < 4; ++q) PYR_HIP(pyr_alloc(pyr, &L.img[q], npix));
+        if (l >= dl) PYR_HIP(pyr_alloc(pyr, &L.disp, npix));
+    }
+    const size_t n0 = (size_t)pyr->lv[0].rows * pyr->lv[0].cols, nd = (size_t)pyr->lv[dl].rows * pyr->lv[dl].cols;
+    memcpy(stage, ref_u8, n0);
+    memcpy(stage + n0, track_u8, n0);
+    const size_t od = (2 * n0 + 255) / 256 * 256;
+    memcpy(stage + od, disparity, nd * sizeof(double));
+    hipStream_t s = pyr->stream;
+    PYR_HIP(hipMemcpyAsync(pyr->lv[0].u8[0], stage, n0, hipMemcpyHostToDevice, s));
+    PYR_HIP(hipMemcpyAsync(pyr->lv[0].u8[1], stage + n0, n0, hipMemcpyHostToDevice, s));
+    PYR_HIP(hipMemcpyAsync(pyr->lv[dl].disp, stage + od, nd * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int l = 0; l < n; ++l) {
+        const ssba_image_pyramid::Level &L = pyr->lv[l];
+        const dim3 grid((L.cols + PYR_TW - 1) / PYR_TW, (L.rows + PYR_TH - 1) / PYR_TH, 1);
+        if (l > 0) {
+            const ssba_image_pyramid::Level &F = pyr->lv[l - 1];
+            hipLaunchKernelGGL(k_pyr_down, dim3(grid.x, grid.y, 2), dim3(PYR_THREADS), 0, s, (const uint8_t *)F.u8[0], (const uint8_t *)F.u8[1], L.u8[0],
+                               L.u8[1], F.rows, F.cols, L.rows, L.cols);
+            PYR_HIP(hipGetLastError());
+        }
+        const bool derive = l > dl;
+        hipLaunchKernelGGL(k_pyr_finish, grid, dim3(PYR_THREADS), 0, s, (const uint8_t *)L.u8[0], (const uint8_t *)L.u8[1], L.img[0], L.img[1], L.img[2],
+                           L.img[3], L.rows, L.cols, pyr->gradient_source, pyr->gradient_scale, derive ? (const double *)pyr->lv[l - 1].disp : nullptr,
+                           derive ? L.disp : nullptr, derive ? pyr->lv[l - 1].cols : 0);
+        PYR_HIP(hipGetLastError());
+    }
+    PYR_HIP(hipStreamSynchronize(s));
+    return SSBA_OK;
+}
+
+static int pyr_invalid(const char *call, const char *what) {
+    set_last_error(std::string(call) + ": " + what);
+    return SSBA_ERR_INVALID_ARGUMENT;
+}
+
+}  // namespace ssba
+
+using namespace ssba;
+
+extern "C" {
+
+int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, uint32_t rows, uint32_t cols,
+                              uint32_t levels, uint32_t disparity_level, int gradient_source, double gradient_scale, int device,
+                              ssba_image_pyramid **out) {
+    const char *call = "ssba_image_pyramid_create";
+    if (!out) return pyr_invalid(call, "NULL output");
+    *out = nullptr;
+    if (!ref_u8 || !track_u8 || !disparity) return pyr_invalid(call, "NULL array");
+    if (levels == 0) return pyr_invalid(call, "levels = 0");
+    if (disparity_level >= levels) return pyr_invalid(call, "disparity_level must be below levels");
+    if (gradient_source != SSBA_GRADIENT_OF_REFERENCE && gradient_source != SSBA_GRADIENT_OF_TRACKED) return pyr_invalid(call, "unknown gradient source");
+    if (!std::isfinite(gradient_scale) || gradient_scale == 0.0) return pyr_invalid(call, "gradient_scale must be finite and not zero");
+    if (levels > 31 || (rows >> (levels - 1)) < (uint32_t)PYR_MIN_SIDE || (cols >> (levels - 1)) < (uint32_t)PYR_MIN_SIDE)
+        return pyr_invalid(call, "every level needs at least 8 rows and 8 columns");
+    if ((uint64_t)rows * cols >= (1ull << 31)) {
+        set_last_error(std::string(call) + ": image too large for the 32-bit pixel references of this build");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        set_last_error(std::string(call) + ": hipGetDeviceCount found no device");
+        return SSBA_ERR_NO_DEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return SSBA_ERR_NO_DEVICE;
+    if (device >= n) return pyr_invalid(call, "no such device");
+    PYR_HIP(hipSetDevice(device));
+    ssba_image_pyramid *pyr = new ssba_image_pyramid();
+    pyr->device = device;
+    pyr->disparity_level = (int)disparity_level;
+    pyr->gradient_source = gradient_source;
+    pyr->gradient_scale = gradient_scale;
+    pyr->lv.resize(levels);
+    for (uint32_t l = 0; l < levels; ++l) { pyr->lv[l].rows = (int)(rows >> l); pyr->lv[l].cols = (int)(cols >> l); }
+    int rc = SSBA_OK;
+    void *stage = nullptr;
+    const size_t n0 = (size_t)rows * cols, nd = (size_t)pyr->lv[disparity_level].rows * pyr->lv[disparity_level].cols;
+    if (pool_stream_acquire(&pyr->stream) != hipSuccess || pool_host_malloc(&stage, (2 * n0 + 255) / 256 * 256 + nd * sizeof(double)) != hipSuccess) {
+        set_last_error(std::string(call) + ": no stream or no pinned staging memory");
+        rc = SSBA_ERR_HIP;
+    } else {
+        rc = pyr_build(pyr, ref_u8, track_u8, disparity, (char *)stage);
+    }
+    if (stage) { if (pyr->stream) hipStreamSynchronize(pyr->stream); pool_host_free(stage); }
+    if (rc) { pyr_free(pyr); return rc; }
+    *out = pyr;
+    return SSBA_OK;
+}
+
+int ssba_image_pyramid_destroy(ssba_image_pyramid *pyr) {
+    if (!pyr) return pyr_invalid("ssba_image_pyramid_destroy", "NULL pyramid");
+    pyr_free(pyr);
+    return SSBA_OK;
+}
+
+int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, uint32_t *rows, uint32_t *cols, uint8_t *ref_u8, uint8_t *track_u8,
+                             double *ref, double *track, double *gradx, double *grady, double *disparity) {
+    const char *call = "ssba_image_pyramid_level";
+    if (!pyr) return pyr_invalid(call, "NULL pyramid");
+    if (level >= pyr->lv.size()) return pyr_invalid(call, "no such level");
+    if (disparity && (int)level < pyr->disparity_level) return pyr_invalid(call, "levels finer than disparity_level have no disparity map");
+    const ssba_image_pyramid::Level &L = pyr->lv[level];
+    if (rows) *rows = (uint32_t)L.rows;
+    if (cols) *cols = (uint32_t)L.cols;
+    const size_t npix = (size_t)L.rows * L.cols;
+    PYR_HIP(hipSetDevice(pyr->device));
+    if (ref_u8) PYR_HIP(hipMemcpyAsync(ref_u8, L.u8[0], npix, hipMemcpyDeviceToHost, pyr->stream));
+    if (track_u8) PYR_HIP(hipMemcpyAsync(track_u8, L.u8[1], npix, hipMemcpyDeviceToHost, pyr->stream));
+    double *dst[5] = {ref, track, gradx, grady, disparity};
+    const double *src[5] = {L.img[0], L.img[1], L.img[2], L.img[3], L.disp};
+    for (int q = 0; q < 5; ++q)
+        if (dst[q]) PYR_HIP(hipMemcpyAsync(dst[q], src[q], npix * sizeof(double), hipMemcpyDeviceToHost, pyr->stream));
+    PYR_HIP(hipStreamSynchronize(pyr->stream));
+    return SSBA_OK;
+}
+
+// Coarse to fine: the reference's main from :94 on, once per level, the pose carried down.  Levels above disparity_level hold
+// their derived disparities constant (free, they absorb the motion and the pose does not move).
+int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
+                             int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries) {
+    const char *call = "ssba_image_pyramid_align";
+    if (!pyr || !camera0 || !pose || !disparity || !options) return pyr_invalid(call, "NULL argument");
+    if (coarsest_level >= pyr->lv.size()) return pyr_invalid(call, "no such level");
+    if ((int)coarsest_level < pyr->disparity_level) return pyr_invalid(call, "coarsest_level is finer than disparity_level: no disparity map there");
+    if (interpolation != SSBA_IMAGE_NEAREST && interpolation != SSBA_IMAGE_BILINEAR) return pyr_invalid(call, "unknown interpolation");
+    if (options->trust_region_strategy_type != 0) {
+        set_last_error(std::string(call) + ": image blocks are solved with Levenberg-Marquardt only (DOGLEG asked for)");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    std::vector<double> derived;
+    for (int l = (int)coarsest_level; l >= pyr->disparity_level; --l) {
+        const ssba_image_pyramid::Level &L = pyr->lv[l];
+        const bool base = l == pyr->disparity_level;
+        const double s = ldexp(1.0, -l);       // pyrDown samples at even pixels: u_l = u / 2^l exactly
+        const ssba_camera cam = {camera0->fu * s, camera0->fv * s, camera0->cu * s, camera0->cv * s, camera0->b};
+        double *map = disparity;
+        int rc;
+        if (!base) {
+            derived.resize((size_t)L.rows * L.cols);
+            if ((rc = ssba_image_pyramid_level(pyr, (uint32_t)l, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, derived.data()))) return rc;
+            map = derived.data();
+        }
+        ssba_problem *h = nullptr;
+        if ((rc = ssba_create(&cam, pyr->device, &h))) return rc;
+        ssba_summary sum;
+        memset(&sum, 0, sizeof sum);
+        if (!(rc = ssba_add_image_level(h, pyr, (uint32_t)l, pose, map, interpolation)) &&
+            !(rc = ssba_set_disparity_blocks_constant(h, base ? (disparities_constant != 0) : 1)) && !(rc = ssba_finalize(h)))
+            rc = ssba_solve(h, options, &sum);
+        const std::string msg = rc ? std::string(ssba_last_error()) : std::string();
+        ssba_destroy(h);
+        if (rc) { set_last_error(std::string(call) + ": level " + std::to_string(l) + ": " + msg); }
+        if (summaries && (rc == SSBA_OK || rc == SSBA_ERR_NUMERICAL_FAILURE)) summaries[coarsest_level - (uint32_t)l] = sum;
+        if (rc) return rc;      // an unusable solution left the pose (and the map) as they were before this level
+    }
+    return SSBA_OK;
+}
+
+}  // extern "C"

@@ -415,6 +415,30 @@ class ImageAlignment(StereoBA):
     def from_synth(cls, pair, **kw):
         return cls(pair.camera, pair.pose_init.copy(), pair.disparity.copy(), pair.ref, pair.track, pair.gradx, pair.grady, **kw)
 
+    @classmethod
+    def from_pyramid_level(cls, pyramid: "ImagePyramid", level: int, camera: dict, pose, disparity, interpolation: int = capi.IMAGE_BILINEAR,
+                           disparity_const: bool = False, finalize: bool = True):
+        """The handle of one pyramid level (ssba_add_image_level): the four images stay on the device.  ``camera`` is the camera
+        of that level; ``disparity`` the caller-owned map of that level."""
+        self = cls.__new__(cls)
+        self.pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self.poses = self.pose.reshape(1, 12)
+        self.disparity = np.ascontiguousarray(disparity, dtype=np.float64)
+        rows, cols = pyramid.shape(level)
+        if self.disparity.shape != (rows, cols):
+            raise ValueError(f"disparity of shape {self.disparity.shape}, level {level} is {(rows, cols)}")
+        self._imgs = []
+        self._pyramid = pyramid         # read at ssba_finalize
+        self.points = np.zeros((0, 3))
+        self._create(camera, pyramid.device)
+        capi.check(self.lib.ssba_add_image_level(self.h, pyramid.h, int(level), capi.dptr(self.pose), capi.dptr(self.disparity), int(interpolation)),
+                   "ssba_add_image_level")
+        if disparity_const:
+            capi.check(self.lib.ssba_set_disparity_blocks_constant(self.h, 1), "ssba_set_disparity_blocks_constant")
+        if finalize:
+            self.finalize()
+        return self
+
     def solve(self, options: capi.Options = None):
         return super().solve(options or capi.default_options(use_nonmonotonic_steps=1))      # dense_stereo_test.cpp:120-125
 
@@ -427,3 +451,112 @@ class ImageAlignment(StereoBA):
         capi.check(self.lib.ssba_image_step(self.h, C.byref(o), float(radius), C.byref(cost), capi.dptr(r), capi.dptr(Jp), capi.dptr(Jd),
                                             capi.dptr(S), capi.dptr(rhs), capi.dptr(dp), capi.dptr(dd), C.byref(mcc)), "ssba_image_step")
         return ImageStep(cost.value, r, Jp, Jd, S, rhs, dp, dd, mcc.value)
+
+
+class PyramidLevel(NamedTuple):
+    """What ssba_image_pyramid_level returns for one level, and the level-0 camera scaled to it."""
+    ref_u8: np.ndarray          # (rows, cols) uint8
+    track_u8: np.ndarray
+    ref: np.ndarray             # (rows, cols) float64
+    track: np.ndarray
+    gradx: np.ndarray
+    grady: np.ndarray
+    disparity: np.ndarray       # None below disparity_level
+    camera: dict                # None when the pyramid was given no camera
+
+
+class ImagePyramid:
+    """The dense driver's pre-processing on the device (ssba_image_pyramid_create; tests/dense_stereo_test.cpp:52-72): every
+    level of the 8-bit pair halved as cv::pyrDown does, converted, Sobel gradients, and the disparity map of ONE level carried to
+    the coarser ones.  ``camera`` is the level-0 camera (optional: level() and align() scale it)."""
+
+    def __init__(self, ref_u8, track_u8, disparity, levels: int, disparity_level: int = 0,
+                 gradient_source: int = capi.GRADIENT_OF_TRACKED, gradient_scale: float = 0.125, camera: dict = None, device: int = -1):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        ref_u8, track_u8 = (np.ascontiguousarray(a) for a in (ref_u8, track_u8))
+        if ref_u8.dtype != np.uint8 or track_u8.dtype != np.uint8 or ref_u8.ndim != 2 or ref_u8.shape != track_u8.shape:
+            raise ValueError("the pair must be two uint8 images of one shape")
+        rows, cols = ref_u8.shape
+        disparity = np.ascontiguousarray(disparity, dtype=np.float64)
+        if 0 <= disparity_level < 32 and disparity.shape != (rows >> disparity_level, cols >> disparity_level):
+            raise ValueError(f"disparity of shape {disparity.shape}, level {disparity_level} is {(rows >> disparity_level, cols >> disparity_level)}")
+        self.rows, self.cols, self.levels, self.disparity_level, self.device = rows, cols, int(levels), int(disparity_level), device
+        self.camera = dict(camera) if camera is not None else None
+        u8 = C.POINTER(C.c_uint8)
+        capi.check(self.lib.ssba_image_pyramid_create(ref_u8.ctypes.data_as(u8), track_u8.ctypes.data_as(u8), capi.dptr(disparity), rows, cols,
+                                                      int(levels), int(disparity_level), int(gradient_source), float(gradient_scale), device,
+                                                      C.byref(self.h)), "ssba_image_pyramid_create")
+
+    @classmethod
+    def create(cls, ref_u8, track_u8, disparity, levels: int, **kw):
+        return cls(ref_u8, track_u8, disparity, levels, **kw)
+
+    def close(self):
+        if self.h:
+            self.lib.ssba_image_pyramid_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def shape(self, level: int):
+        if not 0 <= level < self.levels:
+            raise ValueError(f"level {level} of a pyramid of {self.levels}")
+        return self.rows >> level, self.cols >> level
+
+    def level_camera(self, level: int, camera: dict = None) -> dict:
+        """fu, fv, cu, cv over 2^level, b unchanged (pyrDown samples at even pixels)."""
+        cam = camera if camera is not None else self.camera
+        if cam is None:
+            return None
+        s = 0.5 ** level
+        return dict(fu=cam["fu"] * s, fv=cam["fv"] * s, cu=cam["cu"] * s, cv=cam["cv"] * s, b=cam["b"])
+
+    def level(self, level: int) -> PyramidLevel:
+        rows, cols = self.shape(level)
+        u8 = [np.zeros((rows, cols), np.uint8) for _ in range(2)]
+        f64 = [np.zeros((rows, cols)) for _ in range(4)]
+        disp = np.zeros((rows, cols)) if level >= self.disparity_level else None
+        r, c = C.c_uint32(), C.c_uint32()
+        capi.check(self.lib.ssba_image_pyramid_level(self.h, level, C.byref(r), C.byref(c), *[a.ctypes.data_as(C.POINTER(C.c_uint8)) for a in u8],
+                                                     *[capi.dptr(a) for a in f64], capi.dptr(disp) if disp is not None else None),
+                   "ssba_image_pyramid_level")
+        assert (r.value, c.value) == (rows, cols)
+        return PyramidLevel(u8[0], u8[1], *f64, disp, self.level_camera(level))
+
+    def handle(self, level: int, camera: dict, pose, disparity, interpolation: int = capi.IMAGE_BILINEAR, disparity_const: bool = False,
+               finalize: bool = True) -> ImageAlignment:
+        """An ImageAlignment on one level through ssba_add_image_level.  ``camera`` is the camera OF THAT LEVEL (level_camera, or
+        the caller's own, as the reference driver keeps its full-resolution one); None takes level_camera(level)."""
+        cam = camera if camera is not None else self.level_camera(level)
+        if cam is None:
+            raise ValueError("no camera: pass one, or give the pyramid its level-0 camera")
+        return ImageAlignment.from_pyramid_level(self, level, cam, pose, disparity, interpolation, disparity_const, finalize)
+
+    def align(self, pose, disparity, coarsest_level: int = None, camera: dict = None, interpolation: int = capi.IMAGE_BILINEAR,
+              disparity_const: bool = False, options: capi.Options = None):
+        """Coarse to fine (ssba_image_pyramid_align) from ``coarsest_level`` (default: the coarsest) down to disparity_level.
+        ``pose`` (12,) and ``disparity`` (the float64 map at disparity_level) are updated in place; ``camera`` is the LEVEL-0
+        camera.  Returns (status, summaries): one summary per level solved, coarsest first."""
+        cam = camera if camera is not None else self.camera
+        if cam is None:
+            raise ValueError("no camera: pass the level-0 camera, or give it to the pyramid")
+        if not (isinstance(pose, np.ndarray) and pose.dtype == np.float64 and pose.flags.c_contiguous and pose.size == 12):
+            raise ValueError("pose must be a contiguous float64 array of 12: it is updated in place")
+        if not (isinstance(disparity, np.ndarray) and disparity.dtype == np.float64 and disparity.flags.c_contiguous):
+            raise ValueError("disparity must be a contiguous float64 array: it is updated in place")
+        if disparity.shape != self.shape(self.disparity_level):
+            raise ValueError(f"disparity of shape {disparity.shape}, level {self.disparity_level} is {self.shape(self.disparity_level)}")
+        top = self.levels - 1 if coarsest_level is None else int(coarsest_level)
+        o = options or capi.default_options(use_nonmonotonic_steps=1)
+        sums = (capi.Summary * max(top - self.disparity_level + 1, 1))()
+        c = capi.Camera(**cam)
+        rc = self.lib.ssba_image_pyramid_align(self.h, C.byref(c), capi.dptr(pose), capi.dptr(disparity), top, int(interpolation),
+                                               int(disparity_const), C.byref(o), sums)
+        if rc not in (0, -3):
+            capi.check(rc, "ssba_image_pyramid_align")
+        return rc, list(sums)

@@ -45,6 +45,7 @@
 #define CERES_SLAM_AMD_CERES_SHIM_HPP_
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -197,6 +198,77 @@ struct Image {
     int rows, cols;
     const double *data;
     Image(int rows_, int cols_, const double *data_) : rows(rows_), cols(cols_), data(data_) {}
+    // an image handed out by ImagePyramid is also one of the four device images (which: 0 ref, 1 track, 2 gradx, 3 grady) of a level
+    ssba_image_pyramid *pyramid = nullptr;
+    int level = -1, which = -1;
+};
+
+// The pre-processing of the dense driver (tests/dense_stereo_test.cpp:52-72: pyrDown, convertTo, Sobel) on the device, in place of
+// the cv::Mat the driver holds per level: built once from the raw 8-bit pair and the disparity map of ONE level
+// (ssba_image_pyramid_create), it hands out std::shared_ptr<const Image> per level.  The images are backed by the device level;
+// their host copy (Image::data) is filled EAGERLY, in the constructor, so every image behaves like a caller-made one.  When the
+// four images of ImageError::Create are the ref / track / gradx / grady of one level, the problem binds the level with
+// ssba_add_image_level and nothing is uploaded from the host.  The images keep the pyramid alive.
+class ImagePyramid {
+ public:
+    ImagePyramid(const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, int rows, int cols, int levels, int disparity_level,
+                 int gradient_source = SSBA_GRADIENT_OF_REFERENCE, double gradient_scale = 1.0, int device = -1)
+        : s_(std::make_shared<State>()) {
+        int rc = ssba_image_pyramid_create(ref_u8, track_u8, disparity, (uint32_t)rows, (uint32_t)cols, (uint32_t)levels, (uint32_t)disparity_level,
+                                           gradient_source, gradient_scale, device, &s_->h);
+        if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_create: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
+        s_->disparity_level = disparity_level;
+        s_->lv.resize((size_t)levels);
+        for (int l = 0; l < levels; ++l) {
+            Level &L = s_->lv[(size_t)l];
+            const size_t npix = (size_t)(rows >> l) * (size_t)(cols >> l);
+            for (int q = 0; q < 4; ++q) L.host[q].resize(npix);
+            if (l >= disparity_level) L.disparity.resize(npix);
+            uint32_t r = 0, c = 0;
+            rc = ssba_image_pyramid_level(s_->h, (uint32_t)l, &r, &c, NULL, NULL, L.host[0].data(), L.host[1].data(), L.host[2].data(), L.host[3].data(),
+                                          l >= disparity_level ? L.disparity.data() : NULL);
+            if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_level: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
+            for (int q = 0; q < 4; ++q) {
+                L.img.push_back(Image((int)r, (int)c, L.host[q].data()));
+                L.img.back().pyramid = s_->h; L.img.back().level = l; L.img.back().which = q;
+            }
+        }
+    }
+    int levels() const { return (int)s_->lv.size(); }
+    int disparity_level() const { return s_->disparity_level; }
+    int rows(int level) const { return s_->lv.at((size_t)level).img[0].rows; }
+    int cols(int level) const { return s_->lv.at((size_t)level).img[0].cols; }
+    std::shared_ptr<const Image> image(int level, int which) const {
+        return std::shared_ptr<const Image>(s_, &s_->lv.at((size_t)level).img.at((size_t)which));
+    }
+    std::shared_ptr<const Image> ref(int level) const { return image(level, 0); }
+    std::shared_ptr<const Image> track(int level) const { return image(level, 1); }
+    std::shared_ptr<const Image> gradx(int level) const { return image(level, 2); }
+    std::shared_ptr<const Image> grady(int level) const { return image(level, 3); }
+    // the host copy of a level's disparity map (levels >= disparity_level): memory for the disparity blocks of that level
+    std::vector<double> &disparity(int level) {
+        if (level < s_->disparity_level) throw std::invalid_argument("ceres_shim: levels finer than disparity_level have no disparity map");
+        return s_->lv.at((size_t)level).disparity;
+    }
+    // fu, fv, cu, cv over 2^level, b unchanged (pyrDown samples at even pixels)
+    static StereoCamera camera(const StereoCamera &level0, int level) {
+        const double s = std::ldexp(1.0, -level);
+        return StereoCamera(level0.fu * s, level0.fv * s, level0.cu * s, level0.cv * s, level0.b);
+    }
+    ssba_image_pyramid *handle() const { return s_->h; }
+
+ private:
+    struct Level {
+        std::vector<double> host[4], disparity;
+        std::vector<Image> img;
+    };
+    struct State {
+        ssba_image_pyramid *h = nullptr;
+        int disparity_level = 0;
+        std::vector<Level> lv;
+        ~State() { if (h) ssba_image_pyramid_destroy(h); }
+    };
+    std::shared_ptr<State> s_;
 };
 
 // include/ceres_slam/image_error.hpp:136-144: blocks (pose 12 = T_track_ref, disparity 1) -> 1 residual at reference pixel (u, v).
@@ -572,8 +644,15 @@ inline const char *shim_prepare(Problem &P, int *rc_out) {
         ssba_camera cam = ssba_camera{f.camera->fu, f.camera->fv, f.camera->cu, f.camera->cv, f.camera->b};
         if ((rc = ssba_create(&cam, -1, &P.h_))) { P.h_ = nullptr; return "ssba_create"; }
         const char *where = nullptr;
-        if ((rc = ssba_add_image_blocks(P.h_, P.image_pose_, P.image_disp_, f.img[0]->data, f.img[1]->data, f.img[2]->data, f.img[3]->data,
+        // ref, track, gradx, grady of ONE pyramid level: the level is bound on the device, nothing is uploaded from the host
+        bool one_level = f.img[0]->pyramid != nullptr;
+        for (int q = 0; q < 4; ++q) one_level = one_level && f.img[q]->pyramid == f.img[0]->pyramid && f.img[q]->level == f.img[0]->level && f.img[q]->which == q;
+        if (one_level) {
+            if ((rc = ssba_add_image_level(P.h_, f.img[0]->pyramid, (uint32_t)f.img[0]->level, P.image_pose_, P.image_disp_, f.interpolation)))
+                where = "ssba_add_image_level";
+        } else if ((rc = ssba_add_image_blocks(P.h_, P.image_pose_, P.image_disp_, f.img[0]->data, f.img[1]->data, f.img[2]->data, f.img[3]->data,
                                         (uint32_t)f.img[0]->rows, (uint32_t)f.img[0]->cols, f.interpolation))) where = "ssba_add_image_blocks";
+        if (where) {}
         else if (n_const && (rc = ssba_set_disparity_blocks_constant(P.h_, 1))) where = "ssba_set_disparity_blocks_constant";
         else if ((rc = ssba_finalize(P.h_))) where = "ssba_finalize";
         if (where) { ssba_destroy(P.h_); P.h_ = nullptr; return where; }
@@ -694,6 +773,60 @@ inline const char *shim_prepare(Problem &P, int *rc_out) {
     return nullptr;
 }
 
+inline ssba_options shim_options(const Solver::Options &options) {
+    ssba_options o;
+    ssba_default_options(&o);
+    o.max_num_iterations = options.max_num_iterations;
+    o.use_nonmonotonic_steps = options.use_nonmonotonic_steps ? 1 : 0;
+    o.minimizer_progress_to_stdout = options.minimizer_progress_to_stdout ? 1 : 0;
+    o.num_threads = options.num_threads;
+    o.num_linear_solver_threads = options.num_linear_solver_threads;
+    o.function_tolerance = options.function_tolerance;
+    o.gradient_tolerance = options.gradient_tolerance;
+    o.parameter_tolerance = options.parameter_tolerance;
+    o.initial_trust_region_radius = options.initial_trust_region_radius;
+    o.trust_region_strategy_type = options.trust_region_strategy_type == DOGLEG ? 1 : 0;
+    o.dogleg_type = options.dogleg_type == SUBSPACE_DOGLEG ? 1 : 0;
+    return o;
+}
+inline void shim_summary(const ssba_summary &s, Solver::Summary *summary) {
+    summary->termination_type = (TerminationType)s.termination_type;
+    summary->num_successful_steps = s.num_successful_steps;
+    summary->num_unsuccessful_steps = s.num_unsuccessful_steps;
+    summary->num_line_search_steps = s.num_line_search_steps;
+    summary->initial_cost = s.initial_cost;
+    summary->final_cost = s.final_cost;
+    summary->total_time_in_seconds = s.total_time_s;
+}
+
+// Coarse to fine on an image pyramid (ssba_image_pyramid_align): one Levenberg-Marquardt solve per level from coarsest_level down
+// to the pyramid's disparity_level, the pose carried along.  level0_camera is the camera of level 0; pose (12) and disparity (the
+// map at disparity_level, e.g. pyramid.disparity(pyramid.disparity_level())) are updated in place.  summaries gets one entry per
+// level solved, coarsest first; a call that fails outright leaves one FAILURE entry with the message.
+inline void SolveCoarseToFine(const Solver::Options &options, ceres_slam::ImagePyramid &pyramid, const ceres_slam::StereoCamera &level0_camera,
+                              double *pose, double *disparity, int coarsest_level, int interpolation, bool disparities_constant,
+                              std::vector<Solver::Summary> *summaries) {
+    const ssba_options o = shim_options(options);
+    const ssba_camera cam = ssba_camera{level0_camera.fu, level0_camera.fv, level0_camera.cu, level0_camera.cv, level0_camera.b};
+    const int n = std::max(coarsest_level - pyramid.disparity_level() + 1, 1);
+    std::vector<ssba_summary> s((size_t)n);
+    std::memset(s.data(), 0, s.size() * sizeof(ssba_summary));
+    for (ssba_summary &x : s) x.termination_type = -1;
+    const int rc = ssba_image_pyramid_align(pyramid.handle(), &cam, pose, disparity, (uint32_t)coarsest_level, interpolation, disparities_constant ? 1 : 0,
+                                            &o, s.data());
+    summaries->clear();
+    for (const ssba_summary &x : s) {
+        if (x.termination_type < 0) break;      // levels the loop did not reach
+        summaries->push_back(Solver::Summary());
+        shim_summary(x, &summaries->back());
+    }
+    if (rc && rc != SSBA_ERR_NUMERICAL_FAILURE) {
+        summaries->push_back(Solver::Summary());
+        summaries->back().termination_type = FAILURE;
+        summaries->back().message = std::string("ssba_image_pyramid_align: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
+    }
+}
+
 // ceres::Solve(options, &problem, &summary) (tests/dataset_vo.cpp:81).  Never throws for
 // solver outcomes: the result is in `summary` (as with Ceres); API misuse throws.
 inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summary *summary) {
@@ -715,29 +848,11 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
     std::vector<double *> &normal_blocks = P.normal_blocks_, &phong_blocks = P.phong_blocks_, &texture_blocks = P.texture_blocks_;
     double (&light)[3] = P.st_light_;
     const bool lighting = !P.intensity_.empty();
-    ssba_options o;
-    ssba_default_options(&o);
-    o.max_num_iterations = options.max_num_iterations;
-    o.use_nonmonotonic_steps = options.use_nonmonotonic_steps ? 1 : 0;
-    o.minimizer_progress_to_stdout = options.minimizer_progress_to_stdout ? 1 : 0;
-    o.num_threads = options.num_threads;
-    o.num_linear_solver_threads = options.num_linear_solver_threads;
-    o.function_tolerance = options.function_tolerance;
-    o.gradient_tolerance = options.gradient_tolerance;
-    o.parameter_tolerance = options.parameter_tolerance;
-    o.initial_trust_region_radius = options.initial_trust_region_radius;
-    o.trust_region_strategy_type = options.trust_region_strategy_type == DOGLEG ? 1 : 0;
-    o.dogleg_type = options.dogleg_type == SUBSPACE_DOGLEG ? 1 : 0;
+    const ssba_options o = shim_options(options);
     ssba_summary s;
     rc = ssba_solve(h, &o, &s);
     if (rc && rc != SSBA_ERR_NUMERICAL_FAILURE) return fail("ssba_solve");
-    summary->termination_type = (TerminationType)s.termination_type;
-    summary->num_successful_steps = s.num_successful_steps;
-    summary->num_unsuccessful_steps = s.num_unsuccessful_steps;
-    summary->num_line_search_steps = s.num_line_search_steps;
-    summary->initial_cost = s.initial_cost;
-    summary->final_cost = s.final_cost;
-    summary->total_time_in_seconds = s.total_time_s;
+    shim_summary(s, summary);
     if (summary->IsSolutionUsable() && P.image_blocks_.empty()) {      // (ImageError blocks: the back end wrote the caller's pose and map itself)
         for (size_t i = 0; i < P.pose_blocks_.size(); ++i) std::memcpy(P.pose_blocks_[i], &poses[12 * i], 12 * sizeof(double));
         for (size_t i = 0; i < P.point_blocks_.size(); ++i) std::memcpy(P.point_blocks_[i], &points[3 * i], 3 * sizeof(double));

@@ -541,6 +541,59 @@ SSBA_API int ssba_set_disparity_blocks_constant(ssba_problem *p, int is_constant
 SSBA_API int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose,
                     double *J_disp, double *S, double *rhs, double *delta_pose, double *delta_disp, double *model_cost_change);
 
+/* ---- dense photometric alignment: the driver's pre-processing and a coarse-to-fine solve ------------------------------
+ * An image pyramid replaces tests/dense_stereo_test.cpp:52-72 (everything between imread / SGBM and the residual blocks): it is
+ * built once from the raw 8-bit pair and one disparity map and holds every level in device memory.  Level 0 is the caller's
+ * rows x cols image; level l is floor(rows / 2^l) x floor(cols / 2^l).
+ *
+ * The arithmetic:
+ *     halving     cv::pyrDown(src, dst, Size(cols / 2, rows / 2)) on CV_8U as the driver calls it (:52-59), in integers:
+ *                     dst[y][x] = (sum_{i,j=-2..2} w_i w_j src[2y+i][2x+j] + 128) >> 8,   w = [1 4 6 4 1],
+ *                 border BORDER_REFLECT_101 (index -1 -> 1, -2 -> 2, n -> n-2, n+1 -> n-3); each level from the rounded 8-bit
+ *                 level above it, as the driver's in-place calls do.
+ *     conversion  I = (double)u8 * (1.0 / 255.0): one multiplication by that constant (convertTo(CV_64F, 1./255.), :62-64)
+ *     gradients   the 3 x 3 Sobel on the converted image, BORDER_REFLECT_101, times gradient_scale, summed as synth.sobel sums:
+ *                     gx = scale * (((p[y-1][x+1] - p[y-1][x-1]) + 2 (p[y][x+1] - p[y][x-1])) + (p[y+1][x+1] - p[y+1][x-1]))
+ *                     gy = scale * (((p[y+1][x-1] - p[y-1][x-1]) + 2 (p[y+1][x] - p[y-1][x])) + (p[y+1][x+1] - p[y-1][x+1]))
+ *                 gradient_scale 1 is cv::Sobel(img, out, -1, 1, 0) (:70-72); 0.125 gives per-pixel slopes.
+ *                 SSBA_GRADIENT_OF_REFERENCE differentiates the reference image, which is what :70-72 does as it stands (under
+ *                 its TODO); SSBA_GRADIENT_OF_TRACKED the tracked image, which is what the functor samples.
+ *     disparity   the caller's map belongs to ONE level, disparity_level, in pixels of that level (the driver runs SGBM after two
+ *                 halvings: 2).  Coarser levels: d_{l+1}[y][x] = d_l[2y][2x] / 2; invalid entries (NaN, +-inf, <= 0) stay
+ *                 invalid.  Finer levels have no map and cannot be aligned.
+ *     camera      of level l from a level-0 camera: fu / 2^l, fv / 2^l, cu / 2^l, cv / 2^l, b (pyrDown samples at even pixels,
+ *                 so u_l = u / 2^l exactly).  The reference driver keeps the full-resolution intrinsics at level 2 (:22-27
+ *                 against :52-59); a caller who wants that hands its own camera to the handle.  The pyramid forces none.
+ *
+ * create: the work runs on the pyramid's own stream and is complete on return; device memory comes from the library's pool.
+ *   SSBA_ERR_INVALID_ARGUMENT: a NULL array, levels = 0, disparity_level >= levels, an unknown gradient source, a non-finite or
+ *   zero gradient_scale, a level with fewer than 8 rows or columns.  SSBA_ERR_NO_DEVICE as for a problem handle.
+ * level: downloads whichever outputs are not NULL (rows * cols of that level each); the disparity exists for
+ *   level >= disparity_level only (SSBA_ERR_INVALID_ARGUMENT when asked for below it).
+ * ssba_add_image_level: ssba_add_image_blocks with the four images of a level.  pose (12) and disparity (rows * cols of the level)
+ *   are caller-owned and updated in place, exactly as there; the blocks are the finite positive entries of the CALLER's map at
+ *   ssba_finalize.  ssba_finalize copies the images device to device into the handle's own buffers: the pyramid must live until
+ *   then and may be destroyed afterwards, and no image crosses the host.  Refusals as ssba_add_image_blocks, plus
+ *   SSBA_ERR_INVALID_ARGUMENT when the handle's device differs from the pyramid's or level < disparity_level.
+ * align: coarse to fine.  For l = coarsest_level ... disparity_level: a handle with camera0 scaled to l on the level, a
+ *   Levenberg-Marquardt solve with `options`, the pose carried to the next level.  Levels above disparity_level hold their derived
+ *   disparities constant (free, they absorb the motion and the pose never moves) and leave no trace in the caller's map; the base
+ *   level follows disparities_constant and updates `disparity` (the map at disparity_level) in place.  summaries (may be NULL)
+ *   has coarsest_level - disparity_level + 1 entries; summaries[coarsest_level - l] is level l's.  A level that ends without a
+ *   usable solution stops the loop and returns its status; the pose is then the last usable one. */
+typedef struct ssba_image_pyramid ssba_image_pyramid;
+#define SSBA_GRADIENT_OF_REFERENCE 0
+#define SSBA_GRADIENT_OF_TRACKED 1
+SSBA_API int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, uint32_t rows, uint32_t cols,
+                              uint32_t levels, uint32_t disparity_level, int gradient_source, double gradient_scale, int device,
+                              ssba_image_pyramid **out);
+SSBA_API int ssba_image_pyramid_destroy(ssba_image_pyramid *pyr);
+SSBA_API int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, uint32_t *rows, uint32_t *cols, uint8_t *ref_u8, uint8_t *track_u8,
+                             double *ref, double *track, double *gradx, double *grady, double *disparity);
+SSBA_API int ssba_add_image_level(ssba_problem *p, ssba_image_pyramid *pyr, uint32_t level, double *pose, double *disparity, int interpolation);
+SSBA_API int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
+                             int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries);
+
 /* ---- front end: the VO initial guess --------------------------------- */
 /* ssba_frontend_ransac replaces, for `num_pairs` pairs of consecutive states at once,
  *   PointCloudAligner::compute_transformation_and_inliers (src/ceres_slam/point_cloud_aligner.cpp:64-136)

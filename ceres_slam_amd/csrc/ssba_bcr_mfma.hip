@@ -60,7 +60,8 @@ static __device__ __forceinline__ double mf_rsqrt(double a) {
 #endif
 #define MF_STAMP(i) do { if (bx == SSBA_STAMP_BX && by == 0 && (threadIdx.x & 63) == 0) d.dbg[(threadIdx.x >> 6) * 64 + (i)] = clock64(); } while (0)
 // phases of EVERY workgroup (its thread 0) on the chip-wide 100 MHz clock: 0 entry, 1 loaded, 2 factored, 3 staged, 4 done,
-// 6 through the prologue (operands resolved, hand-off words initialised: the first load is issued next)
+// 6 through the prologue (operands resolved, hand-off words initialised: the first load is issued next), 7 operands resolved
+// (fused_ops: the scalar loads from the kernel arguments and the address arithmetic are done)
 #define MF_WG_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 500) d.dbg[4096 + 8 * (int)blockIdx.x + (k)] = wall_clock64(); } while (0)
 #else
 #define MF_STAMP(i) do { } while (0)
@@ -179,93 +180,125 @@ static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top
     return true;
 }
 
-// Operands of block bx in step `lev` (stride 1 << lev) of the fused plan, or of its decoupled last step (top).  Step 0 reads
-// the level's own D / L / r; step q >= 1 assembles them from what step q - 1 left (see PcrFused).
-// which = 2: the plan of the chain (d.pcr), 3: the separator system of a partitioned solve (d.spcr, solution into d.xsep).
-// Chains with pinned ends (P.pin0 / P.pin1, see PcrPlan): a pinned block is never factored -- it folds its neighbours like
-// every block (it is assembled) -- and never folded: a block whose neighbour at the current stride is pinned, or beyond the
-// chain, KEEPS its coupling to the pinned block from then on (PcrFused::Lkeep / Ukeep).
-static __device__ __forceinline__ void fused_ops(const Dev &d, int which, int lev, int top, int bx, FactorOps &o) {
+// Everything about a fused step (or the decoupled last step) that is known when the launch is enqueued, resolved on the host
+// and passed by value: the kernel adds only the block index.  (Derived in the kernel from (which, lev) and the by-value Dev,
+// the same pointers cost three rounds of DEPENDENT scalar loads -- which plan, which level, that level's fields -- in
+// front of the first vector load.)
+struct FusedStep {
+    double *D, *L, *r;                      // the level's own blocks, row-major (the last step factors in place)
+    const int *pos;                         // level-0 position of each block
+    int n, pin0, pin1, chain0;
+    const double *Din, *GLLin, *GUUin, *GULin, *GULTin;      // what the previous step left: PcrFused set (lev - 1) & 1
+    double *Dout, *GLLout, *GUUout, *GULout, *GULTout;        // what this step leaves: set lev & 1
+    double *Lkeep, *Ukeep;
+    double *YL, *YU, *Lbuf;                 // the decoupled last step of a chain with pinned ends
+    double *x;                              // where the solution goes (chain: x0 + chain0 * BD, separator system: xsep)
+};
+static FusedStep fused_step_args(const Dev &d, int which, int lev) {
     const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
     const PcrFused &F = which == 3 ? d.spcrf : d.pcrf;
     const BcrLevel &B = which == 3 ? d.slev[0] : d.lev[P.level];
+    const int in = lev >= 1 ? (lev - 1) & 1 : 0, out = lev & 1;
+    FusedStep a;
+    a.D = B.D; a.L = B.L; a.r = B.r; a.pos = B.pos;
+    a.n = B.n; a.pin0 = P.pin0; a.pin1 = P.pin1; a.chain0 = d.chain0;
+    a.Din = F.Dpp[in]; a.GLLin = F.GLL[in]; a.GUUin = F.GUU[in]; a.GULin = F.GUL[in]; a.GULTin = F.GULT[in];
+    a.Dout = F.Dpp[out]; a.GLLout = F.GLL[out]; a.GUUout = F.GUU[out]; a.GULout = F.GUL[out]; a.GULTout = F.GULT[out];
+    a.Lkeep = F.Lkeep; a.Ukeep = F.Ukeep;
+    a.YL = P.YL; a.YU = P.YU; a.Lbuf = P.Lbuf;
+    a.x = which == 3 ? d.xsep : d.x0 + (size_t)d.chain0 * BD;
+    return a;
+}
+// Operands of block bx in step `lev` (stride 1 << lev) of the fused plan, or of its decoupled last step (top).  Step 0 reads
+// the level's own D / L / r; step q >= 1 assembles them from what step q - 1 left (see PcrFused).
+// The plan's buffers arrive resolved (FusedStep): the chain's own plan or the separator system of a partitioned solve.
+// Chains with pinned ends (pin0 / pin1, see PcrPlan): a pinned block is never factored -- it folds its neighbours like
+// every block (it is assembled) -- and never folded: a block whose neighbour at the current stride is pinned, or beyond the
+// chain, KEEPS its coupling to the pinned block from then on (PcrFused::Lkeep / Ukeep).
+static __device__ __forceinline__ void fused_ops(const FusedStep &a, int lev, int top, int bx, FactorOps &o) {
     const size_t blk = (size_t)BD * BD, isym = PCR_IMG_SYM, ifull = PCR_IMG_FULL;     // row-major blocks; tile images of the plan's own buffers
-    const int s = 1 << lev, h = s >> 1, last = B.n - 1, e = bx;
-    const int lo = P.pin0 ? 1 : 0, hi = P.pin1 ? last - 1 : last;          // the blocks that are factored (and folded by others)
+    const int s = 1 << lev, h = s >> 1, last = a.n - 1, e = bx;
+    const int lo = a.pin0 ? 1 : 0, hi = a.pin1 ? last - 1 : last;          // the blocks that are factored (and folded by others)
     o.saveU = o.saveL = nullptr; o.Bg = nullptr; o.oYB = nullptr; o.xsol = nullptr;
     o.oYL = o.oYU = nullptr;
     o.GA = o.GB = nullptr;
     o.nD = o.nr = nullptr;
     o.imgD = lev >= 2; o.imgR = lev >= 1;
     o.pinned = e < lo || e > hi;
-    const bool pinned_chain = P.pin0 || P.pin1;
+    const bool pinned_chain = a.pin0 || a.pin1;
     // couplings of this block at this stride: to e -/+ s, or the kept one to the pinned end; the decoupled last step of a
     // pinned chain still carries the kept ones
     // (in the decoupled last step s >= n: only kept couplings are left)
-    o.hasL = e >= 1 && (e - s >= 0 || P.pin0);
-    o.hasU = e <= last - 1 && (e + s <= last || P.pin1);
+    o.hasL = e >= 1 && (e - s >= 0 || a.pin0);
+    o.hasU = e <= last - 1 && (e + s <= last || a.pin1);
     if (o.pinned) {     // no right-hand sides, except that the pinned last block tracks its coupling to the pinned first one
         o.hasU = false;
-        o.hasL = e == last && e >= 1 && P.pin0 && P.pin1;
+        o.hasL = e == last && e >= 1 && a.pin0 && a.pin1;
     }
     o.trL = o.trU = false;
     o.sgnL = o.sgnU = 1.0;
-    o.Lg = B.L + e * blk; o.Ug = B.L + e * blk;         // (never read without hasL / hasU)
+    o.Lg = a.L + e * blk; o.Ug = a.L + e * blk;         // (never read without hasL / hasU)
     if (lev == 0) {
-        o.Dg = B.D + e * blk; o.rin = B.r + (size_t)e * BD;
-        o.Lg = B.L + e * blk; o.Ug = B.L + (size_t)(e < last ? e + 1 : e) * blk;
+        o.Dg = a.D + e * blk; o.rin = a.r + (size_t)e * BD;
+        o.Lg = a.L + e * blk; o.Ug = a.L + (size_t)(e < last ? e + 1 : e) * blk;
         o.trL = o.trU = (e & 1) == 0;       // even coupling blocks of a level are stored transposed (ssba_bcr.hip)
     } else {
-        const int set = (lev - 1) & 1, prev = e - h, next = e + h;
-        o.Lg = o.Ug = F.GUL[set] + e * ifull;           // (an absent coupling's lanes still read: somewhere an image's extent is valid)
-        o.Dg = lev == 1 ? B.D + e * blk : F.Dpp[(lev - 1) & 1] + e * isym;       // (an image carries its r in column 72)
-        o.rin = B.r + (size_t)e * BD;
-        if (prev >= lo) o.GA = F.GUU[set] + prev * isym;
-        if (next <= hi) o.GB = F.GLL[set] + next * isym;
+        const int prev = e - h, next = e + h;
+        o.Lg = o.Ug = a.GULin + e * ifull;           // (an absent coupling's lanes still read: somewhere an image's extent is valid)
+        o.Dg = lev == 1 ? a.D + e * blk : a.Din + e * isym;       // (an image carries its r in column 72)
+        o.rin = a.r + (size_t)e * BD;
+        if (prev >= lo) o.GA = a.GUUin + prev * isym;
+        if (next <= hi) o.GB = a.GLLin + next * isym;
         // the coupling was renewed by the last step iff the neighbour at half the stride was folded; else it is a kept one
-        if (o.hasL) { if (prev >= lo) { o.Lg = F.GUL[set] + prev * ifull; o.sgnL = -1.0; } else o.Lg = F.Lkeep + e * ifull; }
-        if (o.hasU) { if (next <= hi) { o.Ug = F.GULT[set] + next * ifull; o.sgnU = -1.0; } else o.Ug = F.Ukeep + e * ifull; }
-        if (!top) o.nD = F.Dpp[lev & 1] + e * isym;
+        if (o.hasL) { if (prev >= lo) { o.Lg = a.GULin + prev * ifull; o.sgnL = -1.0; } else o.Lg = a.Lkeep + e * ifull; }
+        if (o.hasU) { if (next <= hi) { o.Ug = a.GULTin + next * ifull; o.sgnU = -1.0; } else o.Ug = a.Ukeep + e * ifull; }
+        if (!top) o.nD = a.Dout + e * isym;
     }
     if (pinned_chain && !top) {
         // save a coupling when the NEXT step will find it kept (its half-stride neighbour, e -/+ s, pinned or outside) and this
         // step did not read it from the keep buffer already
-        if (o.hasL && e - s < lo && o.Lg != F.Lkeep + e * ifull) o.saveL = F.Lkeep + e * ifull;
-        if (o.hasU && e + s > hi && o.Ug != F.Ukeep + e * ifull) o.saveU = F.Ukeep + e * ifull;
+        if (o.hasL && e - s < lo && o.Lg != a.Lkeep + e * ifull) o.saveL = a.Lkeep + e * ifull;
+        if (o.hasU && e + s > hi && o.Ug != a.Ukeep + e * ifull) o.saveU = a.Ukeep + e * ifull;
     }
     // the Gram products somebody reads: the next step's block e - s / e + s assembles from them (a kept coupling feeds nobody's D)
     o.gLL = o.hasL && e - s >= 0 && !top;
     o.gUU = o.hasU && e + s <= last && !top;
     o.gUL = o.hasL && o.hasU && !top;
-    o.oD = top ? B.D + e * blk : nullptr;
-    o.orr = top ? B.r + (size_t)e * BD : nullptr;
+    o.oD = top ? a.D + e * blk : nullptr;
+    o.orr = top ? a.r + (size_t)e * BD : nullptr;
     if (top) {
-        o.xsol = which == 3 ? d.xsep + (size_t)B.pos[e] * BD : d.x0 + (size_t)d.chain0 * BD + (size_t)B.pos[e] * BD;
-        o.f0 = (d.chain0 + B.pos[e]) * SBP;
+        o.xsol = a.x + (size_t)a.pos[e] * BD;
+        o.f0 = (a.chain0 + a.pos[e]) * SBP;
         if (pinned_chain) {         // the factor outputs k_bcr_backsub reads after the separator solve; the pinned rows in place
             o.xsol = nullptr;
-            o.oYL = o.hasL ? P.YL + e * blk : nullptr;
-            o.oYU = o.hasU ? P.YU + e * blk : nullptr;
-            if (o.pinned) { o.nD = B.D + e * blk; o.nr = B.r + (size_t)e * BD; }
+            o.oYL = o.hasL ? a.YL + e * blk : nullptr;
+            o.oYU = o.hasU ? a.YU + e * blk : nullptr;
+            if (o.pinned) { o.nD = a.D + e * blk; o.nr = a.r + (size_t)e * BD; }
             // S[last, first], for k_sep_pack: the pinned last block's coupling to the pinned first one
-            if (o.pinned && e == last && P.pin0 && P.pin1) o.saveL = P.Lbuf + e * blk;
+            if (o.pinned && e == last && a.pin0 && a.pin1) o.saveL = a.Lbuf + e * blk;
         }
     }
-    const int oset = lev & 1;
-    o.oGLL = F.GLL[oset] + e * isym; o.oGUU = F.GUU[oset] + e * isym;
-    o.oGUL = F.GUL[oset] + e * ifull; o.oGULT = F.GULT[oset] + e * ifull;
+    o.oGLL = a.GLLout + e * isym; o.oGUU = a.GUUout + e * isym;
+    o.oGUL = a.GULout + e * ifull; o.oGULT = a.GULTout + e * ifull;
 }
 
 // One tile image (ssba_types.h) <-> the accumulator registers of a wave: two 16-byte accesses per lane.
+// The images are written at the end of one launch and read by the next: they leave WRITE-THROUGH (buffer stores with the
+// sc1 bit), so that the launch does not end on an L2 full of dirty lines whose write-back the next launch waits for.
+// base and tile are wave-uniform (the buffer descriptor lives in scalar registers); a descriptor spans exactly one image.
 static __device__ __forceinline__ mf_d4 img_load(const double *base, int tile, int lane) {
     const double2 *p = reinterpret_cast<const double2 *>(base) + tile * (PCR_IMG_TILE / 2) + lane;
     const double2 a = p[0], b = p[64];
     return mf_d4{a.x, a.y, b.x, b.y};
 }
 static __device__ __forceinline__ void img_store(double *base, int tile, int lane, const mf_d4 &v) {
-    double2 *p = reinterpret_cast<double2 *>(base) + tile * (PCR_IMG_TILE / 2) + lane;
-    p[0] = make_double2(v[0], v[1]);
-    p[64] = make_double2(v[2], v[3]);
+    typedef unsigned img_u4 __attribute__((ext_vector_type(4)));
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(base + tile * PCR_IMG_TILE, 0, PCR_IMG_TILE * (int)sizeof(double), 0x00020000);
+    const img_u4 lo = {(unsigned)__double2loint(v[0]), (unsigned)__double2hiint(v[0]), (unsigned)__double2loint(v[1]), (unsigned)__double2hiint(v[1])};
+    const img_u4 hi = {(unsigned)__double2loint(v[2]), (unsigned)__double2hiint(v[2]), (unsigned)__double2loint(v[3]), (unsigned)__double2hiint(v[3])};
+    constexpr int IMG_WRITE_THROUGH = 16;       // aux: sc1
+    __builtin_amdgcn_raw_buffer_store_b128(lo, rs, 16 * lane, 0, IMG_WRITE_THROUGH);
+    __builtin_amdgcn_raw_buffer_store_b128(hi, rs, 16 * lane + PCR_IMG_TILE * (int)sizeof(double) / 2, 0, IMG_WRITE_THROUGH);
 }
 // tile (ti, tj), ti <= tj, of the 15 upper tiles
 static __device__ __forceinline__ int img_sym_tile(int ti, int tj) { return (ti == 4 ? 14 : ti == 3 ? 12 : ti == 2 ? 9 : ti == 1 ? 5 : 0) + tj - ti; }
@@ -334,15 +367,21 @@ constexpr int MF_THREADS2 = 512;
 // 0..3), ROLE 2: right-hand-side tiles only (waves 4..7) -- so that neither role carries the other's register arrays
 // (one body with run-time roles needed 538 spilled registers at the 256 a wave of a 512-lane workgroup may use).
 template <int NRW, int MODE, int ROLE>
-static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, double *mf_solve_lds, int lev, int top, int which, int nblocks, int ns, int rlo, int nrt, int solve) {
+static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep &fa, FactorLds &S, double *mf_solve_lds, int lev, int top, int which, int nblocks, int ns, int rlo, int nrt, int solve) {
     constexpr bool HAS_D = ROLE != 2, HAS_R = ROLE != 1;
     State &st = *d.st;
     const StateFlags sf = state_flags_vmem(d.st);       // tested once the operand reads are in flight (ssba_device.h)
     FactorOps o;
     int bx, by;
     xcd_map((int)blockIdx.x, nblocks, ns, bx, by);
-    if (MODE) fused_ops(d, which, lev, top, bx, o);
+    if (MODE) fused_ops(fa, lev, top, bx, o);
     else if (!factor_ops(d, lev, top, which, bx, by == 0, nrt > NRT, o)) return;
+#ifdef SSBA_STAMPS
+    if (MODE) {     // the operand pointers exist in registers: what is left of the prologue is the hand-off words and the barrier
+        asm volatile("" ::"s"(o.Dg), "s"(o.Lg), "s"(o.Ug), "s"(o.GA), "s"(o.GB), "s"(o.oGUL));
+        MF_WG_STAMP(7);
+    }
+#endif
     const int t = threadIdx.x, lane = t & 63, g = lane >> 4, j = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr bool rwave = HAS_R;       // this wave carries right-hand-side tiles
@@ -1011,7 +1050,7 @@ static __device__ __forceinline__ void factor_body(const Dev &d, FactorLds &S, d
 }
 
 template <int NRW, int MODE>
-__global__ __launch_bounds__(MODE == 2 ? MF_THREADS2 : MF_THREADS) void k_bcr_factor_mf(Dev d, int lev, int top, int which, int nblocks, int ns, int rlo, int nrt, int solve) {
+__global__ __launch_bounds__(MODE == 2 ? MF_THREADS2 : MF_THREADS) void k_bcr_factor_mf(Dev d, int lev, int top, int which, int nblocks, int ns, int rlo, int nrt, int solve, FusedStep fa) {
     __shared__ FactorLds S;
     extern __shared__ __align__(16) double mf_dyn_lds[];
 #ifdef SSBA_STAMPS
@@ -1023,10 +1062,10 @@ __global__ __launch_bounds__(MODE == 2 ? MF_THREADS2 : MF_THREADS) void k_bcr_fa
     }
 #endif
     if (MODE == 2) {
-        if (threadIdx.x < MF_THREADS) factor_body<0, 2, 1>(d, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
-        else factor_body<NRW, 2, 2>(d, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
+        if (threadIdx.x < MF_THREADS) factor_body<0, 2, 1>(d, fa, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
+        else factor_body<NRW, 2, 2>(d, fa, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
     } else {
-        factor_body<NRW, MODE, 0>(d, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
+        factor_body<NRW, MODE, 0>(d, fa, S, mf_dyn_lds, lev, top, which, nblocks, ns, rlo, nrt, solve);
     }
 }
 
@@ -1491,10 +1530,10 @@ void launch_bcr_factor_mf(Launcher &L, const Dev &d, int nblocks, int lev, int t
     const int per_wg = (nrt - rlo + ns - 1) / ns;
     const int grid = xcd_grid(nblocks, ns);
     const size_t sh_solve = (size_t)(BD * BD + 2 * BD) * sizeof(double);
-    if (!coupled && !ride) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 0>), dim3(grid), dim3(MF_THREADS), solve ? sh_solve : 0, d, lev, top, which, nblocks, ns, rlo, nrt, solve);
-    else if (per_wg <= 3) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<1, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0);
-    else if (per_wg <= 7) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<2, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0);
-    else LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0);
+    if (!coupled && !ride) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 0>), dim3(grid), dim3(MF_THREADS), solve ? sh_solve : 0, d, lev, top, which, nblocks, ns, rlo, nrt, solve, FusedStep{});
+    else if (per_wg <= 3) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<1, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0, FusedStep{});
+    else if (per_wg <= 7) LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<2, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0, FusedStep{});
+    else LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 0>), dim3(grid), dim3(MF_THREADS), 0, d, lev, top, which, nblocks, ns, rlo, nrt, 0, FusedStep{});
 }
 
 // Fused plan (PcrFused): step q = factorisation of every block at stride 2^q + the Gram products the next step assembles its
@@ -1503,16 +1542,16 @@ void launch_bcr_factor_mf(Launcher &L, const Dev &d, int nblocks, int lev, int t
 constexpr size_t FUSED_LDS = (size_t)2 * BD * 80 * sizeof(double);
 void launch_pcr_fused_step(Launcher &L, const Dev &d, int n, int q, int which) {
     const int ns = n <= 85 ? 3 : 2;         // (a plan has at most PCR_MAX_BLOCKS = 128 blocks; the kernel's tile share assumes ns >= 2; 2 at C2: 0.372 against 0.364 ms)
-    LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 2>), dim3(xcd_grid(n, ns)), dim3(MF_THREADS2), FUSED_LDS, d, q, 0, which, n, ns, 0, NRT, 0);
+    LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 2>), dim3(xcd_grid(n, ns)), dim3(MF_THREADS2), FUSED_LDS, d, q, 0, which, n, ns, 0, NRT, 0, fused_step_args(d, which, q));
 }
 void launch_pcr_fused_top(Launcher &L, const Dev &d, int n, int steps, int solve, int which) {
     const size_t sh_solve = (size_t)(BD * BD + 2 * BD) * sizeof(double);
     const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
     if (P.pin0 || P.pin1) {     // a chain with pinned ends: its blocks keep their couplings to those (right-hand-side tiles), nothing is solved yet
-        LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), 0, d, steps, 1, which, n, 1, 0, NRT, 0);
+        LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), 0, d, steps, 1, which, n, 1, 0, NRT, 0, fused_step_args(d, which, steps));
         return;
     }
-    LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), solve ? sh_solve : 0, d, steps, 1, which, n, 1, 0, NRT, solve);
+    LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), solve ? sh_solve : 0, d, steps, 1, which, n, 1, 0, NRT, solve, fused_step_args(d, which, steps));
 }
 
 // ny: 2, or 3 with the coupling to a pinned last block

@@ -384,7 +384,7 @@ int main(int argc, char **argv) {
             }
             {   // the same phases as intervals, averaged over the blocks with both couplings at stride 8 and over the end blocks
                 const int ny = n <= 85 ? 3 : 2, nwg = n * ny;
-                double sum[2][5] = {{0}};
+                double sum[2][6] = {{0}};
                 int cnt[2] = {0, 0};
                 auto host_map2 = [&](int id, int &e, int &y) {
                     const int N = n * ny, c = id & 7, q = (N + 7) >> 3, r = (N + 7) & 7;
@@ -396,7 +396,7 @@ int main(int argc, char **argv) {
                         idx -= sk;
                     }
                 };
-                printf("fused step 3, intervals in us: entry->prologue prologue->loaded loaded->factored factored->staged staged->done\n");
+                printf("fused step 3, intervals in us: entry->prologue prologue->loaded loaded->factored factored->staged staged->done | entry->operands resolved\n");
                 for (int g = 0; g < nwg && g < 500; ++g) {
                     int e, y;
                     host_map2(g, e, y);
@@ -408,15 +408,16 @@ int main(int argc, char **argv) {
                         const int c = (hasL && hasU) ? 0 : 1;
                         ++cnt[c];
                         for (int k = 0; k < 5; ++k) sum[c][k] += iv[k];
+                        sum[c][5] += (double)(long long)(s[7] - s[0]) / 100.0;
                     }
 #ifdef SSBA_STAMP_BX
-                    if (e == SSBA_STAMP_BX) printf("  block %d part %d (wg %d): %.2f %.2f %.2f %.2f %.2f\n", e, y, g, iv[0], iv[1], iv[2], iv[3], iv[4]);
+                    if (e == SSBA_STAMP_BX) printf("  block %d part %d (wg %d): %.2f %.2f %.2f %.2f %.2f | %.2f\n", e, y, g, iv[0], iv[1], iv[2], iv[3], iv[4], (double)(long long)(s[7] - s[0]) / 100.0);
 #endif
                 }
                 for (int c = 0; c < 2; ++c) {
                     printf("  mean of %3d workgroups of %s:", cnt[c], c == 0 ? "middle blocks (both couplings)" : "end blocks (one coupling)   ");
                     for (int k = 0; k < 5; ++k) printf(" %.2f", cnt[c] ? sum[c][k] / cnt[c] : 0.0);
-                    printf("\n");
+                    printf(" | %.2f\n", cnt[c] ? sum[c][5] / cnt[c] : 0.0);
                 }
             }
             for (int w = 0; w < 8; ++w) {

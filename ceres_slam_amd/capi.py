@@ -40,6 +40,7 @@ SYMBOLS = [
     "ssba_rccl_describe", "ssba_rccl_ranks", "ssba_armijo_trace", "ssba_debug_stamps", "ssba_covariance_blocks",
     "ssba_add_image_blocks", "ssba_set_disparity_blocks_constant", "ssba_image_step",
     "ssba_image_pyramid_create", "ssba_image_pyramid_destroy", "ssba_image_pyramid_level", "ssba_add_image_level", "ssba_image_pyramid_align",
+    "ssba_sgbm_default_params", "ssba_stereo_sgbm", "ssba_image_pyramid_create_stereo",
 ]
 
 
@@ -70,6 +71,12 @@ class CovBlock(C.Structure):
 LEVENBERG_MARQUARDT, DOGLEG = 0, 1
 IMAGE_NEAREST, IMAGE_BILINEAR = 0, 1     # SSBA_IMAGE_NEAREST / SSBA_IMAGE_BILINEAR
 GRADIENT_OF_REFERENCE, GRADIENT_OF_TRACKED = 0, 1     # SSBA_GRADIENT_OF_REFERENCE / SSBA_GRADIENT_OF_TRACKED
+
+
+class SgbmParams(C.Structure):
+    """ssba_sgbm_params; sgbm_params(**kw) fills in the driver's defaults."""
+    _fields_ = [(n, C.c_int32) for n in ("min_disparity", "num_disparities", "block_size", "p1", "p2", "disp12_max_diff", "pre_filter_cap",
+                                         "uniqueness_ratio", "speckle_window_size", "speckle_range", "full_dp")]
 
 
 class Summary(C.Structure):
@@ -178,6 +185,11 @@ def load():
     L.ssba_image_pyramid_level.argtypes = [H, C.c_uint32, _u32p, _u32p, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp]
     L.ssba_add_image_level.argtypes = [H, H, C.c_uint32, _dp, _dp, C.c_int]
     L.ssba_image_pyramid_align.argtypes = [H, C.POINTER(Camera), _dp, _dp, C.c_uint32, C.c_int, C.c_int, C.POINTER(Options), C.POINTER(Summary)]
+    L.ssba_sgbm_default_params.argtypes = [C.POINTER(SgbmParams)]
+    L.ssba_sgbm_default_params.restype = None
+    L.ssba_stereo_sgbm.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_int, C.POINTER(C.c_int16), _dp]
+    L.ssba_image_pyramid_create_stereo.argtypes = [_u8p, _u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_int,
+                                                   C.c_double, C.c_int, C.POINTER(H)]
     L.ssba_ransac_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_int, _u32p]
     L.ssba_frontend_ransac.argtypes = [C.POINTER(Camera), C.c_int, C.c_uint32, _u32p, _dp, _dp, _u32p, C.c_uint32, C.c_double, _dp,
                                        C.POINTER(C.c_uint8), _u32p, _dp]
@@ -202,6 +214,17 @@ def default_options(**kw) -> Options:
             raise AttributeError(k)
         setattr(o, k, v)
     return o
+
+
+def sgbm_params(**kw) -> SgbmParams:
+    """ssba_sgbm_default_params (minimum disparity 0, 64 disparities, block size 15, zeros for the rest) with overrides."""
+    p = SgbmParams()
+    load().ssba_sgbm_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v))
+    return p
 
 
 def dptr(a: np.ndarray):

@@ -10,6 +10,11 @@
 //     k_pyr_finish  per level, one lane per pixel: ref and track as double, the two Sobel images of the chosen source, and above
 //                   disparity_level the disparity d_l[y][x] = d_{l-1}[2 y][2 x] / 2
 // No atomics and no sums across lanes: two builds give the same bits.
+//
+// ssba_image_pyramid_create_stereo has no disparity map to upload: the right image of the reference instant is halved down to
+// disparity_level by the same k_pyr_down (one more launch per level, on levels that only the matcher reads) and the semi-global
+// matcher of ssba_sgbm.hip writes its double map straight into the level's disparity buffer, ahead of the k_pyr_finish that
+// derives the next level from it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -21,6 +26,7 @@
 #include "../../include/ssba.h"
 #include "ssba_image_pyramid.h"
 #include "ssba_pool.h"
+#include "ssba_sgbm.h"
 
 namespace ssba {
 
@@ -116,8 +122,17 @@ static void pyr_free(ssba_image_pyramid *pyr) {
         }                                                                                              \
     } while (0)
 
-static int pyr_build(ssba_image_pyramid *pyr, const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, char *stage) {
+// disparity: the caller's map at disparity_level, or nullptr with right_u8 and the matcher's plan for that level
+static int pyr_build(ssba_image_pyramid *pyr, const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, const uint8_t *right_u8,
+                     const SgbmPlan *plan, char *stage, std::vector<void *> *temps) {
     const int n = (int)pyr->lv.size(), dl = pyr->disparity_level;
+    std::vector<uint8_t *> right(right_u8 ? dl + 1 : 0, nullptr);
+    for (size_t l = 0; l < right.size(); ++l) {      // the right levels and the matcher's volumes are released when the build is complete
+        void *ptr = nullptr;
+        PYR_HIP(pool_malloc(&ptr, (size_t)pyr->lv[l].rows * pyr->lv[l].cols));
+        temps->push_back(ptr);
+        right[l] = (uint8_t *)ptr;
+    }
     for (int l = 0; l < n; ++l) {
         ssba_image_pyramid::Level &L = pyr->lv[l];
         const size_t npix = (size_t)L.rows * L.cols;
@@ -129,11 +144,13 @@ static int pyr_build(ssba_image_pyramid *pyr, const uint8_t *ref_u8, const uint8
     memcpy(stage, ref_u8, n0);
     memcpy(stage + n0, track_u8, n0);
     const size_t od = (2 * n0 + 255) / 256 * 256;
-    memcpy(stage + od, disparity, nd * sizeof(double));
+    if (disparity) memcpy(stage + od, disparity, nd * sizeof(double));
+    else memcpy(stage + od, right_u8, n0);
     hipStream_t s = pyr->stream;
     PYR_HIP(hipMemcpyAsync(pyr->lv[0].u8[0], stage, n0, hipMemcpyHostToDevice, s));
     PYR_HIP(hipMemcpyAsync(pyr->lv[0].u8[1], stage + n0, n0, hipMemcpyHostToDevice, s));
-    PYR_HIP(hipMemcpyAsync(pyr->lv[dl].disp, stage + od, nd * sizeof(double), hipMemcpyHostToDevice, s));
+    if (disparity) PYR_HIP(hipMemcpyAsync(pyr->lv[dl].disp, stage + od, nd * sizeof(double), hipMemcpyHostToDevice, s));
+    else PYR_HIP(hipMemcpyAsync(right[0], stage + od, n0, hipMemcpyHostToDevice, s));
     for (int l = 0; l < n; ++l) {
         const ssba_image_pyramid::Level &L = pyr->lv[l];
         const dim3 grid((L.cols + PYR_TW - 1) / PYR_TW, (L.rows + PYR_TH - 1) / PYR_TH, 1);
@@ -142,7 +159,13 @@ static int pyr_build(ssba_image_pyramid *pyr, const uint8_t *ref_u8, const uint8
             hipLaunchKernelGGL(k_pyr_down, dim3(grid.x, grid.y, 2), dim3(PYR_THREADS), 0, s, (const uint8_t *)F.u8[0], (const uint8_t *)F.u8[1], L.u8[0],
                                L.u8[1], F.rows, F.cols, L.rows, L.cols);
             PYR_HIP(hipGetLastError());
+            if (l < (int)right.size()) {
+                hipLaunchKernelGGL(k_pyr_down, dim3(grid.x, grid.y, 1), dim3(PYR_THREADS), 0, s, (const uint8_t *)right[l - 1], (const uint8_t *)right[l - 1],
+                                   right[l], right[l], F.rows, F.cols, L.rows, L.cols);
+                PYR_HIP(hipGetLastError());
+            }
         }
+        if (l == dl && !disparity) PYR_HIP(sgbm_enqueue(*plan, L.u8[0], right[dl], nullptr, L.disp, s, temps));
         const bool derive = l > dl;
         hipLaunchKernelGGL(k_pyr_finish, grid, dim3(PYR_THREADS), 0, s, (const uint8_t *)L.u8[0], (const uint8_t *)L.u8[1], L.img[0], L.img[1], L.img[2],
                            L.img[3], L.rows, L.cols, pyr->gradient_source, pyr->gradient_scale, derive ? (const double *)pyr->lv[l - 1].disp : nullptr,
@@ -158,19 +181,13 @@ static int pyr_invalid(const char *call, const char *what) {
     return SSBA_ERR_INVALID_ARGUMENT;
 }
 
-}  // namespace ssba
-
-using namespace ssba;
-
-extern "C" {
-
-int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, uint32_t rows, uint32_t cols,
-                              uint32_t levels, uint32_t disparity_level, int gradient_source, double gradient_scale, int device,
-                              ssba_image_pyramid **out) {
-    const char *call = "ssba_image_pyramid_create";
+// ssba_image_pyramid_create (disparity) and ssba_image_pyramid_create_stereo (right_u8 and params)
+static int pyr_create(const char *call, const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, const uint8_t *right_u8,
+                      const ssba_sgbm_params *params, uint32_t rows, uint32_t cols, uint32_t levels, uint32_t disparity_level, int gradient_source,
+                      double gradient_scale, int device, ssba_image_pyramid **out) {
     if (!out) return pyr_invalid(call, "NULL output");
     *out = nullptr;
-    if (!ref_u8 || !track_u8 || !disparity) return pyr_invalid(call, "NULL array");
+    if (!ref_u8 || !track_u8 || (!disparity && !right_u8)) return pyr_invalid(call, "NULL array");
     if (levels == 0) return pyr_invalid(call, "levels = 0");
     if (disparity_level >= levels) return pyr_invalid(call, "disparity_level must be below levels");
     if (gradient_source != SSBA_GRADIENT_OF_REFERENCE && gradient_source != SSBA_GRADIENT_OF_TRACKED) return pyr_invalid(call, "unknown gradient source");
@@ -181,6 +198,9 @@ int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, co
         set_last_error(std::string(call) + ": image too large for the 32-bit pixel references of this build");
         return SSBA_ERR_UNSUPPORTED;
     }
+    SgbmPlan plan{};
+    if (!disparity)
+        if (const int rc = sgbm_check(call, rows >> disparity_level, cols >> disparity_level, params, &plan)) return rc;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
         set_last_error(std::string(call) + ": hipGetDeviceCount found no device");
@@ -198,17 +218,44 @@ int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, co
     for (uint32_t l = 0; l < levels; ++l) { pyr->lv[l].rows = (int)(rows >> l); pyr->lv[l].cols = (int)(cols >> l); }
     int rc = SSBA_OK;
     void *stage = nullptr;
+    std::vector<void *> temps;
     const size_t n0 = (size_t)rows * cols, nd = (size_t)pyr->lv[disparity_level].rows * pyr->lv[disparity_level].cols;
-    if (pool_stream_acquire(&pyr->stream) != hipSuccess || pool_host_malloc(&stage, (2 * n0 + 255) / 256 * 256 + nd * sizeof(double)) != hipSuccess) {
+    const size_t tail = disparity ? nd * sizeof(double) : n0;
+    if (pool_stream_acquire(&pyr->stream) != hipSuccess || pool_host_malloc(&stage, (2 * n0 + 255) / 256 * 256 + tail) != hipSuccess) {
         set_last_error(std::string(call) + ": no stream or no pinned staging memory");
         rc = SSBA_ERR_HIP;
     } else {
-        rc = pyr_build(pyr, ref_u8, track_u8, disparity, (char *)stage);
+        rc = pyr_build(pyr, ref_u8, track_u8, disparity, right_u8, &plan, (char *)stage, &temps);
     }
     if (stage) { if (pyr->stream) hipStreamSynchronize(pyr->stream); pool_host_free(stage); }
+    for (void *t : temps) pool_free(t);
     if (rc) { pyr_free(pyr); return rc; }
     *out = pyr;
     return SSBA_OK;
+}
+
+}  // namespace ssba
+
+using namespace ssba;
+
+extern "C" {
+
+int ssba_image_pyramid_create(const uint8_t *ref_u8, const uint8_t *track_u8, const double *disparity, uint32_t rows, uint32_t cols,
+                              uint32_t levels, uint32_t disparity_level, int gradient_source, double gradient_scale, int device,
+                              ssba_image_pyramid **out) {
+    if (out) *out = nullptr;
+    if (!disparity) return pyr_invalid("ssba_image_pyramid_create", "NULL array");
+    return pyr_create("ssba_image_pyramid_create", ref_u8, track_u8, disparity, nullptr, nullptr, rows, cols, levels, disparity_level, gradient_source,
+                      gradient_scale, device, out);
+}
+
+int ssba_image_pyramid_create_stereo(const uint8_t *ref_left_u8, const uint8_t *ref_right_u8, const uint8_t *track_u8, uint32_t rows, uint32_t cols,
+                                     uint32_t levels, uint32_t disparity_level, const ssba_sgbm_params *params, int gradient_source,
+                                     double gradient_scale, int device, ssba_image_pyramid **out) {
+    if (out) *out = nullptr;
+    if (!ref_right_u8) return pyr_invalid("ssba_image_pyramid_create_stereo", "NULL array");
+    return pyr_create("ssba_image_pyramid_create_stereo", ref_left_u8, track_u8, nullptr, ref_right_u8, params, rows, cols, levels, disparity_level,
+                      gradient_source, gradient_scale, device, out);
 }
 
 int ssba_image_pyramid_destroy(ssba_image_pyramid *pyr) {

@@ -492,6 +492,28 @@ class ImagePyramid:
     def create(cls, ref_u8, track_u8, disparity, levels: int, **kw):
         return cls(ref_u8, track_u8, disparity, levels, **kw)
 
+    @classmethod
+    def create_stereo(cls, ref_left_u8, ref_right_u8, track_u8, levels: int, disparity_level: int = 0, params: dict = None,
+                      gradient_source: int = capi.GRADIENT_OF_TRACKED, gradient_scale: float = 0.125, camera: dict = None, device: int = -1):
+        """The pyramid from what a stereo rig delivers (ssba_image_pyramid_create_stereo): the semi-global matcher runs on the
+        two 8-bit reference images at disparity_level and its map stays on the device.  ``params``: the matcher's parameters
+        (capi.sgbm_params keywords).  level(disparity_level).disparity downloads the map a handle or align() needs."""
+        self = cls.__new__(cls)
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        imgs = [np.ascontiguousarray(a) for a in (ref_left_u8, ref_right_u8, track_u8)]
+        if any(a.dtype != np.uint8 or a.ndim != 2 or a.shape != imgs[0].shape for a in imgs):
+            raise ValueError("the triple must be three uint8 images of one shape")
+        rows, cols = imgs[0].shape
+        self.rows, self.cols, self.levels, self.disparity_level, self.device = rows, cols, int(levels), int(disparity_level), device
+        self.camera = dict(camera) if camera is not None else None
+        u8 = C.POINTER(C.c_uint8)
+        q = capi.sgbm_params(**(params or {}))
+        capi.check(self.lib.ssba_image_pyramid_create_stereo(*[a.ctypes.data_as(u8) for a in imgs], rows, cols, int(levels), int(disparity_level),
+                                                             C.byref(q), int(gradient_source), float(gradient_scale), device, C.byref(self.h)),
+                   "ssba_image_pyramid_create_stereo")
+        return self
+
     def close(self):
         if self.h:
             self.lib.ssba_image_pyramid_destroy(self.h)
@@ -560,3 +582,20 @@ class ImagePyramid:
         if rc not in (0, -3):
             capi.check(rc, "ssba_image_pyramid_align")
         return rc, list(sums)
+
+
+def stereo_sgbm(left, right, device: int = -1, **params):
+    """The semi-global matcher on a rectified 8-bit pair (ssba_stereo_sgbm; cv::StereoSGBM(0, 64, 15) as the dense driver calls it).
+    ``params``: capi.sgbm_params keywords (min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap,
+    uniqueness_ratio, ...).  Returns (disp16 int16, disparity float64 with NaN at invalid pixels)."""
+    left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
+        raise ValueError("the pair must be two uint8 images of one shape")
+    rows, cols = left.shape
+    lib = capi.load()
+    q = capi.sgbm_params(**params)
+    disp16, disparity = np.zeros((rows, cols), np.int16), np.zeros((rows, cols))
+    u8 = C.POINTER(C.c_uint8)
+    capi.check(lib.ssba_stereo_sgbm(left.ctypes.data_as(u8), right.ctypes.data_as(u8), rows, cols, C.byref(q), device,
+                                    disp16.ctypes.data_as(C.POINTER(C.c_int16)), capi.dptr(disparity)), "ssba_stereo_sgbm")
+    return disp16, disparity

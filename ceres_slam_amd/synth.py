@@ -579,15 +579,8 @@ def sobel(img: np.ndarray, scale: float = 0.125):
     return scale * gx, scale * gy
 
 
-def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, slant=(0.25, -0.15), motion: float = 1.0,
-                    invalid_fraction: float = 0.0, min_wavelength_px: float = 10.0) -> ImagePair:
-    """A textured slanted plane rendered exactly (no resampling) from two poses.
-
-    The plane a x + b y + z = depth in the reference camera frame carries a band-limited texture (six sinusoids whose
-    wavelengths on the image are at least min_wavelength_px pixels); the tracked image is the same plane seen from
-    T_track_ref = pose_true, a motion of a fraction of a pixel to about a pixel (scaled by `motion`).  The disparity map is the
-    exact one of the reference view; invalid_fraction of its entries are replaced by NaN, 0 and negative values in turn."""
-    rng = np.random.Generator(np.random.PCG64(seed))
+def _plane_scene(rows: int, cols: int, rng, depth: float, slant, min_wavelength_px: float):
+    """The camera, the plane normal, the texture on the plane and the pixel rays of make_image_pair (its first random draws)."""
     fu = 0.6 * cols
     cam = dict(fu=fu, fv=fu, cu=0.5 * (cols - 1), cv=0.5 * (rows - 1), b=0.54)
     a, b = slant
@@ -606,6 +599,19 @@ def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, 
 
     v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64), indexing="ij")
     ray = np.stack([(u - cam["cu"]) / cam["fu"], (v - cam["cv"]) / cam["fv"], np.ones_like(u)], axis=-1)
+    return cam, n, texture, ray, px_on_plane
+
+
+def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, slant=(0.25, -0.15), motion: float = 1.0,
+                    invalid_fraction: float = 0.0, min_wavelength_px: float = 10.0) -> ImagePair:
+    """A textured slanted plane rendered exactly (no resampling) from two poses.
+
+    The plane a x + b y + z = depth in the reference camera frame carries a band-limited texture (six sinusoids whose
+    wavelengths on the image are at least min_wavelength_px pixels); the tracked image is the same plane seen from
+    T_track_ref = pose_true, a motion of a fraction of a pixel to about a pixel (scaled by `motion`).  The disparity map is the
+    exact one of the reference view; invalid_fraction of its entries are replaced by NaN, 0 and negative values in turn."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam, n, texture, ray, px_on_plane = _plane_scene(rows, cols, rng, depth, slant, min_wavelength_px)
     # reference view: the ray through a pixel meets the plane at Z ray with Z = depth / (n . ray)
     Z = depth / (ray @ n)
     ref = texture(ray * Z[..., None])
@@ -627,3 +633,32 @@ def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, 
     t0, R0 = np.array([-0.011, 0.013, -0.017]) * px_on_plane, so3_exp(np.array([2e-4, -3e-4, 2.5e-4]))
     return ImagePair(camera=cam, ref=ref, track=track, gradx=gradx, grady=grady, disparity=disparity,
                      pose_true=pose_pack(t, R), pose_init=pose_pack(t0, R0))
+
+
+@dataclass
+class StereoTriple:
+    """What a rectified stereo rig delivers to the dense driver (tests/dense_stereo_test.cpp:38-50), as 8-bit images."""
+
+    pair: ImagePair             # the exact images, disparity map and poses the triple was rendered from
+    left0: np.ndarray           # (rows, cols) uint8: the reference view
+    right0: np.ndarray          # (rows, cols) uint8: the same plane from (+b, 0, 0), so u_right = u - d
+    left1: np.ndarray           # (rows, cols) uint8: the tracked view
+
+
+def quantise_u8(img: np.ndarray) -> np.ndarray:
+    """An image in [0, 1] as the 8-bit image a file holds: clipped and rounded."""
+    return np.rint(np.clip(np.asarray(img, dtype=np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def make_stereo_triple(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, slant=(0.25, -0.15), motion: float = 1.0,
+                       min_wavelength_px: float = 10.0) -> StereoTriple:
+    """make_image_pair's plane as a rectified rig sees it: the reference view, the right view of the same instant and the
+    tracked view, clipped and rounded to 8 bits.  The right camera sits at (+b, 0, 0) of the reference frame with the same
+    orientation, so a point at reference column u lies at column u - d of the right image."""
+    pair = make_image_pair(rows, cols, seed, depth=depth, slant=slant, motion=motion, min_wavelength_px=min_wavelength_px)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam, n, texture, ray, _ = _plane_scene(rows, cols, rng, depth, slant, min_wavelength_px)
+    o = np.array([cam["b"], 0.0, 0.0])
+    s = (depth - n @ o) / (ray @ n)
+    right = texture(o + ray * s[..., None])
+    return StereoTriple(pair=pair, left0=quantise_u8(pair.ref), right0=quantise_u8(right), left1=quantise_u8(pair.track))

@@ -203,6 +203,56 @@ struct Image {
     int level = -1, which = -1;
 };
 
+// A row-major 8-bit image: what the dense driver holds in cv::Mat (CV_8U) after imread and pyrDown
+struct Image8 {
+    int rows, cols;
+    const uint8_t *data;
+    Image8(int rows_, int cols_, const uint8_t *data_) : rows(rows_), cols(cols_), data(data_) {}
+};
+
+// What cv::StereoSGBM writes (disp16: CV_16S, sixteenths of a pixel, (minDisparity - 1) * 16 at invalid pixels) and what the
+// driver's disp0.convertTo(disp0, CV_64F, 1. / 16.) makes of it, with NaN instead of minDisparity - 1 at invalid pixels
+struct DisparityMap {
+    int rows = 0, cols = 0;
+    std::vector<int16_t> disp16;
+    std::vector<double> disparity;
+};
+
+// cv::StereoSGBM in the call shape of the dense driver (tests/dense_stereo_test.cpp:61-65):
+//     ceres_slam::StereoSGBM sgbm(0, 64, 15);  sgbm(left0, right0, disp0);
+// The semi-global matcher of ssba_stereo_sgbm (include/ssba.h states its arithmetic; bit parity with OpenCV is unpinned).
+// std::invalid_argument where the C call refuses (images of different sizes included), std::runtime_error for every other failure.
+class StereoSGBM {
+ public:
+    StereoSGBM(int minDisparity = 0, int numDisparities = 64, int SADWindowSize = 15, int P1 = 0, int P2 = 0, int disp12MaxDiff = 0, int preFilterCap = 0,
+               int uniquenessRatio = 0, int speckleWindowSize = 0, int speckleRange = 0, bool fullDP = false, int device_ = -1)
+        : device(device_) {
+        ssba_sgbm_default_params(&params);
+        params.min_disparity = minDisparity; params.num_disparities = numDisparities; params.block_size = SADWindowSize;
+        params.p1 = P1; params.p2 = P2; params.disp12_max_diff = disp12MaxDiff; params.pre_filter_cap = preFilterCap;
+        params.uniqueness_ratio = uniquenessRatio; params.speckle_window_size = speckleWindowSize; params.speckle_range = speckleRange;
+        params.full_dp = fullDP ? 1 : 0;
+    }
+    void operator()(const Image8 &left, const Image8 &right, DisparityMap &disp) const {
+        if (left.rows != right.rows || left.cols != right.cols || left.rows <= 0 || left.cols <= 0)
+            throw std::invalid_argument("ceres_shim: StereoSGBM needs two images of one size");
+        const size_t npix = (size_t)left.rows * (size_t)left.cols;
+        disp.rows = left.rows; disp.cols = left.cols;
+        disp.disp16.assign(npix, 0);
+        disp.disparity.assign(npix, 0.0);
+        Raise("ssba_stereo_sgbm", ssba_stereo_sgbm(left.data, right.data, (uint32_t)left.rows, (uint32_t)left.cols, &params, device, disp.disp16.data(),
+                                                   disp.disparity.data()));
+    }
+    static void Raise(const char *call, int rc) {
+        if (!rc) return;
+        const std::string msg = std::string(call) + ": " + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
+        if (rc == SSBA_ERR_INVALID_ARGUMENT || rc == SSBA_ERR_UNSUPPORTED) throw std::invalid_argument(msg);
+        throw std::runtime_error(msg);
+    }
+    ssba_sgbm_params params;
+    int device;
+};
+
 // The pre-processing of the dense driver (tests/dense_stereo_test.cpp:52-72: pyrDown, convertTo, Sobel) on the device, in place of
 // the cv::Mat the driver holds per level: built once from the raw 8-bit pair and the disparity map of ONE level
 // (ssba_image_pyramid_create), it hands out std::shared_ptr<const Image> per level.  The images are backed by the device level;
@@ -217,22 +267,18 @@ class ImagePyramid {
         int rc = ssba_image_pyramid_create(ref_u8, track_u8, disparity, (uint32_t)rows, (uint32_t)cols, (uint32_t)levels, (uint32_t)disparity_level,
                                            gradient_source, gradient_scale, device, &s_->h);
         if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_create: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
-        s_->disparity_level = disparity_level;
-        s_->lv.resize((size_t)levels);
-        for (int l = 0; l < levels; ++l) {
-            Level &L = s_->lv[(size_t)l];
-            const size_t npix = (size_t)(rows >> l) * (size_t)(cols >> l);
-            for (int q = 0; q < 4; ++q) L.host[q].resize(npix);
-            if (l >= disparity_level) L.disparity.resize(npix);
-            uint32_t r = 0, c = 0;
-            rc = ssba_image_pyramid_level(s_->h, (uint32_t)l, &r, &c, NULL, NULL, L.host[0].data(), L.host[1].data(), L.host[2].data(), L.host[3].data(),
-                                          l >= disparity_level ? L.disparity.data() : NULL);
-            if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_level: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
-            for (int q = 0; q < 4; ++q) {
-                L.img.push_back(Image((int)r, (int)c, L.host[q].data()));
-                L.img.back().pyramid = s_->h; L.img.back().level = l; L.img.back().which = q;
-            }
-        }
+        Download(rows, cols, levels, disparity_level);
+    }
+    // From what the rig delivers (ssba_image_pyramid_create_stereo): the right image of the reference instant instead of a disparity
+    // map; `matcher` runs on the device at disparity_level, where the driver calls SGBM (:52-64), and disparity(level) is its map.
+    // std::invalid_argument where the C call refuses.
+    ImagePyramid(const uint8_t *ref_left_u8, const uint8_t *ref_right_u8, const uint8_t *track_u8, int rows, int cols, int levels, int disparity_level,
+                 const StereoSGBM &matcher, int gradient_source = SSBA_GRADIENT_OF_REFERENCE, double gradient_scale = 1.0, int device = -1)
+        : s_(std::make_shared<State>()) {
+        StereoSGBM::Raise("ssba_image_pyramid_create_stereo",
+                          ssba_image_pyramid_create_stereo(ref_left_u8, ref_right_u8, track_u8, (uint32_t)rows, (uint32_t)cols, (uint32_t)levels,
+                                                           (uint32_t)disparity_level, &matcher.params, gradient_source, gradient_scale, device, &s_->h));
+        Download(rows, cols, levels, disparity_level);
     }
     int levels() const { return (int)s_->lv.size(); }
     int disparity_level() const { return s_->disparity_level; }
@@ -258,6 +304,25 @@ class ImagePyramid {
     ssba_image_pyramid *handle() const { return s_->h; }
 
  private:
+    struct Level;
+    void Download(int rows, int cols, int levels, int disparity_level) {
+        s_->disparity_level = disparity_level;
+        s_->lv.resize((size_t)levels);
+        for (int l = 0; l < levels; ++l) {
+            Level &L = s_->lv[(size_t)l];
+            const size_t npix = (size_t)(rows >> l) * (size_t)(cols >> l);
+            for (int q = 0; q < 4; ++q) L.host[q].resize(npix);
+            if (l >= disparity_level) L.disparity.resize(npix);
+            uint32_t r = 0, c = 0;
+            const int rc = ssba_image_pyramid_level(s_->h, (uint32_t)l, &r, &c, NULL, NULL, L.host[0].data(), L.host[1].data(), L.host[2].data(), L.host[3].data(),
+                                          l >= disparity_level ? L.disparity.data() : NULL);
+            if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_level: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
+            for (int q = 0; q < 4; ++q) {
+                L.img.push_back(Image((int)r, (int)c, L.host[q].data()));
+                L.img.back().pyramid = s_->h; L.img.back().level = l; L.img.back().which = q;
+            }
+        }
+    }
     struct Level {
         std::vector<double> host[4], disparity;
         std::vector<Image> img;

@@ -594,6 +594,71 @@ SSBA_API int ssba_add_image_level(ssba_problem *p, ssba_image_pyramid *pyr, uint
 SSBA_API int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
                              int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries);
 
+/* ---- dense photometric alignment: the disparity map from a rectified pair ------------------------------------------------
+ * ssba_stereo_sgbm replaces cv::StereoSGBM sgbm(0, 64, 15); sgbm(left0, right0, disp0) (tests/dense_stereo_test.cpp:61-65): a
+ * semi-global matcher (Hirschmueller 2008) in the single-pass, five-direction mode that call uses, stated here entirely in
+ * integers.  cv::StereoSGBM cannot be compiled or run where this library is built and tested, so bit parity with OpenCV is
+ * UNPINNED; the yardstick is the numpy statement tests/sgbm_reference.py, which the device equals to the bit.
+ *
+ * left, right: rectified 8-bit images, rows x cols, row-major.  D = num_disparities, maxD = min_disparity + D.  The computable
+ * columns are x in [maxD, cols), W of them; every other pixel is invalid.  Derived constants:
+ *     cap = max(pre_filter_cap, 15) | 1,  P1 = p1 > 0 ? p1 : 2,  P2 = max(p2 > 0 ? p2 : 5, P1 + 1),  r = block_size / 2
+ * The arithmetic:
+ *     pre-filter  on both images:  g = (I[y-1][x+1] - I[y-1][x-1]) + 2 (I[y][x+1] - I[y][x-1]) + (I[y+1][x+1] - I[y+1][x-1]),
+ *                 rows reflected (-1 -> 1, rows -> rows - 2), g = 0 in columns 0 and cols - 1;  P = clamp(g, -cap, cap) + cap
+ *     pixel cost  Birchfield-Tomasi of a row signal A (left, at x) against B (right, at x - d):
+ *                     a- = (A[x] + A[x-1]) / 2,  a+ = (A[x] + A[x+1]) / 2   (floor division, the neighbour clamped to the row)
+ *                     amin / amax = the minimum / maximum of A[x], a-, a+;  B likewise at x - d
+ *                     c0 = max(0, a - bmax, bmin - a),  c1 = max(0, b - amax, amin - b),  BT = min(c0, c1)
+ *                 c(x, y, d) = BT(P_left, P_right) + (BT(left, right) >> 2)
+ *     block cost  C(x, y, d) = sum_{i,j=-r..r} c(x + i, y + j, d), rows clamped to [0, rows), columns to the computable range.
+ *                 C <= (2 cap + 63) block_size^2: 93 block_size^2 at the default cap, 20 925 at block size 15.
+ *     paths       for the predecessors q = (x-1, y), (x+1, y), (x-1, y-1), (x, y-1), (x+1, y-1) of p:
+ *                     L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + P1, L(q, d+1) + P1, m(q) + P2) - m(q),  m(q) = min_k L(q, k)
+ *                 d -+ 1 outside [min_disparity, maxD) does not take part; L(p, d) = C(p, d) where q lies outside the computable
+ *                 columns or above row 0.  L <= C + P2 fits 16 bits.  S = the sum of the five L (more than 16 bits).
+ *     winner      d* = argmin_d S, the smallest d on ties.  Uniqueness: invalid if some d with |d - d*| > 1 has
+ *                 S(d) (100 - uniqueness_ratio) < S(d*) 100.  Sub-pixel, where d* is neither the first nor the last disparity:
+ *                     den = max(S(d*-1) + S(d*+1) - 2 S(d*), 1)
+ *                     disp16 = 16 d* + ((S(d*-1) - S(d*+1)) 16 + den) / (2 den)      (C's truncating division)
+ *                 elsewhere disp16 = 16 d*.
+ *     left-right  when disp12_max_diff >= 0; a NEGATIVE value switches the check off (this library's own rule).  Per row the
+ *                 right view's map: for x from the last computable column down to the first, of the pixels that passed
+ *                 uniqueness, x2 = x - d*(x); if S(x, d*) < cost2[x2] strictly, cost2[x2] = S(x, d*) and disp2[x2] = d* (ties
+ *                 keep the larger x).  Then for every valid pixel lo = disp16 >> 4, hi = (disp16 + 15) >> 4, a = x - lo,
+ *                 b = x - hi; it becomes invalid if BOTH hold: 0 <= a < cols, disp2[a] >= min_disparity and
+ *                 |disp2[a] - lo| > disp12_max_diff; the same three conditions for b against hi.
+ *     outputs     disp16 (int16, rows * cols): invalid pixels hold (min_disparity - 1) * 16.  disparity (double, rows * cols):
+ *                 disp16 / 16.0 where valid, NaN elsewhere.  (The driver's convertTo(CV_64F, 1./16.) gives -1 at an invalid pixel
+ *                 for min_disparity 0; its test isfinite(d) && d > 0 drops -1 and NaN alike, and NaN stays dropped for any
+ *                 min_disparity.)
+ * SSBA_ERR_INVALID_ARGUMENT: a NULL image or parameter block, min_disparity < 0, num_disparities not a multiple of 16 in
+ *   16 ... 256, block_size not odd in 1 ... 15, uniqueness_ratio outside 0 ... 100, pre_filter_cap > 127 (P no longer fits
+ *   8 bits), full_dp (the eight-direction mode), rows < 2, cols <= maxD (no computable column), maxD > 2047 (disp16 overflows),
+ *   (2 cap + 63) block_size^2 + P2 > 65535 (a path cost would not be exact in 16 bits).
+ * SSBA_ERR_UNSUPPORTED: nonzero speckle_window_size or speckle_range (no connected-components filter), more than 5461 columns
+ *   or 2^31 volume entries rows * W * D.
+ * ssba_stereo_sgbm is synchronous: host arrays in and out (either output may be NULL), the work on a pooled stream, the memory
+ * (six 16-bit volumes of rows * W * D) from the library's pool.  ssba_sgbm_default_params: the driver's (0, 64, 15), zeros
+ * for the rest.
+ *
+ * ssba_image_pyramid_create_stereo is ssba_image_pyramid_create without a disparity argument: the right image is halved down to
+ * disparity_level like the other two, the matcher runs there on the two 8-bit levels (the state in which the driver calls it,
+ * :52-64), and its double map is the pyramid's map at disparity_level, from which the coarser levels derive as ever.  No
+ * disparity crosses the host.  A handle's blocks are the finite positive entries of the CALLER's map: download it once with
+ * ssba_image_pyramid_level and hand it to ssba_add_image_level or ssba_image_pyramid_align.  Refusals: those of
+ * ssba_image_pyramid_create and of ssba_stereo_sgbm at the size of disparity_level. */
+typedef struct {
+    int32_t min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap, uniqueness_ratio;
+    int32_t speckle_window_size, speckle_range, full_dp;
+} ssba_sgbm_params;
+SSBA_API void ssba_sgbm_default_params(ssba_sgbm_params *params);
+SSBA_API int ssba_stereo_sgbm(const uint8_t *left, const uint8_t *right, uint32_t rows, uint32_t cols, const ssba_sgbm_params *params, int device,
+                     int16_t *disp16_out, double *disparity_out);
+SSBA_API int ssba_image_pyramid_create_stereo(const uint8_t *ref_left_u8, const uint8_t *ref_right_u8, const uint8_t *track_u8, uint32_t rows,
+                                     uint32_t cols, uint32_t levels, uint32_t disparity_level, const ssba_sgbm_params *params,
+                                     int gradient_source, double gradient_scale, int device, ssba_image_pyramid **out);
+
 /* ---- front end: the VO initial guess --------------------------------- */
 /* ssba_frontend_ransac replaces, for `num_pairs` pairs of consecutive states at once,
  *   PointCloudAligner::compute_transformation_and_inliers (src/ceres_slam/point_cloud_aligner.cpp:64-136)

@@ -47,6 +47,7 @@ namespace ssba { void set_last_error(const std::string &s) { g_last_error = s; }
         }                                                                                \
     } while (0)
 
+struct ImageBatchRun;      // what ssba_image_solve_batch keeps on handles[0] between calls (below)
 constexpr int LS_ROUNDS_FIRST = 2, LS_ROUNDS_MOST = 4;      // device-side evaluations of the projected line search per iteration (ssba_solve_begin)
 struct ssba_problem {
     ssba_camera cam{};
@@ -148,7 +149,9 @@ struct ssba_problem {
     std::vector<int32_t> log_ok;
     std::vector<double> log_stage;
     int log_capacity = 0;
+    ImageBatchRun *batch_run = nullptr;       // buffers, events and graphs of the last ssba_image_solve_batch led by this handle
 };
+static void batch_run_free(ssba_problem *p);
 
 template <class T>
 static int dalloc(ssba_problem *p, T **out, size_t n) {
@@ -264,6 +267,7 @@ static void drop_graph(ssba_problem *p) {
 }
 
 static void free_device(ssba_problem *p) {
+    batch_run_free(p);
     drop_graph(p);
     stage_release(p);
     if (!p->allocs.empty()) hipStreamSynchronize(p->launcher.stream);      // cached buffers go to the next handle
@@ -2236,6 +2240,204 @@ int ssba_solve(ssba_problem *p, const ssba_options *o, ssba_summary *s) {
     pool_host_free(ring);
     if (rc) { p->began = false; return rc; }
     return ssba_solve_end(p, s);
+}
+
+// ---------------------------------------------------------------------------------
+// n image handles in shared launches (ssba_image.hip: k_imb_*)
+// ---------------------------------------------------------------------------------
+static int batch_refuse(int status, uint32_t k, const char *what) {
+    set_error("ssba_image_solve_batch: handle " + std::to_string(k) + ": " + what);
+    return status;
+}
+
+// What the call needs next to the handles.  It stays on handles[0] between calls: allocating the Dev array and the termination
+// words, creating two events and capturing and instantiating the graphs cost about 1 ms per call, which is what a batch of one
+// lost against the solo path.  The graphs hold d_devs, d_term and the launch shapes only (the Dev array is uploaded again by
+// every call), so they serve every later call with the same key.
+struct ImageBatchRun {
+    uint32_t n = 0;
+    int max_wg = 0, best_groups = 0;
+    hipStream_t stream = nullptr;
+    Dev *d_devs = nullptr;
+    int *d_term = nullptr;
+    char *h_pinned = nullptr;       // [n Dev | 2 x n termination words]
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipGraph_t graph = nullptr, graph10 = nullptr;              // one round; GRAPH_ITERS rounds (ignore_convergence)
+    hipGraphExec_t gexec = nullptr, gexec10 = nullptr;
+    void release() {
+        if (stream) hipStreamSynchronize(stream);
+        if (gexec) hipGraphExecDestroy(gexec);
+        if (gexec10) hipGraphExecDestroy(gexec10);
+        if (graph) hipGraphDestroy(graph);
+        if (graph10) hipGraphDestroy(graph10);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+        pool_free(d_devs);
+        pool_free(d_term);
+        if (h_pinned) pool_host_free(h_pinned);
+    }
+};
+static void batch_run_free(ssba_problem *p) {
+    if (!p->batch_run) return;
+    p->batch_run->release();
+    delete p->batch_run;
+    p->batch_run = nullptr;
+}
+
+// `rounds` rounds of the batch into a graph: a linear chain of 5 * rounds kernel nodes.  The capture is ended on every path.
+static int capture_batch_rounds(hipStream_t s, const ImageBatchRun &R, int rounds, hipGraph_t *graph, hipGraphExec_t *exec) {
+    HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+    for (int q = 0; q < rounds; ++q) launch_image_batch(s, R.d_devs, (int)R.n, R.max_wg, R.best_groups, R.d_term);
+    const hipError_t e = hipStreamEndCapture(s, graph);
+    if (e != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); *graph = nullptr; return SSBA_ERR_HIP; }
+    HIPCHECK(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
+    return SSBA_OK;
+}
+
+static int image_batch_loop(ssba_problem **h, uint32_t n, const ssba_options *o, int ignore_convergence) {
+    ssba_problem *p0 = h[0];
+    hipStream_t s = p0->launcher.stream;
+    // begin wrote p->d (the log pointers): the Dev array is uploaded after every begin, on handles[0]'s stream behind them all
+    for (uint32_t k = 1; k < n; ++k)
+        if (h[k]->launcher.stream != s) HIPCHECK(hipStreamWaitEvent(s, h[k]->ev_begin, 0));
+    int max_wg = 0, best_groups = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        max_wg = std::max(max_wg, h[k]->launcher.image.n_wg);
+        best_groups = std::max(best_groups, image_best_groups(h[k]->d));
+    }
+    const size_t dev_bytes = (size_t)n * sizeof(Dev), term_bytes = (size_t)n * sizeof(int);
+    if (p0->batch_run && (p0->batch_run->n != n || p0->batch_run->max_wg != max_wg || p0->batch_run->best_groups != best_groups || p0->batch_run->stream != s))
+        batch_run_free(p0);
+    if (!p0->batch_run) {
+        p0->batch_run = new ImageBatchRun();
+        ImageBatchRun &N = *p0->batch_run;
+        N.n = n; N.max_wg = max_wg; N.best_groups = best_groups; N.stream = s;
+        HIPCHECK(pool_malloc((void **)&N.d_devs, dev_bytes));
+        HIPCHECK(pool_malloc((void **)&N.d_term, term_bytes));
+        HIPCHECK(pool_host_malloc((void **)&N.h_pinned, dev_bytes + 2 * term_bytes));
+        HIPCHECK(hipEventCreateWithFlags(&N.ev[0], hipEventDisableTiming));
+        HIPCHECK(hipEventCreateWithFlags(&N.ev[1], hipEventDisableTiming));
+    }
+    ImageBatchRun &R = *p0->batch_run;
+    for (uint32_t k = 0; k < n; ++k) memcpy(R.h_pinned + (size_t)k * sizeof(Dev), &h[k]->d, sizeof(Dev));
+    int *ring = reinterpret_cast<int *>(R.h_pinned + dev_bytes);
+    HIPCHECK(hipMemcpyAsync(R.d_devs, R.h_pinned, dev_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(R.d_term, 0, term_bytes, s));
+    // ssba_solve's loop: the device decides, the host reads the termination words one round behind.  ignore_convergence: no
+    // member ever terminates, the call runs max_num_iterations rounds (ssba_solve_step(max_num_iterations) on every member).
+    const long rounds = ignore_convergence ? (long)o->max_num_iterations : (long)o->max_num_iterations + 3;
+    const bool graphs = p0->use_graph;
+    int rc;
+    if (ignore_convergence) {
+        // nothing can terminate: no termination words are read, and GRAPH_ITERS rounds go into one replay (enqueue_batch's shape)
+        long it = 0;
+        if (graphs && (R.gexec10 || rounds >= 2 * GRAPH_ITERS)) {
+            if (!R.gexec10 && (rc = capture_batch_rounds(s, R, GRAPH_ITERS, &R.graph10, &R.gexec10))) return rc;
+            for (; it + GRAPH_ITERS <= rounds; it += GRAPH_ITERS) HIPCHECK(hipGraphLaunch(R.gexec10, s));
+        }
+        for (; it < rounds; ++it) launch_image_batch(s, R.d_devs, (int)n, max_wg, best_groups, R.d_term);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return SSBA_ERR_HIP; }
+        HIPCHECK(hipStreamSynchronize(s));
+        return SSBA_OK;
+    }
+    bool done = false;
+    for (long it = 0; it < rounds && !done; ++it) {
+        // the five launches are a linear chain on one stream: captured after LAZY_GRAPH_ITERS eager rounds (enqueue_iteration's
+        // rule), and the graph of an earlier call with the same shapes is replayed from the first round on
+        if (graphs && !R.gexec && it >= LAZY_GRAPH_ITERS && (rc = capture_batch_rounds(s, R, 1, &R.graph, &R.gexec))) return rc;
+        if (R.gexec) HIPCHECK(hipGraphLaunch(R.gexec, s));
+        else {
+            launch_image_batch(s, R.d_devs, (int)n, max_wg, best_groups, R.d_term);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return SSBA_ERR_HIP; }
+        }
+        const int slot = (int)(it & 1);
+        HIPCHECK(hipMemcpyAsync(ring + (size_t)slot * n, R.d_term, term_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipEventRecord(R.ev[slot], s));
+        if (it >= 1) {
+            const int *prev = ring + (size_t)(slot ^ 1) * n;
+            HIPCHECK(hipEventSynchronize(R.ev[slot ^ 1]));
+            done = true;
+            for (uint32_t k = 0; k < n && done; ++k) done = prev[k] != 0;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    return SSBA_OK;
+}
+
+int ssba_image_solve_batch(ssba_problem **handles, uint32_t n, const ssba_options *options, int ignore_convergence, ssba_summary *summaries,
+                           int *statuses) {
+    ApiTimer api_timer("ssba_image_solve_batch");
+    const char *call = "ssba_image_solve_batch";
+    if (!handles || !options) { set_error(std::string(call) + ": NULL argument"); return SSBA_ERR_INVALID_ARGUMENT; }
+    if (n == 0) { set_error(std::string(call) + ": n = 0"); return SSBA_ERR_INVALID_ARGUMENT; }
+    if (n > SSBA_IMAGE_BATCH_MAX) {
+        set_error(std::string(call) + ": n = " + std::to_string(n) + " is above the cap of " + std::to_string(SSBA_IMAGE_BATCH_MAX) + " handles per call");
+        return SSBA_ERR_INVALID_ARGUMENT;
+    }
+    // every refusal comes before anything is touched: the handles stay as they were
+    for (uint32_t k = 0; k < n; ++k)
+        if (!handles[k]) return batch_refuse(SSBA_ERR_INVALID_ARGUMENT, k, "NULL");
+    {
+        std::vector<ssba_problem *> sorted(handles, handles + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            uint32_t k = n;
+            while (k-- > 0 && handles[k] != *dup) {}
+            return batch_refuse(SSBA_ERR_INVALID_ARGUMENT, k, "the same handle twice in one batch");
+        }
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const ssba_problem *p = handles[k];
+        if (p->device != handles[0]->device) return batch_refuse(SSBA_ERR_INVALID_ARGUMENT, k, "lives on a different device than handle 0");
+        if (!p->image) return batch_refuse(SSBA_ERR_UNSUPPORTED, k, "has no image blocks (a batch holds image handles only)");
+        if (p->launcher.timing) return batch_refuse(SSBA_ERR_UNSUPPORTED, k, "has kernel timing switched on (the shared launches belong to no single handle)");
+        if (!p->finalized) return batch_refuse(SSBA_ERR_STATE, k, "is not finalized");
+        if (p->began) return batch_refuse(SSBA_ERR_STATE, k, "is inside a stepwise solve (ssba_solve_end first)");
+    }
+    if (options->trust_region_strategy_type == 1) {
+        set_error(std::string(call) + ": DOGLEG asked for in the options: image blocks are solved with Levenberg-Marquardt only");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    if (options->max_num_iterations < 0 || !(options->initial_trust_region_radius > 0.0) || options->trust_region_strategy_type != 0) {
+        set_error(std::string(call) + ": max_num_iterations < 0, initial_trust_region_radius <= 0 or an unknown trust_region_strategy_type");
+        return SSBA_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 1) {
+        // A batch of one has nothing to share: it takes the solo path (the same five launches from the handle's own argument
+        // segment, its own cached graphs), which is what it is compared with to the bit and must not be slower than.
+        ssba_options o1 = *options;
+        o1.minimizer_progress_to_stdout = 0;
+        int r1;
+        if (!ignore_convergence) r1 = ssba_solve(handles[0], &o1, summaries);
+        else {
+            r1 = ssba_solve_begin(handles[0], &o1, 1);
+            if (!r1) r1 = enqueue_n(handles[0], o1.max_num_iterations);
+            if (r1) { handles[0]->began = false; return r1; }
+            r1 = ssba_solve_end(handles[0], summaries);
+        }
+        if (r1 && r1 != SSBA_ERR_NUMERICAL_FAILURE) return r1;
+        if (statuses) statuses[0] = r1;
+        return r1;
+    }
+    int rc = SSBA_OK;
+    uint32_t begun = 0;
+    for (; begun < n && !rc; ++begun) rc = ssba_solve_begin(handles[begun], options, ignore_convergence);
+    if (!rc) rc = image_batch_loop(handles, n, options, ignore_convergence);
+    if (rc) {       // a HIP error: no handle stays inside a solve, and nothing of the run is kept
+        hipStreamSynchronize(handles[0]->launcher.stream);
+        batch_run_free(handles[0]);
+        for (uint32_t k = 0; k < n; ++k) handles[k]->began = false;
+        return rc;
+    }
+    int first = SSBA_OK;
+    for (uint32_t k = 0; k < n; ++k) {      // summaries, iteration logs, the caller's pose and disparity map: as after ssba_solve
+        const int rk = ssba_solve_end(handles[k], summaries ? &summaries[k] : nullptr);
+        if (statuses) statuses[k] = rk;
+        if (rk && !first) first = rk;
+    }
+    return first;
 }
 
 int ssba_brief_report(const ssba_summary *s, char *buf, size_t n) {

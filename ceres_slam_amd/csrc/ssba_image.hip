@@ -61,13 +61,16 @@ static __device__ __forceinline__ double im_sample(const ImageSys &im, const dou
 }
 
 // triangulate, transform, project: p (camera frame of the reference image), q = R p + t, (u, v)
-static __device__ __forceinline__ void im_project(const Dev &d, const double *__restrict__ T, double ur, double vr, double dd, double q[3],
+template <bool LIN> static __device__ __forceinline__ void im_project(const Dev &d, const double *__restrict__ T, double ur, double vr, double dd, double q[3],
                                                   double &iz, double &u, double &v) {
     const double bd = d.b / dd, ff = d.fu / d.fv;
     const double px = (ur - d.cu) * bd, py = (vr - d.cv) * bd * ff, pz = d.fu * bd;
-    q[0] = T[3] * px + T[4] * py + T[5] * pz + T[0];
-    q[1] = T[6] * px + T[7] * py + T[8] * pz + T[1];
-    q[2] = T[9] * px + T[10] * py + T[11] * pz + T[2];
+    // Which product of a sum of two the compiler fuses into an fma is its own choice, and it falls differently in different
+    // kernels around the same source line; the solo and the batched kernels must agree to the bit, so the rows say it themselves
+    // (the forms k_im_lin and k_im_eval had before the bodies were shared, read off their assembly: they differ in row 0).
+    q[0] = (LIN ? fma(T[5], pz, fma(T[4], py, T[3] * px)) : fma(T[5], pz, fma(T[3], px, T[4] * py))) + T[0];
+    q[1] = fma(T[8], pz, fma(T[6], px, T[7] * py)) + T[1];
+    q[2] = fma(T[11], pz, fma(T[9], px, T[10] * py)) + T[2];
     iz = 1.0 / q[2];
     u = d.fu * q[0] * iz + d.cu;
     v = d.fv * q[1] * iz + d.cv;
@@ -77,7 +80,7 @@ static __device__ __forceinline__ void im_project(const Dev &d, const double *__
 static __device__ __forceinline__ double im_residual(const Dev &d, const ImageSys &im, const double *__restrict__ T, uint32_t pix, double dd) {
     const uint32_t vr = pix / (uint32_t)im.cols, ur = pix - vr * (uint32_t)im.cols;
     double q[3], iz, u, v;
-    im_project(d, T, (double)ur, (double)vr, dd, q, iz, u, v);
+    im_project<false>(d, T, (double)ur, (double)vr, dd, q, iz, u, v);
     if (!im_in_bounds(im, u, v)) return 0.0;
     return im_sample(im, im.track, u, v) - im.ref[pix];
 }
@@ -87,7 +90,7 @@ static __device__ __forceinline__ void im_row(const Dev &d, const ImageSys &im, 
                                               double &r, double jp[6], double &jd) {
     const uint32_t vr = pix / (uint32_t)im.cols, ur = pix - vr * (uint32_t)im.cols;
     double q[3], iz, u, v;
-    im_project(d, T, (double)ur, (double)vr, dd, q, iz, u, v);
+    im_project<true>(d, T, (double)ur, (double)vr, dd, q, iz, u, v);
     r = 0.0; jd = 0.0;
 #pragma unroll
     for (int c = 0; c < 6; ++c) jp[c] = 0.0;
@@ -104,7 +107,8 @@ static __device__ __forceinline__ void im_row(const Dev &d, const ImageSys &im, 
     // dp/dd = third column of the triangulation Jacobian (stereo_camera.hpp:125-140)
     const double bd2 = d.b / dd / dd, ff = d.fu / d.fv;
     const double t0 = (d.cu - (double)ur) * bd2, t1 = (d.cv - (double)vr) * bd2 * ff, t2 = -d.fu * bd2;
-    const double w0 = T[3] * t0 + T[4] * t1 + T[5] * t2, w1 = T[6] * t0 + T[7] * t1 + T[8] * t2, w2 = T[9] * t0 + T[10] * t1 + T[11] * t2;
+    const double w0 = fma(T[5], t2, fma(T[4], t1, T[3] * t0)), w1 = fma(T[8], t2, fma(T[6], t0, T[7] * t1));      // (as im_project's rows)
+    const double w2 = fma(T[11], t2, fma(T[9], t0, T[10] * t1));
     jd = a0 * w0 + a1 * w1 + a2 * w2;
 }
 
@@ -118,7 +122,10 @@ static __device__ __forceinline__ double im_damping(const State &st, double jd, 
 // on the way (as k_po_step does).  The linearisation is repeated after a rejected step: same point, same sums, another radius.
 // Per work-group: IM_NSUM sums into ImageSys::part, and (cost, |d|^2 of the free disparities, max |J_d r|) into Dev::part_lin,
 // which check_body reduces.
-template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev d) {
+// The three bodies below take the problem's Dev and the index of the work-group inside the problem: k_im_* hand them the
+// kernel argument and blockIdx.x, the batched kernels k_imb_* an entry of their device array and blockIdx.x under that problem's
+// count.  Nothing is written through `d` itself (only through the pointers it holds), so a batched work-group reads it in place.
+template <bool FREE> static __device__ __forceinline__ void im_lin_body(const Dev &d, const uint32_t wg) {
     const State &st = *d.st;
     const ImageSys &im = *d.image;
     if (st.terminated) return;
@@ -128,7 +135,7 @@ template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev 
     double T[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = PS[i];
-    const uint32_t i = blockIdx.x * IM_THREADS + threadIdx.x;
+    const uint32_t i = wg * IM_THREADS + threadIdx.x;
     double acc[NS + 2];      // .. | cost | |d|^2
 #pragma unroll
     for (int q = 0; q < NS + 2; ++q) acc[q] = 0.0;
@@ -167,7 +174,7 @@ template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev 
         }
         acc[NS] = 0.5 * r * r;
     }
-    if (commit && blockIdx.x == 0 && threadIdx.x < 12) d.poses[threadIdx.x] = T[threadIdx.x];
+    if (commit && wg == 0 && threadIdx.x < 12) d.poses[threadIdx.x] = T[threadIdx.x];
     __shared__ double sm[IM_THREADS / 64][NS + 3];
     const int w = threadIdx.x >> 6;
 #pragma unroll
@@ -187,98 +194,104 @@ template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev 
 #pragma unroll
         for (int q = 0; q < IM_THREADS / 64; ++q) v += sm[q][threadIdx.x];
     }
-    if (threadIdx.x < NS) im.part[(size_t)blockIdx.x * IM_REC + threadIdx.x] = v;
-    else d.part_lin[(size_t)blockIdx.x * 4 + (threadIdx.x - NS)] = v;
+    if (threadIdx.x < NS) im.part[(size_t)wg * IM_REC + threadIdx.x] = v;
+    else d.part_lin[(size_t)wg * 4 + (threadIdx.x - NS)] = v;
 }
+template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev d) { im_lin_body<FREE>(d, blockIdx.x); }
 
 // One work-group: the sums of k_im_lin's partials in fixed order (lane = column of the record, 8 slices of work-groups, the
 // slices added in order), then lane 0 scales, damps, solves and forms the candidate pose, and leaves the pose shares that
 // check_body (gradient max norm, |x|^2) and k_decide (|dx|^2, non-finite) read.
-__global__ __launch_bounds__(IM_SOLVE_THREADS) void k_im_solve(Dev d) {
-    State &st = *d.st;
-    const ImageSys &im = *d.image;
-    if (st.terminated) return;
-    __shared__ double sm[IM_SLICES][64];
-    __shared__ double tot[IM_NSUM];
-    const int col = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int ns = im.disp_const ? 27 : IM_NSUM;
-    double v = 0.0;
-    if (col < ns) {
-        const double *__restrict__ P = im.part + col;
-        int wg = slice;
-        for (; wg + 3 * IM_SLICES < im.n_wg; wg += 4 * IM_SLICES) {
-            const double x0 = P[(size_t)wg * IM_REC], x1 = P[(size_t)(wg + IM_SLICES) * IM_REC];
-            const double x2 = P[(size_t)(wg + 2 * IM_SLICES) * IM_REC], x3 = P[(size_t)(wg + 3 * IM_SLICES) * IM_REC];
-            v += x0; v += x1; v += x2; v += x3;
-        }
-        for (; wg < im.n_wg; wg += IM_SLICES) v += P[(size_t)wg * IM_REC];
-    }
-    sm[slice][col] = v;
-    __syncthreads();
-    if (threadIdx.x < IM_NSUM) {
-        double t = 0.0;
-        if ((int)threadIdx.x < ns) {
-#pragma unroll
-            for (int q = 0; q < IM_SLICES; ++q) t += sm[q][threadIdx.x];
-        }
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double T[12], H[21], A[21], g[6], gf[6], hd[6];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = d.poses[i];
-#pragma unroll
-    for (int i = 0; i < 21; ++i) { H[i] = tot[i]; A[i] = tot[i]; d.hpp[i] = tot[i]; }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        g[c] = tot[21 + c];                                         // reduced gradient
-        hd[c] = im.disp_const ? H[tri21(c, c)] : tot[27 + c];       // diagonal of the full H_pp
-        gf[c] = im.disp_const ? g[c] : tot[33 + c];                 // full gradient of the pose
-        d.gp[c] = gf[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {       // Jacobi scale at iteration 0, LM damping in unscaled coordinates (as k_po_step)
-        double sc;
-        if (st.iteration == 0) { sc = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(hd[c])) : 1.0; d.sp[c] = sc; }
-        else sc = d.sp[c];
-        const double s2 = sc * sc;
-        A[tri21(c, c)] += fmin(fmax(hd[c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag) / (damp_radius(st) * s2);
-        im.sys[IM_SYS_SP + c] = sc;
-    }
-    double dx[6] = {0, 0, 0, 0, 0, 0}, Tn[12], dn = 0.0, nonfinite = 0.0;
-    if (po_solve6(A, g, dx)) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) if (!isfinite(dx[c])) nonfinite = 1.0;
-        se3_plus(T, dx, Tn);
-#pragma unroll
-        for (int c = 0; c < 12; ++c) { const double df = Tn[c] - T[c]; dn += df * df; }
-    } else {
-        st.step_failed = 1;      // LINEAR_SOLVER_FAILURE
-#pragma unroll
-        for (int c = 0; c < 6; ++c) dx[c] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 12; ++c) Tn[c] = T[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 12; ++c) d.cand_poses[c] = Tn[c];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) im.sys[6 * r + c] = A[tri21(r < c ? r : c, r < c ? c : r)];
-        im.sys[IM_SYS_RHS + r] = -g[r];
-        im.sys[IM_SYS_DP + r] = dx[r];
-    }
-    d.part_pose[0] = dn; d.part_pose[1] = nonfinite; d.part_pose[2] = 0.0; d.part_pose[3] = 0.0;
-    // the pose's share of the gradient max norm |x - Plus(x, -g)|_inf and of |x|^2 (check_body's arithmetic)
-    double ng[6], Tg[12], gm = 0.0, xn = 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) ng[c] = -gf[c];
-    se3_plus(T, ng, Tg);
-#pragma unroll
-    for (int c = 0; c < 12; ++c) { gm = fmax(gm, fabs(T[c] - Tg[c])); xn += T[c] * T[c]; }
-    d.part_chk[0] = gm;
+// k_im_solve's body as text and not as a function, so that k_im_solve keeps the very code it had: as a __forceinline__ function
+// called from a wrapper kernel its sums of two products (se3_plus, po_solve6: shared headers that cannot say fma themselves
+// without changing the stereo kernels) were contracted differently in a rarely taken path, and a solo solve lost its recorded
+// bits at iteration 32 of one case.  `d` is the problem's Dev in scope.
+#define IM_SOLVE_BODY \
+    State &st = *d.st; \
+    const ImageSys &im = *d.image; \
+    if (st.terminated) return; \
+    __shared__ double sm[IM_SLICES][64]; \
+    __shared__ double tot[IM_NSUM]; \
+    const int col = threadIdx.x & 63, slice = threadIdx.x >> 6; \
+    const int ns = im.disp_const ? 27 : IM_NSUM; \
+    double v = 0.0; \
+    if (col < ns) { \
+        const double *__restrict__ P = im.part + col; \
+        int wg = slice; \
+        for (; wg + 3 * IM_SLICES < im.n_wg; wg += 4 * IM_SLICES) { \
+            const double x0 = P[(size_t)wg * IM_REC], x1 = P[(size_t)(wg + IM_SLICES) * IM_REC]; \
+            const double x2 = P[(size_t)(wg + 2 * IM_SLICES) * IM_REC], x3 = P[(size_t)(wg + 3 * IM_SLICES) * IM_REC]; \
+            v += x0; v += x1; v += x2; v += x3; \
+        } \
+        for (; wg < im.n_wg; wg += IM_SLICES) v += P[(size_t)wg * IM_REC]; \
+    } \
+    sm[slice][col] = v; \
+    __syncthreads(); \
+    if (threadIdx.x < IM_NSUM) { \
+        double t = 0.0; \
+        if ((int)threadIdx.x < ns) { \
+_Pragma("unroll") \
+            for (int q = 0; q < IM_SLICES; ++q) t += sm[q][threadIdx.x]; \
+        } \
+        tot[threadIdx.x] = t; \
+    } \
+    __syncthreads(); \
+    if (threadIdx.x != 0) return; \
+    double T[12], H[21], A[21], g[6], gf[6], hd[6]; \
+_Pragma("unroll") \
+    for (int i = 0; i < 12; ++i) T[i] = d.poses[i]; \
+_Pragma("unroll") \
+    for (int i = 0; i < 21; ++i) { H[i] = tot[i]; A[i] = tot[i]; d.hpp[i] = tot[i]; } \
+_Pragma("unroll") \
+    for (int c = 0; c < 6; ++c) { \
+        g[c] = tot[21 + c]; \
+        hd[c] = im.disp_const ? H[tri21(c, c)] : tot[27 + c]; \
+        gf[c] = im.disp_const ? g[c] : tot[33 + c]; \
+        d.gp[c] = gf[c]; \
+    } \
+_Pragma("unroll") \
+    for (int c = 0; c < 6; ++c) { \
+        double sc; \
+        if (st.iteration == 0) { sc = st.opt.jacobi_scaling ? 1.0 / (1.0 + sqrt(hd[c])) : 1.0; d.sp[c] = sc; } \
+        else sc = d.sp[c]; \
+        const double s2 = sc * sc; \
+        A[tri21(c, c)] += fmin(fmax(hd[c] * s2, st.opt.min_lm_diag), st.opt.max_lm_diag) / (damp_radius(st) * s2); \
+        im.sys[IM_SYS_SP + c] = sc; \
+    } \
+    double dx[6] = {0, 0, 0, 0, 0, 0}, Tn[12], dn = 0.0, nonfinite = 0.0; \
+    if (po_solve6(A, g, dx)) { \
+_Pragma("unroll") \
+        for (int c = 0; c < 6; ++c) if (!isfinite(dx[c])) nonfinite = 1.0; \
+        se3_plus(T, dx, Tn); \
+_Pragma("unroll") \
+        for (int c = 0; c < 12; ++c) { const double df = Tn[c] - T[c]; dn += df * df; } \
+    } else { \
+        st.step_failed = 1; \
+_Pragma("unroll") \
+        for (int c = 0; c < 6; ++c) dx[c] = 0.0; \
+_Pragma("unroll") \
+        for (int c = 0; c < 12; ++c) Tn[c] = T[c]; \
+    } \
+_Pragma("unroll") \
+    for (int c = 0; c < 12; ++c) d.cand_poses[c] = Tn[c]; \
+_Pragma("unroll") \
+    for (int r = 0; r < 6; ++r) { \
+_Pragma("unroll") \
+        for (int c = 0; c < 6; ++c) im.sys[6 * r + c] = A[tri21(r < c ? r : c, r < c ? c : r)]; \
+        im.sys[IM_SYS_RHS + r] = -g[r]; \
+        im.sys[IM_SYS_DP + r] = dx[r]; \
+    } \
+    d.part_pose[0] = dn; d.part_pose[1] = nonfinite; d.part_pose[2] = 0.0; d.part_pose[3] = 0.0; \
+    double ng[6], Tg[12], gm = 0.0, xn = 0.0; \
+_Pragma("unroll") \
+    for (int c = 0; c < 6; ++c) ng[c] = -gf[c]; \
+    se3_plus(T, ng, Tg); \
+_Pragma("unroll") \
+    for (int c = 0; c < 12; ++c) { gm = fmax(gm, fabs(T[c] - Tg[c])); xn += T[c] * T[c]; } \
+    d.part_chk[0] = gm; \
     d.part_chk[1] = xn;
+__global__ __launch_bounds__(IM_SOLVE_THREADS) void k_im_solve(Dev d) {
+    IM_SOLVE_BODY
 }
 
 // Work-group 0 does k_check's work (check_body reads what k_im_lin and k_im_solve left; nothing it writes is read here beyond
@@ -287,12 +300,11 @@ __global__ __launch_bounds__(IM_SOLVE_THREADS) void k_im_solve(Dev d) {
 // not read st.iteration, st.accepted or st.last_successful, which check_body changes in this launch.  The others, one lane per block: the disparity step, the
 // candidate disparity, the candidate cost, the row's share of the model cost change; part_eval[w] = (cost, model cost change,
 // |dd|^2, non-finite) of work-group w: the shape k_decide reduces.
-template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_eval(Dev d, double *__restrict__ delta_disp) {
+template <bool FREE> static __device__ __forceinline__ void im_eval_body(const Dev &d, const uint32_t wg, double *__restrict__ delta_disp) {
     const ImageSys &im = *d.image;
-    if (blockIdx.x == 0) { check_body(d, im.n_wg, false); return; }
     const State &st = *d.st;
     if (st.terminated) return;
-    const uint32_t wg = blockIdx.x - 1, i = wg * IM_THREADS + threadIdx.x;
+    const uint32_t i = wg * IM_THREADS + threadIdx.x;
     double Tc[12], dp[6];
 #pragma unroll
     for (int c = 0; c < 12; ++c) Tc[c] = d.cand_poses[c];
@@ -325,6 +337,38 @@ template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_eval(Dev
     block_sums(red, sm);
     if (threadIdx.x == 0) reinterpret_cast<double4 *>(d.part_eval)[wg] = make_double4(red[0], red[1], red[2], red[3]);
 }
+template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_eval(Dev d, double *__restrict__ delta_disp) {
+    if (blockIdx.x == 0) { check_body(d, d.image->n_wg, false); return; }
+    im_eval_body<FREE>(d, blockIdx.x - 1, delta_disp);
+}
+
+// ------------------------------------------------------------------- batch ---
+// n image handles in shared launches (ssba_image_solve_batch): blockIdx.y is the problem, gridDim.x the largest work-group
+// count of the batch, and a work-group past its own problem's count returns at once.  The Dev of a work-group is an entry of a
+// device array; its index is uniform over the work-group, so its fields arrive by scalar loads and no lane holds a copy.  Free or
+// constant disparities (the template argument of the solo kernels) are a branch on ImageSys::disp_const, uniform per work-group.
+// No atomics, every sum in the solo kernels' order.  k_imb_lin and k_imb_eval call the bodies k_im_lin and k_im_eval are wrappers
+// over; k_imb_solve compiles k_im_solve's statements (IM_SOLVE_BODY).  A member's result is bit-equal to solving it alone as far
+// as the compiler contracts the same sums the same way in both kernels, which tests/test_gpu_image_batch.py checks on the device.
+__global__ __launch_bounds__(IM_THREADS) void k_imb_lin(const Dev *__restrict__ devs) {
+    const Dev &d = devs[blockIdx.y];
+    if (blockIdx.x >= (unsigned)d.image->n_wg) return;
+    if (d.image->disp_const) im_lin_body<false>(d, blockIdx.x);
+    else im_lin_body<true>(d, blockIdx.x);
+}
+__global__ __launch_bounds__(IM_SOLVE_THREADS) void k_imb_solve(const Dev *__restrict__ devs) {
+    const Dev &d = devs[blockIdx.y];
+    IM_SOLVE_BODY
+}
+// work-group 0 of every problem does check_body, as in k_im_eval
+__global__ __launch_bounds__(IM_THREADS) void k_imb_eval(const Dev *__restrict__ devs) {
+    Dev &d = const_cast<Dev &>(devs[blockIdx.y]);      // (check_body's signature; it writes through the pointers d holds only)
+    const int n_wg = d.image->n_wg;
+    if (blockIdx.x > (unsigned)n_wg) return;
+    if (blockIdx.x == 0) { check_body(d, n_wg, false); return; }
+    if (d.image->disp_const) im_eval_body<false>(d, blockIdx.x - 1, nullptr);
+    else im_eval_body<true>(d, blockIdx.x - 1, nullptr);
+}
 
 // ----------------------------------------------------------------- launchers ---
 void launch_image_lin_solve(Launcher &L, const Dev &d) {
@@ -341,6 +385,15 @@ void launch_image(Launcher &L, const Dev &d, double *delta_disp) {
     else LAUNCH(KC_BACKSUB_EVAL, k_im_eval<true>, dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
     launch_decide_commit(L, d, true, true, 1);      // k_decide alone: Dev::n_groups = n_wg evaluation partials, one pose partial
     launch_best(L, d);
+}
+
+// One iteration of n problems: five launches whatever n is.  max_wg: the largest ImageSys::n_wg, best_groups: the largest grid
+// launch_best would take, terminated: n words (State::terminated of every problem after its decision).
+void launch_image_batch(hipStream_t stream, const Dev *devs, int n, int max_wg, int best_groups, int *terminated) {
+    hipLaunchKernelGGL(k_imb_lin, dim3(max_wg, n), dim3(IM_THREADS), 0, stream, devs);
+    hipLaunchKernelGGL(k_imb_solve, dim3(1, n), dim3(IM_SOLVE_THREADS), 0, stream, devs);
+    hipLaunchKernelGGL(k_imb_eval, dim3(max_wg + 1, n), dim3(IM_THREADS), 0, stream, devs);
+    launch_batch_decide_best(stream, devs, n, best_groups, terminated);
 }
 
 }  // namespace ssba

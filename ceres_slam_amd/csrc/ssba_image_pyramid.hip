@@ -16,6 +16,7 @@
 // matcher of ssba_sgbm.hip writes its double map straight into the level's disparity buffer, ahead of the k_pyr_finish that
 // derives the next level from it.
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -285,8 +286,38 @@ int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, uint32_t *
     return SSBA_OK;
 }
 
-// Coarse to fine: the reference's main from :94 on, once per level, the pose carried down.  Levels above disparity_level hold
-// their derived disparities constant (free, they absorb the motion and the pose does not move).
+// Per-level set-up shared by ssba_image_pyramid_align and ssba_image_pyramid_align_batch: the map the handle's blocks come from
+// (the caller's at disparity_level, the level's derived map in `derived` above it) and the finalized handle on the level, with
+// camera0 scaled to it.  Levels above disparity_level hold their derived disparities constant (free, they absorb the motion and
+// the pose does not move).
+static int pyr_level_handle(ssba_image_pyramid *pyr, const ssba_camera *camera0, int l, double *pose, double *disparity, std::vector<double> &derived,
+                            int interpolation, int disparities_constant, ssba_problem **out) {
+    *out = nullptr;
+    const ssba_image_pyramid::Level &L = pyr->lv[l];
+    const bool base = l == pyr->disparity_level;
+    const double s = ldexp(1.0, -l);       // pyrDown samples at even pixels: u_l = u / 2^l exactly
+    const ssba_camera cam = {camera0->fu * s, camera0->fv * s, camera0->cu * s, camera0->cv * s, camera0->b};
+    double *map = disparity;
+    int rc;
+    if (!base) {
+        derived.resize((size_t)L.rows * L.cols);
+        if ((rc = ssba_image_pyramid_level(pyr, (uint32_t)l, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, derived.data()))) return rc;
+        map = derived.data();
+    }
+    ssba_problem *h = nullptr;
+    if ((rc = ssba_create(&cam, pyr->device, &h))) return rc;
+    if ((rc = ssba_add_image_level(h, pyr, (uint32_t)l, pose, map, interpolation)) ||
+        (rc = ssba_set_disparity_blocks_constant(h, base ? (disparities_constant != 0) : 1)) || (rc = ssba_finalize(h))) {
+        const std::string msg = ssba_last_error();
+        ssba_destroy(h);
+        set_last_error(msg);
+        return rc;
+    }
+    *out = h;
+    return SSBA_OK;
+}
+
+// Coarse to fine: the reference's main from :94 on, once per level, the pose carried down.
 int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
                              int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries) {
     const char *call = "ssba_image_pyramid_align";
@@ -300,31 +331,88 @@ int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0
     }
     std::vector<double> derived;
     for (int l = (int)coarsest_level; l >= pyr->disparity_level; --l) {
-        const ssba_image_pyramid::Level &L = pyr->lv[l];
-        const bool base = l == pyr->disparity_level;
-        const double s = ldexp(1.0, -l);       // pyrDown samples at even pixels: u_l = u / 2^l exactly
-        const ssba_camera cam = {camera0->fu * s, camera0->fv * s, camera0->cu * s, camera0->cv * s, camera0->b};
-        double *map = disparity;
-        int rc;
-        if (!base) {
-            derived.resize((size_t)L.rows * L.cols);
-            if ((rc = ssba_image_pyramid_level(pyr, (uint32_t)l, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, derived.data()))) return rc;
-            map = derived.data();
-        }
         ssba_problem *h = nullptr;
-        if ((rc = ssba_create(&cam, pyr->device, &h))) return rc;
         ssba_summary sum;
         memset(&sum, 0, sizeof sum);
-        if (!(rc = ssba_add_image_level(h, pyr, (uint32_t)l, pose, map, interpolation)) &&
-            !(rc = ssba_set_disparity_blocks_constant(h, base ? (disparities_constant != 0) : 1)) && !(rc = ssba_finalize(h)))
-            rc = ssba_solve(h, options, &sum);
+        int rc = pyr_level_handle(pyr, camera0, l, pose, disparity, derived, interpolation, disparities_constant, &h);
+        if (!rc) rc = ssba_solve(h, options, &sum);
         const std::string msg = rc ? std::string(ssba_last_error()) : std::string();
-        ssba_destroy(h);
+        if (h) ssba_destroy(h);
         if (rc) { set_last_error(std::string(call) + ": level " + std::to_string(l) + ": " + msg); }
         if (summaries && (rc == SSBA_OK || rc == SSBA_ERR_NUMERICAL_FAILURE)) summaries[coarsest_level - (uint32_t)l] = sum;
         if (rc) return rc;      // an unusable solution left the pose (and the map) as they were before this level
     }
     return SSBA_OK;
+}
+
+// The same over n pyramids in lockstep: per level one handle per pyramid still in the run and one ssba_image_solve_batch.
+int ssba_image_pyramid_align_batch(ssba_image_pyramid **pyramids, uint32_t n, const ssba_camera *camera0, double *poses, double **disparities,
+                                   uint32_t coarsest_level, int interpolation, int disparities_constant, const ssba_options *options,
+                                   ssba_summary *summaries, int *statuses) {
+    const char *call = "ssba_image_pyramid_align_batch";
+    if (!pyramids || !camera0 || !poses || !disparities || !options) return pyr_invalid(call, "NULL argument");
+    if (n == 0) return pyr_invalid(call, "n = 0");
+    if (n > SSBA_IMAGE_BATCH_MAX) return pyr_invalid(call, "n is above SSBA_IMAGE_BATCH_MAX");
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string who = "pyramid " + std::to_string(k);
+        if (!pyramids[k] || !disparities[k]) return pyr_invalid(call, (who + ": NULL pyramid or disparity map").c_str());
+        if (pyramids[k]->device != pyramids[0]->device) return pyr_invalid(call, (who + " lives on a different device than pyramid 0").c_str());
+        if (pyramids[k]->disparity_level != pyramids[0]->disparity_level) return pyr_invalid(call, (who + " has a different disparity_level than pyramid 0").c_str());
+        if (coarsest_level >= pyramids[k]->lv.size()) return pyr_invalid(call, (who + " has no such level (coarsest_level)").c_str());
+    }
+    const int dl = pyramids[0]->disparity_level;
+    if ((int)coarsest_level < dl) return pyr_invalid(call, "coarsest_level is finer than disparity_level: no disparity map there");
+    if (interpolation != SSBA_IMAGE_NEAREST && interpolation != SSBA_IMAGE_BILINEAR) return pyr_invalid(call, "unknown interpolation");
+    if (options->trust_region_strategy_type != 0) {
+        set_last_error(std::string(call) + ": image blocks are solved with Levenberg-Marquardt only (DOGLEG asked for)");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    const uint32_t levels = coarsest_level - (uint32_t)dl + 1;
+    if (summaries) memset(summaries, 0, sizeof(ssba_summary) * (size_t)n * levels);
+    std::vector<int> status(n, SSBA_OK);
+    std::vector<std::vector<double>> derived(n);
+    std::vector<uint32_t> who;
+    std::vector<ssba_problem *> hs;
+    std::vector<ssba_summary> sums;
+    std::vector<int> sts;
+    int fatal = SSBA_OK;
+    std::string fatal_msg;
+    for (int l = (int)coarsest_level; l >= dl && !fatal; --l) {
+        who.clear(); hs.clear();
+        for (uint32_t k = 0; k < n; ++k) {
+            if (status[k]) continue;       // dropped out at a coarser level: its pose stays the last usable one
+            ssba_problem *h = nullptr;
+            const int rc = pyr_level_handle(pyramids[k], camera0, l, poses + (size_t)k * 12, disparities[k], derived[k], interpolation, disparities_constant, &h);
+            if (rc) { status[k] = rc; continue; }
+            who.push_back(k); hs.push_back(h);
+        }
+        if (hs.empty()) break;
+        constexpr int UNSET = INT32_MIN;
+        sums.assign(hs.size(), ssba_summary{});
+        sts.assign(hs.size(), UNSET);
+        const int rc = ssba_image_solve_batch(hs.data(), (uint32_t)hs.size(), options, 0, sums.data(), sts.data());
+        if (rc && sts[0] == UNSET) {       // the batch itself failed (not a member's solve): nothing more can run
+            fatal = rc;
+            fatal_msg = std::string(call) + ": level " + std::to_string(l) + ": " + ssba_last_error();
+        }
+        for (size_t q = 0; q < hs.size(); ++q) {
+            ssba_destroy(hs[q]);
+            if (fatal) continue;
+            const uint32_t k = who[q];
+            if (summaries && (sts[q] == SSBA_OK || sts[q] == SSBA_ERR_NUMERICAL_FAILURE)) summaries[(size_t)k * levels + (coarsest_level - (uint32_t)l)] = sums[q];
+            status[k] = sts[q];
+        }
+    }
+    if (fatal) { set_last_error(fatal_msg); return fatal; }
+    int first = SSBA_OK;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (statuses) statuses[k] = status[k];
+        if (status[k] && !first) {
+            first = status[k];
+            set_last_error(std::string(call) + ": pyramid " + std::to_string(k) + " ended without a usable solution or could not be set up at one level");
+        }
+    }
+    return first;
 }
 
 }  // extern "C"

@@ -781,7 +781,7 @@ __global__ __launch_bounds__(1024) void k_check(Dev d, int fused_parts) {      /
 }
 
 
-__global__ __launch_bounds__(256) void k_best(Dev d) {
+static __device__ __forceinline__ void best_body(const Dev &d) {
     const State &st = *d.st;
     if (st.copy_best != st.check_count) return;       // set by the k_check just before; a later k_check moves the count on
     const size_t n = (size_t)d.P * 12 > (size_t)d.Lpad * 3 ? (size_t)d.P * 12 : (size_t)d.Lpad * 3;
@@ -794,6 +794,9 @@ __global__ __launch_bounds__(256) void k_best(Dev d) {
         if (d.phong && i < (size_t)d.nsh) d.best_sh[i] = d.sh[i];
     }
 }
+__global__ __launch_bounds__(256) void k_best(Dev d) { best_body(d); }
+// batched image handles (ssba_image.hip, k_imb_*): blockIdx.y is the problem; the stride of the copy is the grid of the largest
+__global__ __launch_bounds__(256) void k_imb_best(const Dev *__restrict__ devs) { best_body(devs[blockIdx.y]); }
 
 // candidate poses = Plus(x, delta_p)  [Evaluator::Plus with SE3Perturbation]
 // fuse_best: also does k_best's share for the poses (x -> best when the k_check of this iteration saw the cost improve;
@@ -1031,6 +1034,14 @@ __device__ __forceinline__ void decide_body(Dev &d, State &st, int n_eval_parts,
 __global__ __launch_bounds__(256) void k_decide(Dev d, int n_eval_parts, int n_pose_parts) {
     State &st = *d.st;
     decide_body(d, st, n_eval_parts, n_pose_parts);       // tests st.terminated itself, after its partial sums are read
+}
+// batched image handles: one work-group per problem (blockIdx.y), k_decide's arguments of an image handle (Dev::n_groups
+// evaluation partials, one pose partial), and the problem's termination word into terminated[problem] for the host
+__global__ __launch_bounds__(256) void k_imb_decide(const Dev *__restrict__ devs, int *__restrict__ terminated) {
+    Dev &d = const_cast<Dev &>(devs[blockIdx.y]);      // (decide_body's signature; it writes through the pointers d holds only)
+    State &st = *d.st;
+    decide_body(d, st, d.n_groups, 1);
+    if (threadIdx.x == 0) terminated[blockIdx.y] = st.terminated;
 }
 
 // The same pass in the window layout with SP lanes per landmark (see k_linearize_landmarks_w): wave w takes the slots
@@ -2228,6 +2239,15 @@ void launch_pose_only_step(Launcher &L, const Dev &d) {
 }
 void launch_pose_only_cov(Launcher &L, const Dev &d, const int *poses, int n, double *out, int *fail) {
     LAUNCH(KC_SMALL, k_po_cov, dim3((n + 63) / 64), dim3(64), 0, d, poses, n, out, fail);
+}
+// the two launches that close an iteration of batched image handles (ssba_image.hip: launch_image_batch)
+int image_best_groups(const Dev &d) {
+    const size_t n = (size_t)d.P * 12 > (size_t)d.Lpad * 3 ? (size_t)d.P * 12 : (size_t)d.Lpad * 3;
+    return (int)std::min<size_t>((n + 255) / 256, 512);
+}
+void launch_batch_decide_best(hipStream_t stream, const Dev *devs, int n, int best_groups, int *terminated) {
+    hipLaunchKernelGGL(k_imb_decide, dim3(1, n), dim3(256), 0, stream, devs, terminated);
+    hipLaunchKernelGGL(k_imb_best, dim3(best_groups, n), dim3(256), 0, stream, devs);
 }
 // k_best alone (dense photometric alignment, ssba_image.hip: the launch that closes its iteration)
 void launch_best(Launcher &L, const Dev &d) {

@@ -139,6 +139,12 @@ void launch_best(Launcher &L, const Dev &d);
 // k_im_eval also leaves the disparity step per block (test hook), or null.
 void launch_image(Launcher &L, const Dev &d, double *delta_disp = nullptr);
 void launch_image_lin_solve(Launcher &L, const Dev &d);
+// n image handles in shared launches (ssba_image_solve_batch): k_imb_lin . k_imb_solve . k_imb_eval . k_imb_decide . k_imb_best over
+// a device array of n Dev, blockIdx.y = problem.  max_wg: the largest ImageSys::n_wg; best_groups: the largest image_best_groups;
+// terminated: n device words, State::terminated of every problem after its decision.  Not timed per kernel class.
+void launch_image_batch(hipStream_t stream, const Dev *devs, int n, int max_wg, int best_groups, int *terminated);
+int image_best_groups(const Dev &d);
+void launch_batch_decide_best(hipStream_t stream, const Dev *devs, int n, int best_groups, int *terminated);
 // config 3 (ssba_phong_solver.hip)
 int upload_phong_tables(hipStream_t s);
 int configure_phong();

@@ -453,6 +453,23 @@ class ImageAlignment(StereoBA):
         return ImageStep(cost.value, r, Jp, Jd, S, rhs, dp, dd, mcc.value)
 
 
+def solve_image_batch(alignments, options: capi.Options = None, ignore_convergence: bool = False):
+    """ssba_image_solve_batch: the finalized ImageAlignment handles solved together, five launches per iteration of the whole
+    batch.  Every member's pose, disparity map, summary and iteration_log() are bit-equal to its own solve().  Returns a list of
+    (summary, status), status 0 or -3 (no usable solution: that member's blocks are left as they were); refusals raise."""
+    alignments = list(alignments)
+    n = len(alignments)
+    lib = capi.load()
+    o = options or capi.default_options(use_nonmonotonic_steps=1)
+    hs = (C.c_void_p * max(n, 1))(*[a.h for a in alignments])
+    sums = (capi.Summary * max(n, 1))()
+    sts = (C.c_int32 * max(n, 1))()
+    rc = lib.ssba_image_solve_batch(hs, n, C.byref(o), int(ignore_convergence), sums, sts)
+    if rc != 0 and not (rc == -3 and any(s == -3 for s in sts) and all(s in (0, -3) for s in sts)):
+        capi.check(rc, "ssba_image_solve_batch")
+    return [(sums[k], int(sts[k])) for k in range(n)]
+
+
 class PyramidLevel(NamedTuple):
     """What ssba_image_pyramid_level returns for one level, and the level-0 camera scaled to it."""
     ref_u8: np.ndarray          # (rows, cols) uint8
@@ -582,6 +599,46 @@ class ImagePyramid:
         if rc not in (0, -3):
             capi.check(rc, "ssba_image_pyramid_align")
         return rc, list(sums)
+
+
+    @staticmethod
+    def align_batch(pyramids, poses, disparities, coarsest_level: int = None, camera: dict = None, interpolation: int = capi.IMAGE_BILINEAR,
+                    disparity_const: bool = False, options: capi.Options = None):
+        """Coarse to fine over n pyramids in lockstep (ssba_image_pyramid_align_batch): one shared solve per level.  ``poses``
+        (n, 12) and every map of ``disparities`` (float64, at disparity_level) are updated in place; ``camera`` is the level-0
+        camera (default: the first pyramid's).  Returns (status, summaries, statuses): summaries[k] is pyramid k's list, coarsest
+        level first; statuses[k] is 0, or what stopped pyramid k (it keeps its last usable pose).  Refusals raise."""
+        pyramids = list(pyramids)
+        n = len(pyramids)
+        cam = camera if camera is not None else (pyramids[0].camera if n else None)
+        if n and cam is None:
+            raise ValueError("no camera: pass the level-0 camera, or give it to the first pyramid")
+        if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags.c_contiguous and poses.size == 12 * n):
+            raise ValueError("poses must be a contiguous float64 array of n x 12: it is updated in place")
+        disparities = list(disparities)
+        if len(disparities) != n:
+            raise ValueError("one disparity map per pyramid")
+        for k, d in enumerate(disparities):
+            if not (isinstance(d, np.ndarray) and d.dtype == np.float64 and d.flags.c_contiguous):
+                raise ValueError("every disparity map must be a contiguous float64 array: it is updated in place")
+            lvl = pyramids[k].disparity_level
+            if 0 <= lvl < pyramids[k].levels and d.shape != pyramids[k].shape(lvl):
+                raise ValueError(f"disparity {k} of shape {d.shape}, level {lvl} is {pyramids[k].shape(lvl)}")
+        lib = capi.load()
+        dl = pyramids[0].disparity_level if n else 0
+        top = (pyramids[0].levels - 1 if n else 0) if coarsest_level is None else int(coarsest_level)
+        levels = max(top - dl + 1, 1)
+        o = options or capi.default_options(use_nonmonotonic_steps=1)
+        hs = (C.c_void_p * max(n, 1))(*[p.h for p in pyramids])
+        maps = (capi._dp * max(n, 1))(*[capi.dptr(d) for d in disparities])
+        sums = (capi.Summary * (max(n, 1) * levels))()
+        sts = (C.c_int32 * max(n, 1))()
+        c = capi.Camera(**cam) if cam is not None else capi.Camera()
+        rc = lib.ssba_image_pyramid_align_batch(hs, n, C.byref(c), capi.dptr(poses), maps, top, int(interpolation), int(disparity_const),
+                                                C.byref(o), sums, sts)
+        if rc != 0 and not (any(s != 0 for s in sts) and rc == next(s for s in sts if s != 0)):
+            capi.check(rc, "ssba_image_pyramid_align_batch")
+        return rc, [[sums[k * levels + i] for i in range(levels)] for k in range(n)], [int(s) for s in sts]
 
 
 def stereo_sgbm(left, right, device: int = -1, **params):

@@ -662,3 +662,54 @@ def make_stereo_triple(rows: int, cols: int, seed: int = 0, *, depth: float = 6.
     s = (depth - n @ o) / (ray @ n)
     right = texture(o + ray * s[..., None])
     return StereoTriple(pair=pair, left0=quantise_u8(pair.ref), right0=quantise_u8(right), left1=quantise_u8(pair.track))
+
+
+@dataclass
+class StereoSequence:
+    """F frames of a rectified rig moving past make_image_pair's plane: what a dataset delivers to a sequence driver."""
+
+    camera: dict
+    left: np.ndarray            # (F, rows, cols) uint8
+    right: np.ndarray           # (F, rows, cols) uint8: the same instant from (+b, 0, 0)
+    poses_true: np.ndarray      # (F, 12) T_k_0, frame 0 the identity
+    pose_init: np.ndarray       # (12,) the start of every pair (make_image_pair's)
+
+
+def make_stereo_sequence(rows: int, cols: int, frames: int, seed: int = 0, *, depth: float = 6.0, slant=(0.25, -0.15), motion: float = 1.0,
+                         min_wavelength_px: float = 10.0) -> StereoSequence:
+    """Consecutive make_stereo_triple-style views of the one plane: frame k is the plane a x + b y + z = depth of frame 0 seen from
+    T_k_0 = T_step^k, with T_step drawn as make_image_pair draws its motion (frames 0 and 1 are that pair's two views).  Pair k of a
+    sequence driver is (left_k, right_k, left_{k+1}); its true pose is T_step for every k."""
+    if frames < 2:
+        raise ValueError("a sequence has at least two frames")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam, n, texture, ray, px_on_plane = _plane_scene(rows, cols, rng, depth, slant, min_wavelength_px)
+    t = motion * np.array([0.05, -0.03, 0.08]) * (1.0 + 0.2 * rng.standard_normal(3))
+    R = so3_exp(motion * np.array([0.004, -0.006, 0.008]) * (1.0 + 0.2 * rng.standard_normal(3)))
+    left, right, poses = [], [], []
+    Rk, tk = np.eye(3), np.zeros(3)
+    for _ in range(frames):
+        dirs = ray @ Rk                                             # rows of Rk^T ray
+        views = []
+        for centre in (np.zeros(3), np.array([cam["b"], 0.0, 0.0])):
+            o = Rk.T @ (centre - tk)                                # the camera centre in frame 0
+            s = (depth - n @ o) / (dirs @ n)
+            views.append(quantise_u8(texture(o + dirs * s[..., None])))
+        left.append(views[0]); right.append(views[1]); poses.append(pose_pack(tk, Rk))
+        Rk, tk = R @ Rk, R @ tk + t
+    t0, R0 = np.array([-0.011, 0.013, -0.017]) * px_on_plane, so3_exp(np.array([2e-4, -3e-4, 2.5e-4]))
+    return StereoSequence(camera=cam, left=np.stack(left), right=np.stack(right), poses_true=np.stack(poses), pose_init=pose_pack(t0, R0))
+
+
+def write_stereo_sequence(path: str, seq: StereoSequence, levels: int, disparity_level: int, sgbm_params: bytes, interpolation: int = 1,
+                          disparities_constant: bool = True, gradient_source: int = 1, gradient_scale: float = 0.125) -> None:
+    """The raw file examples/dense_stereo_sequence_gpu.cpp reads (its header states the layout); sgbm_params: the 11 int32 of
+    ssba_sgbm_params (bytes(capi.sgbm_params(...)))."""
+    F, rows, cols = seq.left.shape
+    with open(path, "wb") as f:
+        f.write(np.array([F, rows, cols, levels, disparity_level, interpolation, int(disparities_constant), gradient_source], np.int32).tobytes())
+        f.write(np.array([gradient_scale] + [seq.camera[k] for k in ("fu", "fv", "cu", "cv", "b")], np.float64).tobytes())
+        f.write(np.ascontiguousarray(seq.pose_init, dtype=np.float64).tobytes())
+        f.write(bytes(sgbm_params))
+        for k in range(F):
+            f.write(seq.left[k].tobytes() + seq.right[k].tobytes())

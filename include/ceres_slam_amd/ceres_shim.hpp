@@ -553,6 +553,7 @@ class Problem {
 
  private:
     friend void Solve(const Solver::Options &, Problem *, Solver::Summary *);
+    friend void SolveBatch(const Solver::Options &, const std::vector<Problem *> &, std::vector<Solver::Summary> *);
     friend const char *shim_prepare(Problem &, int *);
     friend class Covariance;
     // back-end handle of the current structure and the contiguous staging tables it points into
@@ -892,6 +893,50 @@ inline void SolveCoarseToFine(const Solver::Options &options, ceres_slam::ImageP
     }
 }
 
+// Coarse to fine over several pyramids in lockstep (ssba_image_pyramid_align_batch): the pairs of a sequence, one shared solve per
+// level.  poses holds 12 doubles per pyramid, disparities one map at disparity_level per pyramid; both are updated in place.
+// summaries gets one vector per pyramid (the levels solved, coarsest first); a pyramid that ends a level without a usable solution
+// keeps its last usable pose and its last entry says FAILURE.  Throws std::invalid_argument where the C call refuses.
+inline void SolveCoarseToFine(const Solver::Options &options, const std::vector<ceres_slam::ImagePyramid *> &pyramids,
+                              const ceres_slam::StereoCamera &level0_camera, double *poses, const std::vector<double *> &disparities,
+                              int coarsest_level, int interpolation, bool disparities_constant,
+                              std::vector<std::vector<Solver::Summary>> *summaries) {
+    if (pyramids.size() != disparities.size()) throw std::invalid_argument("ceres_shim: SolveCoarseToFine needs one disparity map per pyramid");
+    const ssba_options o = shim_options(options);
+    const ssba_camera cam = ssba_camera{level0_camera.fu, level0_camera.fv, level0_camera.cu, level0_camera.cv, level0_camera.b};
+    std::vector<ssba_image_pyramid *> hs;
+    for (ceres_slam::ImagePyramid *p : pyramids) hs.push_back(p ? p->handle() : nullptr);
+    const int levels = pyramids.empty() || !pyramids[0] ? 1 : std::max(coarsest_level - pyramids[0]->disparity_level() + 1, 1);
+    std::vector<ssba_summary> s(std::max<size_t>(pyramids.size(), 1) * (size_t)levels);
+    std::vector<int> st(std::max<size_t>(pyramids.size(), 1), 0);
+    std::vector<double *> maps(disparities);
+    if (maps.empty()) maps.push_back(nullptr);
+    if (hs.empty()) hs.push_back(nullptr);
+    const int rc = ssba_image_pyramid_align_batch(hs.data(), (uint32_t)pyramids.size(), &cam, poses, maps.data(), (uint32_t)coarsest_level, interpolation,
+                                                  disparities_constant ? 1 : 0, &o, s.data(), st.data());
+    bool member = false;
+    for (size_t k = 0; k < pyramids.size(); ++k) member = member || st[k] != 0;
+    if (rc && !member) {
+        const std::string msg = std::string("ssba_image_pyramid_align_batch: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
+        if (rc == SSBA_ERR_INVALID_ARGUMENT || rc == SSBA_ERR_UNSUPPORTED || rc == SSBA_ERR_STATE) throw std::invalid_argument(msg);
+        throw std::runtime_error(msg);
+    }
+    summaries->assign(pyramids.size(), std::vector<Solver::Summary>());
+    for (size_t k = 0; k < pyramids.size(); ++k) {
+        for (int l = 0; l < levels; ++l) {
+            const ssba_summary &x = s[k * (size_t)levels + (size_t)l];
+            if (x.num_iterations == 0) break;      // levels this pyramid did not reach
+            (*summaries)[k].push_back(Solver::Summary());
+            shim_summary(x, &(*summaries)[k].back());
+        }
+        if (st[k] && st[k] != SSBA_ERR_NUMERICAL_FAILURE) {
+            (*summaries)[k].push_back(Solver::Summary());
+            (*summaries)[k].back().termination_type = FAILURE;
+            (*summaries)[k].back().message = std::string("ssba_image_pyramid_align_batch: ") + ssba_status_string(st[k]);
+        }
+    }
+}
+
 // ceres::Solve(options, &problem, &summary) (tests/dataset_vo.cpp:81).  Never throws for
 // solver outcomes: the result is in `summary` (as with Ceres); API misuse throws.
 inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summary *summary) {
@@ -926,6 +971,47 @@ inline void Solve(const Solver::Options &options, Problem *problem, Solver::Summ
             for (size_t m = 0; m < phong_blocks.size(); ++m) { std::memcpy(phong_blocks[m], &phong[3 * m], 3 * sizeof(double)); *texture_blocks[m] = texture[m]; }
             std::memcpy(P.light_, light, sizeof light);
         }
+    }
+}
+
+// Several problems that hold only ImageError blocks, solved in shared launches (ssba_image_solve_batch): every summary is what
+// ceres::Solve would have given for that problem alone, and the callers' poses and disparity maps are written as there.  A problem
+// whose minimiser fails does not stop the others.  Throws std::invalid_argument where the C call refuses: an empty vector, a NULL
+// entry, the same problem twice, a problem with other blocks than ImageError, DOGLEG.
+inline void SolveBatch(const Solver::Options &options, const std::vector<Problem *> &problems, std::vector<Solver::Summary> *summaries) {
+    if (problems.empty()) throw std::invalid_argument("ceres_shim: SolveBatch: no problem");
+    for (size_t k = 0; k < problems.size(); ++k) {
+        if (!problems[k]) throw std::invalid_argument("ceres_shim: SolveBatch: problem " + std::to_string(k) + " is NULL");
+        for (size_t q = 0; q < k; ++q)
+            if (problems[q] == problems[k]) throw std::invalid_argument("ceres_shim: SolveBatch: problem " + std::to_string(k) + " is in the batch twice");
+        if (problems[k]->image_blocks_.empty() || !problems[k]->obs_pose_.empty())
+            throw std::invalid_argument("ceres_shim: SolveBatch: problem " + std::to_string(k) + " must hold ImageError blocks and nothing else");
+    }
+    if (options.trust_region_strategy_type == DOGLEG) throw std::invalid_argument("ceres_shim: SolveBatch: ImageError blocks are solved with Levenberg-Marquardt only");
+    std::vector<ssba_problem *> hs;
+    for (size_t k = 0; k < problems.size(); ++k) {
+        int rc = 0;
+        if (const char *where = shim_prepare(*problems[k], &rc))
+            throw std::runtime_error(std::string("ceres_shim: SolveBatch: problem ") + std::to_string(k) + ": " + where + ": " + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
+        hs.push_back(problems[k]->h_);
+    }
+    const ssba_options o = shim_options(options);
+    std::vector<ssba_summary> s(problems.size());
+    std::vector<int> st(problems.size(), 0);
+    const int rc = ssba_image_solve_batch(hs.data(), (uint32_t)hs.size(), &o, 0, s.data(), st.data());
+    bool member = false;
+    for (int x : st) member = member || x != 0;
+    if (rc && !member) {
+        const std::string msg = std::string("ssba_image_solve_batch: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
+        if (rc == SSBA_ERR_INVALID_ARGUMENT || rc == SSBA_ERR_UNSUPPORTED || rc == SSBA_ERR_STATE) throw std::invalid_argument(msg);
+        throw std::runtime_error(msg);
+    }
+    summaries->assign(problems.size(), Solver::Summary());
+    for (size_t k = 0; k < problems.size(); ++k) {
+        if (st[k] && st[k] != SSBA_ERR_NUMERICAL_FAILURE) {
+            (*summaries)[k].termination_type = FAILURE;
+            (*summaries)[k].message = std::string("ssba_image_solve_batch: ") + ssba_status_string(st[k]);
+        } else shim_summary(s[k], &(*summaries)[k]);
     }
 }
 

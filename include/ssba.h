@@ -541,6 +541,40 @@ SSBA_API int ssba_set_disparity_blocks_constant(ssba_problem *p, int is_constant
 SSBA_API int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose,
                     double *J_disp, double *S, double *rhs, double *delta_pose, double *delta_disp, double *model_cost_change);
 
+/* ---- dense photometric alignment: many handles in shared launches --------------------------------------------------------
+ * A sequence of N stereo frames is N - 1 alignments that do not depend on each other, and one of the driver's size leaves the GPU
+ * nearly idle.  ssba_image_solve_batch solves n finalized image handles together: one iteration of the whole batch is five
+ * launches whatever n is (k_imb_lin . k_imb_solve . k_imb_eval . k_imb_decide . k_imb_best, the problem in blockIdx.y), members
+ * that have terminated ride along as no-ops, and every member's result -- pose, disparity map, summary, iteration log -- is
+ * bit-equal to ssba_solve on that handle alone: the batched kernels run the solo kernels' source (shared functions, every sum in
+ * the same order, no atomics).  That equality is tested on the device (tests/test_gpu_image_batch.py), not guaranteed by the
+ * language: a compiler may contract the same sum of two products differently in two kernels.
+ * n = 1 has nothing to share and takes the solo path (ssba_solve, or the stepwise calls with ignore_convergence).
+ * The buffers, events and captured graphs of a call stay on handles[0] and serve the next call with the same n and launch shapes;
+ * they are released with that handle.
+ *
+ * The call: ssba_solve_begin on every handle (uploads, options, a reset trust-region state), the rounds, ssba_solve_end on every
+ * handle, so pose and disparity of each caller are written back exactly as after ssba_solve.  It returns when every member has
+ * terminated, or after max_num_iterations + 3 rounds as ssba_solve does.  ignore_convergence != 0: exactly max_num_iterations
+ * rounds, i.e. ssba_solve_begin(.., 1) / ssba_solve_step(max_num_iterations) / ssba_solve_end on every member.
+ * Stream: the shared launches run on handles[0]'s stream (ssba_set_stream), ordered behind the begin of every other handle by
+ * events (hipStreamWaitEvent); that stream is synchronised before the ends.  The call is synchronous.
+ * summaries (n) and statuses (n) may be NULL.  statuses[k] is what ssba_solve would have returned for handle k: SSBA_OK, or
+ * SSBA_ERR_NUMERICAL_FAILURE when its minimiser ended without a usable solution (its blocks are then left as they were).  Such a
+ * member does not stop the others.  The call returns the first non-zero status in handle order, or SSBA_OK.
+ * minimizer_progress_to_stdout is ignored in a batch.
+ * Refusals, each with a message (ssba_last_error) that names the call and the index of the offending handle; after a refusal
+ * every handle is as it was:
+ *   SSBA_ERR_INVALID_ARGUMENT  n = 0, a NULL entry, the same handle twice, handles on different devices,
+ *                              n > SSBA_IMAGE_BATCH_MAX (the device array of the handles' states is 3.5 KB per member)
+ *   SSBA_ERR_UNSUPPORTED       a handle without image blocks, a DOGLEG solve, a handle with kernel timing switched on
+ *   SSBA_ERR_STATE             a handle that is not finalized, a handle inside a stepwise solve
+ * Afterwards every handle is an ordinary handle again: ssba_solve, ssba_solve_restart (after a new ssba_solve_begin),
+ * ssba_iteration_log and ssba_pose_covariance work on it. */
+#define SSBA_IMAGE_BATCH_MAX 4096
+SSBA_API int ssba_image_solve_batch(ssba_problem **handles, uint32_t n, const ssba_options *options, int ignore_convergence,
+                           ssba_summary *summaries, int *statuses);
+
 /* ---- dense photometric alignment: the driver's pre-processing and a coarse-to-fine solve ------------------------------
  * An image pyramid replaces tests/dense_stereo_test.cpp:52-72 (everything between imread / SGBM and the residual blocks): it is
  * built once from the raw 8-bit pair and one disparity map and holds every level in device memory.  Level 0 is the caller's
@@ -593,6 +627,19 @@ SSBA_API int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, u
 SSBA_API int ssba_add_image_level(ssba_problem *p, ssba_image_pyramid *pyr, uint32_t level, double *pose, double *disparity, int interpolation);
 SSBA_API int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
                              int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries);
+/* align_batch: coarse to fine over n pyramids in lockstep (the pairs of a sequence).  Per level one handle per pyramid, built
+ *   exactly as ssba_image_pyramid_align builds it, and ONE ssba_image_solve_batch; every pyramid's pose, map and summaries are
+ *   bit-equal to ssba_image_pyramid_align on it alone.  poses: n x 12; disparities: n caller-owned maps at disparity_level, updated
+ *   in place as there; summaries (may be NULL): n x (coarsest_level - disparity_level + 1), pyramid-major, each row laid out as the
+ *   solo call's, zero where a level was not solved; statuses (may be NULL): n.  Image sizes may differ between the pyramids.
+ *   A pyramid whose level ends without a usable solution (or cannot be set up: no usable disparity on a level) keeps its last
+ *   usable pose, drops out of the finer levels and gets that status; the others go on.  Returns the first non-zero status in
+ *   pyramid order, or SSBA_OK.  SSBA_ERR_INVALID_ARGUMENT (nothing is touched): n = 0 or above SSBA_IMAGE_BATCH_MAX, a NULL entry,
+ *   pyramids that differ in device or disparity_level, a pyramid without coarsest_level, coarsest_level < disparity_level, an
+ *   unknown interpolation.  SSBA_ERR_UNSUPPORTED: DOGLEG. */
+SSBA_API int ssba_image_pyramid_align_batch(ssba_image_pyramid **pyramids, uint32_t n, const ssba_camera *camera0, double *poses, double **disparities,
+                                   uint32_t coarsest_level, int interpolation, int disparities_constant, const ssba_options *options,
+                                   ssba_summary *summaries, int *statuses);
 
 /* ---- dense photometric alignment: the disparity map from a rectified pair ------------------------------------------------
  * ssba_stereo_sgbm replaces cv::StereoSGBM sgbm(0, 64, 15); sgbm(left0, right0, disp0) (tests/dense_stereo_test.cpp:61-65): a

@@ -41,7 +41,7 @@ SYMBOLS = [
     "ssba_add_image_blocks", "ssba_set_disparity_blocks_constant", "ssba_image_step",
     "ssba_image_pyramid_create", "ssba_image_pyramid_destroy", "ssba_image_pyramid_level", "ssba_add_image_level", "ssba_image_pyramid_align",
     "ssba_sgbm_default_params", "ssba_stereo_sgbm", "ssba_image_pyramid_create_stereo",
-    "ssba_image_solve_batch", "ssba_image_pyramid_align_batch",
+    "ssba_image_solve_batch", "ssba_image_pyramid_align_batch", "ssba_image_pyramid_set_huber_loss",
 ]
 
 
@@ -187,6 +187,7 @@ def load():
     L.ssba_image_pyramid_level.argtypes = [H, C.c_uint32, _u32p, _u32p, _u8p, _u8p, _dp, _dp, _dp, _dp, _dp]
     L.ssba_add_image_level.argtypes = [H, H, C.c_uint32, _dp, _dp, C.c_int]
     L.ssba_image_pyramid_align.argtypes = [H, C.POINTER(Camera), _dp, _dp, C.c_uint32, C.c_int, C.c_int, C.POINTER(Options), C.POINTER(Summary)]
+    L.ssba_image_pyramid_set_huber_loss.argtypes = [H, C.c_double]
     L.ssba_image_solve_batch.argtypes = [C.POINTER(H), C.c_uint32, C.POINTER(Options), C.c_int, C.POINTER(Summary), _i32p]
     L.ssba_image_pyramid_align_batch.argtypes = [C.POINTER(H), C.c_uint32, C.POINTER(Camera), _dp, C.POINTER(_dp), C.c_uint32, C.c_int, C.c_int,
                                                  C.POINTER(Options), C.POINTER(Summary), _i32p]

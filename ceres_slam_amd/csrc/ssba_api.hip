@@ -447,8 +447,8 @@ static int add_image(ssba_problem *p, const char *call, double *pose, double *di
     if (p->finalized) return SSBA_ERR_STATE;
     if (p->image) { set_error(std::string(call) + ": a second call (one tracked frame per handle)"); return SSBA_ERR_UNSUPPORTED; }
     if (p->P || p->L || !p->obs_pose.empty() || p->num_normals || p->M || p->user_light || !p->pose_factors.empty() || !p->rel_factors.empty() ||
-        !p->ph_intensity.empty() || p->world_size > 1 || !p->sep_sb.empty() || p->xfn || p->huber_a > 0.0) {
-        set_error(std::string(call) + ": the handle already holds pose, point, stereo, lighting or pose-factor blocks, a loss or a sharding "
+        !p->ph_intensity.empty() || p->world_size > 1 || !p->sep_sb.empty() || p->xfn) {
+        set_error(std::string(call) + ": the handle already holds pose, point, stereo, lighting or pose-factor blocks or a sharding "
                   "(an image handle holds nothing else, on one GPU)");
         return SSBA_ERR_UNSUPPORTED;
     }
@@ -689,8 +689,7 @@ int ssba_set_point_constant(ssba_problem *p, const uint32_t *points, uint64_t nu
     return SSBA_OK;
 }
 
-int ssba_set_huber_loss(ssba_problem *p, double a) {
-    if (int irc = refuse_on_image(p, "ssba_set_huber_loss")) return irc;
+int ssba_set_huber_loss(ssba_problem *p, double a) {      // image handles too: ssba_image.hip's kernels dispatch on Dev::huber_a
     if (!p) return SSBA_ERR_INVALID_ARGUMENT;
     p->huber_a = a > 0.0 ? a : 0.0;
     if (p->finalized) { p->d.huber_a = p->huber_a; drop_graph(p); }   // kernel arguments are baked into the graph
@@ -2945,6 +2944,7 @@ static int image_begin(ssba_problem *p, const ssba_options *o, double radius) {
     opt.trust_region_strategy_type = 0;
     p->opt = opt;
     p->ignore_convergence = 1;
+    p->d.huber_a = p->huber_a;
     int rc = ensure_log(p, 16);
     if (rc) return rc;
     if ((rc = upload_params(p))) return rc;

@@ -1,6 +1,12 @@
 // Dense photometric alignment: the reference's ImageError blocks (include/ceres_slam/image_error.hpp, driven by
 // tests/dense_stereo_test.cpp:94-136) on the device.  One SE(3) pose T_track_ref and one 1-D disparity block per reference pixel
-// with a usable disparity; no loss, no stiffness, cost = 1/2 sum r^2.
+// with a usable disparity; no stiffness; the loss is NULL (cost = 1/2 sum r^2) or Ceres' HuberLoss of width a = Dev::huber_a > 0
+// (ssba_set_huber_loss), cost = 1/2 sum rho(r^2), applied by Ceres' corrector with rho'' <= 0 as on the stereo rows
+// (ssba_device.h: obs_linearize_S):
+//     r^2 > a^2:  sc = sqrt(max(DBL_MIN, a / |r|)),  r~ = sc r,  J~ = sc J,  1/2 rho = 1/2 (2 a |r| - a^2);   else unchanged.
+// The row buffer, every sum, the Jacobi scales, the damping, V and dd are formed from the corrected row (LOSS = true below); the
+// candidate cost is 1/2 rho of the raw candidate residual.  Out-of-bounds rows have r = 0 and are never corrected.  The kernels
+// without a loss (LOSS = false) keep every expression they had.
 //
 // A block at reference pixel (u_r, v_r) with disparity d and pose [t | R] (all fp64):
 //     p = triangulate(u_r, v_r, d)                      stereo_camera.hpp:112-144
@@ -112,6 +118,12 @@ static __device__ __forceinline__ void im_row(const Dev &d, const ImageSys &im, 
     jd = a0 * w0 + a1 * w1 + a2 * w2;
 }
 
+// Huber: 1/2 rho(r^2) of a raw residual (the fma is written out: the solo and the batched kernels must round alike)
+static __device__ __forceinline__ double im_half_rho(double a, double r) {
+    const double sq = r * r;
+    return sq > a * a ? 0.5 * fma(2.0 * a, fabs(r), -(a * a)) : 0.5 * sq;
+}
+
 // damping of a free disparity in unscaled coordinates (landmark_damping's rule for a 1 x 1 block)
 static __device__ __forceinline__ double im_damping(const State &st, double jd, double s) {
     const double s2 = s * s;
@@ -125,7 +137,7 @@ static __device__ __forceinline__ double im_damping(const State &st, double jd, 
 // The three bodies below take the problem's Dev and the index of the work-group inside the problem: k_im_* hand them the
 // kernel argument and blockIdx.x, the batched kernels k_imb_* an entry of their device array and blockIdx.x under that problem's
 // count.  Nothing is written through `d` itself (only through the pointers it holds), so a batched work-group reads it in place.
-template <bool FREE> static __device__ __forceinline__ void im_lin_body(const Dev &d, const uint32_t wg) {
+template <bool FREE, bool LOSS> static __device__ __forceinline__ void im_lin_body(const Dev &d, const uint32_t wg) {
     const State &st = *d.st;
     const ImageSys &im = *d.image;
     if (st.terminated) return;
@@ -146,6 +158,17 @@ template <bool FREE> static __device__ __forceinline__ void im_lin_body(const De
         if (FREE && commit) d.pts[pix] = dd;
         double r, jp[6], jd;
         im_row(d, im, T, pix, dd, r, jp, jd);
+        double half_rho = 0.0;
+        if (LOSS) {      // the corrector: everything below reads the corrected row
+            const double a = d.huber_a;
+            half_rho = im_half_rho(a, r);
+            if (r * r > a * a) {
+                const double sc = sqrt(fmax(DBL_MIN, a / fabs(r)));
+                r *= sc; jd *= sc;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) jp[c] *= sc;
+            }
+        }
 #pragma unroll
         for (int c = 0; c < 6; ++c) im.row[(size_t)c * im.n_blk + i] = jp[c];
         im.row[(size_t)6 * im.n_blk + i] = jd;
@@ -172,7 +195,7 @@ template <bool FREE> static __device__ __forceinline__ void im_lin_body(const De
 #pragma unroll
             for (int a = 0; a < 6; ++a) { acc[27 + a] = jp[a] * jp[a]; acc[33 + a] = jp[a] * r; }
         }
-        acc[NS] = 0.5 * r * r;
+        acc[NS] = LOSS ? half_rho : 0.5 * r * r;
     }
     if (commit && wg == 0 && threadIdx.x < 12) d.poses[threadIdx.x] = T[threadIdx.x];
     __shared__ double sm[IM_THREADS / 64][NS + 3];
@@ -197,7 +220,7 @@ template <bool FREE> static __device__ __forceinline__ void im_lin_body(const De
     if (threadIdx.x < NS) im.part[(size_t)wg * IM_REC + threadIdx.x] = v;
     else d.part_lin[(size_t)wg * 4 + (threadIdx.x - NS)] = v;
 }
-template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev d) { im_lin_body<FREE>(d, blockIdx.x); }
+template <bool FREE, bool LOSS> __global__ __launch_bounds__(IM_THREADS) void k_im_lin(Dev d) { im_lin_body<FREE, LOSS>(d, blockIdx.x); }
 
 // One work-group: the sums of k_im_lin's partials in fixed order (lane = column of the record, 8 slices of work-groups, the
 // slices added in order), then lane 0 scales, damps, solves and forms the candidate pose, and leaves the pose shares that
@@ -300,7 +323,7 @@ __global__ __launch_bounds__(IM_SOLVE_THREADS) void k_im_solve(Dev d) {
 // not read st.iteration, st.accepted or st.last_successful, which check_body changes in this launch.  The others, one lane per block: the disparity step, the
 // candidate disparity, the candidate cost, the row's share of the model cost change; part_eval[w] = (cost, model cost change,
 // |dd|^2, non-finite) of work-group w: the shape k_decide reduces.
-template <bool FREE> static __device__ __forceinline__ void im_eval_body(const Dev &d, const uint32_t wg, double *__restrict__ delta_disp) {
+template <bool FREE, bool LOSS> static __device__ __forceinline__ void im_eval_body(const Dev &d, const uint32_t wg, double *__restrict__ delta_disp) {
     const ImageSys &im = *d.image;
     const State &st = *d.st;
     if (st.terminated) return;
@@ -330,31 +353,37 @@ template <bool FREE> static __device__ __forceinline__ void im_eval_body(const D
         }
         red[1] = -jdelta * (r + 0.5 * jdelta);
         const double rc = im_residual(d, im, Tc, pix, dc);
-        red[0] = 0.5 * rc * rc;
+        red[0] = LOSS ? im_half_rho(d.huber_a, rc) : 0.5 * rc * rc;
         if (delta_disp) delta_disp[i] = ddl;
     }
     __shared__ double sm[4 * IM_THREADS / 64];
     block_sums(red, sm);
     if (threadIdx.x == 0) reinterpret_cast<double4 *>(d.part_eval)[wg] = make_double4(red[0], red[1], red[2], red[3]);
 }
-template <bool FREE> __global__ __launch_bounds__(IM_THREADS) void k_im_eval(Dev d, double *__restrict__ delta_disp) {
+template <bool FREE, bool LOSS> __global__ __launch_bounds__(IM_THREADS) void k_im_eval(Dev d, double *__restrict__ delta_disp) {
     if (blockIdx.x == 0) { check_body(d, d.image->n_wg, false); return; }
-    im_eval_body<FREE>(d, blockIdx.x - 1, delta_disp);
+    im_eval_body<FREE, LOSS>(d, blockIdx.x - 1, delta_disp);
 }
 
 // ------------------------------------------------------------------- batch ---
 // n image handles in shared launches (ssba_image_solve_batch): blockIdx.y is the problem, gridDim.x the largest work-group
 // count of the batch, and a work-group past its own problem's count returns at once.  The Dev of a work-group is an entry of a
 // device array; its index is uniform over the work-group, so its fields arrive by scalar loads and no lane holds a copy.  Free or
-// constant disparities (the template argument of the solo kernels) are a branch on ImageSys::disp_const, uniform per work-group.
+// constant disparities and the loss (the template arguments of the solo kernels) are branches on ImageSys::disp_const and on the
+// member's own Dev::huber_a > 0, uniform per work-group: the members of a batch may differ in both.
 // No atomics, every sum in the solo kernels' order.  k_imb_lin and k_imb_eval call the bodies k_im_lin and k_im_eval are wrappers
 // over; k_imb_solve compiles k_im_solve's statements (IM_SOLVE_BODY).  A member's result is bit-equal to solving it alone as far
 // as the compiler contracts the same sums the same way in both kernels, which tests/test_gpu_image_batch.py checks on the device.
 __global__ __launch_bounds__(IM_THREADS) void k_imb_lin(const Dev *__restrict__ devs) {
     const Dev &d = devs[blockIdx.y];
     if (blockIdx.x >= (unsigned)d.image->n_wg) return;
-    if (d.image->disp_const) im_lin_body<false>(d, blockIdx.x);
-    else im_lin_body<true>(d, blockIdx.x);
+    if (d.huber_a > 0.0) {
+        if (d.image->disp_const) im_lin_body<false, true>(d, blockIdx.x);
+        else im_lin_body<true, true>(d, blockIdx.x);
+        return;
+    }
+    if (d.image->disp_const) im_lin_body<false, false>(d, blockIdx.x);
+    else im_lin_body<true, false>(d, blockIdx.x);
 }
 __global__ __launch_bounds__(IM_SOLVE_THREADS) void k_imb_solve(const Dev *__restrict__ devs) {
     const Dev &d = devs[blockIdx.y];
@@ -366,23 +395,40 @@ __global__ __launch_bounds__(IM_THREADS) void k_imb_eval(const Dev *__restrict__
     const int n_wg = d.image->n_wg;
     if (blockIdx.x > (unsigned)n_wg) return;
     if (blockIdx.x == 0) { check_body(d, n_wg, false); return; }
-    if (d.image->disp_const) im_eval_body<false>(d, blockIdx.x - 1, nullptr);
-    else im_eval_body<true>(d, blockIdx.x - 1, nullptr);
+    if (d.huber_a > 0.0) {
+        if (d.image->disp_const) im_eval_body<false, true>(d, blockIdx.x - 1, nullptr);
+        else im_eval_body<true, true>(d, blockIdx.x - 1, nullptr);
+        return;
+    }
+    if (d.image->disp_const) im_eval_body<false, false>(d, blockIdx.x - 1, nullptr);
+    else im_eval_body<true, false>(d, blockIdx.x - 1, nullptr);
 }
 
 // ----------------------------------------------------------------- launchers ---
 void launch_image_lin_solve(Launcher &L, const Dev &d) {
     const ImageSys &im = L.image;
-    if (im.disp_const) LAUNCH(KC_LIN_LM, k_im_lin<false>, dim3(im.n_wg), dim3(IM_THREADS), 0, d);
-    else LAUNCH(KC_LIN_LM, k_im_lin<true>, dim3(im.n_wg), dim3(IM_THREADS), 0, d);
+    const bool loss = d.huber_a > 0.0;
+    if (im.disp_const) {
+        if (loss) LAUNCH(KC_LIN_LM, (k_im_lin<false, true>), dim3(im.n_wg), dim3(IM_THREADS), 0, d);
+        else LAUNCH(KC_LIN_LM, (k_im_lin<false, false>), dim3(im.n_wg), dim3(IM_THREADS), 0, d);
+    } else {
+        if (loss) LAUNCH(KC_LIN_LM, (k_im_lin<true, true>), dim3(im.n_wg), dim3(IM_THREADS), 0, d);
+        else LAUNCH(KC_LIN_LM, (k_im_lin<true, false>), dim3(im.n_wg), dim3(IM_THREADS), 0, d);
+    }
     LAUNCH(KC_SMALL, k_im_solve, dim3(1), dim3(IM_SOLVE_THREADS), 0, d);
 }
 
 void launch_image(Launcher &L, const Dev &d, double *delta_disp) {
     const ImageSys &im = L.image;
     launch_image_lin_solve(L, d);
-    if (im.disp_const) LAUNCH(KC_BACKSUB_EVAL, k_im_eval<false>, dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
-    else LAUNCH(KC_BACKSUB_EVAL, k_im_eval<true>, dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
+    const bool loss = d.huber_a > 0.0;
+    if (im.disp_const) {
+        if (loss) LAUNCH(KC_BACKSUB_EVAL, (k_im_eval<false, true>), dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
+        else LAUNCH(KC_BACKSUB_EVAL, (k_im_eval<false, false>), dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
+    } else {
+        if (loss) LAUNCH(KC_BACKSUB_EVAL, (k_im_eval<true, true>), dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
+        else LAUNCH(KC_BACKSUB_EVAL, (k_im_eval<true, false>), dim3(im.n_wg + 1), dim3(IM_THREADS), 0, d, delta_disp);
+    }
     launch_decide_commit(L, d, true, true, 1);      // k_decide alone: Dev::n_groups = n_wg evaluation partials, one pose partial
     launch_best(L, d);
 }

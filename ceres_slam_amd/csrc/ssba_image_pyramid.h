@@ -16,6 +16,7 @@ struct ssba_image_pyramid {
     int device = 0;
     int disparity_level = 0, gradient_source = 0;
     double gradient_scale = 1.0;
+    double huber_a = 0.0;                                          // ssba_image_pyramid_set_huber_loss: every level's handle gets it
     hipStream_t stream = nullptr;
     std::vector<Level> lv;
     std::vector<void *> allocs;

@@ -286,6 +286,13 @@ int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, uint32_t *
     return SSBA_OK;
 }
 
+// the loss of every level's handle: one width for all levels, intensities do not scale with the level
+int ssba_image_pyramid_set_huber_loss(ssba_image_pyramid *pyr, double a) {
+    if (!pyr) return pyr_invalid("ssba_image_pyramid_set_huber_loss", "NULL pyramid");
+    pyr->huber_a = a > 0.0 ? a : 0.0;
+    return SSBA_OK;
+}
+
 // Per-level set-up shared by ssba_image_pyramid_align and ssba_image_pyramid_align_batch: the map the handle's blocks come from
 // (the caller's at disparity_level, the level's derived map in `derived` above it) and the finalized handle on the level, with
 // camera0 scaled to it.  Levels above disparity_level hold their derived disparities constant (free, they absorb the motion and
@@ -306,7 +313,7 @@ static int pyr_level_handle(ssba_image_pyramid *pyr, const ssba_camera *camera0,
     }
     ssba_problem *h = nullptr;
     if ((rc = ssba_create(&cam, pyr->device, &h))) return rc;
-    if ((rc = ssba_add_image_level(h, pyr, (uint32_t)l, pose, map, interpolation)) ||
+    if ((rc = ssba_add_image_level(h, pyr, (uint32_t)l, pose, map, interpolation)) || (rc = ssba_set_huber_loss(h, pyr->huber_a)) ||
         (rc = ssba_set_disparity_blocks_constant(h, base ? (disparities_constant != 0) : 1)) || (rc = ssba_finalize(h))) {
         const std::string msg = ssba_last_error();
         ssba_destroy(h);

@@ -389,11 +389,12 @@ class ImageStep(NamedTuple):
 class ImageAlignment(StereoBA):
     """Dense photometric alignment (ssba_add_image_blocks): one pose T_track_ref and one disparity block per reference pixel,
     the reference's ImageError blocks (tests/dense_stereo_test.cpp:94-136).  ``pose`` (12,) and ``disparity`` (rows, cols) are
-    the caller-owned blocks, updated in place by a solve.  Solving, the stepwise calls, the iteration log, streams, kernel
-    timing and stats are StereoBA's."""
+    the caller-owned blocks, updated in place by a solve.  ``huber_a`` > 0 puts ceres::HuberLoss(huber_a) on every block
+    (set_huber_loss changes it later, finalized or not); 0 is the NULL loss.  Solving, the stepwise calls, the iteration log,
+    streams, kernel timing and stats are StereoBA's."""
 
     def __init__(self, camera: dict, pose, disparity, ref, track, gradx, grady, interpolation: int = capi.IMAGE_BILINEAR,
-                 disparity_const: bool = False, device: int = -1, finalize: bool = True):
+                 disparity_const: bool = False, device: int = -1, finalize: bool = True, huber_a: float = 0.0):
         self.pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
         self.poses = self.pose.reshape(1, 12)           # (the view StereoBA's helpers use)
         self.disparity = np.ascontiguousarray(disparity, dtype=np.float64)
@@ -408,8 +409,14 @@ class ImageAlignment(StereoBA):
                                                   rows, cols, int(interpolation)), "ssba_add_image_blocks")
         if disparity_const:
             capi.check(self.lib.ssba_set_disparity_blocks_constant(self.h, 1), "ssba_set_disparity_blocks_constant")
+        if huber_a > 0.0:
+            self.set_huber_loss(huber_a)
         if finalize:
             self.finalize()
+
+    def set_huber_loss(self, a: float):
+        """ssba_set_huber_loss on the image blocks: a > 0 the width, a <= 0 the NULL loss again; before or after finalize."""
+        capi.check(self.lib.ssba_set_huber_loss(self.h, float(a)), "ssba_set_huber_loss")
 
     @classmethod
     def from_synth(cls, pair, **kw):
@@ -485,7 +492,8 @@ class PyramidLevel(NamedTuple):
 class ImagePyramid:
     """The dense driver's pre-processing on the device (ssba_image_pyramid_create; tests/dense_stereo_test.cpp:52-72): every
     level of the 8-bit pair halved as cv::pyrDown does, converted, Sobel gradients, and the disparity map of ONE level carried to
-    the coarser ones.  ``camera`` is the level-0 camera (optional: level() and align() scale it)."""
+    the coarser ones.  ``camera`` is the level-0 camera (optional: level() and align() scale it).  set_huber_loss(a) gives every
+    level's handle of align() / align_batch() that loss."""
 
     def __init__(self, ref_u8, track_u8, disparity, levels: int, disparity_level: int = 0,
                  gradient_source: int = capi.GRADIENT_OF_TRACKED, gradient_scale: float = 0.125, camera: dict = None, device: int = -1):
@@ -541,6 +549,10 @@ class ImagePyramid:
             self.close()
         except Exception:
             pass
+
+    def set_huber_loss(self, a: float):
+        """ssba_image_pyramid_set_huber_loss: the width align and align_batch put on every level's blocks (a <= 0: NULL loss)."""
+        capi.check(self.lib.ssba_image_pyramid_set_huber_loss(self.h, float(a)), "ssba_image_pyramid_set_huber_loss")
 
     def shape(self, level: int):
         if not 0 <= level < self.levels:

@@ -635,6 +635,45 @@ def make_image_pair(rows: int, cols: int, seed: int = 0, *, depth: float = 6.0, 
                      pose_true=pose_pack(t, R), pose_init=pose_pack(t0, R0))
 
 
+def _occluder(rows: int, cols: int, fraction: float, seed: int):
+    """(top row, left column, height, width, pattern) of the rectangle occlude_tracked and occlude_tracked_u8 repaint."""
+    side = np.sqrt(fraction)
+    h, w = int(round(rows * side)), int(round(cols * side))
+    if not (0 < h <= rows - 4 and 0 < w <= cols - 4):
+        raise ValueError("the rectangle must hold a pixel and stay two pixels inside the border")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    y0 = 2 + int(rng.integers(0, rows - 4 - h + 1))
+    x0 = 2 + int(rng.integers(0, cols - 4 - w + 1))
+    phase = rng.random() * 2.0 * np.pi
+    v, u = np.meshgrid(np.arange(y0, y0 + h, dtype=np.float64), np.arange(x0, x0 + w, dtype=np.float64), indexing="ij")
+    return y0, x0, h, w, 0.5 + 0.45 * np.sin(2.0 * np.pi * (u / 7.0 + v / 5.0) + phase)
+
+
+def occlude_tracked(pair: ImagePair, fraction: float, seed: int) -> ImagePair:
+    """The pair with an occluder in the tracked image: a rectangle of round(rows sqrt(fraction)) x round(cols sqrt(fraction))
+    pixels, its position drawn from PCG64(seed) at least two pixels inside the border, repainted with an unrelated sinusoid
+    0.5 + 0.45 sin(2 pi (u / 7 + v / 5) + phase); gradx and grady are derived again with sobel.  Everything else is shared with
+    `pair`, which is not written."""
+    rows, cols = pair.track.shape
+    y0, x0, h, w, paint = _occluder(rows, cols, fraction, seed)
+    track = np.array(pair.track, dtype=np.float64)
+    track[y0:y0 + h, x0:x0 + w] = paint
+    gradx, grady = sobel(track)
+    return ImagePair(camera=pair.camera, ref=pair.ref, track=track, gradx=gradx, grady=grady, disparity=pair.disparity,
+                     pose_true=pair.pose_true, pose_init=pair.pose_init)
+
+
+def occlude_tracked_u8(track_u8: np.ndarray, fraction: float, seed: int) -> np.ndarray:
+    """occlude_tracked's rectangle on an 8-bit tracked image (the pyramid path derives the gradients itself): the same position
+    and pattern, clipped and rounded as quantise_u8 does.  Returns a new image."""
+    track_u8 = np.asarray(track_u8)
+    rows, cols = track_u8.shape
+    y0, x0, h, w, paint = _occluder(rows, cols, fraction, seed)
+    out = track_u8.copy()
+    out[y0:y0 + h, x0:x0 + w] = quantise_u8(paint)
+    return out
+
+
 @dataclass
 class StereoTriple:
     """What a rectified stereo rig delivers to the dense driver (tests/dense_stereo_test.cpp:38-50), as 8-bit images."""

@@ -7,13 +7,16 @@
 //     double T_track_ref[12]                 the start, [t | R row-major]
 //     double disparity, ref, track, gradx, grady   rows * cols each, row-major
 //
-// usage: dense_stereo_gpu pair.raw [max_num_iterations]
+// usage: dense_stereo_gpu pair.raw [max_num_iterations] [--huber a]
+// --huber a: every block carries ceres::HuberLoss(a) (the trailing argument of ImageError::Create); the covariance printed with
+// constant disparities is then the one of the corrected rows.
 // Output (17 significant digits): "blocks n", "report <BriefReport>", "steps <successful> <unsuccessful>", "pose <12>", and with
 // free disparities "disparity_sum <sum over the blocks>", with constant ones "cov <36>" (ceres::Covariance of the pose).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <memory>
 #include <utility>
@@ -23,8 +26,14 @@
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "usage: dense_stereo_gpu pair.raw [max_num_iterations]" << std::endl;
+        std::cerr << "usage: dense_stereo_gpu pair.raw [max_num_iterations] [--huber a]" << std::endl;
         return EXIT_FAILURE;
+    }
+    double huber_a = 0.0;
+    int max_iterations = -1;
+    for (int a = 2; a < argc; ++a) {
+        if (!std::strcmp(argv[a], "--huber") && a + 1 < argc) huber_a = std::atof(argv[++a]);
+        else max_iterations = std::atoi(argv[a]);
     }
     FILE *f = std::fopen(argv[1], "rb");
     int32_t head[4];
@@ -58,7 +67,7 @@ int main(int argc, char **argv) {
             const double d = row_ptr[u];
             if (std::isfinite(d) && d > 0.) {
                 ceres::CostFunction *image_cost = ceres_slam::ImageError::Create(stereo_camera, left0_ptr, left1_ptr, gradx_ptr, grady_ptr,
-                                                                                 (double)u, (double)v, head[2]);
+                                                                                 (double)u, (double)v, head[2], huber_a);
                 problem.AddResidualBlock(image_cost, NULL, transform_to_estimate, row_ptr + u);
                 if (head[3]) problem.SetParameterBlockConstant(row_ptr + u);
                 ++blocks;
@@ -69,7 +78,7 @@ int main(int argc, char **argv) {
 
     ceres::Solver::Options solver_options;
     solver_options.use_nonmonotonic_steps = true;
-    if (argc > 2) solver_options.max_num_iterations = std::atoi(argv[2]);
+    if (max_iterations >= 0) solver_options.max_num_iterations = max_iterations;
     ceres::Solver::Summary summary;
     ceres::Solve(solver_options, &problem, &summary);
 

@@ -11,8 +11,9 @@
 //            speckle_window_size, speckle_range, full_dp     the matcher's parameters (ssba_sgbm_params)
 //     uint8  left_0, right_0, left_1, right_1, ...      rows * cols each, row-major
 //
-// usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>]
+// usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>] [--huber <a>]
 // --sequential aligns the same pairs one by one (ceres::SolveCoarseToFine per pyramid); the printed poses are identical.
+// --huber a puts ceres::HuberLoss(a) on the blocks of every level of every pyramid (ImagePyramid::SetHuberLoss).
 // Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
 #include <cstdint>
 #include <cstdio>
@@ -26,14 +27,16 @@
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>]" << std::endl;
+        std::cerr << "usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>] [--huber <a>]" << std::endl;
         return EXIT_FAILURE;
     }
     bool sequential = false;
     int max_iterations = -1;
+    double huber_a = 0.0;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--sequential")) sequential = true;
         else if (!std::strcmp(argv[a], "--max-iterations") && a + 1 < argc) max_iterations = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--huber") && a + 1 < argc) huber_a = std::atof(argv[++a]);
         else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
     }
     FILE *f = std::fopen(argv[1], "rb");
@@ -65,6 +68,7 @@ int main(int argc, char **argv) {
     for (int k = 0; k < pairs; ++k) {
         pyramids.emplace_back(new ceres_slam::ImagePyramid(left[k].data(), right[k].data(), left[k + 1].data(), rows, cols, levels, disparity_level, sgbm,
                                                            head[7], scale_cam[0]));
+        if (huber_a > 0.0) pyramids.back()->SetHuberLoss(huber_a);
         pyramid_ptrs.push_back(pyramids.back().get());
         maps.push_back(pyramids.back()->disparity(disparity_level).data());      // the blocks' memory: the matcher's map, downloaded once
         std::memcpy(&poses[(size_t)k * 12], start, sizeof start);

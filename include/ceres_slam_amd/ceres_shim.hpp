@@ -302,6 +302,12 @@ class ImagePyramid {
         return StereoCamera(level0.fu * s, level0.fv * s, level0.cu * s, level0.cv * s, level0.b);
     }
     ssba_image_pyramid *handle() const { return s_->h; }
+    // the ceres::HuberLoss(a) of every level's blocks in both SolveCoarseToFine overloads (ssba_image_pyramid_set_huber_loss);
+    // a <= 0: the NULL loss again
+    void SetHuberLoss(double a) {
+        const int rc = ssba_image_pyramid_set_huber_loss(s_->h, a);
+        if (rc) throw std::runtime_error(std::string("ssba_image_pyramid_set_huber_loss: ") + ssba_status_string(rc) + " (" + ssba_last_error() + ")");
+    }
 
  private:
     struct Level;
@@ -338,22 +344,26 @@ class ImagePyramid {
 
 // include/ceres_slam/image_error.hpp:136-144: blocks (pose 12 = T_track_ref, disparity 1) -> 1 residual at reference pixel (u, v).
 // interpolation: SSBA_IMAGE_NEAREST is the functor as it stands (:156-164), SSBA_IMAGE_BILINEAR what its comment announces.
+// huber_a > 0 is the width of the ceres::HuberLoss(huber_a) a caller would hand to AddResidualBlock (ssba_set_huber_loss on the
+// image handle); AddResidualBlock itself still takes a NULL loss for these blocks, and all blocks of a problem share one width.
 class ImageError : public ceres::CostFunction {
  public:
     static ceres::CostFunction *Create(const std::shared_ptr<const StereoCamera> &camera, const std::shared_ptr<const Image> &ref_img,
                                        const std::shared_ptr<const Image> &track_img, const std::shared_ptr<const Image> &track_gradx,
                                        const std::shared_ptr<const Image> &track_grady, double u_ref, double v_ref,
-                                       int interpolation = SSBA_IMAGE_NEAREST) {
+                                       int interpolation = SSBA_IMAGE_NEAREST, double huber_a = 0.0) {
         ImageError *c = new ImageError;
         c->camera = camera;
         c->img[0] = ref_img; c->img[1] = track_img; c->img[2] = track_gradx; c->img[3] = track_grady;
         c->u = u_ref; c->v = v_ref; c->interpolation = interpolation;
+        c->huber_a = huber_a > 0.0 ? huber_a : 0.0;
         return c;
     }
     std::shared_ptr<const StereoCamera> camera;
     std::shared_ptr<const Image> img[4];
     double u, v;
     int interpolation;
+    double huber_a = 0.0;
 };
 
 }  // namespace ceres_slam
@@ -621,6 +631,7 @@ class Problem {
             if (rows != image_first_.img[0]->rows || cols != image_first_.img[0]->cols || im->interpolation != image_first_.interpolation ||
                 std::memcmp(im->camera.get(), image_first_.camera.get(), sizeof(ceres_slam::StereoCamera)) != 0)
                 throw std::invalid_argument("ceres_shim: all ImageError blocks must share image size, camera and interpolation");
+            if (im->huber_a != image_first_.huber_a) throw std::invalid_argument("ceres_shim: all ImageError blocks must share one loss width (huber_a)");
             if (pose != image_pose_) throw std::invalid_argument("ceres_shim: all ImageError blocks must share one pose block");
             if (base != image_disp_)
                 throw std::invalid_argument("ceres_shim: the disparity block of ImageError pixel (u, v) must be element v * cols + u of one rows * cols array");
@@ -719,6 +730,7 @@ inline const char *shim_prepare(Problem &P, int *rc_out) {
         } else if ((rc = ssba_add_image_blocks(P.h_, P.image_pose_, P.image_disp_, f.img[0]->data, f.img[1]->data, f.img[2]->data, f.img[3]->data,
                                         (uint32_t)f.img[0]->rows, (uint32_t)f.img[0]->cols, f.interpolation))) where = "ssba_add_image_blocks";
         if (where) {}
+        else if (f.huber_a > 0.0 && (rc = ssba_set_huber_loss(P.h_, f.huber_a))) where = "ssba_set_huber_loss";
         else if (n_const && (rc = ssba_set_disparity_blocks_constant(P.h_, 1))) where = "ssba_set_disparity_blocks_constant";
         else if ((rc = ssba_finalize(P.h_))) where = "ssba_finalize";
         if (where) { ssba_destroy(P.h_); P.h_ = nullptr; return where; }

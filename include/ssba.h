@@ -510,7 +510,14 @@ SSBA_API int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *block
  *     J_pose = g P(q) [I | -q^]   (1 x 6, local coordinates of SE3Perturbation, translation then rotation, as on stereo blocks;
  *                                  P = the first two rows of the projection Jacobian)
  *     J_disp = g P(q) R dp/dd     (dp/dd = the third column of the triangulation Jacobian)
- *     out of bounds: r = 0, J_pose = 0, J_disp = 0 (:102-128).  No loss, no stiffness: cost = 1/2 sum r^2.
+ *     out of bounds: r = 0, J_pose = 0, J_disp = 0 (:102-128).  No stiffness.  NULL loss: cost = 1/2 sum r^2.
+ *     ssba_set_huber_loss(p, a) with a > 0 (before or after ssba_finalize; a <= 0 restores the NULL loss) puts ceres::HuberLoss(a)
+ *     on every block, applied by Ceres' corrector with rho'' <= 0 exactly as on the stereo blocks:
+ *         r^2 > a^2 (strictly):  sc = sqrt(max(DBL_MIN, a / |r|)),  r~ = sc r,  J~_pose = sc J_pose,  J~_disp = sc J_disp,
+ *                                the block's cost is 1/2 (2 a |r| - a^2);
+ *         otherwise the row is unchanged and the block's cost is 1/2 r^2.  Out-of-bounds rows (r = 0) are never corrected.
+ *     Everything the minimiser forms (sums, Jacobi scales, damping, V, delta_d, gradient norm, model cost change) comes from the
+ *     corrected row; the cost of a candidate is 1/2 sum rho of its raw residuals.
  * Two deliberate differences from the reference's text.  Its bounds test (u < cols, v < rows, :167-172) lets round() pick column
  * `cols` or row `rows`, one past the end; here a block is in bounds only when every pixel it reads is inside the image, which
  * differs from the reference exactly where the reference reads past the end of a row.  And :97-99 takes
@@ -521,12 +528,12 @@ SSBA_API int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *block
  *
  * An image handle holds nothing else and lives on one GPU (ssba_stats.general_structure = 4; num_active_points and
  * num_observations = the block count).  SSBA_ERR_UNSUPPORTED with a message that names the call: pose, point, stereo,
- * lighting, pose-factor, loss and constant-block calls on it, a second ssba_add_image_blocks, ssba_set_distributed /
+ * lighting, pose-factor and constant-block calls on it, a second ssba_add_image_blocks, ssba_set_distributed /
  * ssba_set_partition / an exchange, a DOGLEG solve, ssba_evaluate, ssba_lm_step, ssba_dogleg_step, ssba_covariance_blocks.
  * rows or cols = 0, a NULL array, an unknown interpolation: SSBA_ERR_INVALID_ARGUMENT (so is a map without a usable disparity,
  * at ssba_finalize).  ssba_solve, the stepwise calls, ssba_iteration_log, ssba_set_stream, ssba_set_kernel_timing work as on
- * every handle.  ssba_pose_covariance(p, 0, cov) with constant disparities: the inverse of sum J_pose^T J_pose
- * (SSBA_ERR_NUMERICAL_FAILURE when singular); with free disparities SSBA_ERR_NUMERICAL_FAILURE (more columns than rows: Ceres
+ * every handle.  ssba_pose_covariance(p, 0, cov) with constant disparities: the inverse of sum J_pose^T J_pose, of the corrected
+ * rows J~_pose under a loss (SSBA_ERR_NUMERICAL_FAILURE when singular); with free disparities SSBA_ERR_NUMERICAL_FAILURE (more columns than rows: Ceres
  * reports a failed covariance computation there too). */
 #define SSBA_IMAGE_NEAREST 0
 #define SSBA_IMAGE_BILINEAR 1
@@ -537,7 +544,9 @@ SSBA_API int ssba_set_disparity_blocks_constant(ssba_problem *p, int is_constant
 /* test hook: one Levenberg-Marquardt step from the caller's current pose and disparities at the given radius.  cost; residuals
  * (rows * cols), J_pose (rows * cols * 6), J_disp (rows * cols): the rows, zero at pixels without a block; S (36) the damped
  * reduced 6 x 6 system and rhs (6); delta_pose (6), delta_disp (rows * cols, zero when constant); model_cost_change.  Any
- * output may be NULL.  Writes nothing back. */
+ * output may be NULL.  Writes nothing back.  Under a loss (ssba_set_huber_loss) residuals, J_pose and J_disp are the corrected
+ * rows r~, J~, cost is 1/2 sum rho(r^2), and S, rhs, delta_pose, delta_disp and model_cost_change are what the solver forms from
+ * the corrected rows. */
 SSBA_API int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose,
                     double *J_disp, double *S, double *rhs, double *delta_pose, double *delta_disp, double *model_cost_change);
 
@@ -614,7 +623,10 @@ SSBA_API int ssba_image_solve_batch(ssba_problem **handles, uint32_t n, const ss
  *   disparities constant (free, they absorb the motion and the pose never moves) and leave no trace in the caller's map; the base
  *   level follows disparities_constant and updates `disparity` (the map at disparity_level) in place.  summaries (may be NULL)
  *   has coarsest_level - disparity_level + 1 entries; summaries[coarsest_level - l] is level l's.  A level that ends without a
- *   usable solution stops the loop and returns its status; the pose is then the last usable one. */
+ *   usable solution stops the loop and returns its status; the pose is then the last usable one.
+ * ssba_image_pyramid_set_huber_loss: the width a that align and align_batch give every level's handle (ssba_set_huber_loss on
+ *   it); a <= 0, the state after create, is the NULL loss.  One width serves all levels: intensities do not scale with the
+ *   level.  The pyramids of one align_batch may differ in it. */
 typedef struct ssba_image_pyramid ssba_image_pyramid;
 #define SSBA_GRADIENT_OF_REFERENCE 0
 #define SSBA_GRADIENT_OF_TRACKED 1
@@ -625,6 +637,7 @@ SSBA_API int ssba_image_pyramid_destroy(ssba_image_pyramid *pyr);
 SSBA_API int ssba_image_pyramid_level(ssba_image_pyramid *pyr, uint32_t level, uint32_t *rows, uint32_t *cols, uint8_t *ref_u8, uint8_t *track_u8,
                              double *ref, double *track, double *gradx, double *grady, double *disparity);
 SSBA_API int ssba_add_image_level(ssba_problem *p, ssba_image_pyramid *pyr, uint32_t level, double *pose, double *disparity, int interpolation);
+SSBA_API int ssba_image_pyramid_set_huber_loss(ssba_image_pyramid *pyr, double a);
 SSBA_API int ssba_image_pyramid_align(ssba_image_pyramid *pyr, const ssba_camera *camera0, double *pose, double *disparity, uint32_t coarsest_level,
                              int interpolation, int disparities_constant, const ssba_options *options, ssba_summary *summaries);
 /* align_batch: coarse to fine over n pyramids in lockstep (the pairs of a sequence).  Per level one handle per pyramid, built

@@ -8,6 +8,9 @@ frame), on the synthetic pair of ceres_slam_amd.synth.make_image_pair, BILINEAR,
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/image_bench.py --rounds 1 --out /dev/null
                                                      # per-kernel times, a run of its own; then
     python tools/image_bench.py --merge-trace DIR/.../*_kernel_trace.csv      # medians, bounds and shares into the JSON (no GPU)
+    python tools/image_bench.py --loss-fraction 0.1 --parent-tree DIR --out profiles/image_loss.json
+                                                     # every configuration also under ceres::HuberLoss(a), a correcting about a tenth of
+                                                     # the rows; the windows alternate with a build of the parent commit in DIR
 
 Per handle: ssba_solve_begin with ignore_convergence, 17 steps (the graph captures), --warmup steps; then --rounds windows of
 --steps iterations between two device events on the handle's stream, the configurations taking turns.  The iterations run on
@@ -20,7 +23,10 @@ import ctypes as C
 import json
 import os
 import statistics
+import subprocess
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -85,6 +91,44 @@ def merge_kernels(doc: dict, table: dict) -> None:
     doc["kernel_times_from"] = "rocprofv3 --kernel-trace, a run of its own; bounds at 8 TB/s and 78.6 TFLOP/s fp64"
 
 
+def alternate(args):
+    """--parent-tree: `rounds` windows of this tree and of the parent's, alternating, one process each (two builds of one library
+    cannot share a process); every window is a full run of this tool with --child --rounds 1."""
+    runs = {}
+    for _ in range(args.rounds):
+        for who, tree in (("this", ROOT), ("parent", os.path.abspath(args.parent_tree))):
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--rounds", "1", "--package-root", tree, "--sizes", args.sizes,
+                   "--steps", str(args.steps), "--warmup", str(args.warmup)]
+            if who == "this" and args.loss_fraction > 0.0:
+                cmd += ["--loss-fraction", str(args.loss_fraction)]
+            out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if out.returncode != 0:
+                raise RuntimeError(f"window of the {who} tree failed:\n{out.stdout[-2000:]}{out.stderr[-2000:]}")
+            for name, r in json.loads(out.stdout.strip().splitlines()[-1]).items():
+                e = runs.setdefault(name, dict(blocks=r["blocks"]))
+                e.setdefault(who, []).extend(r["samples"])
+                if r.get("huber_a") is not None:
+                    e.update(huber_a=r["huber_a"], corrected_at_start=r["corrected_at_start"])
+
+    def summary(a):
+        return dict(median=round(statistics.median(a), 5), min=min(a), max=max(a), windows=len(a))
+    doc = dict(tool="tools/image_bench.py --parent-tree", steps=args.steps, warmup=args.warmup, interpolation="BILINEAR", loss_fraction=args.loss_fraction, runs={})
+    for name, e in runs.items():
+        d = dict(blocks=e["blocks"], ms_per_iteration_samples=e["this"], ms_per_iteration=summary(e["this"]))
+        if "parent" in e:
+            d.update(parent=dict(ms_per_iteration_samples=e["parent"], ms_per_iteration=summary(e["parent"])))
+        if "huber_a" in e:
+            base = runs[name[:-len("/huber")]]["this"]
+            d.update(huber_a=e["huber_a"], corrected_at_start=e["corrected_at_start"],
+                     loss_costs_ms_per_iteration=round(statistics.median(e["this"]) - statistics.median(base), 5))
+        doc["runs"][name] = d
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(doc, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(json.dumps({k: (v["ms_per_iteration"]["median"], v.get("parent", {}).get("ms_per_iteration", {}).get("median")) for k, v in doc["runs"].items()}), flush=True)
+
+
 class Hip:
     def __init__(self):
         self.lib = C.CDLL("libamdhip64.so")
@@ -122,7 +166,17 @@ def main():
     ap.add_argument("--kernel-timing", action="store_true", help="per-kernel-class HIP-event times of one window per configuration instead")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "image_alignment.json"))
     ap.add_argument("--merge-trace", metavar="CSV", default=None, help="no run: merge the per-kernel medians of a rocprofv3 kernel trace into --out")
+    ap.add_argument("--loss-fraction", type=float, default=0.0,
+                    help="also time every configuration under ceres::HuberLoss(a), a = the width that corrects about this fraction of the rows at the start "
+                         "(the matching quantile of |r| of a NULL-loss ssba_image_step); runs named <size>/<free|constant>/huber")
+    ap.add_argument("--parent-tree", metavar="DIR", default=None,
+                    help="a checkout of the parent commit with its library built: the windows alternate between this tree and that one, one process per "
+                         "window; the parent's figures go under 'parent' of every run it can time (it has no loss on image blocks)")
+    ap.add_argument("--package-root", metavar="DIR", default=ROOT, help="where ceres_slam_amd is imported from (a window of --parent-tree)")
+    ap.add_argument("--child", action="store_true", help="a window of --parent-tree: print the samples as one JSON line, write nothing")
     args = ap.parse_args()
+    if args.parent_tree:
+        return alternate(args)
     if args.merge_trace:
         doc = json.load(open(args.out))
         merge_kernels(doc, summarise_trace(args.merge_trace))
@@ -132,6 +186,7 @@ def main():
         print(json.dumps({k: v.get("kernels") for k, v in doc["runs"].items()}))
         return
 
+    sys.path.insert(0, os.path.abspath(args.package_root))
     from ceres_slam_amd import capi, synth
     from ceres_slam_amd.solver import ImageAlignment
 
@@ -141,9 +196,16 @@ def main():
     for size in args.sizes.split(","):
         rows, cols = SIZES[size]
         pair = synth.make_image_pair(rows, cols, seed=0, invalid_fraction=0.03)
-        for const in (False, True):
-            name = f"{size}/{'constant' if const else 'free'}"
+        for const, loss in [(c, l) for c in (False, True) for l in ((False, True) if args.loss_fraction > 0.0 else (False,))]:
+            name = f"{size}/{'constant' if const else 'free'}" + ("/huber" if loss else "")
             ba = ImageAlignment.from_synth(pair, interpolation=capi.IMAGE_BILINEAR, disparity_const=const)
+            width = corrected = None
+            if loss:
+                blk = np.isfinite(pair.disparity) & (pair.disparity > 0)
+                r0 = np.abs(ba.image_step(1e4).residuals[blk])
+                width = float(np.quantile(r0[r0 > 0], 1.0 - args.loss_fraction))
+                ba.set_huber_loss(width)
+                corrected = float((np.abs(ba.image_step(1e4).residuals[blk]) != r0).mean())
             st = ba.stats()
             assert st.general_structure == 4
             stream = hip.stream()
@@ -155,7 +217,7 @@ def main():
             ba.step(args.warmup)
             ba.synchronize()
             runs[name] = dict(ba=ba, stream=stream, a=hip.event(), b=hip.event(), samples=[], blocks=int(st.num_observations), rows=rows, cols=cols,
-                              free=not const, device_bytes=int(st.device_bytes))
+                              free=not const, device_bytes=int(st.device_bytes), huber_a=width, corrected_at_start=corrected)
     kernels = {}
     if args.kernel_timing:
         for name, r in runs.items():
@@ -174,6 +236,12 @@ def main():
                 r["ba"].step(args.steps)
                 hip.record(r["b"], r["stream"])
                 r["samples"].append(round(hip.elapsed_ms(r["a"], r["b"]) / args.steps, 5))
+    if args.child:
+        for r in runs.values():
+            r["ba"].solve_end()
+        print(json.dumps({k: dict(samples=r["samples"], blocks=r["blocks"], huber_a=r["huber_a"], corrected_at_start=r["corrected_at_start"])
+                          for k, r in runs.items()}), flush=True)
+        return
     doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
     doc.update(tool="tools/image_bench.py", steps=args.steps, warmup=args.warmup, interpolation="BILINEAR")
     doc.setdefault("runs", {})
@@ -182,6 +250,8 @@ def main():
         e = doc["runs"].setdefault(name, {})
         e.update(rows=r["rows"], cols=r["cols"], blocks=r["blocks"], free_disparities=r["free"], device_bytes=r["device_bytes"],
                  per_block=per_block_counts(r["free"]))
+        if r["huber_a"] is not None:
+            e.update(huber_a=r["huber_a"], corrected_at_start=r["corrected_at_start"])
         if args.kernel_timing:
             e["kernel_classes"] = kernels[name]
         else:

@@ -1300,7 +1300,7 @@ int ssba_finalize(ssba_problem *p) {
             // tile images (ssba_types.h): the symmetric ones hold 15 tiles per block, the couplings 25 of the padded block
             TRY(dzero(p, &F.Dpp[q], n * PCR_IMG_SYM));
             TRY(dzero(p, &F.GLL[q], n * PCR_IMG_SYM)); TRY(dzero(p, &F.GUU[q], n * PCR_IMG_SYM));
-            TRY(dzero(p, &F.GUL[q], n * PCR_IMG_FULL)); TRY(dzero(p, &F.GULT[q], n * PCR_IMG_FULL));
+            TRY(dzero(p, &F.GUL[q], n * PCR_IMG_FULL));
         }
         if (pins) { TRY(dzero(p, &F.Lkeep, n * PCR_IMG_FULL)); TRY(dzero(p, &F.Ukeep, n * PCR_IMG_FULL)); }
         F.on = 1;

@@ -106,8 +106,9 @@ struct FactorOps {
     // and nD of a fused step are tile images (ssba_types.h); imgD / imgR: so are Dg (with r in column 72) / Lg and Ug
     const double *GA, *GB;
     double sgnL, sgnU;
-    double *nD, *nr, *oGLL, *oGUU, *oGUL, *oGULT;
+    double *nD, *nr, *oGLL, *oGUU, *oGUL;
     bool imgD, imgR;
+    bool utr;                               // Ug is the GUL image of the block that produced it: U^T is transposed on load
     // chains with pinned ends: saveL (like saveU) keeps a coupling that will not be folded again; a pinned block is only
     // assembled (and, the last one, tracks its coupling to the first); which Gram products somebody will read
     double *saveL;
@@ -125,7 +126,7 @@ static __device__ __forceinline__ bool factor_ops(const Dev &d, int lev, int top
     o.trL = o.trU = false;
     o.saveU = nullptr;
     o.Bg = nullptr; o.oYB = nullptr; o.xsol = nullptr;
-    o.GA = o.GB = nullptr; o.sgnL = o.sgnU = 1.0; o.nD = o.nr = nullptr; o.imgD = o.imgR = false;
+    o.GA = o.GB = nullptr; o.sgnL = o.sgnU = 1.0; o.nD = o.nr = nullptr; o.imgD = o.imgR = o.utr = false;
     o.saveL = nullptr; o.pinned = false; o.gLL = o.gUU = o.gUL = false;
     if (which >= 2) {
         const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
@@ -188,8 +189,8 @@ struct FusedStep {
     double *D, *L, *r;                      // the level's own blocks, row-major (the last step factors in place)
     const int *pos;                         // level-0 position of each block
     int n, pin0, pin1, chain0;
-    const double *Din, *GLLin, *GUUin, *GULin, *GULTin;      // what the previous step left: PcrFused set (lev - 1) & 1
-    double *Dout, *GLLout, *GUUout, *GULout, *GULTout;        // what this step leaves: set lev & 1
+    const double *Din, *GLLin, *GUUin, *GULin;      // what the previous step left: PcrFused set (lev - 1) & 1
+    double *Dout, *GLLout, *GUUout, *GULout;        // what this step leaves: set lev & 1
     double *Lkeep, *Ukeep;
     double *YL, *YU, *Lbuf;                 // the decoupled last step of a chain with pinned ends
     double *x;                              // where the solution goes (chain: x0 + chain0 * BD, separator system: xsep)
@@ -202,8 +203,8 @@ static FusedStep fused_step_args(const Dev &d, int which, int lev) {
     FusedStep a;
     a.D = B.D; a.L = B.L; a.r = B.r; a.pos = B.pos;
     a.n = B.n; a.pin0 = P.pin0; a.pin1 = P.pin1; a.chain0 = d.chain0;
-    a.Din = F.Dpp[in]; a.GLLin = F.GLL[in]; a.GUUin = F.GUU[in]; a.GULin = F.GUL[in]; a.GULTin = F.GULT[in];
-    a.Dout = F.Dpp[out]; a.GLLout = F.GLL[out]; a.GUUout = F.GUU[out]; a.GULout = F.GUL[out]; a.GULTout = F.GULT[out];
+    a.Din = F.Dpp[in]; a.GLLin = F.GLL[in]; a.GUUin = F.GUU[in]; a.GULin = F.GUL[in];
+    a.Dout = F.Dpp[out]; a.GLLout = F.GLL[out]; a.GUUout = F.GUU[out]; a.GULout = F.GUL[out];
     a.Lkeep = F.Lkeep; a.Ukeep = F.Ukeep;
     a.YL = P.YL; a.YU = P.YU; a.Lbuf = P.Lbuf;
     a.x = which == 3 ? d.xsep : d.x0 + (size_t)d.chain0 * BD;
@@ -223,7 +224,7 @@ static __device__ __forceinline__ void fused_ops(const FusedStep &a, int lev, in
     o.oYL = o.oYU = nullptr;
     o.GA = o.GB = nullptr;
     o.nD = o.nr = nullptr;
-    o.imgD = lev >= 2; o.imgR = lev >= 1;
+    o.imgD = lev >= 2; o.imgR = lev >= 1; o.utr = false;
     o.pinned = e < lo || e > hi;
     const bool pinned_chain = a.pin0 || a.pin1;
     // couplings of this block at this stride: to e -/+ s, or the kept one to the pinned end; the decoupled last step of a
@@ -249,9 +250,11 @@ static __device__ __forceinline__ void fused_ops(const FusedStep &a, int lev, in
         o.rin = a.r + (size_t)e * BD;
         if (prev >= lo) o.GA = a.GUUin + prev * isym;
         if (next <= hi) o.GB = a.GLLin + next * isym;
-        // the coupling was renewed by the last step iff the neighbour at half the stride was folded; else it is a kept one
+        // the coupling was renewed by the last step iff the neighbour at half the stride was folded; else it is a kept one.
+        // There is ONE image of YU^T YL: block `prev` left this block's L in it as it stands, block `next` this block's U, whose
+        // transpose the right-hand-side tiles hold (utr: transposed on load).  Kept couplings are stored as they were held.
         if (o.hasL) { if (prev >= lo) { o.Lg = a.GULin + prev * ifull; o.sgnL = -1.0; } else o.Lg = a.Lkeep + e * ifull; }
-        if (o.hasU) { if (next <= hi) { o.Ug = a.GULTin + next * ifull; o.sgnU = -1.0; } else o.Ug = a.Ukeep + e * ifull; }
+        if (o.hasU) { if (next <= hi) { o.Ug = a.GULin + next * ifull; o.sgnU = -1.0; o.utr = true; } else o.Ug = a.Ukeep + e * ifull; }
         if (!top) o.nD = a.Dout + e * isym;
     }
     if (pinned_chain && !top) {
@@ -279,7 +282,7 @@ static __device__ __forceinline__ void fused_ops(const FusedStep &a, int lev, in
         }
     }
     o.oGLL = a.GLLout + e * isym; o.oGUU = a.GUUout + e * isym;
-    o.oGUL = a.GULout + e * ifull; o.oGULT = a.GULTout + e * ifull;
+    o.oGUL = a.GULout + e * ifull;
 }
 
 // One tile image (ssba_types.h) <-> the accumulator registers of a wave: two 16-byte accesses per lane.
@@ -361,7 +364,7 @@ struct FactorLds {
 // The buffers only MODE 1 / 2 read and write (PcrFused: assembled blocks, Gram products, kept couplings) are tile images
 // (ssba_types.h): half a tile per 16-byte access and lane, no row predicates.  What other kernels read stays row-major.
 static __device__ __forceinline__ void gram_tile(int u, int &kind, int &ti, int &tj);
-static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], double *scr, int lane);
+static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], int lane);
 constexpr int MF_THREADS2 = 512;
 // ROLE 0: every wave runs both streams (MODE 0, 1).  MODE 2 instantiates the body twice -- ROLE 1: the D stream only (waves
 // 0..3), ROLE 2: right-hand-side tiles only (waves 4..7) -- so that neither role carries the other's register arrays
@@ -403,7 +406,8 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
     if (t == 0) { S.bad = 0; S.seqPQ = 0; }
     if (t < 4) S.seqA[t] = 0;
     if (t < 8) { S.rc[72 + t] = 1.0; S.seqY[t] = 0; }
-    // mf_solve_lds: solve: G (BD x BD) | yr (BD) | x;  MODE 2: [YL | yr] and [YU | yr], 72 x 80 each
+    // mf_solve_lds: solve: G (BD x BD) | yr (BD) | x;  MODE 2: [YL | yr] and [YU | yr], 72 x 80 each, then a 16 x 17 tile per
+    // right-hand-side wave (U^T out of the GUL image, load phase);  MODE 1 with right-hand sides: those four tiles alone
     if (MODE == 2) {        // columns 72..79 of both staged operands: yr goes into column 72 later, the rest stays zero
         for (int i = t; i < 2 * BD * 8; i += MF_THREADS2) mf_solve_lds[(i >> 3) * 80 + BD + (i & 7)] = 0.0;
     }
@@ -486,6 +490,15 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
             for (int k = 0; k < NDT; ++k) dt[k] = mf_d4{0.0, 0.0, 0.0, 0.0};
         }
         bool rok[NRA];
+        // U^T out of the one image of YU^T YL (o.utr).  The columns 16 c0 + 8 .. 16 c0 + 23 of U^T that column tile 5 + c0 holds
+        // are rows of the image: the second half of tile (c0, k) and the first half of tile (c0 + 1, k), together the
+        // accumulator layout of a 16 x 16 piece whose transpose is block row k of the column tile.  Loaded with the same
+        // 16-byte accesses as everything else and turned through a 16 x 17 LDS tile of this wave's own, once every load of
+        // the wave is in flight.  The mixed column tile 4 (c0 = -1) holds columns 64..71 of L in its lanes j < 8, which read
+        // as ever, and columns 0..7 of U^T in the others: the first half of tile (0, k) as the piece's rows 8..15.
+        double2 mixU[NRW > 0 ? NDT : 1];
+        const bool utr = MODE && NRW > 0 && o.imgR && o.utr;
+        double *tscr = mf_solve_lds + (MODE == 2 ? 2 * BD * 80 : 0) + (w & 3) * (16 * 17);
 #pragma unroll
         for (int q = 0; q < NRW; ++q) {
             const int col = 16 * rcol[q] + j;
@@ -497,6 +510,16 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
             if (!ract[q]) {
 #pragma unroll
                 for (int k = 0; k < NDT; ++k) rt[q][k] = mf_d4{0.0, 0.0, 0.0, 0.0};
+            } else if (utr && rcol[q] >= 4 && rcol[q] < NRT) {
+                const int c0 = rcol[q] - 5;
+                const double *pu = o.Ug + 2 * lane, *pl = o.Lg + 4 * PCR_IMG_TILE + 2 * lane;
+#pragma unroll
+                for (int k = 0; k < NDT; ++k) {
+                    const double2 a = *reinterpret_cast<const double2 *>(c0 < 0 ? pl + 5 * k * PCR_IMG_TILE : pu + (5 * c0 + k) * PCR_IMG_TILE + PCR_IMG_TILE / 2);
+                    const double2 b = *reinterpret_cast<const double2 *>(c0 < 0 ? pl + 5 * k * PCR_IMG_TILE + PCR_IMG_TILE / 2 : pu + (5 * (c0 + 1) + k) * PCR_IMG_TILE);
+                    rt[q][k] = mf_d4{a.x, a.y, b.x, b.y};
+                    if (c0 < 0) mixU[k] = *reinterpret_cast<const double2 *>(pu + k * PCR_IMG_TILE);
+                }
             } else if (isB) {                            // border columns: BD x NBP, row-major
                 const double *pp = o.Bg + g * NBP + (col - 2 * BD);
 #pragma unroll
@@ -526,6 +549,30 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
             }
         }
         if (sf.dead()) return;
+        if (utr) {      // the pieces of U^T: lane (g, j) gives rows 4 q + g, column j and takes rows j, columns 4 q + g
+#pragma unroll
+            for (int q = 0; q < NRW; ++q) {
+                if (!(ract[q] && rcol[q] >= 4 && rcol[q] < NRT)) continue;
+                const bool mixed = rcol[q] == 4;
+#pragma unroll
+                for (int k = 0; k < NDT; ++k) {
+                    if (mixed) {
+                        tscr[(8 + g) * 17 + j] = mixU[k].x;
+                        tscr[(12 + g) * 17 + j] = mixU[k].y;
+                    } else {
+#pragma unroll
+                        for (int qq = 0; qq < 4; ++qq) tscr[(4 * qq + g) * 17 + j] = rt[q][k][qq];
+                    }
+                    MF_FENCE();
+                    double r[4];
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) r[qq] = tscr[j * 17 + 4 * qq + g];
+                    MF_FENCE();
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) rt[q][k][qq] = (mixed && j < 8) ? rt[q][k][qq] : r[qq];
+                }
+            }
+        }
         // masks: column 72 of [D | r] is the right-hand side, the columns after it are zero; absent couplings are zero
         if (!MODE && dj == 4) {
 #pragma unroll
@@ -533,6 +580,8 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dt[k][q] = colD < BD ? dt[k][q] : colD == BD ? rv[k][q] : 0.0;
         }
+        // (every workgroup of the block holds the same assembled block; sharing these stores out over them -- tile index mod ns
+        // -- measured slower than leaving them to workgroup 0: DESIGN.md Appendix A)
         if (HAS_D && MODE == 2 && o.nD && by == 0) {     // the assembled [D | r] (upper tiles, as images) for the next step
 #pragma unroll
             for (int k = 0; k < NDT; ++k)
@@ -908,15 +957,16 @@ static __device__ __forceinline__ void factor_body(const Dev &d, const FusedStep
         return;
     }
     if (MODE == 2) {
-        // ---- the Gram tiles of this wave (the hand-off slots of the factorisation are dead: S.A is the transposition scratch) ----
+        // ---- the Gram tiles of this wave.  The waves hold very different numbers of them (D wave 1: six, wave 0: none), but
+        //      what bounds this phase is the chip's write path, not the wave that issues most: dealing the stores over all
+        //      eight waves through LDS measured slower ----
         MF_STAMP(32);
         MF_WG_STAMP(3);
-        double *scr = &S.A[0][0][0][0] + w * (16 * 17);
 #pragma unroll
         for (int i = 0; i < NG; ++i) {
             if (!ghave[i]) continue;
             const double v[4] = {gacc[i][0], gacc[i][1], gacc[i][2], gacc[i][3]};
-            gram_store(o, gkind[i], gti[i], gtj[i], v, scr, lane);
+            gram_store(o, gkind[i], gti[i], gtj[i], v, lane);
         }
         MF_STAMP(33);
         MF_WG_STAMP(4);
@@ -1121,8 +1171,8 @@ static __device__ __forceinline__ mf_d4 tn_mma(const TnOps &O, mf_d4 acc) {
 // middle end, a scheduling barrier for the machine scheduler, which would otherwise sink the reads again)
 
 // Gram products of one block's own factor outputs (fused plan, see PcrFused): units 0..14 the upper tiles of
-// GLL = [YL | yr]^T [YL | yr] (column 72 = YL^T yr), 15..29 the same for YU, 30..54 the tiles of GUL = YU^T YL, which is
-// stored in both orientations.  u -> (kind, tile row, tile column).
+// GLL = [YL | yr]^T [YL | yr] (column 72 = YL^T yr), 15..29 the same for YU, 30..54 the tiles of GUL = YU^T YL (one
+// image: whoever needs its transpose turns it on load).  u -> (kind, tile row, tile column).
 static __device__ __forceinline__ void gram_tile(int u, int &kind, int &ti, int &tj) {
     kind = u < 15 ? 0 : u < 30 ? 1 : 2;
     if (kind == 2) {
@@ -1137,11 +1187,11 @@ static __device__ __forceinline__ void gram_tile(int u, int &kind, int &ti, int 
         tj = min(a + (n - st0), NDT - 1);
     }
 }
-static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], double *scr, int lane) {
+static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, int ti, int tj, const double (&v)[4], int lane) {
     // tile images (ssba_types.h): the whole accumulator leaves in two 16-byte stores per lane.  Rows 72..79 (registers 2, 3
     // of tile row 4) would hold the products with the right-hand-side column: they are stored as zeros, which is what the
     // loader's row predicates used to supply
-    const int g = lane >> 4, j = lane & 15;
+    const int j = lane & 15;
     const bool rows = ti < 4;
     if (kind < 2) {
         img_store(kind == 0 ? o.oGLL : o.oGUU, img_sym_tile(ti, tj), lane, mf_d4{v[0], v[1], rows ? v[2] : 0.0, rows ? v[3] : 0.0});
@@ -1149,16 +1199,6 @@ static __device__ __forceinline__ void gram_store(const FactorOps &o, int kind, 
     }
     const bool cols = tj < 4 || j < 8;          // columns 72..79 of a coupling are never read: zeros, to keep the image clean
     img_store(o.oGUL, 5 * ti + tj, lane, mf_d4{cols ? v[0] : 0.0, cols ? v[1] : 0.0, (cols && rows) ? v[2] : 0.0, (cols && rows) ? v[3] : 0.0});
-    // the transposed copy goes through a per-wave LDS tile and leaves as the image of tile (tj, ti)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) scr[j * 17 + 4 * q + g] = v[q];
-    MF_FENCE();
-    double r[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) r[q] = scr[(4 * q + g) * 17 + j];
-    MF_FENCE();
-    const bool rowsT = tj < 4, colsT = ti < 4 || j < 8;
-    img_store(o.oGULT, 5 * tj + ti, lane, mf_d4{colsT ? r[0] : 0.0, colsT ? r[1] : 0.0, (colsT && rowsT) ? r[2] : 0.0, (colsT && rowsT) ? r[3] : 0.0});
 }
 
 // One block's reduction as a job of three staged operands -- A0 = YU(prev) | yr(prev), A1 = YL(next) | yr(next),
@@ -1539,7 +1579,8 @@ void launch_bcr_factor_mf(Launcher &L, const Dev &d, int nblocks, int lev, int t
 // Fused plan (PcrFused): step q = factorisation of every block at stride 2^q + the Gram products the next step assembles its
 // operands from, ONE launch; the workgroups of a block (3 up to 85 blocks, 2 up to 128) repeat the factorisation and share
 // the Gram tiles.  The decoupled last step assembles its blocks the same way, solves them and (solve = 2) updates the poses.
-constexpr size_t FUSED_LDS = (size_t)2 * BD * 80 * sizeof(double);
+constexpr size_t TSCR_LDS = (size_t)4 * 16 * 17 * sizeof(double);        // a 16 x 17 tile per right-hand-side wave: U^T out of the GUL image
+constexpr size_t FUSED_LDS = (size_t)2 * BD * 80 * sizeof(double) + TSCR_LDS;
 void launch_pcr_fused_step(Launcher &L, const Dev &d, int n, int q, int which) {
     const int ns = n <= 85 ? 3 : 2;         // (a plan has at most PCR_MAX_BLOCKS = 128 blocks; the kernel's tile share assumes ns >= 2; 2 at C2: 0.372 against 0.364 ms)
     LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 2>), dim3(xcd_grid(n, ns)), dim3(MF_THREADS2), FUSED_LDS, d, q, 0, which, n, ns, 0, NRT, 0, fused_step_args(d, which, q));
@@ -1548,7 +1589,7 @@ void launch_pcr_fused_top(Launcher &L, const Dev &d, int n, int steps, int solve
     const size_t sh_solve = (size_t)(BD * BD + 2 * BD) * sizeof(double);
     const PcrPlan &P = which == 3 ? d.spcr : d.pcr;
     if (P.pin0 || P.pin1) {     // a chain with pinned ends: its blocks keep their couplings to those (right-hand-side tiles), nothing is solved yet
-        LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), 0, d, steps, 1, which, n, 1, 0, NRT, 0, fused_step_args(d, which, steps));
+        LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<3, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), TSCR_LDS, d, steps, 1, which, n, 1, 0, NRT, 0, fused_step_args(d, which, steps));
         return;
     }
     LAUNCH(KC_BCR_FACTOR, (k_bcr_factor_mf<0, 1>), dim3(xcd_grid(n, 1)), dim3(MF_THREADS), solve ? sh_solve : 0, d, steps, 1, which, n, 1, 0, NRT, solve, fused_step_args(d, which, steps));

@@ -153,7 +153,8 @@ struct PcrFused {
     int on;
     double *Dpp[2];                             // assembled [D | r] of a step: n x PCR_IMG_SYM
     double *GLL[2], *GUU[2];                    // [YL | yr]^T [YL | yr], the same for YU: n x PCR_IMG_SYM each
-    double *GUL[2], *GULT[2];                   // YU^T YL and its transpose: n x PCR_IMG_FULL each (columns 72..79 are never read)
+    double *GUL[2];                             // YU^T YL: n x PCR_IMG_FULL (columns 72..79 are never read).  ONE image: block b - s reads
+                                                // its U^T out of it, transposed on load
     // chains with pinned ends (partitioned solve): a coupling that points at a pinned block is never folded again; the
     // block that holds it saves it once (canonical orientation: rows of the block) and reads it back in every later step
     double *Lkeep, *Ukeep;                      // n x PCR_IMG_FULL each, or null

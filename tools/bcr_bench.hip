@@ -213,7 +213,7 @@ int main(int argc, char **argv) {
         for (int q = 0; q < 2; ++q) {
             d.pcrf.Dpp[q] = dalloc<double>((size_t)n * PCR_IMG_SYM);
             d.pcrf.GLL[q] = dalloc<double>((size_t)n * PCR_IMG_SYM); d.pcrf.GUU[q] = dalloc<double>((size_t)n * PCR_IMG_SYM);
-            d.pcrf.GUL[q] = dalloc<double>((size_t)n * PCR_IMG_FULL); d.pcrf.GULT[q] = dalloc<double>((size_t)n * PCR_IMG_FULL);
+            d.pcrf.GUL[q] = dalloc<double>((size_t)n * PCR_IMG_FULL);
         }
         d.pcrf.on = 1;
         auto upload2 = [&] {

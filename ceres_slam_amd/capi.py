@@ -42,6 +42,7 @@ SYMBOLS = [
     "ssba_image_pyramid_create", "ssba_image_pyramid_destroy", "ssba_image_pyramid_level", "ssba_add_image_level", "ssba_image_pyramid_align",
     "ssba_sgbm_default_params", "ssba_stereo_sgbm", "ssba_image_pyramid_create_stereo",
     "ssba_image_solve_batch", "ssba_image_pyramid_align_batch", "ssba_image_pyramid_set_huber_loss",
+    "ssba_stereo_sgbm_batch", "ssba_image_sequence_create", "ssba_image_sequence_pyramid", "ssba_image_sequence_destroy",
 ]
 
 
@@ -72,6 +73,8 @@ class CovBlock(C.Structure):
 LEVENBERG_MARQUARDT, DOGLEG = 0, 1
 IMAGE_NEAREST, IMAGE_BILINEAR = 0, 1     # SSBA_IMAGE_NEAREST / SSBA_IMAGE_BILINEAR
 IMAGE_BATCH_MAX = 4096                   # SSBA_IMAGE_BATCH_MAX
+SGBM_DEFAULT_WORKSPACE_BYTES = 1 << 30   # SSBA_SGBM_DEFAULT_WORKSPACE_BYTES
+SGBM_MAX_CHUNK = 65535                   # the pairs of a matcher chunk are a grid dimension
 GRADIENT_OF_REFERENCE, GRADIENT_OF_TRACKED = 0, 1     # SSBA_GRADIENT_OF_REFERENCE / SSBA_GRADIENT_OF_TRACKED
 
 
@@ -196,6 +199,12 @@ def load():
     L.ssba_stereo_sgbm.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_int, C.POINTER(C.c_int16), _dp]
     L.ssba_image_pyramid_create_stereo.argtypes = [_u8p, _u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_int,
                                                    C.c_double, C.c_int, C.POINTER(H)]
+    L.ssba_stereo_sgbm_batch.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_uint64, C.c_int,
+                                         C.POINTER(C.c_int16), _dp]
+    L.ssba_image_sequence_create.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SgbmParams), C.c_uint64,
+                                             C.c_int, C.c_double, C.c_int, C.POINTER(H)]
+    L.ssba_image_sequence_pyramid.argtypes = [H, C.c_uint32, C.POINTER(H)]
+    L.ssba_image_sequence_destroy.argtypes = [H]
     L.ssba_ransac_samples.argtypes = [C.c_uint32, C.c_uint32, C.c_int, _u32p]
     L.ssba_frontend_ransac.argtypes = [C.POINTER(Camera), C.c_int, C.c_uint32, _u32p, _dp, _dp, _u32p, C.c_uint32, C.c_double, _dp,
                                        C.POINTER(C.c_uint8), _u32p, _dp]
@@ -231,6 +240,24 @@ def sgbm_params(**kw) -> SgbmParams:
             raise AttributeError(k)
         setattr(p, k, int(v))
     return p
+
+
+def sgbm_pair_bytes(rows: int, cols: int, num_disparities: int = 64, min_disparity: int = 0) -> int:
+    """The matcher's volumes for one pair: six 16-bit values per (row, computable column, disparity)."""
+    return 12 * int(rows) * (int(cols) - int(min_disparity) - int(num_disparities)) * int(num_disparities)
+
+
+def sgbm_chunk_pairs(n: int, workspace_bytes: int, rows: int, cols: int, num_disparities: int = 64, min_disparity: int = 0) -> int:
+    """How many of n pairs ssba_stereo_sgbm_batch and ssba_image_sequence_create process per chunk of five launches
+    (include/ssba.h): as many as fit workspace_bytes (0: the 1 GiB default), at most n and 65535.  A bound below one pair's
+    volumes is refused there; here it raises ValueError."""
+    need = sgbm_pair_bytes(rows, cols, num_disparities, min_disparity)
+    have = int(workspace_bytes) or SGBM_DEFAULT_WORKSPACE_BYTES
+    if need <= 0 or n <= 0:
+        raise ValueError("no computable column or no pair")
+    if have < need:
+        raise ValueError(f"workspace_bytes {have} is below the volumes of one pair: {need} bytes needed")
+    return min(int(n), have // need, SGBM_MAX_CHUNK)
 
 
 def dptr(a: np.ndarray):

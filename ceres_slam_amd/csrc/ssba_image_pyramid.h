@@ -20,4 +20,15 @@ struct ssba_image_pyramid {
     hipStream_t stream = nullptr;
     std::vector<Level> lv;
     std::vector<void *> allocs;
+    bool borrowed = false;                                         // ssba_image_sequence_pyramid: levels, stream and memory are the sequence's
+};
+
+// A stereo sequence of F frames (ssba_image_sequence_create): per level one frame-major buffer each for the 8-bit images (the F
+// left frames, then the F - 1 right frames down to disparity_level), the double images, both gradients, and from disparity_level
+// on the F - 1 disparity maps.  pairs[k] is the borrowed pyramid of pair k: its level pointers lie in these buffers.
+struct ssba_image_sequence {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<void *> allocs;
+    std::vector<ssba_image_pyramid *> pairs;
 };

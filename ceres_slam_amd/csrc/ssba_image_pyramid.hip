@@ -45,12 +45,8 @@ static __device__ __forceinline__ int pyr_reflect(int i, int n) {
     return min(max(i, 0), n - 1);
 }
 
-__global__ __launch_bounds__(PYR_THREADS) void k_pyr_down(const uint8_t *__restrict__ src0, const uint8_t *__restrict__ src1,
-                                                          uint8_t *__restrict__ dst0, uint8_t *__restrict__ dst1, int srows, int scols,
-                                                          int drows, int dcols) {
-    __shared__ uint8_t tile[PYR_SH * PYR_STRIDE];
-    const uint8_t *__restrict__ src = blockIdx.z ? src1 : src0;
-    uint8_t *__restrict__ dst = blockIdx.z ? dst1 : dst0;
+static __device__ __forceinline__ void pyr_down_body(uint8_t *tile, const uint8_t *src, uint8_t *dst, int srows, int scols,
+                                                     int drows, int dcols) {
     const int x0 = blockIdx.x * PYR_TW, y0 = blockIdx.y * PYR_TH;
     for (int i = threadIdx.x; i < PYR_SH * PYR_SW; i += PYR_THREADS) {
         const int r = i / PYR_SW, c = i - r * PYR_SW;
@@ -71,29 +67,80 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyr_down(const uint8_t *__restr
     dst[(size_t)y * dcols + x] = (uint8_t)((sum + 128) >> 8);
 }
 
+__global__ __launch_bounds__(PYR_THREADS) void k_pyr_down(const uint8_t *__restrict__ src0, const uint8_t *__restrict__ src1,
+                                                          uint8_t *__restrict__ dst0, uint8_t *__restrict__ dst1, int srows, int scols,
+                                                          int drows, int dcols) {
+    __shared__ uint8_t tile[PYR_SH * PYR_STRIDE];
+    pyr_down_body(tile, blockIdx.z ? src1 : src0, blockIdx.z ? dst1 : dst0, srows, scols, drows, dcols);
+}
+
+// One level of a sequence: image blockIdx.z of a frame-major buffer, the strides in pixels of the two levels
+__global__ __launch_bounds__(PYR_THREADS) void k_pyr_down_seq(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int srows, int scols, int drows,
+                                                              int dcols) {
+    __shared__ uint8_t tile[PYR_SH * PYR_STRIDE];
+    pyr_down_body(tile, src + (size_t)blockIdx.z * srows * scols, dst + (size_t)blockIdx.z * drows * dcols, srows, scols, drows, dcols);
+}
+
+// convertTo(CV_64F, 1. / 255.): the converted image is rounded before it is differenced, as convertTo stores it
+static __device__ __forceinline__ double pyr_convert(uint8_t u) {
+#pragma clang fp contract(off)
+    const double k = 1.0 / 255.0;
+    return (double)u * k;
+}
+
+// the two Sobel images of g at (x, y), border reflected
+static __device__ __forceinline__ void pyr_sobel(const uint8_t *__restrict__ g, int x, int y, int rows, int cols, double scale, double *gx, double *gy) {
+#pragma clang fp contract(off)
+    const int xm = x > 0 ? x - 1 : 1, xp = x + 1 < cols ? x + 1 : cols - 2;
+    const int ym = y > 0 ? y - 1 : 1, yp = y + 1 < rows ? y + 1 : rows - 2;
+    const uint8_t *__restrict__ r0 = g + (size_t)ym * cols, *__restrict__ r1 = g + (size_t)y * cols, *__restrict__ r2 = g + (size_t)yp * cols;
+    const double a00 = pyr_convert(r0[xm]), a01 = pyr_convert(r0[x]), a02 = pyr_convert(r0[xp]);
+    const double a10 = pyr_convert(r1[xm]), a12 = pyr_convert(r1[xp]);
+    const double a20 = pyr_convert(r2[xm]), a21 = pyr_convert(r2[x]), a22 = pyr_convert(r2[xp]);
+    // the summation order of synth.sobel: (first row + 2 * middle row) + last row, then the scale
+    *gx = scale * (((a02 - a00) + 2.0 * (a12 - a10)) + (a22 - a20));
+    *gy = scale * (((a20 - a00) + 2.0 * (a21 - a01)) + (a22 - a02));
+}
+
+// d_l[y][x] = d_{l-1}[2 y][2 x] / 2
+static __device__ __forceinline__ double pyr_disp_down(const double *__restrict__ disp_src, int x, int y, int src_cols) {
+    return disp_src[(size_t)(2 * y) * src_cols + 2 * x] / 2.0;
+}
+
 // disp_dst = nullptr below and at disparity_level; disp_src is the finer level's map, src_cols wide
 __global__ __launch_bounds__(PYR_THREADS) void k_pyr_finish(const uint8_t *__restrict__ u0, const uint8_t *__restrict__ u1, double *__restrict__ ref,
                                                             double *__restrict__ track, double *__restrict__ gradx, double *__restrict__ grady, int rows,
                                                             int cols, int gradient_source, double scale, const double *__restrict__ disp_src,
                                                             double *__restrict__ disp_dst, int src_cols) {
-#pragma clang fp contract(off)      // the converted image is rounded before it is differenced, as convertTo stores it
     const int x = blockIdx.x * PYR_TW + threadIdx.x % PYR_TW, y = blockIdx.y * PYR_TH + threadIdx.x / PYR_TW;
     if (x >= cols || y >= rows) return;
     const size_t i = (size_t)y * cols + x;
-    const double k = 1.0 / 255.0;
-    ref[i] = (double)u0[i] * k;
-    track[i] = (double)u1[i] * k;
-    const uint8_t *__restrict__ g = gradient_source == SSBA_GRADIENT_OF_TRACKED ? u1 : u0;
-    const int xm = x > 0 ? x - 1 : 1, xp = x + 1 < cols ? x + 1 : cols - 2;
-    const int ym = y > 0 ? y - 1 : 1, yp = y + 1 < rows ? y + 1 : rows - 2;
-    const uint8_t *__restrict__ r0 = g + (size_t)ym * cols, *__restrict__ r1 = g + (size_t)y * cols, *__restrict__ r2 = g + (size_t)yp * cols;
-    const double a00 = (double)r0[xm] * k, a01 = (double)r0[x] * k, a02 = (double)r0[xp] * k;
-    const double a10 = (double)r1[xm] * k, a12 = (double)r1[xp] * k;
-    const double a20 = (double)r2[xm] * k, a21 = (double)r2[x] * k, a22 = (double)r2[xp] * k;
-    // the summation order of synth.sobel: (first row + 2 * middle row) + last row, then the scale
-    gradx[i] = scale * (((a02 - a00) + 2.0 * (a12 - a10)) + (a22 - a20));
-    grady[i] = scale * (((a20 - a00) + 2.0 * (a21 - a01)) + (a22 - a02));
-    if (disp_dst) disp_dst[i] = disp_src[(size_t)(2 * y) * src_cols + 2 * x] / 2.0;
+    ref[i] = pyr_convert(u0[i]);
+    track[i] = pyr_convert(u1[i]);
+    double gx, gy;
+    pyr_sobel(gradient_source == SSBA_GRADIENT_OF_TRACKED ? u1 : u0, x, y, rows, cols, scale, &gx, &gy);
+    gradx[i] = gx;
+    grady[i] = gy;
+    if (disp_dst) disp_dst[i] = pyr_disp_down(disp_src, x, y, src_cols);
+}
+
+// One level of a sequence, frame blockIdx.z: the frame's double image and its two Sobel images, once for both of its roles (the
+// tracked image of pair z - 1, the reference image of pair z), and for z < npairs above disparity_level pair z's disparity map.
+// u8, img, gradx, grady and disp_dst are frame-major with rows * cols between frames, disp_src with src_rows * src_cols.
+__global__ __launch_bounds__(PYR_THREADS) void k_pyr_finish_seq(const uint8_t *__restrict__ u8, double *__restrict__ img, double *__restrict__ gradx,
+                                                                double *__restrict__ grady, int rows, int cols, double scale, int npairs,
+                                                                const double *__restrict__ disp_src, double *__restrict__ disp_dst, int src_rows,
+                                                                int src_cols) {
+    const int x = blockIdx.x * PYR_TW + threadIdx.x % PYR_TW, y = blockIdx.y * PYR_TH + threadIdx.x / PYR_TW;
+    if (x >= cols || y >= rows) return;
+    const size_t npix = (size_t)rows * cols, f = blockIdx.z, i = f * npix + (size_t)y * cols + x;
+    const uint8_t *__restrict__ u = u8 + f * npix;
+    img[i] = pyr_convert(u[(size_t)y * cols + x]);
+    double gx, gy;
+    pyr_sobel(u, x, y, rows, cols, scale, &gx, &gy);
+    gradx[i] = gx;
+    grady[i] = gy;
+    if (disp_dst && (int)f < npairs) disp_dst[i] = pyr_disp_down(disp_src + f * (size_t)src_rows * src_cols, x, y, src_cols);
 }
 
 template <class T>
@@ -235,6 +282,91 @@ static int pyr_create(const char *call, const uint8_t *ref_u8, const uint8_t *tr
     return SSBA_OK;
 }
 
+template <class T>
+static hipError_t seq_alloc(ssba_image_sequence *seq, T **out, size_t n) {
+    void *p = nullptr;
+    const hipError_t e = pool_malloc(&p, n * sizeof(T));
+    if (e != hipSuccess) return e;
+    seq->allocs.push_back(p);
+    *out = (T *)p;
+    return hipSuccess;
+}
+
+static void seq_free(ssba_image_sequence *seq) {
+    hipSetDevice(seq->device);
+    if (seq->stream) hipStreamSynchronize(seq->stream);
+    for (ssba_image_pyramid *p : seq->pairs) delete p;
+    for (void *a : seq->allocs) pool_free(a);
+    if (seq->stream) pool_stream_release(seq->stream);
+    delete seq;
+}
+
+// The build of a sequence: 2 levels + 4 launches while the pairs fit one matcher chunk (levels - 1 k_pyr_down_seq, the five
+// matcher kernels per chunk, levels k_pyr_finish_seq), one copy up and one synchronisation.
+static int seq_build(ssba_image_sequence *seq, const uint8_t *left, const uint8_t *right, uint32_t frames, uint32_t rows, uint32_t cols, uint32_t levels,
+                     uint32_t dl, const SgbmPlan &plan, uint32_t chunk_pairs, int gradient_source, double gradient_scale, char *stage,
+                     std::vector<void *> *temps) {
+    const uint32_t npairs = frames - 1;
+    const size_t n0 = (size_t)rows * cols;
+    std::vector<uint8_t *> u8(levels, nullptr);
+    std::vector<double *> img(levels, nullptr), gx(levels, nullptr), gy(levels, nullptr), disp(levels, nullptr);
+    for (uint32_t l = 0; l < levels; ++l) {
+        const size_t npix = (size_t)(rows >> l) * (cols >> l);
+        PYR_HIP(seq_alloc(seq, &u8[l], npix * (frames + (l <= dl ? npairs : 0))));
+        PYR_HIP(seq_alloc(seq, &img[l], npix * frames));
+        PYR_HIP(seq_alloc(seq, &gx[l], npix * frames));
+        PYR_HIP(seq_alloc(seq, &gy[l], npix * frames));
+        if (l >= dl) PYR_HIP(seq_alloc(seq, &disp[l], npix * npairs));
+    }
+    memcpy(stage, left, n0 * frames);
+    memcpy(stage + n0 * frames, right, n0 * npairs);
+    hipStream_t s = seq->stream;
+    PYR_HIP(hipMemcpyAsync(u8[0], stage, n0 * (frames + npairs), hipMemcpyHostToDevice, s));
+    for (uint32_t l = 0; l < levels; ++l) {
+        const int r = (int)(rows >> l), c = (int)(cols >> l);
+        const size_t npix = (size_t)r * c;
+        const dim3 grid((c + PYR_TW - 1) / PYR_TW, (r + PYR_TH - 1) / PYR_TH, 1);
+        if (l > 0) {
+            hipLaunchKernelGGL(k_pyr_down_seq, dim3(grid.x, grid.y, frames + (l <= dl ? npairs : 0)), dim3(PYR_THREADS), 0, s, (const uint8_t *)u8[l - 1], u8[l],
+                               (int)(rows >> (l - 1)), (int)(cols >> (l - 1)), r, c);
+            PYR_HIP(hipGetLastError());
+        }
+        if (l == dl) PYR_HIP(sgbm_enqueue_batch(plan, u8[l], u8[l] + npix * frames, npix, npairs, chunk_pairs, nullptr, disp[l], s, temps));
+        const bool derive = l > dl;
+        hipLaunchKernelGGL(k_pyr_finish_seq, dim3(grid.x, grid.y, frames), dim3(PYR_THREADS), 0, s, (const uint8_t *)u8[l], img[l], gx[l], gy[l], r, c, gradient_scale,
+                           (int)npairs, derive ? (const double *)disp[l - 1] : nullptr, derive ? disp[l] : nullptr, derive ? (int)(rows >> (l - 1)) : 0,
+                           derive ? (int)(cols >> (l - 1)) : 0);
+        PYR_HIP(hipGetLastError());
+    }
+    for (uint32_t k = 0; k < npairs; ++k) {
+        ssba_image_pyramid *pyr = new ssba_image_pyramid();
+        seq->pairs.push_back(pyr);
+        pyr->borrowed = true;
+        pyr->device = seq->device;
+        pyr->stream = s;
+        pyr->disparity_level = (int)dl;
+        pyr->gradient_source = gradient_source;
+        pyr->gradient_scale = gradient_scale;
+        pyr->lv.resize(levels);
+        const size_t g = gradient_source == SSBA_GRADIENT_OF_TRACKED ? k + 1 : k;
+        for (uint32_t l = 0; l < levels; ++l) {
+            ssba_image_pyramid::Level &L = pyr->lv[l];
+            L.rows = (int)(rows >> l);
+            L.cols = (int)(cols >> l);
+            const size_t npix = (size_t)L.rows * L.cols;
+            L.u8[0] = u8[l] + npix * k;
+            L.u8[1] = u8[l] + npix * (k + 1);
+            L.img[0] = img[l] + npix * k;
+            L.img[1] = img[l] + npix * (k + 1);
+            L.img[2] = gx[l] + npix * g;
+            L.img[3] = gy[l] + npix * g;
+            L.disp = l >= dl ? disp[l] + npix * k : nullptr;
+        }
+    }
+    PYR_HIP(hipStreamSynchronize(s));
+    return SSBA_OK;
+}
+
 }  // namespace ssba
 
 using namespace ssba;
@@ -261,7 +393,72 @@ int ssba_image_pyramid_create_stereo(const uint8_t *ref_left_u8, const uint8_t *
 
 int ssba_image_pyramid_destroy(ssba_image_pyramid *pyr) {
     if (!pyr) return pyr_invalid("ssba_image_pyramid_destroy", "NULL pyramid");
+    if (pyr->borrowed) return pyr_invalid("ssba_image_pyramid_destroy", "the pyramid is borrowed from an image sequence and ends with it (ssba_image_sequence_destroy)");
     pyr_free(pyr);
+    return SSBA_OK;
+}
+
+int ssba_image_sequence_create(const uint8_t *left, const uint8_t *right, uint32_t frames, uint32_t rows, uint32_t cols, uint32_t levels,
+                               uint32_t disparity_level, const ssba_sgbm_params *params, uint64_t workspace_bytes, int gradient_source,
+                               double gradient_scale, int device, ssba_image_sequence **out) {
+    const char *call = "ssba_image_sequence_create";
+    if (!out) return pyr_invalid(call, "NULL output");
+    *out = nullptr;
+    if (!left || !right) return pyr_invalid(call, "NULL array");
+    if (frames < 2) return pyr_invalid(call, "a sequence needs at least 2 frames");
+    if (levels == 0) return pyr_invalid(call, "levels = 0");
+    if (disparity_level >= levels) return pyr_invalid(call, "disparity_level must be below levels");
+    if (gradient_source != SSBA_GRADIENT_OF_REFERENCE && gradient_source != SSBA_GRADIENT_OF_TRACKED) return pyr_invalid(call, "unknown gradient source");
+    if (!std::isfinite(gradient_scale) || gradient_scale == 0.0) return pyr_invalid(call, "gradient_scale must be finite and not zero");
+    if (levels > 31 || (rows >> (levels - 1)) < (uint32_t)PYR_MIN_SIDE || (cols >> (levels - 1)) < (uint32_t)PYR_MIN_SIDE)
+        return pyr_invalid(call, "every level needs at least 8 rows and 8 columns");
+    if ((uint64_t)rows * cols >= (1ull << 31)) {
+        set_last_error(std::string(call) + ": image too large for the 32-bit pixel references of this build");
+        return SSBA_ERR_UNSUPPORTED;
+    }
+    if (frames > 32768) return pyr_invalid(call, "at most 32768 frames (the 2 frames - 1 images of a level are one grid dimension)");
+    SgbmPlan plan{};
+    if (const int rc = sgbm_check(call, rows >> disparity_level, cols >> disparity_level, params, &plan)) return rc;
+    uint32_t chunk_pairs = 0;
+    if (const int rc = sgbm_chunk_pairs(call, plan, frames - 1, workspace_bytes, &chunk_pairs)) return rc;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        set_last_error(std::string(call) + ": hipGetDeviceCount found no device");
+        return SSBA_ERR_NO_DEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return SSBA_ERR_NO_DEVICE;
+    if (device >= n) return pyr_invalid(call, "no such device");
+    PYR_HIP(hipSetDevice(device));
+    ssba_image_sequence *seq = new ssba_image_sequence();
+    seq->device = device;
+    int rc = SSBA_OK;
+    void *stage = nullptr;
+    std::vector<void *> temps;
+    if (pool_stream_acquire(&seq->stream) != hipSuccess || pool_host_malloc(&stage, (size_t)rows * cols * (2 * (size_t)frames - 1)) != hipSuccess) {
+        set_last_error(std::string(call) + ": no stream or no pinned staging memory");
+        rc = SSBA_ERR_HIP;
+    } else {
+        rc = seq_build(seq, left, right, frames, rows, cols, levels, disparity_level, plan, chunk_pairs, gradient_source, gradient_scale, (char *)stage, &temps);
+    }
+    if (stage) { if (seq->stream) hipStreamSynchronize(seq->stream); pool_host_free(stage); }
+    for (void *t : temps) pool_free(t);
+    if (rc) { seq_free(seq); return rc; }
+    *out = seq;
+    return SSBA_OK;
+}
+
+int ssba_image_sequence_pyramid(ssba_image_sequence *seq, uint32_t k, ssba_image_pyramid **out) {
+    const char *call = "ssba_image_sequence_pyramid";
+    if (out) *out = nullptr;
+    if (!seq || !out) return pyr_invalid(call, "NULL argument");
+    if (k >= seq->pairs.size()) return pyr_invalid(call, ("no such pair: the sequence has " + std::to_string(seq->pairs.size())).c_str());
+    *out = seq->pairs[k];
+    return SSBA_OK;
+}
+
+int ssba_image_sequence_destroy(ssba_image_sequence *seq) {
+    if (!seq) return pyr_invalid("ssba_image_sequence_destroy", "NULL sequence");
+    seq_free(seq);
     return SSBA_OK;
 }
 

@@ -40,6 +40,7 @@ constexpr int SG_INF = 0x3fffffff;              // "no such disparity": survives
 constexpr int SG_MAX_COLS = 5461;               // twelve byte signals of a row in 64 KiB of LDS
 constexpr int SG_PREFETCH = 4;
 constexpr uint16_t SG_NO_WINNER = 0xffff;
+constexpr uint32_t SG_MAX_CHUNK = 65535;        // the pairs of a chunk are a grid's y or z dimension
 
 struct SgbmVolumes {
     uint16_t *L[5];
@@ -108,9 +109,8 @@ static __device__ __forceinline__ int sg_bt(int a, int amin, int amax, int b, in
 }
 
 // hsum[y][xi][d] = sum_{i=-r..r} c(clamp(x + i), y, d).  LDS: sig[(4 signals x {value, min, max})][cols] bytes.
-__global__ __launch_bounds__(SG_THREADS) void k_sgbm_hcost(const uint8_t *__restrict__ left, const uint8_t *__restrict__ right, uint16_t *__restrict__ hsum,
-                                                          SgbmPlan p, int per_chunk) {
-    extern __shared__ uint8_t sig[];
+static __device__ __forceinline__ void sg_hcost_body(uint8_t *sig, const uint8_t *left, const uint8_t *right,
+                                                     uint16_t *hsum, SgbmPlan p, int per_chunk) {
     const int y = blockIdx.y, cols = p.cols, rows = p.rows;
     const int ym = y > 0 ? y - 1 : 1, yp = y + 1 < rows ? y + 1 : rows - 2;
     for (int x = threadIdx.x; x < cols; x += SG_THREADS) {
@@ -148,8 +148,14 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgbm_hcost(const uint8_t *__rest
     }
 }
 
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_hcost(const uint8_t *__restrict__ left, const uint8_t *__restrict__ right, uint16_t *__restrict__ hsum,
+                                                          SgbmPlan p, int per_chunk) {
+    extern __shared__ uint8_t sig[];
+    sg_hcost_body(sig, left, right, hsum, p, per_chunk);
+}
+
 // C[y][xi][d] = sum_{j=-r..r} hsum[clamp(y + j)][xi][d]; four disparities per lane (D is a multiple of 16)
-__global__ __launch_bounds__(SG_THREADS) void k_sgbm_vcost(const uint16_t *__restrict__ hsum, uint16_t *__restrict__ C, SgbmPlan p) {
+static __device__ __forceinline__ void sg_vcost_body(const uint16_t *hsum, uint16_t *C, SgbmPlan p) {
     const size_t row4 = (size_t)p.W * p.D / 4, i = (size_t)blockIdx.x * SG_THREADS + threadIdx.x;
     if (i >= row4 * p.rows) return;
     const int y = (int)(i / row4);
@@ -166,11 +172,15 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgbm_vcost(const uint16_t *__res
     reinterpret_cast<uint2 *>(C)[i] = make_uint2(s0 | (s1 << 16), s2 | (s3 << 16));
 }
 
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_vcost(const uint16_t *__restrict__ hsum, uint16_t *__restrict__ C, SgbmPlan p) {
+    sg_vcost_body(hsum, C, p);
+}
+
 // One wave per path.  Chains in order: rows from the left (predecessor x - 1), rows from the right (x + 1), W columns downwards,
 // W + rows - 1 diagonals down-right (predecessor (x - 1, y - 1): they start in row 0 or in the first computable column), as
 // many down-left.  L = C where the predecessor lies outside, which is C + min(0, P1, P1, P2) - 0 from an all-zero predecessor.
 template <int K>
-__global__ __launch_bounds__(SG_THREADS) void k_sgbm_paths(const uint16_t *__restrict__ C, SgbmVolumes vol, SgbmPlan p, int nchains) {
+static __device__ __forceinline__ void sg_paths_body(const uint16_t *C, SgbmVolumes vol, SgbmPlan p, int nchains) {
     const int lane = threadIdx.x & 63;
     int c = blockIdx.x * SG_WAVES + (threadIdx.x >> 6);
     if (c >= nchains) return;       // a whole wave
@@ -220,10 +230,15 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgbm_paths(const uint16_t *__res
     }
 }
 
+template <int K>
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_paths(const uint16_t *__restrict__ C, SgbmVolumes vol, SgbmPlan p, int nchains) {
+    sg_paths_body<K>(C, vol, p, nchains);
+}
+
 // One wave per pixel.  winner: the disparity (min_disparity included) or SG_NO_WINNER where uniqueness fails.
 template <int K>
-__global__ __launch_bounds__(SG_THREADS) void k_sgbm_select(SgbmVolumes vol, uint16_t *__restrict__ winner, int *__restrict__ smin_out,
-                                                           int16_t *__restrict__ disp16_out, SgbmPlan p) {
+static __device__ __forceinline__ void sg_select_body(SgbmVolumes vol, uint16_t *winner, int *smin_out,
+                                                      int16_t *disp16_out, SgbmPlan p) {
     const int lane = threadIdx.x & 63;
     const size_t px = (size_t)blockIdx.x * SG_WAVES + (threadIdx.x >> 6);
     if (px >= (size_t)p.rows * p.W) return;     // a whole wave
@@ -270,10 +285,16 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgbm_select(SgbmVolumes vol, uin
     }
 }
 
+template <int K>
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_select(SgbmVolumes vol, uint16_t *__restrict__ winner, int *__restrict__ smin_out,
+                                                           int16_t *__restrict__ disp16_out, SgbmPlan p) {
+    sg_select_body<K>(vol, winner, smin_out, disp16_out, p);
+}
+
 // One work-group per row.  LDS: disp2[cols] as int16.
-__global__ __launch_bounds__(SG_THREADS) void k_sgbm_lr(const uint16_t *__restrict__ winner, const int *__restrict__ smin, const int16_t *__restrict__ disp16_w,
-                                                       int16_t *__restrict__ disp16_out, double *__restrict__ disparity_out, SgbmPlan p) {
-    extern __shared__ int16_t disp2[];
+static __device__ __forceinline__ void sg_lr_body(int16_t *disp2, const uint16_t *winner, const int *smin,
+                                                  const int16_t *disp16_w, int16_t *disp16_out, double *disparity_out,
+                                                  SgbmPlan p) {
     const int y = blockIdx.x, cols = p.cols, W = p.W;
     const uint16_t *__restrict__ win = winner + (size_t)y * W;
     const int *__restrict__ cost = smin + (size_t)y * W;
@@ -308,6 +329,60 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgbm_lr(const uint16_t *__restri
         if (disp16_out) disp16_out[i] = (int16_t)v;
         if (disparity_out) disparity_out[i] = ok ? (double)v / 16.0 : __builtin_nan("");
     }
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_lr(const uint16_t *__restrict__ winner, const int *__restrict__ smin, const int16_t *__restrict__ disp16_w,
+                                                       int16_t *__restrict__ disp16_out, double *__restrict__ disparity_out, SgbmPlan p) {
+    extern __shared__ int16_t disp2[];
+    sg_lr_body(disp2, winner, smin, disp16_w, disp16_out, disparity_out, p);
+}
+
+// The five kernels over the pairs of a chunk (ssba_stereo_sgbm_batch, ssba_image_sequence_create): the pair is the grid's last
+// dimension, images, volumes, per-pixel arrays and outputs are pair-major with one stride each, so a work-group's base pointers
+// follow from its block index (wave-uniform) and the bodies above run unchanged: member k's bits are the solo call's.
+struct SgbmStrides {
+    size_t img, vol, px, out;       // elements between two pairs: input images, volumes, winner / smin / disp16_w, outputs
+};
+
+static __device__ __forceinline__ SgbmVolumes sg_pair_volumes(SgbmVolumes vol, size_t off) {
+    SgbmVolumes v;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) v.L[q] = vol.L[q] + off;
+    return v;
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_hcost_batch(const uint8_t *__restrict__ left, const uint8_t *__restrict__ right,
+                                                                uint16_t *__restrict__ hsum, SgbmPlan p, int per_chunk, SgbmStrides st) {
+    extern __shared__ uint8_t sig[];
+    const size_t pair = blockIdx.z;
+    sg_hcost_body(sig, left + pair * st.img, right + pair * st.img, hsum + pair * st.vol, p, per_chunk);
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_vcost_batch(const uint16_t *__restrict__ hsum, uint16_t *__restrict__ C, SgbmPlan p, SgbmStrides st) {
+    const size_t off = (size_t)blockIdx.y * st.vol;
+    sg_vcost_body(hsum + off, C + off, p);
+}
+
+template <int K>
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_paths_batch(const uint16_t *__restrict__ C, SgbmVolumes vol, SgbmPlan p, int nchains, SgbmStrides st) {
+    const size_t off = (size_t)blockIdx.y * st.vol;
+    sg_paths_body<K>(C + off, sg_pair_volumes(vol, off), p, nchains);
+}
+
+template <int K>
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_select_batch(SgbmVolumes vol, uint16_t *__restrict__ winner, int *__restrict__ smin_out,
+                                                                 int16_t *__restrict__ disp16_out, SgbmPlan p, SgbmStrides st) {
+    const size_t pair = blockIdx.y;
+    sg_select_body<K>(sg_pair_volumes(vol, pair * st.vol), winner + pair * st.px, smin_out + pair * st.px, disp16_out + pair * st.px, p);
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sgbm_lr_batch(const uint16_t *__restrict__ winner, const int *__restrict__ smin,
+                                                             const int16_t *__restrict__ disp16_w, int16_t *__restrict__ disp16_out,
+                                                             double *__restrict__ disparity_out, SgbmPlan p, SgbmStrides st) {
+    extern __shared__ int16_t disp2[];
+    const size_t pair = blockIdx.y;
+    sg_lr_body(disp2, winner + pair * st.px, smin + pair * st.px, disp16_w + pair * st.px, disp16_out ? disp16_out + pair * st.out : nullptr,
+               disparity_out ? disparity_out + pair * st.out : nullptr, p);
 }
 
 static int sg_refuse(const char *call, int status, const char *what) {
@@ -401,6 +476,95 @@ hipError_t sgbm_enqueue(const SgbmPlan &p, const uint8_t *left, const uint8_t *r
     return hipGetLastError();
 }
 
+uint64_t sgbm_pair_bytes(const SgbmPlan &p) { return 12ull * (uint64_t)p.rows * (uint64_t)p.W * (uint64_t)p.D; }
+
+int sgbm_chunk_pairs(const char *call, const SgbmPlan &p, uint32_t n, uint64_t workspace_bytes, uint32_t *pairs) {
+    const uint64_t need = sgbm_pair_bytes(p), have = workspace_bytes ? workspace_bytes : SSBA_SGBM_DEFAULT_WORKSPACE_BYTES;
+    if (have < need)
+        return sg_refuse(call, SSBA_ERR_INVALID_ARGUMENT,
+                         ("workspace_bytes " + std::to_string(have) + " is below the volumes of one pair: " + std::to_string(need) + " bytes needed").c_str());
+    uint64_t fit = have / need;
+    if (fit > n) fit = n;
+    if (fit > SG_MAX_CHUNK) fit = SG_MAX_CHUNK;
+    *pairs = (uint32_t)fit;
+    return SSBA_OK;
+}
+
+hipError_t sgbm_enqueue_batch(const SgbmPlan &p, const uint8_t *left, const uint8_t *right, size_t img_stride, uint32_t n, uint32_t chunk_pairs,
+                              int16_t *disp16, double *disparity, hipStream_t s, std::vector<void *> *temps) {
+    const size_t npx = (size_t)p.rows * p.W, nvol = npx * p.D, m = chunk_pairs < n ? chunk_pairs : n;
+    const SgbmStrides st = {img_stride, nvol, npx, (size_t)p.rows * p.cols};
+    uint16_t *C = nullptr, *winner = nullptr;
+    int *smin = nullptr;
+    int16_t *d16w = nullptr;
+    SgbmVolumes vol;
+    SG_TRY(sg_alloc(temps, &C, m * nvol));
+    for (int q = 0; q < 5; ++q) SG_TRY(sg_alloc(temps, &vol.L[q], m * nvol));
+    SG_TRY(sg_alloc(temps, &winner, m * npx));
+    SG_TRY(sg_alloc(temps, &smin, m * npx));
+    SG_TRY(sg_alloc(temps, &d16w, m * npx));
+    // the launch shapes of sgbm_enqueue with the pair behind them; the chunks follow each other on `s` and share the volumes
+    const int total = p.W * p.D;
+    int nchunk = (total + 8191) / 8192;
+    nchunk = nchunk < 1 ? 1 : nchunk > 64 ? 64 : nchunk;
+    const int per_chunk = ((total + nchunk - 1) / nchunk + SG_THREADS - 1) / SG_THREADS * SG_THREADS;
+    const int nchains = 2 * p.rows + p.W + 2 * (p.W + p.rows - 1);
+    for (uint32_t first = 0; first < n; first += (uint32_t)m) {
+        const unsigned c = (unsigned)(n - first < m ? n - first : m);
+        const uint8_t *l = left + first * st.img, *r = right + first * st.img;
+        int16_t *o16 = disp16 ? disp16 + first * st.out : nullptr;
+        double *od = disparity ? disparity + first * st.out : nullptr;
+        hipLaunchKernelGGL(k_sgbm_hcost_batch, dim3((total + per_chunk - 1) / per_chunk, p.rows, c), dim3(SG_THREADS), (size_t)12 * p.cols, s, l, r, vol.L[0], p,
+                           per_chunk, st);
+        SG_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sgbm_vcost_batch, dim3((unsigned)((nvol / 4 + SG_THREADS - 1) / SG_THREADS), c), dim3(SG_THREADS), 0, s, (const uint16_t *)vol.L[0], C, p,
+                           st);
+        SG_TRY(hipGetLastError());
+        const dim3 pgrid((nchains + SG_WAVES - 1) / SG_WAVES, c), sgrid((unsigned)((npx + SG_WAVES - 1) / SG_WAVES), c);
+        switch ((p.D + 63) / 64) {
+        case 1:
+            hipLaunchKernelGGL(k_sgbm_paths_batch<1>, pgrid, dim3(SG_THREADS), 0, s, (const uint16_t *)C, vol, p, nchains, st);
+            hipLaunchKernelGGL(k_sgbm_select_batch<1>, sgrid, dim3(SG_THREADS), 0, s, vol, winner, smin, d16w, p, st);
+            break;
+        case 2:
+            hipLaunchKernelGGL(k_sgbm_paths_batch<2>, pgrid, dim3(SG_THREADS), 0, s, (const uint16_t *)C, vol, p, nchains, st);
+            hipLaunchKernelGGL(k_sgbm_select_batch<2>, sgrid, dim3(SG_THREADS), 0, s, vol, winner, smin, d16w, p, st);
+            break;
+        case 3:
+            hipLaunchKernelGGL(k_sgbm_paths_batch<3>, pgrid, dim3(SG_THREADS), 0, s, (const uint16_t *)C, vol, p, nchains, st);
+            hipLaunchKernelGGL(k_sgbm_select_batch<3>, sgrid, dim3(SG_THREADS), 0, s, vol, winner, smin, d16w, p, st);
+            break;
+        default:
+            hipLaunchKernelGGL(k_sgbm_paths_batch<4>, pgrid, dim3(SG_THREADS), 0, s, (const uint16_t *)C, vol, p, nchains, st);
+            hipLaunchKernelGGL(k_sgbm_select_batch<4>, sgrid, dim3(SG_THREADS), 0, s, vol, winner, smin, d16w, p, st);
+            break;
+        }
+        SG_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sgbm_lr_batch, dim3(p.rows, c), dim3(SG_THREADS), (size_t)2 * p.cols, s, (const uint16_t *)winner, (const int *)smin,
+                           (const int16_t *)d16w, o16, od, p, st);
+        SG_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+static hipError_t sg_run_batch(const SgbmPlan &p, const uint8_t *left, const uint8_t *right, uint32_t n, uint32_t chunk_pairs, int16_t *disp16_out,
+                               double *disparity_out, hipStream_t s, std::vector<void *> *temps) {
+    const size_t npix = (size_t)p.rows * p.cols, all = npix * n;
+    uint8_t *dl = nullptr, *dr = nullptr;
+    int16_t *d16 = nullptr;
+    double *dd = nullptr;
+    SG_TRY(sg_alloc(temps, &dl, all));
+    SG_TRY(sg_alloc(temps, &dr, all));
+    if (disp16_out) SG_TRY(sg_alloc(temps, &d16, all));
+    if (disparity_out) SG_TRY(sg_alloc(temps, &dd, all));
+    SG_TRY(hipMemcpyAsync(dl, left, all, hipMemcpyHostToDevice, s));
+    SG_TRY(hipMemcpyAsync(dr, right, all, hipMemcpyHostToDevice, s));
+    SG_TRY(sgbm_enqueue_batch(p, dl, dr, npix, n, chunk_pairs, d16, dd, s, temps));
+    if (disp16_out) SG_TRY(hipMemcpyAsync(disp16_out, d16, all * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    if (disparity_out) SG_TRY(hipMemcpyAsync(disparity_out, dd, all * sizeof(double), hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
+}
+
 static hipError_t sg_run(const SgbmPlan &p, const uint8_t *left, const uint8_t *right, int16_t *disp16_out, double *disparity_out, hipStream_t s,
                          std::vector<void *> *temps) {
     const size_t n = (size_t)p.rows * p.cols;
@@ -448,6 +612,31 @@ int ssba_stereo_sgbm(const uint8_t *left, const uint8_t *right, uint32_t rows, u
     if (pool_stream_acquire(&s) != hipSuccess) return sg_refuse(call, SSBA_ERR_HIP, "no stream");
     std::vector<void *> temps;
     const hipError_t e = sg_run(plan, left, right, disp16_out, disparity_out, s, &temps);
+    hipStreamSynchronize(s);
+    for (void *t : temps) pool_free(t);
+    pool_stream_release(s);
+    if (e != hipSuccess) return sg_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    return SSBA_OK;
+}
+
+int ssba_stereo_sgbm_batch(const uint8_t *left, const uint8_t *right, uint32_t n, uint32_t rows, uint32_t cols, const ssba_sgbm_params *params,
+                           uint64_t workspace_bytes, int device, int16_t *disp16_out, double *disparity_out) {
+    const char *call = "ssba_stereo_sgbm_batch";
+    if (!left || !right) return sg_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL image");
+    SgbmPlan plan;
+    if (const int rc = sgbm_check(call, rows, cols, params, &plan)) return rc;
+    if (n == 0) return sg_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "n = 0");
+    uint32_t chunk_pairs = 0;
+    if (const int rc = sgbm_chunk_pairs(call, plan, n, workspace_bytes, &chunk_pairs)) return rc;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return sg_refuse(call, SSBA_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return SSBA_ERR_NO_DEVICE;
+    if (device >= nd) return sg_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "no such device");
+    if (hipSetDevice(device) != hipSuccess) return sg_refuse(call, SSBA_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = nullptr;
+    if (pool_stream_acquire(&s) != hipSuccess) return sg_refuse(call, SSBA_ERR_HIP, "no stream");
+    std::vector<void *> temps;
+    const hipError_t e = sg_run_batch(plan, left, right, n, chunk_pairs, disp16_out, disparity_out, s, &temps);
     hipStreamSynchronize(s);
     for (void *t : temps) pool_free(t);
     pool_stream_release(s);

@@ -539,9 +539,23 @@ class ImagePyramid:
                    "ssba_image_pyramid_create_stereo")
         return self
 
+    #: True for a pyramid handed out by an ImageSequence: it owns no device memory, close() only forgets the handle
+    borrowed = False
+
+    @classmethod
+    def _borrow(cls, h, rows: int, cols: int, levels: int, disparity_level: int, camera: dict, device: int):
+        self = cls.__new__(cls)
+        self.lib = capi.load()
+        self.h = C.c_void_p(h)
+        self.borrowed = True
+        self.rows, self.cols, self.levels, self.disparity_level, self.device = rows, cols, int(levels), int(disparity_level), device
+        self.camera = dict(camera) if camera is not None else None
+        return self
+
     def close(self):
         if self.h:
-            self.lib.ssba_image_pyramid_destroy(self.h)
+            if not self.borrowed:
+                self.lib.ssba_image_pyramid_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -668,3 +682,115 @@ def stereo_sgbm(left, right, device: int = -1, **params):
     capi.check(lib.ssba_stereo_sgbm(left.ctypes.data_as(u8), right.ctypes.data_as(u8), rows, cols, C.byref(q), device,
                                     disp16.ctypes.data_as(C.POINTER(C.c_int16)), capi.dptr(disparity)), "ssba_stereo_sgbm")
     return disp16, disparity
+
+
+def pack_frames(lefts, rights):
+    """The frame-major stacks ssba_image_sequence_create reads: (F, rows, cols) uint8 left frames and the (F - 1, rows, cols)
+    right frames 0 ... F - 2, each contiguous.  ``rights`` may hold F or F - 1 frames; the last of F is not needed."""
+    lefts = [np.asarray(a) for a in lefts]
+    rights = [np.asarray(a) for a in rights]
+    if len(lefts) < 2:
+        raise ValueError("a sequence needs at least 2 frames")
+    if len(rights) not in (len(lefts), len(lefts) - 1):
+        raise ValueError(f"{len(lefts)} left frames need {len(lefts) - 1} or {len(lefts)} right frames, not {len(rights)}")
+    if any(a.dtype != np.uint8 or a.ndim != 2 or a.shape != lefts[0].shape for a in lefts + rights):
+        raise ValueError("the frames must be uint8 images of one shape")
+    return np.ascontiguousarray(np.stack(lefts)), np.ascontiguousarray(np.stack(rights[:len(lefts) - 1]))
+
+
+def _pack_pairs(lefts, rights):
+    lefts = [np.asarray(a) for a in lefts]
+    rights = [np.asarray(a) for a in rights]
+    if len(lefts) != len(rights):
+        raise ValueError("as many left images as right images")
+    if lefts and any(a.dtype != np.uint8 or a.ndim != 2 or a.shape != lefts[0].shape for a in lefts + rights):
+        raise ValueError("the pairs must be uint8 images of one shape")
+    if not lefts:
+        return np.zeros((0, 0, 0), np.uint8), np.zeros((0, 0, 0), np.uint8)
+    return np.ascontiguousarray(np.stack(lefts)), np.ascontiguousarray(np.stack(rights))
+
+
+def stereo_sgbm_batch(lefts, rights, workspace_bytes: int = 0, device: int = -1, **params):
+    """stereo_sgbm over n pairs of one shape in shared launches (ssba_stereo_sgbm_batch).  ``workspace_bytes`` bounds the
+    matcher's volumes (capi.sgbm_pair_bytes per pair; 0: 1 GiB): the pairs run in chunks of capi.sgbm_chunk_pairs.  Returns
+    (disp16 (n, rows, cols) int16, disparity (n, rows, cols) float64), member k bit-equal to stereo_sgbm(lefts[k], rights[k])."""
+    L, R = _pack_pairs(lefts, rights)
+    n, rows, cols = L.shape
+    lib = capi.load()
+    q = capi.sgbm_params(**params)
+    disp16, disparity = np.zeros((n, rows, cols), np.int16), np.zeros((n, rows, cols))
+    u8 = C.POINTER(C.c_uint8)
+    capi.check(lib.ssba_stereo_sgbm_batch(L.ctypes.data_as(u8), R.ctypes.data_as(u8), n, rows, cols, C.byref(q), int(workspace_bytes), device,
+                                          disp16.ctypes.data_as(C.POINTER(C.c_int16)), capi.dptr(disparity)), "ssba_stereo_sgbm_batch")
+    return disp16, disparity
+
+
+class ImageSequence:
+    """A rectified stereo sequence prepared once (ssba_image_sequence_create): every frame goes up once, every left frame's
+    levels, double image and gradients are built once, and the semi-global matcher runs over all pairs (left_k, right_k) in
+    shared launches.  pyramid(k) is the borrowed ImagePyramid of pair k (reference frame k, tracked frame k + 1), bit-equal to
+    ImagePyramid.create_stereo(lefts[k], rights[k], lefts[k + 1], ...); it ends with the sequence."""
+
+    def __init__(self, lefts, rights, levels: int, disparity_level: int = 0, params: dict = None, workspace_bytes: int = 0,
+                 gradient_source: int = capi.GRADIENT_OF_TRACKED, gradient_scale: float = 0.125, camera: dict = None, device: int = -1):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        self._pyramids = {}
+        L, R = pack_frames(lefts, rights)
+        self.frames, self.rows, self.cols = L.shape
+        self.levels, self.disparity_level, self.device = int(levels), int(disparity_level), device
+        self.camera = dict(camera) if camera is not None else None
+        u8 = C.POINTER(C.c_uint8)
+        q = capi.sgbm_params(**(params or {}))
+        capi.check(self.lib.ssba_image_sequence_create(L.ctypes.data_as(u8), R.ctypes.data_as(u8), self.frames, self.rows, self.cols, int(levels),
+                                                       int(disparity_level), C.byref(q), int(workspace_bytes), int(gradient_source),
+                                                       float(gradient_scale), device, C.byref(self.h)), "ssba_image_sequence_create")
+
+    @classmethod
+    def create(cls, lefts, rights, levels: int, **kw):
+        return cls(lefts, rights, levels, **kw)
+
+    @property
+    def num_pairs(self) -> int:
+        return self.frames - 1
+
+    def pyramid(self, k: int) -> ImagePyramid:
+        """The borrowed pyramid of pair k (ssba_image_sequence_pyramid): the same object on every call."""
+        if not self.h:
+            raise ValueError("the sequence is closed")
+        if k not in self._pyramids:
+            h = C.c_void_p()
+            capi.check(self.lib.ssba_image_sequence_pyramid(self.h, int(k), C.byref(h)), "ssba_image_sequence_pyramid")
+            self._pyramids[k] = ImagePyramid._borrow(h.value, self.rows, self.cols, self.levels, self.disparity_level, self.camera, self.device)
+        return self._pyramids[k]
+
+    def pyramids(self):
+        return [self.pyramid(k) for k in range(self.num_pairs)]
+
+    def disparities(self):
+        """The F - 1 maps at disparity_level, downloaded: what align() and a handle's block list need."""
+        return [self.pyramid(k).level(self.disparity_level).disparity for k in range(self.num_pairs)]
+
+    def align(self, poses, disparities=None, coarsest_level: int = None, camera: dict = None, interpolation: int = capi.IMAGE_BILINEAR,
+              disparity_const: bool = False, options: capi.Options = None):
+        """ImagePyramid.align_batch over the borrowed pyramids: ``poses`` (F - 1, 12) and the maps are updated in place
+        (``disparities`` None: the sequence's own maps are downloaded).  Returns (status, summaries, statuses, disparities)."""
+        maps = self.disparities() if disparities is None else list(disparities)
+        rc, sums, sts = ImagePyramid.align_batch(self.pyramids(), poses, maps, coarsest_level, camera if camera is not None else self.camera,
+                                                 interpolation, disparity_const, options)
+        return rc, sums, sts, maps
+
+    def close(self):
+        """ssba_image_sequence_destroy: the borrowed pyramids end here."""
+        if self.h:
+            for p in self._pyramids.values():
+                p.h = C.c_void_p()
+            self._pyramids = {}
+            self.lib.ssba_image_sequence_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -11,7 +11,9 @@
 //            speckle_window_size, speckle_range, full_dp     the matcher's parameters (ssba_sgbm_params)
 //     uint8  left_0, right_0, left_1, right_1, ...      rows * cols each, row-major
 //
-// usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>] [--huber <a>]
+// usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--sequence] [--max-iterations <n>] [--huber <a>]
+// --sequence builds ONE ceres_slam::ImageSequence from the frames instead of F - 1 pyramids: every frame is uploaded and prepared
+// once and the matcher runs over all pairs in shared launches; the pyramids of the pairs are borrowed from it.  Same printed bytes.
 // --sequential aligns the same pairs one by one (ceres::SolveCoarseToFine per pyramid); the printed poses are identical.
 // --huber a puts ceres::HuberLoss(a) on the blocks of every level of every pyramid (ImagePyramid::SetHuberLoss).
 // Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
@@ -27,14 +29,15 @@
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--max-iterations <n>] [--huber <a>]" << std::endl;
+        std::cerr << "usage: dense_stereo_sequence_gpu sequence.raw [--sequential] [--sequence] [--max-iterations <n>] [--huber <a>]" << std::endl;
         return EXIT_FAILURE;
     }
-    bool sequential = false;
+    bool sequential = false, sequence = false;
     int max_iterations = -1;
     double huber_a = 0.0;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--sequential")) sequential = true;
+        else if (!std::strcmp(argv[a], "--sequence")) sequence = true;
         else if (!std::strcmp(argv[a], "--max-iterations") && a + 1 < argc) max_iterations = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--huber") && a + 1 < argc) huber_a = std::atof(argv[++a]);
         else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
@@ -62,15 +65,25 @@ int main(int argc, char **argv) {
 
     const int pairs = frames - 1, coarsest = levels - 1;
     std::vector<std::unique_ptr<ceres_slam::ImagePyramid>> pyramids;
+    std::unique_ptr<ceres_slam::ImageSequence> frames_once;
     std::vector<ceres_slam::ImagePyramid *> pyramid_ptrs;
     std::vector<double *> maps;
     std::vector<double> poses((size_t)pairs * 12);
+    if (sequence) {
+        std::vector<const uint8_t *> lp, rp;
+        for (int k = 0; k < frames; ++k) { lp.push_back(left[k].data()); rp.push_back(right[k].data()); }
+        frames_once.reset(new ceres_slam::ImageSequence(lp, rp, rows, cols, levels, disparity_level, sgbm, head[7], scale_cam[0]));
+    }
     for (int k = 0; k < pairs; ++k) {
-        pyramids.emplace_back(new ceres_slam::ImagePyramid(left[k].data(), right[k].data(), left[k + 1].data(), rows, cols, levels, disparity_level, sgbm,
-                                                           head[7], scale_cam[0]));
-        if (huber_a > 0.0) pyramids.back()->SetHuberLoss(huber_a);
-        pyramid_ptrs.push_back(pyramids.back().get());
-        maps.push_back(pyramids.back()->disparity(disparity_level).data());      // the blocks' memory: the matcher's map, downloaded once
+        if (sequence) {
+            pyramid_ptrs.push_back(&frames_once->pyramid(k));
+        } else {
+            pyramids.emplace_back(new ceres_slam::ImagePyramid(left[k].data(), right[k].data(), left[k + 1].data(), rows, cols, levels, disparity_level, sgbm,
+                                                               head[7], scale_cam[0]));
+            pyramid_ptrs.push_back(pyramids.back().get());
+        }
+        if (huber_a > 0.0) pyramid_ptrs.back()->SetHuberLoss(huber_a);
+        maps.push_back(pyramid_ptrs.back()->disparity(disparity_level).data());      // the blocks' memory: the matcher's map, downloaded once
         std::memcpy(&poses[(size_t)k * 12], start, sizeof start);
     }
     ceres::Solver::Options solver_options;
@@ -80,7 +93,7 @@ int main(int argc, char **argv) {
     if (sequential) {
         for (int k = 0; k < pairs; ++k) {
             std::vector<ceres::Solver::Summary> summaries;
-            ceres::SolveCoarseToFine(solver_options, *pyramids[k], camera0, &poses[(size_t)k * 12], maps[k], coarsest, interpolation, disparities_constant,
+            ceres::SolveCoarseToFine(solver_options, *pyramid_ptrs[k], camera0, &poses[(size_t)k * 12], maps[k], coarsest, interpolation, disparities_constant,
                                      &summaries);
             usable = usable && !summaries.empty() && summaries.back().IsSolutionUsable();
         }

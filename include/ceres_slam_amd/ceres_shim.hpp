@@ -243,6 +243,32 @@ class StereoSGBM {
         Raise("ssba_stereo_sgbm", ssba_stereo_sgbm(left.data, right.data, (uint32_t)left.rows, (uint32_t)left.cols, &params, device, disp.disp16.data(),
                                                    disp.disparity.data()));
     }
+    // n pairs of one size in shared launches (ssba_stereo_sgbm_batch): disp[k] is bit-equal to (*this)(left[k], right[k], disp[k]).
+    // workspace_bytes bounds the matcher's volumes (0: the library's 1 GiB); the pairs run in chunks of as many as fit.
+    void operator()(const std::vector<Image8> &left, const std::vector<Image8> &right, std::vector<DisparityMap> &disp, uint64_t workspace_bytes = 0) const {
+        if (left.size() != right.size()) throw std::invalid_argument("ceres_shim: StereoSGBM needs as many left images as right images");
+        const size_t n = left.size();
+        const int rows = n ? left[0].rows : 0, cols = n ? left[0].cols : 0;
+        for (size_t k = 0; k < n; ++k)
+            if (left[k].rows != rows || left[k].cols != cols || right[k].rows != rows || right[k].cols != cols || rows <= 0 || cols <= 0)
+                throw std::invalid_argument("ceres_shim: StereoSGBM needs pairs of one size");
+        const size_t npix = (size_t)rows * (size_t)cols;
+        std::vector<uint8_t> L(n * npix), R(n * npix);
+        for (size_t k = 0; k < n; ++k) {
+            std::memcpy(L.data() + k * npix, left[k].data, npix);
+            std::memcpy(R.data() + k * npix, right[k].data, npix);
+        }
+        std::vector<int16_t> d16(n * npix);
+        std::vector<double> d(n * npix);
+        Raise("ssba_stereo_sgbm_batch", ssba_stereo_sgbm_batch(L.data(), R.data(), (uint32_t)n, (uint32_t)rows, (uint32_t)cols, &params, workspace_bytes, device,
+                                                               d16.data(), d.data()));
+        disp.resize(n);
+        for (size_t k = 0; k < n; ++k) {
+            disp[k].rows = rows; disp[k].cols = cols;
+            disp[k].disp16.assign(d16.begin() + (std::ptrdiff_t)(k * npix), d16.begin() + (std::ptrdiff_t)((k + 1) * npix));
+            disp[k].disparity.assign(d.begin() + (std::ptrdiff_t)(k * npix), d.begin() + (std::ptrdiff_t)((k + 1) * npix));
+        }
+    }
     static void Raise(const char *call, int rc) {
         if (!rc) return;
         const std::string msg = std::string(call) + ": " + ssba_status_string(rc) + " (" + ssba_last_error() + ")";
@@ -310,6 +336,15 @@ class ImagePyramid {
     }
 
  private:
+    friend class ImageSequence;
+    // a pyramid borrowed from an image sequence (ssba_image_sequence_pyramid): never destroyed here, and `owner` keeps the sequence alive
+    ImagePyramid(ssba_image_pyramid *borrowed, const std::shared_ptr<void> &owner, int rows, int cols, int levels, int disparity_level)
+        : s_(std::make_shared<State>()) {
+        s_->h = borrowed;
+        s_->borrowed = true;
+        s_->owner = owner;
+        Download(rows, cols, levels, disparity_level);
+    }
     struct Level;
     void Download(int rows, int cols, int levels, int disparity_level) {
         s_->disparity_level = disparity_level;
@@ -337,8 +372,73 @@ class ImagePyramid {
         ssba_image_pyramid *h = nullptr;
         int disparity_level = 0;
         std::vector<Level> lv;
-        ~State() { if (h) ssba_image_pyramid_destroy(h); }
+        bool borrowed = false;
+        std::shared_ptr<void> owner;       // released after the body of ~State
+        ~State() { if (h && !borrowed) ssba_image_pyramid_destroy(h); }
     };
+    std::shared_ptr<State> s_;
+};
+
+// A rectified stereo sequence prepared once (ssba_image_sequence_create): F left frames and the right frames 0 ... F - 2, each stack
+// contiguous, rows * cols bytes per frame.  Every frame is uploaded once, every left frame's levels, double image and gradients are
+// built once, and `matcher` runs over the F - 1 pairs (left_k, right_k) in shared launches.  pyramid(k) is the ImagePyramid of pair k
+// (reference frame k, tracked frame k + 1), bit-equal to ImagePyramid(left_k, right_k, left_(k+1), ..., matcher, ...); it is borrowed
+// from the sequence, and it and its images keep the sequence alive.  std::invalid_argument where the C call refuses.
+class ImageSequence {
+ public:
+    ImageSequence(const uint8_t *left, const uint8_t *right, int frames, int rows, int cols, int levels, int disparity_level, const StereoSGBM &matcher,
+                  int gradient_source = SSBA_GRADIENT_OF_REFERENCE, double gradient_scale = 1.0, uint64_t workspace_bytes = 0, int device = -1)
+        : s_(std::make_shared<State>()) {
+        Create(left, right, frames, rows, cols, levels, disparity_level, matcher, gradient_source, gradient_scale, workspace_bytes, device);
+    }
+    // the same from one pointer per frame: right may hold F or F - 1 images
+    ImageSequence(const std::vector<const uint8_t *> &left, const std::vector<const uint8_t *> &right, int rows, int cols, int levels, int disparity_level,
+                  const StereoSGBM &matcher, int gradient_source = SSBA_GRADIENT_OF_REFERENCE, double gradient_scale = 1.0, uint64_t workspace_bytes = 0,
+                  int device = -1)
+        : s_(std::make_shared<State>()) {
+        if (left.size() < 2 || (right.size() != left.size() && right.size() + 1 != left.size()) || rows <= 0 || cols <= 0)
+            throw std::invalid_argument("ceres_shim: ImageSequence needs F >= 2 left frames and F or F - 1 right frames of one size");
+        const size_t npix = (size_t)rows * (size_t)cols, F = left.size();
+        std::vector<uint8_t> L(F * npix), R((F - 1) * npix);
+        for (size_t k = 0; k < F; ++k) {
+            if (!left[k] || (k + 1 < F && !right[k])) throw std::invalid_argument("ceres_shim: ImageSequence: NULL frame");
+            std::memcpy(L.data() + k * npix, left[k], npix);
+            if (k + 1 < F) std::memcpy(R.data() + k * npix, right[k], npix);
+        }
+        Create(L.data(), R.data(), (int)F, rows, cols, levels, disparity_level, matcher, gradient_source, gradient_scale, workspace_bytes, device);
+    }
+    int pairs() const { return (int)s_->pyramids.size(); }
+    ImagePyramid &pyramid(int k) {
+        if (k < 0 || k >= pairs()) throw std::invalid_argument("ceres_shim: ImageSequence: no such pair");
+        return *s_->pyramids[(size_t)k];
+    }
+    std::vector<ImagePyramid *> pyramids() {
+        std::vector<ImagePyramid *> out;
+        for (std::unique_ptr<ImagePyramid> &p : s_->pyramids) out.push_back(p.get());
+        return out;
+    }
+
+ private:
+    struct Handle {
+        ssba_image_sequence *h = nullptr;
+        ~Handle() { if (h) ssba_image_sequence_destroy(h); }
+    };
+    struct State {
+        std::shared_ptr<Handle> seq;
+        std::vector<std::unique_ptr<ImagePyramid>> pyramids;
+    };
+    void Create(const uint8_t *left, const uint8_t *right, int frames, int rows, int cols, int levels, int disparity_level, const StereoSGBM &matcher,
+                int gradient_source, double gradient_scale, uint64_t workspace_bytes, int device) {
+        s_->seq = std::make_shared<Handle>();
+        StereoSGBM::Raise("ssba_image_sequence_create",
+                          ssba_image_sequence_create(left, right, (uint32_t)frames, (uint32_t)rows, (uint32_t)cols, (uint32_t)levels, (uint32_t)disparity_level,
+                                                     &matcher.params, workspace_bytes, gradient_source, gradient_scale, device, &s_->seq->h));
+        for (int k = 0; k + 1 < frames; ++k) {
+            ssba_image_pyramid *h = nullptr;
+            StereoSGBM::Raise("ssba_image_sequence_pyramid", ssba_image_sequence_pyramid(s_->seq->h, (uint32_t)k, &h));
+            s_->pyramids.emplace_back(new ImagePyramid(h, s_->seq, rows, cols, levels, disparity_level));
+        }
+    }
     std::shared_ptr<State> s_;
 };
 

@@ -719,6 +719,45 @@ SSBA_API int ssba_image_pyramid_create_stereo(const uint8_t *ref_left_u8, const 
                                      uint32_t cols, uint32_t levels, uint32_t disparity_level, const ssba_sgbm_params *params,
                                      int gradient_source, double gradient_scale, int device, ssba_image_pyramid **out);
 
+/* ---- stereo sequences: every frame prepared once, the matcher batched over the pairs ---------- */
+/* ssba_stereo_sgbm_batch is ssba_stereo_sgbm over n pairs of one size: left and right hold n images of rows x cols each, one
+ * after the other; disp16_out and disparity_out (either may be NULL) receive n maps in the same order.  Member k is bit-equal
+ * to the solo call on pair k: the kernels are the solo kernels' bodies with the pair as one more grid dimension, integer
+ * throughout.  Both image stacks go up in one copy each and the maps come down in one.
+ * workspace_bytes bounds the matcher's volumes, 12 bytes per (row, computable column, disparity) and pair, i.e.
+ * 12 * rows * (cols - min_disparity - num_disparities) * num_disparities bytes per pair: the pairs are processed in chunks of
+ * as many pairs as fit (at most 65535), five launches per chunk on one stream.  0 stands for the library's default,
+ * SSBA_SGBM_DEFAULT_WORKSPACE_BYTES = 1 GiB: a choice, half of what the pool caches by default, so that a long sequence
+ * neither holds the device's memory nor loses its buffers between calls.  The per-pixel arrays and the images are not counted.
+ * Refusals: every one of ssba_stereo_sgbm with the same status, before a device is looked for; SSBA_ERR_INVALID_ARGUMENT also
+ * for n = 0 and for a workspace_bytes below one pair's volumes (the message names the bytes needed).
+ *
+ * ssba_image_sequence_create prepares F = frames rectified stereo frames of one size for the F - 1 alignments of consecutive
+ * left frames: pair k has reference left_k, tracked left_(k+1) and the disparities of (left_k, right_k).  left holds F images,
+ * right F - 1 at least (frames 0 ... F - 2; only those are read).  Every image goes up once, in one copy.  Per left frame all
+ * levels are built once: the 8-bit image, the double image and both Sobel images (the arithmetic of ssba_image_pyramid_create);
+ * per right frame the 8-bit levels down to disparity_level.  The matcher runs over the F - 1 pairs at disparity_level as
+ * ssba_stereo_sgbm_batch does under workspace_bytes, its double maps stay on the device, and the coarser maps follow by the
+ * rule above.  One level of all frames is one launch of each kind: 2 levels + 4 launches in all while the pairs fit one chunk,
+ * whatever F, and one synchronisation.  Refusals: those of ssba_image_pyramid_create_stereo and of ssba_stereo_sgbm_batch at the
+ * size of disparity_level, frames < 2, frames > 32768.
+ * ssba_image_sequence_pyramid hands out the pyramid of pair k < F - 1, bit-equal in every level and image to
+ * ssba_image_pyramid_create_stereo on left_k, right_k, left_(k+1) (gradients of frame k or k + 1 according to gradient_source).
+ * It is BORROWED: its levels point into the sequence's buffers and it owns no device memory.  Every pyramid call takes it
+ * (level, add_image_level, set_huber_loss, align, align_batch) except ssba_image_pyramid_destroy, which refuses it with
+ * SSBA_ERR_INVALID_ARGUMENT and leaves it usable; it ends with the sequence and must not be touched afterwards.  A handle that
+ * was finalized from one of its levels holds copies of the images and outlives the sequence.  The same k gives the same pointer.
+ * ssba_image_sequence_destroy frees the sequence and its borrowed pyramids. */
+#define SSBA_SGBM_DEFAULT_WORKSPACE_BYTES (1ull << 30)
+typedef struct ssba_image_sequence ssba_image_sequence;
+SSBA_API int ssba_stereo_sgbm_batch(const uint8_t *left, const uint8_t *right, uint32_t n, uint32_t rows, uint32_t cols,
+                           const ssba_sgbm_params *params, uint64_t workspace_bytes, int device, int16_t *disp16_out, double *disparity_out);
+SSBA_API int ssba_image_sequence_create(const uint8_t *left, const uint8_t *right, uint32_t frames, uint32_t rows, uint32_t cols, uint32_t levels,
+                               uint32_t disparity_level, const ssba_sgbm_params *params, uint64_t workspace_bytes, int gradient_source,
+                               double gradient_scale, int device, ssba_image_sequence **out);
+SSBA_API int ssba_image_sequence_pyramid(ssba_image_sequence *seq, uint32_t k, ssba_image_pyramid **out);
+SSBA_API int ssba_image_sequence_destroy(ssba_image_sequence *seq);
+
 /* ---- front end: the VO initial guess --------------------------------- */
 /* ssba_frontend_ransac replaces, for `num_pairs` pairs of consecutive states at once,
  *   PointCloudAligner::compute_transformation_and_inliers (src/ceres_slam/point_cloud_aligner.cpp:64-136)

@@ -1879,11 +1879,7 @@ static int refinalize_without_wide(ssba_problem *p, const char *what) {
                   "before the first solve, or set SSBA_NO_WIDE=1)");
         return SSBA_ERR_STATE;
     }
-    const double nf = (double)p->free_pose.size();
-    const double dn_gb = (6.0 * nf + 2 * DN_BS) * (6.0 * nf + DN_BS) * 8.0 / 1e9;
-    const char *mg = getenv("SSBA_DENSE_MAX_GB");
-    const double dn_cap = mg ? atof(mg) : 160.0;
-    if (p->world_size > 1 || dn_gb > dn_cap || (6 * (long)p->free_pose.size() + DN_BS) / DN_BS >= 65535) {
+    if (!dense_system_fits((long)p->free_pose.size(), p->world_size)) {
         set_error(std::string(what) + ": needs the blocked Cholesky of the general path (single GPU, reduced system within SSBA_DENSE_MAX_GB)");
         return SSBA_ERR_UNSUPPORTED;
     }
@@ -1899,12 +1895,10 @@ static int refinalize_without_closure_border(ssba_problem *p, const char *what) 
                   "folded into a border of the chain at ssba_finalize; ask before the first solve, or set SSBA_NO_CLOSURE_BORDER=1)");
         return SSBA_ERR_STATE;
     }
-    // the general layout must fit BEFORE anything of the working layout is torn down (same test as ssba_finalize)
-    const double nf = (double)p->free_pose.size();
-    const double dn_gb = (6.0 * nf + 2 * DN_BS) * (6.0 * nf + DN_BS) * 8.0 / 1e9;
-    const char *mg = getenv("SSBA_DENSE_MAX_GB");
-    const double dn_cap = mg ? atof(mg) : 160.0;
-    if (dn_gb > dn_cap || (6 * (long)p->free_pose.size() + DN_BS) / DN_BS >= 65535) {
+    // the general layout must fit BEFORE anything of the working layout is torn down.  World size 1: this hand-over has never
+    // tested it here (a closure border is not built on a sharded handle; the layout builder refuses one when it runs again)
+    double dn_gb, dn_cap;
+    if (!dense_system_fits((long)p->free_pose.size(), 1, &dn_gb, &dn_cap)) {
         char buf[320];
         snprintf(buf, sizeof buf, "%s: not available on the closure border, and the general layout it would need holds a %.1f GB reduced "
                  "system (SSBA_DENSE_MAX_GB = %.0f): the handle keeps its closure-border layout (LM solves still work)", what, dn_gb, dn_cap);
@@ -1943,6 +1937,27 @@ static int refinalize_without_pose_only(ssba_problem *p, const char *what) {
         return rc2 ? rc2 : rc;
     }
     return rc;
+}
+
+// What every begin has in common (a solve, a test hook, an image step, a pose-only covariance request): the options become the
+// handle's, the caller's parameter blocks go to the device and are kept as the point to restart from, the solver state is reset.
+static int begin_common(ssba_problem *p, const ssba_options &opt, int ignore_convergence, int log_capacity) {
+    HIPCHECK(hipSetDevice(p->device));
+    p->opt = opt;
+    p->ignore_convergence = ignore_convergence;
+    p->d.huber_a = p->huber_a;
+    int rc = ensure_log(p, log_capacity);
+    if (rc) return rc;
+    if ((rc = upload_params(p))) return rc;
+    Dev &d = p->d;
+    hipStream_t s = p->launcher.stream;
+    HIPCHECK(hipMemcpyAsync(d.init_poses, d.poses, (size_t)d.P * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(hipMemcpyAsync(d.init_pts, d.pts, (size_t)d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (d.phong) {
+        HIPCHECK(hipMemcpyAsync(d.init_nrm, d.nrm, (size_t)d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIPCHECK(hipMemcpyAsync(d.init_sh, d.sh, (size_t)d.nsh * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    return reset_solver(p);
 }
 
 int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_convergence) {
@@ -1987,28 +2002,11 @@ int ssba_solve_begin(ssba_problem *p, const ssba_options *o, int ignore_converge
         if (p->xfn) rounds = 0;     // landmark sharding: every evaluation has an exchange in it, the host drives the search (finish_pending_search)
         if (rounds != p->d.ls_rounds) { p->d.ls_rounds = rounds; drop_graph(p); }
     }
-    HIPCHECK(hipSetDevice(p->device));
-    p->opt = *o;
-    p->ignore_convergence = ignore_convergence;
-    p->d.huber_a = p->huber_a;
-    int cap = o->max_num_iterations + 4;
-    if (cap > (1 << 20)) cap = 1 << 20;
-    int rc = ensure_log(p, cap);
-    if (rc) return rc;
     p->t_begin = std::chrono::steady_clock::now();
     p->num_line_search_steps = p->num_line_searches_by_host = 0;
-    rc = upload_params(p);
+    const int rc = begin_common(p, *o, ignore_convergence, std::min(o->max_num_iterations + 4, 1 << 20));
     if (rc) return rc;
-    hipStream_t s = p->launcher.stream;
-    HIPCHECK(hipMemcpyAsync(p->d.init_poses, p->d.poses, (size_t)p->d.P * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(p->d.init_pts, p->d.pts, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (p->d.phong) {
-        HIPCHECK(hipMemcpyAsync(p->d.init_nrm, p->d.nrm, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-        HIPCHECK(hipMemcpyAsync(p->d.init_sh, p->d.sh, (size_t)p->d.nsh * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    rc = reset_solver(p);
-    if (rc) return rc;
-    HIPCHECK(hipEventRecord(p->ev_begin, s));
+    HIPCHECK(hipEventRecord(p->ev_begin, p->launcher.stream));
     p->began = true;
     p->solved_once = true;
     return SSBA_OK;
@@ -2506,7 +2504,6 @@ static int begin_hook(ssba_problem *p, const ssba_options *o, double radius) {
         if (rc) return rc;
     }
     p->step_hook_done = false;
-    HIPCHECK(hipSetDevice(p->device));
     ssba_options opt;
     if (o) opt = *o; else ssba_default_options(&opt);
     if (radius > 0.0) opt.initial_trust_region_radius = radius;
@@ -2516,21 +2513,7 @@ static int begin_hook(ssba_problem *p, const ssba_options *o, double radius) {
     }
     if (p->opt.trust_region_strategy_type != opt.trust_region_strategy_type)
         drop_graph(p);   // other kernel sequence (as in ssba_solve_begin)
-    p->opt = opt;
-    p->ignore_convergence = 1;
-    p->d.huber_a = p->huber_a;
-    int rc = ensure_log(p, 16);
-    if (rc) return rc;
-    rc = upload_params(p);
-    if (rc) return rc;
-    hipStream_t s = p->launcher.stream;
-    HIPCHECK(hipMemcpyAsync(p->d.init_poses, p->d.poses, (size_t)p->d.P * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(p->d.init_pts, p->d.pts, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (p->d.phong) {
-        HIPCHECK(hipMemcpyAsync(p->d.init_nrm, p->d.nrm, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-        HIPCHECK(hipMemcpyAsync(p->d.init_sh, p->d.sh, (size_t)p->d.nsh * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    return reset_solver(p);
+    return begin_common(p, opt, 1, 16);
 }
 
 int ssba_evaluate(ssba_problem *p, double *cost, double *g_p, double *g_l, double *H_pp, double *H_ll) {
@@ -2892,6 +2875,29 @@ struct CallBuffers {
 };
 }  // namespace
 
+// The end of a covariance sweep: what was enqueued has run, and the undamped reduced system could be factored.
+static int sweep_done(ssba_problem *p) {
+    HIPCHECK(hipStreamSynchronize(p->launcher.stream));
+    HIPCHECK(hipGetLastError());
+    if (int rc = fetch_state(p)) return rc;
+    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    return SSBA_OK;
+}
+
+// Windowed layout: the multi-right-hand-side buffers are only allocated with a border; the first covariance request adds them.
+static int ensure_multi_rhs_buffers(ssba_problem *p) {
+    Dev &d = p->d;
+    if (d.Spb) return SSBA_OK;
+    drop_graph(p);
+    int rc;
+    if ((rc = dzero(p, &d.Spb, (size_t)d.nf_pad * 6 * NBP))) return rc;
+    if ((rc = dzero(p, &d.Zb, (size_t)d.nf_pad * 6 * NBP))) return rc;
+    for (int l = 0; l < d.n_levels; ++l)
+        if ((rc = dzero(p, &d.lev[l].B, (size_t)d.lev[l].n * BD * NBP))) return rc;
+    if (configure_border()) { set_error("hipFuncSetAttribute(border kernels) failed"); return SSBA_ERR_HIP; }
+    return SSBA_OK;
+}
+
 // Covariance on a wide handle whose first solve has begun (ssba_wide_covariance.hip).  The panel buffers of the reduction are
 // added by the first request (as d.Spb is on a windowed handle without a border).
 static int wide_panel_ready(ssba_problem *p) {
@@ -2923,35 +2929,44 @@ static int wide_cov_sweep(ssba_problem *p, const int *free_pose, int nq, double 
     launch_dense_schur(L, d);
     launch_finish_check(L, d);
     launch_wide_solve_panel(L, d, free_pose, nq, cols, nrow, col0);
-    HIPCHECK(hipStreamSynchronize(L.stream));
-    HIPCHECK(hipGetLastError());
-    if ((rc = fetch_state(p))) return rc;
-    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
-    return SSBA_OK;
+    return sweep_done(p);
 }
 
-// ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block (tests/dataset_vo_sun.cpp:159-183):
-// the pose's 6x6 block of (J^T J)^-1 in local coordinates = the same block of the inverse of the (undamped) reduced
-// camera system.  Six unit right-hand sides go through the block-cyclic-reduction factors of S.
 // Image handle, one linearisation at the caller's current pose and disparities.  The hook returns what the kernels of an
 // iteration left; the covariance inverts the undamped 6 x 6 sum J^T J (constant disparities only).
 static int image_begin(ssba_problem *p, const ssba_options *o, double radius) {
     if (p->began) return SSBA_ERR_STATE;
-    HIPCHECK(hipSetDevice(p->device));
     ssba_options opt;
     if (o) opt = *o; else ssba_default_options(&opt);
     if (radius > 0.0) opt.initial_trust_region_radius = radius;
     opt.trust_region_strategy_type = 0;
-    p->opt = opt;
-    p->ignore_convergence = 1;
-    p->d.huber_a = p->huber_a;
-    int rc = ensure_log(p, 16);
-    if (rc) return rc;
-    if ((rc = upload_params(p))) return rc;
+    return begin_common(p, opt, 1, 16);      // (Dev::P is 1 on an image handle: finalize_image)
+}
+
+// Pose-only and image handles: the undamped 6 x 6 blocks Dev::hpp of n poses (null: pose 0 alone, the image handle's), as the
+// linearisation just enqueued leaves them, inverted in one launch (k_po_cov) into out, 36 doubles each.  A block that is not
+// positive definite is SSBA_ERR_NUMERICAL_FAILURE with the caller's message.
+static int invert_pose_blocks(ssba_problem *p, const int *poses, size_t n, double *out, const char *not_positive_definite) {
     hipStream_t s = p->launcher.stream;
-    HIPCHECK(hipMemcpyAsync(p->d.init_poses, p->d.poses, 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(p->d.init_pts, p->d.pts, (size_t)p->d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return reset_solver(p);
+    CallBuffers B;
+    int *d_poses = nullptr, *d_fail = nullptr;
+    double *d_out = nullptr;
+    HIPCHECK(B.get((void **)&d_poses, n * sizeof(int)));
+    HIPCHECK(B.get((void **)&d_fail, sizeof(int)));
+    HIPCHECK(B.get((void **)&d_out, n * 36 * sizeof(double)));
+    if (poses) HIPCHECK(hipMemcpyAsync(d_poses, poses, n * sizeof(int), hipMemcpyHostToDevice, s));
+    else HIPCHECK(hipMemsetAsync(d_poses, 0, n * sizeof(int), s));
+    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), s));
+    HIPCHECK(hipMemsetAsync(d_out, 0, n * 36 * sizeof(double), s));
+    if (poses) HIPCHECK(hipStreamSynchronize(s));      // (the index list is pageable memory)
+    launch_pose_only_cov(p->launcher, p->d, d_poses, (int)n, d_out, d_fail);
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    int fail = 0;
+    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
+    if (fail) { set_error(not_positive_definite); return SSBA_ERR_NUMERICAL_FAILURE; }
+    HIPCHECK(hipMemcpy(out, d_out, n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+    return SSBA_OK;
 }
 
 static int image_pose_covariance(ssba_problem *p, double cov[36]) {
@@ -2961,26 +2976,8 @@ static int image_pose_covariance(ssba_problem *p, double cov[36]) {
     }
     int rc = image_begin(p, nullptr, 0.0);
     if (rc) return rc;
-    Dev &d = p->d;
-    Launcher &L = p->launcher;
-    launch_image_lin_solve(L, d);
-    CallBuffers B;
-    int *d_pose = nullptr, *d_fail = nullptr;
-    double *d_out = nullptr;
-    HIPCHECK(B.get((void **)&d_pose, sizeof(int)));
-    HIPCHECK(B.get((void **)&d_fail, sizeof(int)));
-    HIPCHECK(B.get((void **)&d_out, 36 * sizeof(double)));
-    HIPCHECK(hipMemsetAsync(d_pose, 0, sizeof(int), L.stream));
-    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), L.stream));
-    HIPCHECK(hipMemsetAsync(d_out, 0, 36 * sizeof(double), L.stream));
-    launch_pose_only_cov(L, d, d_pose, 1, d_out, d_fail);     // inverts Dev::hpp of pose 0
-    HIPCHECK(hipStreamSynchronize(L.stream));
-    HIPCHECK(hipGetLastError());
-    int fail = 0;
-    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
-    if (fail) { set_error("covariance: the sum J^T J of the image blocks is not positive definite"); return SSBA_ERR_NUMERICAL_FAILURE; }
-    HIPCHECK(hipMemcpy(cov, d_out, 36 * sizeof(double), hipMemcpyDeviceToHost));
-    return SSBA_OK;
+    launch_image_lin_solve(p->launcher, p->d);
+    return invert_pose_blocks(p, nullptr, 1, cov, "covariance: the sum J^T J of the image blocks is not positive definite");
 }
 
 int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, double *cost, double *residuals, double *J_pose, double *J_disp,
@@ -3026,6 +3023,88 @@ int ssba_image_step(ssba_problem *p, const ssba_options *o, double radius, doubl
     return SSBA_OK;
 }
 
+// Columns of Sigma = S^-1, S the undamped reduced camera system at the current parameters (radius -> infinity), for the free
+// poses slot_pose[0 .. nslots): column c of pose slot_pose[s] is column 6 s + c of *cols, nrow rows each, a buffer of B.  One
+// loop per layout; pose q of a sweep has its unit right-hand sides in the sweep's columns 6 q .. 6 q + 5:
+//   windowed     NBP / 6 = 5 poses per multi-right-hand-side sweep through the block-cyclic-reduction factors of every level.  si
+//                (ssba_covariance_blocks): the selected inversion of those factors is enqueued before the sweeps.  Nothing is
+//                awaited: the caller's sweep_done() tells whether S could be factored.
+//   solved wide  WPC / 6 = 8 poses per sweep of its own reduction (wide_cov_sweep)
+//   general      DN_BS / 6 = 10 poses per blocked Cholesky solve: unit entries in the right-hand-side rows of dn_S, forward-solved
+//                with the factorisation, then one back-substitution sweep per row
+// The last two assemble, factor and check S in every sweep, and once when no column is needed.
+static int sigma_columns(ssba_problem *p, CallBuffers &B, const int *slot_pose, int nslots, double **cols, long *nrow, const SelInv *si) {
+    Dev &d = p->d;
+    Launcher &L = p->launcher;
+    int rc;
+    ssba_options o;
+    ssba_default_options(&o);
+    if (!d.dense) {
+        if (nslots && (rc = ensure_multi_rhs_buffers(p))) return rc;
+        if ((rc = begin_hook(p, &o, 1e300))) return rc;        // radius -> infinity: no Levenberg-Marquardt damping in S
+        launch_linearize(L, d);
+        launch_schur(L, d);
+        launch_finish_check(L, d);
+        launch_bcr(L, d, false);       // the selected inversion and the sweeps need the factors of every level
+        if (si) launch_selinv(L, d, *si);
+        *nrow = (long)d.nf_pad * 6;
+        if (!nslots) return SSBA_OK;
+        HIPCHECK(B.get((void **)cols, ((size_t)nslots * 6 * *nrow) * sizeof(double)));
+        constexpr int PER = NBP / 6;
+        std::vector<double> unit((size_t)PER * 6 * NBP, 0.0);
+        for (int s0 = 0; s0 < nslots; s0 += PER) {
+            const int nq = std::min(PER, nslots - s0);
+            HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
+            std::fill(unit.begin(), unit.end(), 0.0);
+            for (int q = 0; q < nq; ++q) {
+                for (int c = 0; c < 6; ++c) unit[(size_t)q * 6 * NBP + (size_t)c * NBP + 6 * q + c] = 1.0;
+                HIPCHECK(hipMemcpyAsync(d.Spb + (size_t)slot_pose[s0 + q] * 6 * NBP, unit.data() + (size_t)q * 6 * NBP,
+                                        (size_t)6 * NBP * sizeof(double), hipMemcpyHostToDevice, L.stream));
+            }
+            HIPCHECK(hipStreamSynchronize(L.stream));
+            launch_bcr_multi_rhs(L, d);
+            launch_cov_gather(L, d.Zb, *cols, s0, nq, *nrow);
+        }
+        HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
+    } else if (d.wide) {
+        if ((rc = wide_panel_ready(p))) return rc;
+        *nrow = (long)L.wide.n * WBD;
+        HIPCHECK(B.get((void **)cols, ((size_t)std::max(nslots, 1) * 6 * *nrow) * sizeof(double)));
+        constexpr int PER = WPC / 6;
+        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {
+            const int nq = std::max(0, std::min(PER, nslots - s0));
+            if ((rc = wide_cov_sweep(p, slot_pose + s0, nq, *cols, *nrow, 6 * s0))) return rc;
+        }
+    } else {
+        const size_t lda = (size_t)d.dn_pad;
+        *nrow = (long)lda;
+        HIPCHECK(B.get((void **)cols, ((size_t)std::max(nslots, 1) * 6 * lda) * sizeof(double)));
+        constexpr int PER = DN_BS / 6;
+        const double one = 1.0;
+        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {
+            const int nq = std::min(PER, nslots - s0);
+            if ((rc = begin_hook(p, &o, 1e300))) return rc;
+            launch_linearize(L, d);
+            launch_dense_schur(L, d);
+            HIPCHECK(hipMemsetAsync(d.dn_S + lda * lda, 0, (size_t)DN_BS * lda * sizeof(double), L.stream));
+            for (int q = 0; q < nq; ++q)
+                for (int c = 0; c < 6; ++c)
+                    HIPCHECK(hipMemcpyAsync(d.dn_S + (lda + 6 * q + c) * lda + (size_t)slot_pose[s0 + q] * 6 + c, &one, sizeof one,
+                                            hipMemcpyHostToDevice, L.stream));
+            launch_finish_check(L, d);
+            launch_dense_solve(L, d, std::max(1, 6 * nq));
+            if (nq > 0)
+                HIPCHECK(hipMemcpyAsync(*cols + (size_t)s0 * 6 * lda, d.dn_S + lda * lda, (size_t)nq * 6 * lda * sizeof(double),
+                                        hipMemcpyDeviceToDevice, L.stream));
+            if ((rc = sweep_done(p))) return rc;
+        }
+    }
+    return SSBA_OK;
+}
+
+// ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for one pose block (tests/dataset_vo_sun.cpp:159-183):
+// the pose's 6x6 block of (J^T J)^-1 in local coordinates = the same block of the inverse of the (undamped) reduced
+// camera system: the pose's six columns of Sigma from the sweep routine above.
 int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     ApiTimer api_timer("ssba_pose_covariance");
     if (!p || !cov || pose >= p->P) return SSBA_ERR_INVALID_ARGUMENT;
@@ -3053,98 +3132,26 @@ int ssba_pose_covariance(ssba_problem *p, uint32_t pose, double cov[36]) {
     const int f = p->pose_free[pose];
     if (f < 0) { set_error("covariance of a constant pose"); return SSBA_ERR_INVALID_ARGUMENT; }
     Dev &d = p->d;
+    if (d.wide && (p->world_size > 1 || p->xfn)) { set_error("covariance: not available on landmark-sharded problems"); return SSBA_ERR_UNSUPPORTED; }
+    // the sweep routine of ssba_covariance_blocks for this one pose, without the selected inversion
     int rc;
-    if (d.wide) {       // a solved wide handle: one sweep of six unit columns through its own reduction
-        if (p->world_size > 1 || p->xfn) { set_error("covariance: not available on landmark-sharded problems"); return SSBA_ERR_UNSUPPORTED; }
-        if ((rc = wide_panel_ready(p))) return rc;
-        const long nrow = (long)p->launcher.wide.n * WBD;
-        CallBuffers B;
-        double *cols = nullptr;
-        HIPCHECK(B.get((void **)&cols, (size_t)6 * nrow * sizeof(double)));
-        if ((rc = wide_cov_sweep(p, &f, 1, cols, nrow, 0))) return rc;
-        for (int c = 0; c < 6; ++c) {
-            double col[6];
-            HIPCHECK(hipMemcpy(col, cols + (size_t)c * nrow + (size_t)f * 6, sizeof col, hipMemcpyDeviceToHost));
-            for (int r = 0; r < 6; ++r) cov[6 * r + c] = col[r];
-        }
-        return SSBA_OK;
-    }
-    if (d.dense) {
-        // general layout: the six unit vectors go into rows 0..5 of the right-hand-side block row, the blocked
-        // Cholesky forward-solves them with the factorisation, then one back-substitution sweep per row
-        ssba_options o;
-        ssba_default_options(&o);
-        if ((rc = begin_hook(p, &o, 1e300))) return rc;
-        Launcher &L = p->launcher;
-        launch_linearize(L, d);
-        launch_dense_schur(L, d);
-        const size_t lda = (size_t)d.dn_pad;
-        HIPCHECK(hipMemsetAsync(d.dn_S + lda * lda, 0, (size_t)DN_BS * lda * sizeof(double), L.stream));
-        const double one = 1.0;
-        for (int c = 0; c < 6; ++c)
-            HIPCHECK(hipMemcpyAsync(d.dn_S + (lda + c) * lda + (size_t)f * 6 + c, &one, sizeof one, hipMemcpyHostToDevice, L.stream));
-        launch_finish_check(L, d);
-        launch_dense_solve(L, d, 6);
-        HIPCHECK(hipStreamSynchronize(L.stream));
-        HIPCHECK(hipGetLastError());
-        if ((rc = fetch_state(p))) return rc;
-        if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
-        for (int c = 0; c < 6; ++c) {
-            double col[6];
-            HIPCHECK(hipMemcpy(col, d.dn_S + (lda + c) * lda + (size_t)f * 6, sizeof col, hipMemcpyDeviceToHost));
-            for (int r = 0; r < 6; ++r) cov[6 * r + c] = col[r];
-        }
-        return SSBA_OK;
-    }
-    if (!d.Spb) {      // multi-right-hand-side buffers are only allocated with a border: add them now
-        drop_graph(p);
-        if ((rc = dzero(p, &d.Spb, (size_t)d.nf_pad * 6 * NBP))) return rc;
-        if ((rc = dzero(p, &d.Zb, (size_t)d.nf_pad * 6 * NBP))) return rc;
-        for (int l = 0; l < d.n_levels; ++l)
-            if ((rc = dzero(p, &d.lev[l].B, (size_t)d.lev[l].n * BD * NBP))) return rc;
-        if (configure_border()) { set_error("hipFuncSetAttribute(border kernels) failed"); return SSBA_ERR_HIP; }
-    }
-    ssba_options o;
-    ssba_default_options(&o);
-    rc = begin_hook(p, &o, 1e300);        // radius -> infinity: no Levenberg-Marquardt damping in S
-    if (rc) return rc;
-    Launcher &L = p->launcher;
-    launch_linearize(L, d);
-    launch_schur(L, d);
-    launch_finish_check(L, d);
-    launch_bcr(L, d, false);       // the multi-right-hand-side sweeps need the factors of every level
-    HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
-    {
-        std::vector<double> unit((size_t)6 * NBP, 0.0);
-        for (int c = 0; c < 6; ++c) unit[(size_t)c * NBP + c] = 1.0;
-        HIPCHECK(hipMemcpyAsync(d.Spb + (size_t)f * 6 * NBP, unit.data(), unit.size() * sizeof(double), hipMemcpyHostToDevice, L.stream));
-        HIPCHECK(hipStreamSynchronize(L.stream));
-    }
-    launch_bcr_multi_rhs(L, d);
-    HIPCHECK(hipStreamSynchronize(L.stream));
-    HIPCHECK(hipGetLastError());
-    if ((rc = fetch_state(p))) return rc;
-    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
-    std::vector<double> z((size_t)6 * NBP);
-    HIPCHECK(hipMemcpy(z.data(), d.Zb + (size_t)f * 6 * NBP, z.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) cov[6 * r + c] = z[(size_t)r * NBP + c];
-    HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
+    CallBuffers B;
+    double *cols = nullptr;
+    long nrow = 0;
+    if ((rc = sigma_columns(p, B, &f, 1, &cols, &nrow, nullptr))) return rc;
+    if (!d.dense && (rc = sweep_done(p))) return rc;      // (the windowed sweeps are not awaited there)
+    double col[6][6];       // rows 6 f .. 6 f + 5 of the six columns
+    HIPCHECK(hipMemcpy2D(col, sizeof col[0], cols + (size_t)f * 6, (size_t)nrow * sizeof(double), sizeof col[0], 6, hipMemcpyDeviceToHost));
+    for (int c = 0; c < 6; ++c)
+        for (int r = 0; r < 6; ++r) cov[6 * r + c] = col[c][r];
     return SSBA_OK;
 }
 
-// ceres::Covariance for any (pose | point, pose | point) pairs (include/ssba.h).  Windowed layout: the band of Sigma from one
-// selected inversion of the kept factors (ssba_covariance.hip), columns of Sigma from multi-right-hand-side sweeps for the
-// poses whose blocks lie outside it; general layout: columns of Sigma for every pose the request touches, DN_BS / 6 poses
-// per blocked Cholesky solve; a wide handle that has been solved: the same columns, 8 poses per sweep of its parallel cyclic
-// reduction (ssba_wide_covariance.hip).  The landmark blocks follow from those in one launch.
 // Pose-only layout: every point is constant, the reduced system is block diagonal.  A (pose, pose) block of one free pose is
 // the inverse of its undamped 6 x 6 block (k_po_step at the current poses leaves H_pp, k_po_cov inverts), every other block is
 // zero.  A block that is not positive definite (a pose with one or two observations): SSBA_ERR_NUMERICAL_FAILURE.
 static int pose_only_covariance(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
     if (p->began) return SSBA_ERR_STATE;
-    Dev &d = p->d;
-    Launcher &L = p->launcher;
     std::vector<uint64_t> off(num + 1, 0);
     for (uint64_t q = 0; q < num; ++q)
         off[q + 1] = off[q] + (blocks[q].kind_a == SSBA_COV_POINT ? 3 : 6) * (blocks[q].kind_b == SSBA_COV_POINT ? 3 : 6);
@@ -3158,43 +3165,23 @@ static int pose_only_covariance(ssba_problem *p, const ssba_cov_block *blocks, u
         where.push_back(off[q]);
     }
     if (poses.empty()) return SSBA_OK;
-    HIPCHECK(hipSetDevice(p->device));
     ssba_options o;
     ssba_default_options(&o);
-    p->opt = o;
-    p->ignore_convergence = 1;
-    d.huber_a = p->huber_a;
-    int rc = ensure_log(p, 16);
+    int rc = begin_common(p, o, 1, 16);
     if (rc) return rc;
-    if ((rc = upload_params(p))) return rc;
-    hipStream_t s = L.stream;
-    HIPCHECK(hipMemcpyAsync(d.init_poses, d.poses, (size_t)d.P * 12 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(d.init_pts, d.pts, (size_t)d.Lpad * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if ((rc = reset_solver(p))) return rc;
-    launch_pose_only_step(L, d);
-    CallBuffers B;
-    int *d_poses = nullptr, *d_fail = nullptr;
-    double *d_out = nullptr;
-    HIPCHECK(B.get((void **)&d_poses, poses.size() * sizeof(int)));
-    HIPCHECK(B.get((void **)&d_fail, sizeof(int)));
-    HIPCHECK(B.get((void **)&d_out, poses.size() * 36 * sizeof(double)));
-    HIPCHECK(hipMemcpyAsync(d_poses, poses.data(), poses.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(d_fail, 0, sizeof(int), s));
-    HIPCHECK(hipMemsetAsync(d_out, 0, poses.size() * 36 * sizeof(double), s));
-    HIPCHECK(hipStreamSynchronize(s));      // (the index list is pageable memory)
-    launch_pose_only_cov(L, d, d_poses, (int)poses.size(), d_out, d_fail);
-    HIPCHECK(hipStreamSynchronize(s));
-    HIPCHECK(hipGetLastError());
-    int fail = 0;
-    HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
-    if (fail) { set_error("covariance: the 6 x 6 block of a requested pose is not positive definite (too few observations?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    launch_pose_only_step(p->launcher, p->d);
     std::vector<double> h(poses.size() * 36);
-    HIPCHECK(hipMemcpy(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if ((rc = invert_pose_blocks(p, poses.data(), poses.size(), h.data(),
+                                 "covariance: the 6 x 6 block of a requested pose is not positive definite (too few observations?)"))) return rc;
     for (size_t i = 0; i < poses.size(); ++i) memcpy(out + where[i], &h[36 * i], 36 * sizeof(double));
     drop_graph(p);      // (huber_a / options are kernel arguments of a captured graph)
     return SSBA_OK;
 }
 
+// ceres::Covariance for any (pose | point, pose | point) pairs (include/ssba.h).  Windowed layout: the band of Sigma from one
+// selected inversion of the kept factors (ssba_covariance.hip), columns of Sigma for the poses whose blocks lie outside it;
+// general layout and a wide handle that has been solved: columns of Sigma for every pose the request touches (sigma_columns
+// above).  The landmark blocks follow from those in one launch.
 int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64_t num, double *out) {
     ApiTimer api_timer("ssba_covariance_blocks");
     if (int irc = refuse_on_image(p, "ssba_covariance_blocks")) return irc;
@@ -3315,91 +3302,20 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
     int *d_fail = nullptr, *d_slot = nullptr;
     CovJob *d_jobs = nullptr;
     CovSrc src{};
-    ssba_options o;
-    ssba_default_options(&o);
-    if (!dense) {
-        if (nslots && !d.Spb) {      // multi-right-hand-side buffers are only allocated with a border: add them now
-            drop_graph(p);
-            if ((rc = dzero(p, &d.Spb, (size_t)d.nf_pad * 6 * NBP))) return rc;
-            if ((rc = dzero(p, &d.Zb, (size_t)d.nf_pad * 6 * NBP))) return rc;
-            for (int l = 0; l < d.n_levels; ++l)
-                if ((rc = dzero(p, &d.lev[l].B, (size_t)d.lev[l].n * BD * NBP))) return rc;
-            if (configure_border()) { set_error("hipFuncSetAttribute(border kernels) failed"); return SSBA_ERR_HIP; }
-        }
-        SelInv si{};
+    SelInv si{};
+    if (!dense) {       // windowed: the band of Sigma by selected inversion
         size_t nsc = 0;
         for (int l = 0; l < d.n_levels; ++l) { si.sc_off[l] = (int)nsc; nsc += (size_t)d.lev[l].n; }
         const size_t bb = (size_t)BD * BD;
         HIPCHECK(B.get((void **)&si.sd, ((size_t)d.Nsb * bb) * sizeof(double)));
         HIPCHECK(B.get((void **)&si.sc, (nsc * bb) * sizeof(double)));
         HIPCHECK(B.get((void **)&si.ws, ((size_t)std::max(1, d.lev[0].n / 2) * 5 * bb) * sizeof(double)));
-        if ((rc = begin_hook(p, &o, 1e300))) return rc;        // radius -> infinity: no Levenberg-Marquardt damping in S
-        launch_linearize(L, d);
-        launch_schur(L, d);
-        launch_finish_check(L, d);
-        launch_bcr(L, d, false);       // the selected inversion and the sweeps need the factors of every level
-        launch_selinv(L, d, si);
-        const long nrow = (long)d.nf_pad * 6;
-        if (nslots) {
-            HIPCHECK(B.get((void **)&cols, ((size_t)nslots * 6 * nrow) * sizeof(double)));
-            constexpr int PER = NBP / 6;       // 5 poses per sweep
-            std::vector<double> unit((size_t)PER * 6 * NBP, 0.0);
-            for (int s0 = 0; s0 < nslots; s0 += PER) {
-                const int nq = std::min(PER, nslots - s0);
-                HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
-                std::fill(unit.begin(), unit.end(), 0.0);
-                for (int q = 0; q < nq; ++q) {
-                    for (int c = 0; c < 6; ++c) unit[(size_t)q * 6 * NBP + (size_t)c * NBP + 6 * q + c] = 1.0;
-                    HIPCHECK(hipMemcpyAsync(d.Spb + (size_t)slot_pose[s0 + q] * 6 * NBP, unit.data() + (size_t)q * 6 * NBP,
-                                            (size_t)6 * NBP * sizeof(double), hipMemcpyHostToDevice, L.stream));
-                }
-                HIPCHECK(hipStreamSynchronize(L.stream));
-                launch_bcr_multi_rhs(L, d);
-                launch_cov_gather(L, d.Zb, cols, s0, nq, nrow);
-            }
-            HIPCHECK(hipMemsetAsync(d.Spb, 0, (size_t)d.nf_pad * 6 * NBP * sizeof(double), L.stream));
-        }
-        src.sd = si.sd;
-        src.sc0 = si.sc;
-        src.nrow = nrow;
-        // the factors and the band must be complete before the buffers they came from are released (hipFree synchronises)
-    } else if (d.wide) {       // a solved wide handle: WPC / 6 = 8 poses per sweep of its own reduction
-        if ((rc = wide_panel_ready(p))) return rc;
-        const long nrow = (long)L.wide.n * WBD;
-        HIPCHECK(B.get((void **)&cols, ((size_t)std::max(nslots, 1) * 6 * nrow) * sizeof(double)));
-        constexpr int PER = WPC / 6;
-        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {     // (no column needed: one sweep still checks the system)
-            const int nq = std::max(0, std::min(PER, nslots - s0));
-            if ((rc = wide_cov_sweep(p, slot_pose.data() + s0, nq, cols, nrow, 6 * s0))) return rc;
-        }
-        src.nrow = nrow;
-    } else {
-        const size_t lda = (size_t)d.dn_pad;
-        HIPCHECK(B.get((void **)&cols, ((size_t)std::max(nslots, 1) * 6 * lda) * sizeof(double)));
-        constexpr int PER = DN_BS / 6;       // 10 poses per blocked Cholesky solve
-        const double one = 1.0;
-        for (int s0 = 0; s0 < std::max(nslots, 1); s0 += PER) {     // (no column needed: one solve still checks the system)
-            const int nq = std::min(PER, nslots - s0);
-            if ((rc = begin_hook(p, &o, 1e300))) return rc;
-            launch_linearize(L, d);
-            launch_dense_schur(L, d);
-            HIPCHECK(hipMemsetAsync(d.dn_S + lda * lda, 0, (size_t)DN_BS * lda * sizeof(double), L.stream));
-            for (int q = 0; q < nq; ++q)
-                for (int c = 0; c < 6; ++c)
-                    HIPCHECK(hipMemcpyAsync(d.dn_S + (lda + 6 * q + c) * lda + (size_t)slot_pose[s0 + q] * 6 + c, &one, sizeof one,
-                                            hipMemcpyHostToDevice, L.stream));
-            launch_finish_check(L, d);
-            launch_dense_solve(L, d, std::max(1, 6 * nq));
-            if (nq > 0)
-                HIPCHECK(hipMemcpyAsync(cols + (size_t)s0 * 6 * lda, d.dn_S + lda * lda, (size_t)nq * 6 * lda * sizeof(double),
-                                        hipMemcpyDeviceToDevice, L.stream));
-            HIPCHECK(hipStreamSynchronize(L.stream));
-            HIPCHECK(hipGetLastError());
-            if ((rc = fetch_state(p))) return rc;
-            if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
-        }
-        src.nrow = (long)lda;
     }
+    if ((rc = sigma_columns(p, B, slot_pose.data(), nslots, &cols, &src.nrow, dense ? nullptr : &si))) return rc;
+    // every buffer the jobs read is one of B: the factors, the band and the columns must be complete before they are released
+    // (hipFree synchronises)
+    src.sd = si.sd;
+    src.sc0 = si.sc;
     src.cols = cols;
     if (nslots) {
         HIPCHECK(B.get((void **)&d_slot, (slot.size()) * sizeof(int)));
@@ -3415,10 +3331,7 @@ int ssba_covariance_blocks(ssba_problem *p, const ssba_cov_block *blocks, uint64
         HIPCHECK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(CovJob), hipMemcpyHostToDevice, L.stream));
         launch_cov_jobs(L, d, src, d_jobs, (int)jobs.size(), d_out, d_fail);
     }
-    HIPCHECK(hipStreamSynchronize(L.stream));
-    HIPCHECK(hipGetLastError());
-    if ((rc = fetch_state(p))) return rc;
-    if (p->h_state->step_failed) { set_error("covariance: the reduced camera system is not positive definite (gauge freedom?)"); return SSBA_ERR_NUMERICAL_FAILURE; }
+    if ((rc = sweep_done(p))) return rc;
     int fail = 0;
     HIPCHECK(hipMemcpy(&fail, d_fail, sizeof fail, hipMemcpyDeviceToHost));
     if (fail) { set_error("covariance: the block of a requested point is not positive definite"); return SSBA_ERR_NUMERICAL_FAILURE; }

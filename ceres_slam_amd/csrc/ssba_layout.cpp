@@ -40,6 +40,16 @@ template <class T, class K> static void stable_count_sort(std::vector<T> &v, std
     v.swap(tmp);
 }
 
+bool dense_system_fits(long nfree, int world_size, double *gb, double *cap) {
+    const double nf = (double)nfree;
+    const double dn_gb = (6.0 * nf + 2 * DN_BS) * (6.0 * nf + DN_BS) * 8.0 / 1e9;
+    const char *mg = getenv("SSBA_DENSE_MAX_GB");
+    const double dn_cap = mg ? atof(mg) : 160.0;
+    if (gb) *gb = dn_gb;
+    if (cap) *cap = dn_cap;
+    return !(world_size > 1 || dn_gb > dn_cap || (6 * nfree + DN_BS) / DN_BS >= 65535);
+}
+
 int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std::function<void(const char *)> &mark) {
     out = Layout{};
     const uint32_t P = in.P, L = in.L;
@@ -308,10 +318,7 @@ int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std
         // the reduced system of the general path is stored as a dense lower triangle + right-hand-side rows; only its
         // structurally non-zero tiles are ever touched (symbolic factorisation below), so its size is bounded by memory,
         // not by time: SSBA_DENSE_MAX_GB (default 160 of the 288 GB of an MI355X; 10 000 free poses = 28.8 GB)
-        const double dn_gb = (double)(6.0 * nfree + 2 * DN_BS) * (6.0 * nfree + DN_BS) * 8.0 / 1e9;
-        const char *mg = getenv("SSBA_DENSE_MAX_GB");
-        const double dn_cap = mg ? atof(mg) : 160.0;
-        if (in.world_size > 1 || dn_gb > dn_cap || (6 * (long)nfree + DN_BS) / DN_BS >= 65535) {
+        if (!dense_system_fits(nfree, in.world_size)) {
             set_error("problem structure (tracks > SSBA_MAX_TRACK or co-visibility span > 12 poses) needs the dense reduced system: "
                       "single GPU only, and its array must fit SSBA_DENSE_MAX_GB (default 160)");
             return SSBA_ERR_UNSUPPORTED;

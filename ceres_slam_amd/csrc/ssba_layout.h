@@ -98,4 +98,10 @@ struct Layout {
 // called at the end of every phase with its name (SSBA_API_TIMING).
 int build_layout(const LayoutInput &in, Layout &out, std::string &err, const std::function<void(const char *)> &mark = nullptr);
 
+// Whether the dense reduced system of the general layout (blocked Cholesky) can be built for nfree free poses: one GPU, its
+// array within SSBA_DENSE_MAX_GB (read from the environment at every call, default 160), and fewer than 65535 block rows
+// (the grid limit of its kernels).  gb / cap: the array's size and the limit in GB, for the caller's message.  The layout
+// builder asks it, and so does every hand-over to that layout BEFORE it tears the working layout down.
+bool dense_system_fits(long nfree, int world_size, double *gb = nullptr, double *cap = nullptr);
+
 }  // namespace ssba

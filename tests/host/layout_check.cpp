@@ -211,8 +211,26 @@ static int check(const char *name, const Prob &q, int expect, int world = 1) {
     return 0;
 }
 
+// dense_system_fits: what the layout builder and every hand-over to the general layout ask before anything is torn down
+static int check_dense_fit() {
+    const char *name = "dense-fit predicate";
+    double gb = 0.0, cap = 0.0;
+    unsetenv("SSBA_DENSE_MAX_GB");
+    if (!dense_system_fits(10000, 1, &gb, &cap)) return fail(name, "10 000 free poses refused at the default cap");
+    if (std::fabs(gb - 28.8) > 0.1 || cap != 160.0) return fail(name, "size " + std::to_string(gb) + " GB, cap " + std::to_string(cap));
+    if (dense_system_fits(10000, 2)) return fail(name, "two ranks accepted");
+    setenv("SSBA_DENSE_MAX_GB", "1e9", 1);      // the grid limit alone: (6 nfree + DN_BS) / DN_BS block rows
+    if (!dense_system_fits(698000, 1) || dense_system_fits(700000, 1)) return fail(name, "the limit of 65535 block rows");
+    setenv("SSBA_DENSE_MAX_GB", "1", 1);
+    const bool fits = dense_system_fits(10000, 1, &gb, &cap);
+    unsetenv("SSBA_DENSE_MAX_GB");
+    if (fits || cap != 1.0) return fail(name, "10 000 free poses accepted with SSBA_DENSE_MAX_GB=1");
+    printf("ok   %-34s 10 000 free poses: %.1f GB\n", name, gb);
+    return 0;
+}
+
 int main() {
-    int bad = 0;
+    int bad = check_dense_fit();
     bad += check("C1 shape (50 / 2 000 / T 12)", make(50, 2000, 12, 1), 0);
     bad += check("C1 shape, caller's order shuffled", make(50, 2000, 12, 2, true), 0);
     bad += check("short tracks, several constant poses", make(200, 5000, 4, 3, false, 7), 0);

@@ -1,0 +1,792 @@
+// libssba_tracks.so: sparse stereo feature tracks from raw frames (include/ssba_tracks.h states the arithmetic; the numpy
+// statement is tests/tracks_reference.py).  Everything is integer arithmetic, and every position in an output comes from a
+// prefix sum, so the results do not depend on scheduling.  The image (or the pair) is a grid dimension of every kernel: the
+// number of launches does not depend on the number of frames.
+//
+//   k_tr_score      ring scores of every pixel of every image                      grid (cols / 64, rows / 4, images)
+//   k_tr_nms        3 x 3 suppression, one 256-bin score histogram per image       grid (cols / 64, rows / 4, images)
+//   k_tr_select     the cut score from the histogram, row-major compaction         grid (images), one work-group walks its image
+//   k_tr_describe   31 x 31 patch -> 27 x 27 box sums in LDS -> 256 bits           grid (max_features, images)
+//   k_tr_best       best train index per query under the gate, both directions     grid (queries / 64, pairs, 2)
+//   k_tr_stereo     cross-check, disparity, survivors compacted in keypoint order  grid (frames)
+//   k_tr_best       the same kernel over the F - 1 pairs of consecutive survivors
+//   k_tr_link       ids: one work-group walks the frames                           grid (1)
+//   k_tr_prune      short tracks out, ids renumbered, observations written         grid (1)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/ssba_tracks.h"
+#include "ssba_brief_pattern.h"
+#include "ssba_pool.h"
+
+namespace ssba {
+namespace {
+
+constexpr int TR_BORDER = SSBA_TRACK_BORDER;
+constexpr int TR_WORDS = SSBA_TRACK_DESC_WORDS;
+constexpr uint32_t TR_NONE = 0xffffffffu;     // packed key (distance << 16) | index of "no train entry passed the gate"
+constexpr int TR_BLOCK = 1024;                // the scanning kernels: 16 waves, 4 items per thread cover SSBA_TRACK_MAX_FEATURES
+constexpr int TR_ITEMS = 4;
+constexpr int TR_SPLIT = 4;                   // k_tr_best: the lanes that share a query, each takes every fourth train entry
+constexpr int TR_QUERIES = 64;                // queries per work-group
+constexpr int TR_THREADS = TR_QUERIES * TR_SPLIT;
+constexpr int TR_TILE = 512;                  // train descriptors staged per step: 16 KiB + 2 KiB of positions
+constexpr int TR_PATCH = 2 * TR_BORDER + 1;   // 31
+constexpr int TR_BOXES = 2 * SSBA_BRIEF_RADIUS + 1;   // 27
+
+static_assert(TR_BLOCK * TR_ITEMS == SSBA_TRACK_MAX_FEATURES, "one pass of the scanning kernels covers every keypoint slot");
+static_assert(SSBA_BRIEF_PAIRS == 256 && SSBA_BRIEF_RADIUS + 2 == TR_BORDER, "pattern and border belong together");
+
+__constant__ int8_t c_brief[SSBA_BRIEF_PAIRS][4] = {SSBA_BRIEF_PATTERN_ROWS};
+
+struct TrackGate {
+    int kind, max_dy, max_disparity, radius;
+};
+
+// exclusive prefix sum of one value per thread over a work-group of TR_BLOCK threads; *total is the sum.  `part` holds one
+// entry per wave and is free again when the call returns.
+__device__ __forceinline__ uint32_t tr_block_exscan(uint32_t v, uint32_t *part, uint32_t *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += up;
+    }
+    if (lane == 63) part[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < TR_BLOCK / 64; ++w) {
+        const uint32_t p = part[w];
+        before += w < wave ? p : 0u;
+        all += p;
+    }
+    __syncthreads();
+    *total = all;
+    return before + inc - v;
+}
+
+// ---- detector ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_tr_score(const uint8_t *__restrict__ images, uint8_t *__restrict__ score, int *__restrict__ hist, int rows,
+                                                  int cols, int threshold) {
+    const int img = blockIdx.z;
+    if (blockIdx.x == 0 && blockIdx.y == 0) hist[img * 256 + threadIdx.y * 64 + threadIdx.x] = 0;      // k_tr_nms adds into it
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= cols || y >= rows) return;
+    const size_t base = (size_t)img * rows * cols;
+    int s = 0;
+    if (x >= TR_BORDER && x < cols - TR_BORDER && y >= TR_BORDER && y < rows - TR_BORDER) {
+        const uint8_t *p = images + base + (size_t)y * cols + x;
+        const int c = p[0];
+        const int dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+        const int dy[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
+        int d[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) d[i] = (int)p[dy[i] * cols + dx[i]] - c;
+        int bright = -255, dark = -255;
+#pragma unroll
+        for (int a = 0; a < 16; ++a) {
+            int lo = 255, hi = -255;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                lo = min(lo, d[(a + k) & 15]);
+                hi = max(hi, d[(a + k) & 15]);
+            }
+            bright = max(bright, lo);
+            dark = max(dark, -hi);
+        }
+        s = max(0, max(bright, dark));
+        if (s <= threshold) s = 0;
+    }
+    score[base + (size_t)y * cols + x] = (uint8_t)s;
+}
+
+__global__ __launch_bounds__(256) void k_tr_nms(const uint8_t *__restrict__ score, uint8_t *__restrict__ kept, int *__restrict__ hist, int rows, int cols) {
+    __shared__ int bins[256];
+    const int img = blockIdx.z, t = threadIdx.y * 64 + threadIdx.x;
+    bins[t] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x < cols && y < rows) {
+        const size_t base = (size_t)img * rows * cols;
+        const uint8_t *p = score + base + (size_t)y * cols + x;
+        const int s = p[0];
+        bool keep = s > 0;           // s > 0 only inside the border, where all eight neighbours exist
+        if (keep) {
+#pragma unroll
+            for (int j = -1; j <= 1; ++j)
+#pragma unroll
+                for (int i = -1; i <= 1; ++i) {
+                    if (i == 0 && j == 0) continue;
+                    const int q = p[j * cols + i];
+                    const bool before = j < 0 || (j == 0 && i < 0);      // q precedes p in row-major order
+                    keep = keep && (s > q || (s == q && !before));
+                }
+        }
+        kept[base + (size_t)y * cols + x] = keep ? (uint8_t)s : (uint8_t)0;
+        if (keep) atomicAdd(&bins[s], 1);                                  // counts: the order of the additions does not matter
+    }
+    __syncthreads();
+    if (bins[t]) atomicAdd(&hist[img * 256 + t], bins[t]);
+}
+
+// One work-group per image.  The cut score T is the largest score with count(s >= T) >= max_features (0: everything is kept);
+// every s > T is kept and the first `quota` pixels with s == T in row-major order.  The work-group walks the image in chunks of
+// TR_BLOCK * TR_ITEMS pixels; one scan per chunk carries both counts, (s > T) in the upper and (s == T) in the lower 16 bits.
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_select(const uint8_t *__restrict__ kept, const int *__restrict__ hist, int rows, int cols, int max_features,
+                                                        uint32_t *__restrict__ count, uint16_t *__restrict__ xy, uint8_t *__restrict__ score_out) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    __shared__ int cut[2];
+    const int img = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int above = 0, T = 0, quota = 0;
+        for (int s = 255; s >= 1; --s) {
+            const int h = hist[img * 256 + s];
+            if (above + h >= max_features) {
+                T = s;
+                quota = max_features - above;
+                break;
+            }
+            above += h;
+        }
+        cut[0] = T;
+        cut[1] = quota;
+    }
+    __syncthreads();
+    const int T = cut[0];
+    const uint32_t quota = (uint32_t)cut[1];
+    const size_t npix = (size_t)rows * cols;
+    const uint8_t *im = kept + (size_t)img * npix;
+    uint16_t *oxy = xy + (size_t)img * max_features * 2;
+    uint8_t *osc = score_out + (size_t)img * max_features;
+    uint32_t run_gt = 0, run_eq = 0;
+    for (size_t chunk = 0; chunk < npix; chunk += (size_t)TR_BLOCK * TR_ITEMS) {
+        const size_t first = chunk + (size_t)threadIdx.x * TR_ITEMS;
+        int s[TR_ITEMS];
+        uint32_t mine = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            s[i] = first + i < npix ? (int)im[first + i] : 0;
+            if (s[i] > T) mine += 1u << 16;
+            else if (T > 0 && s[i] == T) mine += 1u;
+        }
+        uint32_t total;
+        const uint32_t before = tr_block_exscan(mine, part, &total);
+        uint32_t gt = run_gt + (before >> 16), eq = run_eq + (before & 0xffffu);
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const bool is_gt = s[i] > T, is_eq = T > 0 && s[i] == T;
+            if (is_gt || (is_eq && eq < quota)) {
+                const uint32_t pos = gt + min(eq, quota);
+                if (pos < (uint32_t)max_features) {              // holds by construction; the store stays inside the image's slots
+                    const size_t px = first + i;
+                    oxy[2 * pos] = (uint16_t)(px % cols);
+                    oxy[2 * pos + 1] = (uint16_t)(px / cols);
+                    osc[pos] = (uint8_t)s[i];
+                }
+            }
+            gt += is_gt;
+            eq += is_eq;
+        }
+        run_gt += total >> 16;
+        run_eq += total & 0xffffu;
+    }
+    if (threadIdx.x == 0) count[img] = min(run_gt + min(run_eq, quota), (uint32_t)max_features);
+}
+
+// One work-group per keypoint slot: the 31 x 31 patch, its 27 x 27 box sums, one bit per thread, one ballot per wave.
+__global__ __launch_bounds__(256) void k_tr_describe(const uint8_t *__restrict__ images, int rows, int cols, int max_features, const uint32_t *__restrict__ count,
+                                                     const uint16_t *__restrict__ xy, uint32_t *__restrict__ desc) {
+    __shared__ uint8_t patch[TR_PATCH * TR_PATCH];
+    __shared__ uint16_t box[TR_BOXES * TR_BOXES];
+    const int img = blockIdx.y, k = blockIdx.x, t = threadIdx.x;
+    if ((uint32_t)k >= count[img]) return;
+    const size_t slot = (size_t)img * max_features + k;
+    const int x = xy[2 * slot], y = xy[2 * slot + 1];
+    if (x < TR_BORDER || x >= cols - TR_BORDER || y < TR_BORDER || y >= rows - TR_BORDER) return;      // never: k_tr_score keeps the border
+    const uint8_t *im = images + (size_t)img * rows * cols;
+    for (int i = t; i < TR_PATCH * TR_PATCH; i += 256) {
+        const int py = i / TR_PATCH, px = i - py * TR_PATCH;
+        patch[i] = im[(size_t)(y - TR_BORDER + py) * cols + (x - TR_BORDER + px)];
+    }
+    __syncthreads();
+    for (int i = t; i < TR_BOXES * TR_BOXES; i += 256) {
+        const int by = i / TR_BOXES, bx = i - by * TR_BOXES;
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+#pragma unroll
+            for (int l = 0; l < 5; ++l) sum += patch[(by + j) * TR_PATCH + bx + l];
+        box[i] = (uint16_t)sum;          // at most 25 * 255
+    }
+    __syncthreads();
+    const int a = (c_brief[t][1] + SSBA_BRIEF_RADIUS) * TR_BOXES + c_brief[t][0] + SSBA_BRIEF_RADIUS;
+    const int b = (c_brief[t][3] + SSBA_BRIEF_RADIUS) * TR_BOXES + c_brief[t][2] + SSBA_BRIEF_RADIUS;
+    const unsigned long long bits = __ballot(box[a] < box[b]);
+    if ((t & 63) == 0) {
+        desc[slot * TR_WORDS + (t >> 6) * 2] = (uint32_t)bits;
+        desc[slot * TR_WORDS + (t >> 6) * 2 + 1] = (uint32_t)(bits >> 32);
+    }
+}
+
+// ---- matcher ----------------------------------------------------------------------------------------------------------------
+// Pair p matches set A = slots [p * stride, p * stride + count_a[p]) of desc_a / xy_a against set B likewise.  blockIdx.z = 0:
+// the queries are A and the train side B, best_ab[p * stride + a] = the packed key of a's best b; blockIdx.z = 1: the roles
+// swapped, into best_ba.  The train side passes through LDS in tiles of TR_TILE descriptors.  TR_SPLIT neighbouring lanes share a
+// query and take every TR_SPLIT-th entry of the tile: a wave reads TR_SPLIT consecutive entries per step (distinct banks, each
+// broadcast to the lanes of its part), 16 bytes at a time, and the lanes' packed keys meet in two shuffles.
+struct MatchSets {
+    const uint32_t *desc_a, *desc_b;
+    const uint16_t *xy_a, *xy_b;
+    const uint32_t *count_a, *count_b;
+    uint32_t *best_ab, *best_ba;
+    uint32_t stride;
+};
+
+__device__ __forceinline__ bool tr_gate(const TrackGate g, int xa, int ya, int xb, int yb) {
+    if (g.kind == SSBA_TRACK_GATE_STEREO) return abs(ya - yb) < g.max_dy && xa - xb > 0 && xa - xb <= g.max_disparity;
+    if (g.kind == SSBA_TRACK_GATE_TEMPORAL && g.radius > 0) return abs(xa - xb) <= g.radius && abs(ya - yb) <= g.radius;
+    return true;
+}
+
+__global__ __launch_bounds__(TR_THREADS) void k_tr_best(MatchSets m, TrackGate g) {
+    __shared__ uint4 tile[TR_TILE * 2];
+    __shared__ uint32_t tile_xy[TR_TILE];
+    const int pair = blockIdx.y;
+    const bool swapped = blockIdx.z != 0;
+    const size_t off = (size_t)pair * m.stride;
+    const uint32_t nq = min(swapped ? m.count_b[pair] : m.count_a[pair], m.stride);
+    const uint32_t nt = min(swapped ? m.count_a[pair] : m.count_b[pair], m.stride);
+    const uint32_t q = blockIdx.x * TR_QUERIES + threadIdx.x / TR_SPLIT, part = threadIdx.x % TR_SPLIT;
+    if (blockIdx.x * TR_QUERIES >= nq) return;            // the whole work-group leaves together
+    const uint32_t *qd = (swapped ? m.desc_b : m.desc_a) + off * TR_WORDS;
+    const uint16_t *qxy = (swapped ? m.xy_b : m.xy_a) + off * 2;
+    const uint4 *td = (const uint4 *)((swapped ? m.desc_a : m.desc_b) + off * TR_WORDS);
+    const uint32_t *txy = (const uint32_t *)((swapped ? m.xy_a : m.xy_b) + off * 2);
+    uint32_t *best = (swapped ? m.best_ba : m.best_ab) + off;
+    const bool live = q < nq;
+    uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+    int qx = 0, qy = 0;
+    if (live) {
+        const uint4 *src = (const uint4 *)(qd + (size_t)q * TR_WORDS);
+        d0 = src[0];
+        d1 = src[1];
+        qx = qxy[2 * q];
+        qy = qxy[2 * q + 1];
+    }
+    uint32_t key = TR_NONE;
+    for (uint32_t t0 = 0; t0 < nt; t0 += TR_TILE) {
+        const uint32_t n = min((uint32_t)TR_TILE, nt - t0);
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < 2 * n; i += TR_THREADS) tile[i] = td[2 * (size_t)t0 + i];
+        for (uint32_t i = threadIdx.x; i < n; i += TR_THREADS) tile_xy[i] = txy[t0 + i];
+        __syncthreads();
+#pragma unroll 2
+        for (uint32_t j = part; j < n; j += TR_SPLIT) {
+            const uint4 e0 = tile[2 * j], e1 = tile[2 * j + 1];
+            const uint32_t p = tile_xy[j];
+            const int tx = p & 0xffffu, ty = p >> 16;
+            const uint32_t dist = __popc(d0.x ^ e0.x) + __popc(d0.y ^ e0.y) + __popc(d0.z ^ e0.z) + __popc(d0.w ^ e0.w) + __popc(d1.x ^ e1.x) +
+                                  __popc(d1.y ^ e1.y) + __popc(d1.z ^ e1.z) + __popc(d1.w ^ e1.w);
+            const bool pass = swapped ? tr_gate(g, tx, ty, qx, qy) : tr_gate(g, qx, qy, tx, ty);
+            key = min(key, pass ? (dist << 16) | (t0 + j) : TR_NONE);      // the smallest index wins a tie
+        }
+    }
+    static_assert(TR_SPLIT == 4, "two shuffles join four lanes");
+    key = min(key, (uint32_t)__shfl_xor((int)key, 1, 64));
+    key = min(key, (uint32_t)__shfl_xor((int)key, 2, 64));
+    if (live && part == 0) best[q] = key;
+}
+
+// (a, b) is a match when each is the other's best and the distance is within max_hamming
+__device__ __forceinline__ bool tr_mutual(const uint32_t *best_ab, const uint32_t *best_ba, uint32_t a, uint32_t nb, int max_hamming, uint32_t *b_out) {
+    const uint32_t key = best_ab[a];
+    if (key == TR_NONE || (int)(key >> 16) > max_hamming) return false;
+    const uint32_t b = key & 0xffffu;
+    if (b >= nb) return false;
+    const uint32_t back = best_ba[b];
+    if (back == TR_NONE || (back & 0xffffu) != a) return false;
+    *b_out = b;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_tr_crosscheck(const uint32_t *__restrict__ best_ab, const uint32_t *__restrict__ best_ba, uint32_t na, uint32_t nb,
+                                                       int max_hamming, int32_t *__restrict__ match_a, int32_t *__restrict__ dist_a) {
+    const uint32_t a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= na) return;
+    uint32_t b = 0;
+    const bool ok = tr_mutual(best_ab, best_ba, a, nb, max_hamming, &b);
+    match_a[a] = ok ? (int32_t)b : -1;
+    dist_a[a] = ok ? (int32_t)(best_ab[a] >> 16) : -1;
+}
+
+// ---- survivors, ids, observations -------------------------------------------------------------------------------------------
+// Frame f: left keypoints are image f of the feature arrays, right keypoints image frames + f.  A survivor carries its
+// disparity in sixteenths of a pixel, whichever source it has.
+struct Survivors {
+    uint32_t *count;          // frames
+    uint32_t *desc;           // frames * stride * 8
+    uint16_t *xy;             // frames * stride * 2
+    int32_t *d16;             // frames * stride
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_stereo(const uint32_t *__restrict__ count, const uint16_t *__restrict__ xy, const uint32_t *__restrict__ desc,
+                                                        const uint32_t *__restrict__ best_lr, const uint32_t *__restrict__ best_rl,
+                                                        const int16_t *__restrict__ disp16, int frames, int rows, int cols, uint32_t stride, int max_hamming,
+                                                        Survivors out) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    const int f = blockIdx.x;
+    const uint32_t nl = min(count[f], stride), nr = disp16 ? 0u : min(count[frames + f], stride);
+    const size_t lo = (size_t)f * stride, ro = (size_t)(frames + f) * stride;
+    int d16[TR_ITEMS];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        const uint32_t a = threadIdx.x * TR_ITEMS + i;
+        d16[i] = 0;
+        if (a < nl) {
+            const int x = xy[2 * (lo + a)], y = xy[2 * (lo + a) + 1];
+            if (disp16) {
+                if (x < cols && y < rows) d16[i] = disp16[((size_t)f * rows + y) * cols + x];
+            } else {
+                uint32_t b = 0;
+                if (tr_mutual(best_lr + lo, best_rl + lo, a, nr, max_hamming, &b)) d16[i] = 16 * (x - (int)xy[2 * (ro + b)]);
+            }
+        }
+        mine += d16[i] > 0;
+    }
+    uint32_t total;
+    uint32_t pos = tr_block_exscan(mine, part, &total);
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        if (d16[i] <= 0) continue;
+        const uint32_t a = threadIdx.x * TR_ITEMS + i;
+        const size_t src = lo + a, dst = lo + pos;
+        if (pos < stride) {
+            const uint4 *s = (const uint4 *)(desc + src * TR_WORDS);
+            uint4 *d = (uint4 *)(out.desc + dst * TR_WORDS);
+            d[0] = s[0];
+            d[1] = s[1];
+            out.xy[2 * dst] = xy[2 * src];
+            out.xy[2 * dst + 1] = xy[2 * src + 1];
+            out.d16[dst] = d16[i];
+        }
+        ++pos;
+    }
+    if (threadIdx.x == 0) out.count[f] = min(total, stride);
+}
+
+// One work-group walks the frames.  id[f * stride + j] of survivor j of frame f; length[id] counts its observations (every id
+// occurs at most once per frame, because a cross-checked match is one to one, so the thread that owns the survivor adds alone).
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_link(const uint32_t *__restrict__ surv_count, const uint32_t *__restrict__ best_pn, const uint32_t *__restrict__ best_np,
+                                                      int frames, uint32_t stride, int max_hamming, uint32_t *__restrict__ id, uint32_t *__restrict__ length,
+                                                      uint32_t *__restrict__ num_ids) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    for (size_t i = threadIdx.x; i < (size_t)frames * stride; i += TR_BLOCK) length[i] = 0;
+    __syncthreads();
+    uint32_t next = 0;
+    for (int f = 0; f < frames; ++f) {
+        const uint32_t n = min(surv_count[f], stride), np = f ? min(surv_count[f - 1], stride) : 0u;
+        const size_t cur = (size_t)f * stride, prev = (size_t)(f ? f - 1 : 0) * stride;
+        uint32_t inherited[TR_ITEMS], fresh = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            inherited[i] = TR_NONE;
+            if (j >= n) continue;
+            uint32_t a = 0;
+            // pair f - 1 has A = the survivors of frame f - 1 and B = those of frame f: j is a B entry
+            if (f && tr_mutual(best_np + prev, best_pn + prev, j, np, max_hamming, &a)) inherited[i] = id[prev + a];
+            fresh += inherited[i] == TR_NONE;
+        }
+        uint32_t total;
+        uint32_t pos = next + tr_block_exscan(fresh, part, &total);
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            if (j >= n) continue;
+            const uint32_t mine = inherited[i] == TR_NONE ? pos++ : inherited[i];
+            id[cur + j] = mine;
+            if (mine < (uint32_t)frames * stride) length[mine] += 1;
+        }
+        next += total;
+        __syncthreads();          // frame f's ids are read by frame f + 1 of this same work-group
+    }
+    if (threadIdx.x == 0) *num_ids = next;
+}
+
+// The same work-group shape: new ids = a running prefix over (length >= min_track_length) in id order, which is the order of
+// first appearance; then the kept observations of every frame in keypoint order.
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_prune(const uint32_t *__restrict__ surv_count, const uint16_t *__restrict__ surv_xy, const int32_t *__restrict__ surv_d16,
+                                                       const uint32_t *__restrict__ id, const uint32_t *__restrict__ length, const uint32_t *__restrict__ num_ids,
+                                                       int frames, uint32_t stride, int min_track_length, uint32_t *__restrict__ new_id,
+                                                       uint32_t *__restrict__ state_start, uint32_t *__restrict__ point_id, double *__restrict__ uvd,
+                                                       uint32_t *__restrict__ totals) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    const uint32_t ids = min(*num_ids, (uint32_t)frames * stride);
+    uint32_t run = 0;
+    for (uint32_t chunk = 0; chunk < ids; chunk += TR_BLOCK * TR_ITEMS) {
+        uint32_t keep[TR_ITEMS], mine = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t t = chunk + threadIdx.x * TR_ITEMS + i;
+            keep[i] = t < ids && length[t] >= (uint32_t)min_track_length;
+            mine += keep[i];
+        }
+        uint32_t total;
+        uint32_t pos = run + tr_block_exscan(mine, part, &total);
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t t = chunk + threadIdx.x * TR_ITEMS + i;
+            if (t < ids) new_id[t] = keep[i] ? pos++ : TR_NONE;
+        }
+        run += total;
+    }
+    __syncthreads();
+    uint32_t written = 0;
+    for (int f = 0; f < frames; ++f) {
+        const uint32_t n = min(surv_count[f], stride);
+        const size_t cur = (size_t)f * stride;
+        uint32_t renamed[TR_ITEMS], mine = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            renamed[i] = TR_NONE;
+            if (j < n && id[cur + j] < ids) renamed[i] = new_id[id[cur + j]];
+            mine += renamed[i] != TR_NONE;
+        }
+        uint32_t total;
+        uint32_t pos = written + tr_block_exscan(mine, part, &total);
+        if (threadIdx.x == 0) state_start[f] = written;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            if (renamed[i] == TR_NONE) continue;
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            point_id[pos] = renamed[i];                       // pos < frames * stride: at most one observation per survivor slot
+            uvd[3 * (size_t)pos] = (double)surv_xy[2 * (cur + j)];
+            uvd[3 * (size_t)pos + 1] = (double)surv_xy[2 * (cur + j) + 1];
+            uvd[3 * (size_t)pos + 2] = (double)surv_d16[cur + j] / 16.0;
+            ++pos;
+        }
+        written += total;
+    }
+    if (threadIdx.x == 0) {
+        state_start[frames] = written;
+        totals[0] = written;
+        totals[1] = run;
+    }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+std::mutex g_error_mutex;
+std::string g_error;
+thread_local std::string t_error_copy;
+
+int tr_refuse(const char *call, int status, const std::string &what) {
+    std::lock_guard<std::mutex> lock(g_error_mutex);
+    g_error = std::string(call) + ": " + what;
+    return status;
+}
+
+#define TR_TRY(expr)                      \
+    do {                                  \
+        const hipError_t _e = (expr);     \
+        if (_e != hipSuccess) return _e;  \
+    } while (0)
+
+template <class T> hipError_t tr_alloc(std::vector<void *> *temps, T **out, size_t n) {
+    void *ptr = nullptr;
+    const hipError_t e = pool_malloc(&ptr, (n ? n : 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    temps->push_back(ptr);
+    *out = (T *)ptr;
+    return hipSuccess;
+}
+
+int tr_check_params(const char *call, const ssba_track_params *p) {
+    if (!p) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL parameters");
+    if (p->max_features < 1 || p->max_features > SSBA_TRACK_MAX_FEATURES) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "max_features must be in 1 ... 4096");
+    if (p->fast_threshold < 0 || p->fast_threshold > 254) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "fast_threshold must be in 0 ... 254");
+    if (p->max_hamming < 0 || p->max_hamming > 256) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "max_hamming must be in 0 ... 256");
+    if (p->stereo_max_dy < 0 || p->max_disparity < 0 || p->temporal_radius < 0)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "stereo_max_dy, max_disparity and temporal_radius must not be negative");
+    if (p->min_track_length < 1) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "min_track_length must be at least 1");
+    return SSBA_OK;
+}
+
+int tr_check_size(const char *call, uint32_t rows, uint32_t cols) {
+    if (rows < 31 || cols < 31 || rows > 8192 || cols > 8192) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "rows and cols must be in 31 ... 8192");
+    return SSBA_OK;
+}
+
+int tr_open_device(const char *call, int device, hipStream_t *s) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return tr_refuse(call, SSBA_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return tr_refuse(call, SSBA_ERR_NO_DEVICE, "hipGetDevice failed");
+    if (device >= n) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "no such device");
+    if (hipSetDevice(device) != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, "hipSetDevice failed");
+    if (pool_stream_acquire(s) != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, "no stream");
+    return SSBA_OK;
+}
+
+struct Features {
+    uint32_t *count = nullptr;     // n
+    uint16_t *xy = nullptr;        // n * max_features * 2
+    uint8_t *score = nullptr;      // n * max_features
+    uint32_t *desc = nullptr;      // n * max_features * 8
+};
+
+// four launches for n images already on the device
+hipError_t tr_enqueue_features(const uint8_t *images, uint32_t n, int rows, int cols, const ssba_track_params &p, bool clear, Features *f, hipStream_t s,
+                               std::vector<void *> *temps) {
+    const size_t npix = (size_t)rows * cols, slots = (size_t)n * p.max_features;
+    uint8_t *score = nullptr, *kept = nullptr;
+    int *hist = nullptr;
+    TR_TRY(tr_alloc(temps, &score, npix * n));
+    TR_TRY(tr_alloc(temps, &kept, npix * n));
+    TR_TRY(tr_alloc(temps, &hist, (size_t)n * 256));
+    TR_TRY(tr_alloc(temps, &f->count, (size_t)n));
+    TR_TRY(tr_alloc(temps, &f->xy, slots * 2));
+    TR_TRY(tr_alloc(temps, &f->score, slots));
+    TR_TRY(tr_alloc(temps, &f->desc, slots * TR_WORDS));
+    if (clear) {       // a caller that downloads whole arrays gets zeros behind the counts
+        TR_TRY(hipMemsetAsync(f->xy, 0, slots * 2 * sizeof(uint16_t), s));
+        TR_TRY(hipMemsetAsync(f->score, 0, slots, s));
+        TR_TRY(hipMemsetAsync(f->desc, 0, slots * TR_WORDS * sizeof(uint32_t), s));
+    }
+    const dim3 grid((cols + 63) / 64, (rows + 3) / 4, n), block(64, 4);
+    hipLaunchKernelGGL(k_tr_score, grid, block, 0, s, images, score, hist, rows, cols, p.fast_threshold);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_nms, grid, block, 0, s, (const uint8_t *)score, kept, hist, rows, cols);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_select, dim3(n), dim3(TR_BLOCK), 0, s, (const uint8_t *)kept, (const int *)hist, rows, cols, p.max_features, f->count, f->xy, f->score);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_describe, dim3(p.max_features, n), dim3(256), 0, s, images, rows, cols, p.max_features, (const uint32_t *)f->count,
+                       (const uint16_t *)f->xy, f->desc);
+    return hipGetLastError();
+}
+
+hipError_t tr_enqueue_best(const MatchSets &m, uint32_t pairs, const TrackGate &g, hipStream_t s) {
+    if (!pairs) return hipSuccess;
+    hipLaunchKernelGGL(k_tr_best, dim3((m.stride + TR_QUERIES - 1) / TR_QUERIES, pairs, 2), dim3(TR_THREADS), 0, s, m, g);
+    return hipGetLastError();
+}
+
+hipError_t tr_run_features(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const ssba_track_params &p, uint32_t *count, uint16_t *xy,
+                           uint8_t *score, uint32_t *desc, hipStream_t s, std::vector<void *> *temps) {
+    const size_t all = (size_t)rows * cols * n, slots = (size_t)n * p.max_features;
+    uint8_t *dimg = nullptr;
+    Features f;
+    TR_TRY(tr_alloc(temps, &dimg, all));
+    TR_TRY(hipMemcpyAsync(dimg, images, all, hipMemcpyHostToDevice, s));
+    TR_TRY(tr_enqueue_features(dimg, n, (int)rows, (int)cols, p, true, &f, s, temps));
+    TR_TRY(hipMemcpyAsync(count, f.count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipMemcpyAsync(xy, f.xy, slots * 2 * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipMemcpyAsync(score, f.score, slots, hipMemcpyDeviceToHost, s));
+    TR_TRY(hipMemcpyAsync(desc, f.desc, slots * TR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
+}
+
+hipError_t tr_run_match(const uint32_t *desc_a, const uint16_t *xy_a, uint32_t na, const uint32_t *desc_b, const uint16_t *xy_b, uint32_t nb, const TrackGate &g,
+                        int max_hamming, int32_t *match_a, int32_t *dist_a, hipStream_t s, std::vector<void *> *temps) {
+    const uint32_t stride = na > nb ? na : nb;
+    uint32_t *da = nullptr, *db = nullptr, *counts = nullptr, *best_ab = nullptr, *best_ba = nullptr;
+    uint16_t *pa = nullptr, *pb = nullptr;
+    int32_t *dm = nullptr, *dd = nullptr;
+    TR_TRY(tr_alloc(temps, &da, (size_t)stride * TR_WORDS));
+    TR_TRY(tr_alloc(temps, &db, (size_t)stride * TR_WORDS));
+    TR_TRY(tr_alloc(temps, &pa, (size_t)stride * 2));
+    TR_TRY(tr_alloc(temps, &pb, (size_t)stride * 2));
+    TR_TRY(tr_alloc(temps, &counts, (size_t)2));
+    TR_TRY(tr_alloc(temps, &best_ab, (size_t)stride));
+    TR_TRY(tr_alloc(temps, &best_ba, (size_t)stride));
+    TR_TRY(tr_alloc(temps, &dm, (size_t)na));
+    TR_TRY(tr_alloc(temps, &dd, (size_t)na));
+    const uint32_t host_counts[2] = {na, nb};
+    TR_TRY(hipMemcpyAsync(counts, host_counts, sizeof host_counts, hipMemcpyHostToDevice, s));
+    if (na) TR_TRY(hipMemcpyAsync(da, desc_a, (size_t)na * TR_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (na) TR_TRY(hipMemcpyAsync(pa, xy_a, (size_t)na * 2 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    if (nb) TR_TRY(hipMemcpyAsync(db, desc_b, (size_t)nb * TR_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (nb) TR_TRY(hipMemcpyAsync(pb, xy_b, (size_t)nb * 2 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    TR_TRY(hipStreamSynchronize(s));       // host_counts leaves scope with this frame; the copies above read pageable memory
+    if (na) {
+        const MatchSets m = {da, db, pa, pb, counts, counts + 1, best_ab, best_ba, stride};
+        TR_TRY(tr_enqueue_best(m, 1, g, s));
+        hipLaunchKernelGGL(k_tr_crosscheck, dim3((na + 255) / 256), dim3(256), 0, s, (const uint32_t *)best_ab, (const uint32_t *)best_ba, na, nb, max_hamming, dm, dd);
+        TR_TRY(hipGetLastError());
+        TR_TRY(hipMemcpyAsync(match_a, dm, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        TR_TRY(hipMemcpyAsync(dist_a, dd, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    return hipStreamSynchronize(s);
+}
+
+struct SequenceOut {
+    uint64_t capacity;
+    uint32_t *state_start, *point_id;
+    double *uvd;
+    uint64_t *num_observations;
+    uint32_t *num_points;
+    uint32_t needed = 0;
+    bool too_small = false;
+};
+
+hipError_t tr_run_sequence(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
+                           const ssba_track_params &p, SequenceOut *o, hipStream_t s, std::vector<void *> *temps) {
+    const size_t npix = (size_t)rows * cols, stack = npix * frames;
+    const uint32_t n = right ? 2 * frames : frames, stride = (uint32_t)p.max_features;
+    const size_t slots = (size_t)frames * stride;
+    uint8_t *dimg = nullptr;
+    int16_t *dd16 = nullptr;
+    TR_TRY(tr_alloc(temps, &dimg, npix * n));
+    TR_TRY(hipMemcpyAsync(dimg, left, stack, hipMemcpyHostToDevice, s));
+    if (right) {
+        TR_TRY(hipMemcpyAsync(dimg + stack, right, stack, hipMemcpyHostToDevice, s));
+    } else {
+        TR_TRY(tr_alloc(temps, &dd16, stack));
+        TR_TRY(hipMemcpyAsync(dd16, disp16, stack * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    }
+    Features f;
+    TR_TRY(tr_enqueue_features(dimg, n, (int)rows, (int)cols, p, false, &f, s, temps));
+
+    uint32_t *best_lr = nullptr, *best_rl = nullptr, *best_pn = nullptr, *best_np = nullptr, *id = nullptr, *length = nullptr, *new_id = nullptr, *scalars = nullptr;
+    uint32_t *d_start = nullptr, *d_point = nullptr;
+    double *d_uvd = nullptr;
+    Survivors sv;
+    TR_TRY(tr_alloc(temps, &best_lr, slots));
+    TR_TRY(tr_alloc(temps, &best_rl, slots));
+    TR_TRY(tr_alloc(temps, &best_pn, slots));
+    TR_TRY(tr_alloc(temps, &best_np, slots));
+    TR_TRY(tr_alloc(temps, &sv.count, (size_t)frames));
+    TR_TRY(tr_alloc(temps, &sv.desc, slots * TR_WORDS));
+    TR_TRY(tr_alloc(temps, &sv.xy, slots * 2));
+    TR_TRY(tr_alloc(temps, &sv.d16, slots));
+    TR_TRY(tr_alloc(temps, &id, slots));
+    TR_TRY(tr_alloc(temps, &length, slots));
+    TR_TRY(tr_alloc(temps, &new_id, slots));
+    TR_TRY(tr_alloc(temps, &scalars, (size_t)3));                 // the number of ids; observations and points after pruning
+    TR_TRY(tr_alloc(temps, &d_start, (size_t)frames + 1));
+    TR_TRY(tr_alloc(temps, &d_point, slots));
+    TR_TRY(tr_alloc(temps, &d_uvd, slots * 3));
+
+    if (right) {      // left frame f is image f, right frame f image frames + f of the feature arrays
+        const MatchSets m = {f.desc, f.desc + slots * TR_WORDS, f.xy, f.xy + slots * 2, f.count, f.count + frames, best_lr, best_rl, stride};
+        TR_TRY(tr_enqueue_best(m, frames, TrackGate{SSBA_TRACK_GATE_STEREO, p.stereo_max_dy, p.max_disparity, 0}, s));
+    }
+    hipLaunchKernelGGL(k_tr_stereo, dim3(frames), dim3(TR_BLOCK), 0, s, (const uint32_t *)f.count, (const uint16_t *)f.xy, (const uint32_t *)f.desc,
+                       (const uint32_t *)best_lr, (const uint32_t *)best_rl, (const int16_t *)dd16, (int)frames, (int)rows, (int)cols, stride, p.max_hamming, sv);
+    TR_TRY(hipGetLastError());
+    {                 // pair k: A = the survivors of frame k, B = those of frame k + 1
+        const MatchSets m = {sv.desc, sv.desc + (size_t)stride * TR_WORDS, sv.xy, sv.xy + (size_t)stride * 2, sv.count, sv.count + 1, best_pn, best_np, stride};
+        TR_TRY(tr_enqueue_best(m, frames - 1, TrackGate{SSBA_TRACK_GATE_TEMPORAL, 0, 0, p.temporal_radius}, s));
+    }
+    hipLaunchKernelGGL(k_tr_link, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)sv.count, (const uint32_t *)best_pn, (const uint32_t *)best_np, (int)frames, stride,
+                       p.max_hamming, id, length, scalars);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_prune, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)sv.count, (const uint16_t *)sv.xy, (const int32_t *)sv.d16, (const uint32_t *)id,
+                       (const uint32_t *)length, (const uint32_t *)scalars, (int)frames, stride, p.min_track_length, new_id, d_start, d_point, d_uvd, scalars + 1);
+    TR_TRY(hipGetLastError());
+    uint32_t totals[2] = {0, 0};
+    TR_TRY(hipMemcpyAsync(totals, scalars + 1, sizeof totals, hipMemcpyDeviceToHost, s));
+    TR_TRY(hipStreamSynchronize(s));
+    o->needed = totals[0];
+    if ((uint64_t)totals[0] > o->capacity) {
+        o->too_small = true;
+        return hipSuccess;
+    }
+    TR_TRY(hipMemcpyAsync(o->state_start, d_start, ((size_t)frames + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (totals[0]) {
+        TR_TRY(hipMemcpyAsync(o->point_id, d_point, (size_t)totals[0] * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        TR_TRY(hipMemcpyAsync(o->uvd, d_uvd, (size_t)totals[0] * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    TR_TRY(hipStreamSynchronize(s));
+    *o->num_observations = totals[0];
+    *o->num_points = totals[1];
+    return hipSuccess;
+}
+
+int tr_close(const char *call, hipError_t e, hipStream_t s, std::vector<void *> *temps) {
+    (void)hipStreamSynchronize(s);
+    for (void *t : *temps) pool_free(t);
+    pool_stream_release(s);
+    if (e != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    return SSBA_OK;
+}
+
+}  // namespace
+}  // namespace ssba
+
+using namespace ssba;
+
+extern "C" {
+
+void ssba_track_default_params(ssba_track_params *params) {
+    if (!params) return;
+    *params = ssba_track_params{20, 1000, 5, 128, 64, 0, 2};
+}
+
+const char *ssba_track_last_error(void) {
+    std::lock_guard<std::mutex> lock(g_error_mutex);
+    t_error_copy = g_error;
+    return t_error_copy.c_str();
+}
+
+int ssba_track_features(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const ssba_track_params *params, int device, uint32_t *count,
+                        uint16_t *xy, uint8_t *score, uint32_t *desc) {
+    const char *call = "ssba_track_features";
+    if (!images) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL image");
+    if (!count || !xy || !score || !desc) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (const int rc = tr_check_params(call, params)) return rc;
+    if (n < 1 || n > 65535) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "n must be in 1 ... 65535");
+    if (const int rc = tr_check_size(call, rows, cols)) return rc;
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    const hipError_t e = tr_run_features(images, n, rows, cols, *params, count, xy, score, desc, s, &temps);
+    return tr_close(call, e, s, &temps);
+}
+
+int ssba_track_match(const uint32_t *desc_a, const uint16_t *xy_a, uint32_t na, const uint32_t *desc_b, const uint16_t *xy_b, uint32_t nb, int gate,
+                     const ssba_track_params *params, int device, int32_t *match_a, int32_t *dist_a) {
+    const char *call = "ssba_track_match";
+    if ((na && (!desc_a || !xy_a)) || (nb && (!desc_b || !xy_b))) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL descriptors or positions");
+    if (na && (!match_a || !dist_a)) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (const int rc = tr_check_params(call, params)) return rc;
+    if (gate != SSBA_TRACK_GATE_NONE && gate != SSBA_TRACK_GATE_STEREO && gate != SSBA_TRACK_GATE_TEMPORAL)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "unknown gate");
+    if (na > 65535 || nb > 65535) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "na and nb must not exceed 65535 (the index half of the packed key)");
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    const TrackGate g = {gate, params->stereo_max_dy, params->max_disparity, params->temporal_radius};
+    const hipError_t e = tr_run_match(desc_a, xy_a, na, desc_b, xy_b, nb, g, params->max_hamming, match_a, dist_a, s, &temps);
+    return tr_close(call, e, s, &temps);
+}
+
+int ssba_track_sequence(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
+                        const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id, double *uvd,
+                        uint64_t *num_observations, uint32_t *num_points) {
+    const char *call = "ssba_track_sequence";
+    if (!left) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL left images");
+    if (!right == !disp16) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "exactly one of right and disp16 must be given");
+    if (!state_start || !num_observations || !num_points || (capacity && (!point_id || !uvd))) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (const int rc = tr_check_params(call, params)) return rc;
+    if (frames < 1 || frames > 32767) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "frames must be in 1 ... 32767");
+    if (const int rc = tr_check_size(call, rows, cols)) return rc;
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    SequenceOut o = {capacity, state_start, point_id, uvd, num_observations, num_points};
+    const hipError_t e = tr_run_sequence(left, right, disp16, frames, rows, cols, *params, &o, s, &temps);
+    const int rc = tr_close(call, e, s, &temps);
+    if (rc) return rc;
+    if (o.too_small)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(capacity) + " is below the " + std::to_string(o.needed) + " observations found");
+    return SSBA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,127 @@
+"""ctypes binding of include/ssba_tracks.h (ceres_slam_amd/libssba_tracks.so): sparse stereo feature tracks from raw frames.
+
+A loader of its own: the library shares nothing with libssba.so, and capi.SYMBOLS stays the list of include/ssba.h.  HIP only:
+without the library or a device every call raises, there is no CPU path (the numpy statement lives under tests/)."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from .capi import SsbaError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libssba_tracks.so")
+
+#: every symbol include/ssba_tracks.h declares
+SYMBOLS = ["ssba_track_default_params", "ssba_track_features", "ssba_track_match", "ssba_track_sequence", "ssba_track_last_error"]
+BORDER, MAX_FEATURES, DESC_WORDS = 15, 4096, 8
+GATE_NONE, GATE_STEREO, GATE_TEMPORAL = 0, 1, 2
+
+_u8p, _u16p, _u32p, _i16p, _i32p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint16, C.c_uint32, C.c_int16, C.c_int32))
+_dp = C.POINTER(C.c_double)
+
+
+class TrackParams(C.Structure):
+    """ssba_track_params; track_params(**kw) fills in the library's defaults."""
+    _fields_ = [(n, C.c_int32) for n in ("fast_threshold", "max_features", "stereo_max_dy", "max_disparity", "max_hamming", "temporal_radius",
+                                         "min_track_length")]
+
+
+_lib = None
+
+
+def load():
+    """Load libssba_tracks.so; raises if it was not built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(f"{LIB_PATH} is missing: build it with `python -m ceres_slam_amd.build` (the tracker is HIP-only, there is no CPU fallback)")
+    L = C.CDLL(LIB_PATH)
+    P = C.POINTER(TrackParams)
+    L.ssba_track_default_params.argtypes = [P]
+    L.ssba_track_default_params.restype = None
+    L.ssba_track_features.argtypes = [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_int, _u32p, _u16p, _u8p, _u32p]
+    L.ssba_track_match.argtypes = [_u32p, _u16p, C.c_uint32, _u32p, _u16p, C.c_uint32, C.c_int, P, C.c_int, _i32p, _i32p]
+    L.ssba_track_sequence.argtypes = [_u8p, _u8p, _i16p, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_int, C.c_uint64, _u32p, _u32p, _dp,
+                                      C.POINTER(C.c_uint64), _u32p]
+    L.ssba_track_last_error.restype = C.c_char_p
+    _lib = L
+    return L
+
+
+def check(status: int, where: str):
+    if status != 0:
+        raise SsbaError(status, where, load().ssba_track_last_error().decode(errors="replace"))
+
+
+def track_params(**kw) -> TrackParams:
+    p = TrackParams()
+    load().ssba_track_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v))
+    return p
+
+
+def _stack(images, dtype, what):
+    a = np.ascontiguousarray(images, dtype=dtype)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError(f"{what}: a (rows, cols) image or an (n, rows, cols) stack")
+    return a
+
+
+def track_features(images, device: int = -1, **params):
+    """Detector and descriptor over a stack (ssba_track_features).  Returns count (n,), xy (n, max_features, 2) uint16,
+    score (n, max_features) uint8, desc (n, max_features, 8) uint32; zeros behind each count."""
+    img = _stack(images, np.uint8, "images")
+    p = track_params(**params)
+    n, rows, cols = img.shape
+    m = max(int(p.max_features), 1)
+    count, xy = np.zeros(n, np.uint32), np.zeros((n, m, 2), np.uint16)
+    score, desc = np.zeros((n, m), np.uint8), np.zeros((n, m, DESC_WORDS), np.uint32)
+    check(load().ssba_track_features(img.ctypes.data_as(_u8p), n, rows, cols, C.byref(p), device, count.ctypes.data_as(_u32p), xy.ctypes.data_as(_u16p),
+                                     score.ctypes.data_as(_u8p), desc.ctypes.data_as(_u32p)), "ssba_track_features")
+    return count, xy, score, desc
+
+
+def track_match(desc_a, xy_a, desc_b, xy_b, gate: int = GATE_NONE, device: int = -1, **params):
+    """The cross-checked matcher alone (ssba_track_match).  Returns match_a, dist_a (int32, -1: no match)."""
+    da = np.ascontiguousarray(desc_a, dtype=np.uint32).reshape(-1, DESC_WORDS)
+    db = np.ascontiguousarray(desc_b, dtype=np.uint32).reshape(-1, DESC_WORDS)
+    pa = np.ascontiguousarray(xy_a, dtype=np.uint16).reshape(-1, 2)
+    pb = np.ascontiguousarray(xy_b, dtype=np.uint16).reshape(-1, 2)
+    if len(pa) != len(da) or len(pb) != len(db):
+        raise ValueError("one position per descriptor")
+    p = track_params(**params)
+    match, dist = np.full(len(da), -1, np.int32), np.full(len(da), -1, np.int32)
+    check(load().ssba_track_match(da.ctypes.data_as(_u32p), pa.ctypes.data_as(_u16p), len(da), db.ctypes.data_as(_u32p), pb.ctypes.data_as(_u16p), len(db),
+                                  int(gate), C.byref(p), device, match.ctypes.data_as(_i32p), dist.ctypes.data_as(_i32p)), "ssba_track_match")
+    return match, dist
+
+
+def track_sequence(left, right=None, disp16=None, device: int = -1, capacity: int | None = None, **params):
+    """Frames to tracks (ssba_track_sequence): state_start (F + 1,), point_id (N,), uvd (N, 3), num_points -- the inputs of
+    frontend.compute_initial_guess_device / ssba_frontend_vo.  Exactly one of right (F images) and disp16 (F int16 maps, the
+    format solver.stereo_sgbm_batch returns) is given.  capacity: room for observations, by default one per keypoint slot."""
+    L = _stack(left, np.uint8, "left")
+    F, rows, cols = L.shape
+    R = None if right is None else _stack(right, np.uint8, "right")
+    D = None if disp16 is None else _stack(disp16, np.int16, "disp16")
+    for other, what in ((R, "right"), (D, "disp16")):
+        if other is not None and other.shape != L.shape:
+            raise ValueError(f"{what} must have the shape of left")
+    p = track_params(**params)
+    cap = F * max(int(p.max_features), 0) if capacity is None else int(capacity)
+    start, ids, uvd = np.zeros(F + 1, np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros((max(cap, 1), 3))
+    nobs, npts = C.c_uint64(0), C.c_uint32(0)
+    check(load().ssba_track_sequence(L.ctypes.data_as(_u8p), None if R is None else R.ctypes.data_as(_u8p), None if D is None else D.ctypes.data_as(_i16p),
+                                     F, rows, cols, C.byref(p), device, cap, start.ctypes.data_as(_u32p), ids.ctypes.data_as(_u32p), uvd.ctypes.data_as(_dp),
+                                     C.byref(nobs), C.byref(npts)), "ssba_track_sequence")
+    n = int(nobs.value)
+    return start, ids[:n].copy(), uvd[:n].copy(), int(npts.value)

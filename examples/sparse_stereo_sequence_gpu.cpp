@@ -1,0 +1,116 @@
+// sparse_stereo_sequence_gpu -- from raw stereo frames to a bundle-adjusted trajectory on the sparse path: feature tracks on the
+// device (ceres_slam::FeatureTracker, include/ceres_slam_amd/feature_tracks.hpp), the VO initial guess on the device
+// (DatasetProblem::compute_initial_guess = ssba_frontend_vo), then the solve of tests/dataset_vo.cpp:22-85 through the shim.
+// It reads the raw file of examples/dense_stereo_sequence_gpu.cpp (its header states the layout; synth.write_stereo_sequence
+// writes it): the frames, the camera and the matcher's parameters are used, the pyramid fields are not.
+//
+// usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]
+// --sgbm takes the disparities from the semi-global matcher (StereoSGBM over all pairs in shared launches, sub-pixel) instead
+// of from left-right feature matches (whole pixels).
+// Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <memory>
+#include <vector>
+
+#include "ceres_slam_amd/ceres_shim.hpp"
+#include "ceres_slam_amd/dataset_problem.hpp"
+#include "ceres_slam_amd/feature_tracks.hpp"
+
+// tests/dataset_vo.cpp:22-85 over all states, unit stiffness
+static bool solveAll(ceres_slam::DatasetProblem &dataset) {
+    ceres::Problem problem;
+    const double *var = dataset.stereo_obs_var.data();
+    const double stiffness[9] = {1.0 / std::sqrt(var[0]), 0, 0, 0, 1.0 / std::sqrt(var[1]), 0, 0, 0, 1.0 / std::sqrt(var[2])};
+    ceres::LocalParameterization *se3_perturbation = ceres_slam::SE3Perturbation::Create();
+    for (ceres_slam::uint k = 0; k < dataset.num_states; ++k) {
+        bool used = false;
+        for (ceres_slam::uint i : dataset.obs_indices_at_state(k)) {
+            const ceres_slam::uint j = dataset.point_ids[i];
+            if (j >= dataset.num_points || !dataset.initialized_point[j]) continue;     // only initialised map points (:45)
+            ceres::CostFunction *cost = ceres_slam::StereoReprojectionErrorAutomatic::Create(dataset.camera, dataset.stereo_obs_list[i].data(), stiffness);
+            problem.AddResidualBlock(cost, NULL, dataset.poses[k].data(), dataset.map_points[j].data());
+            used = true;
+        }
+        if (used) problem.SetParameterization(dataset.poses[k].data(), se3_perturbation);
+    }
+    problem.SetParameterBlockConstant(dataset.poses[0].data());
+    ceres::Solver::Options solver_options;
+    solver_options.max_num_iterations = 1000;
+    solver_options.use_nonmonotonic_steps = true;
+    ceres::Solver::Summary summary;
+    ceres::Solve(solver_options, &problem, &summary);
+    std::cerr << summary.BriefReport() << std::endl;
+    return summary.IsSolutionUsable();
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) {
+        std::cerr << "usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]" << std::endl;
+        return EXIT_FAILURE;
+    }
+    ceres_slam::FeatureTracker tracker;
+    bool use_sgbm = false;
+    for (int a = 2; a < argc; ++a) {
+        if (!std::strcmp(argv[a], "--sgbm")) use_sgbm = true;
+        else if (!std::strcmp(argv[a], "--fast-threshold") && a + 1 < argc) tracker.params.fast_threshold = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--max-features") && a + 1 < argc) tracker.params.max_features = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--min-track-length") && a + 1 < argc) tracker.params.min_track_length = std::atoi(argv[++a]);
+        else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
+    }
+    FILE *f = std::fopen(argv[1], "rb");
+    int32_t head[8], sg[11];
+    double scale_cam[6], start[12];
+    if (!f || std::fread(head, sizeof head, 1, f) != 1 || std::fread(scale_cam, sizeof scale_cam, 1, f) != 1 || std::fread(start, sizeof start, 1, f) != 1 ||
+        std::fread(sg, sizeof sg, 1, f) != 1 || head[0] < 2 || head[1] <= 0 || head[2] <= 0) {
+        std::cerr << "cannot read " << argv[1] << std::endl;
+        return EXIT_FAILURE;
+    }
+    const int frames = head[0], rows = head[1], cols = head[2];
+    const size_t npix = (size_t)rows * cols;
+    std::vector<uint8_t> left(npix * frames), right(npix * frames);
+    for (int k = 0; k < frames; ++k)
+        if (std::fread(&left[npix * k], 1, npix, f) != npix || std::fread(&right[npix * k], 1, npix, f) != npix) {
+            std::cerr << "short file " << argv[1] << std::endl;
+            return EXIT_FAILURE;
+        }
+    std::fclose(f);
+    ceres_slam::DatasetProblem::CameraPtr camera = std::make_shared<const ceres_slam::StereoCamera>(scale_cam[1], scale_cam[2], scale_cam[3], scale_cam[4], scale_cam[5]);
+
+    ceres_slam::DatasetProblem dataset;
+    try {
+        if (use_sgbm) {
+            ceres_slam::StereoSGBM sgbm(sg[0], sg[1], sg[2], sg[3], sg[4], sg[5], sg[6], sg[7], sg[8], sg[9], sg[10] != 0);
+            std::vector<ceres_slam::Image8> l, r;
+            for (int k = 0; k < frames; ++k) {
+                l.push_back(ceres_slam::Image8(rows, cols, &left[npix * k]));
+                r.push_back(ceres_slam::Image8(rows, cols, &right[npix * k]));
+            }
+            std::vector<ceres_slam::DisparityMap> maps;
+            sgbm(l, r, maps);
+            std::vector<int16_t> disp16(npix * frames);
+            for (int k = 0; k < frames; ++k) std::memcpy(&disp16[npix * k], maps[k].disp16.data(), npix * sizeof(int16_t));
+            tracker.track(left.data(), nullptr, disp16.data(), frames, rows, cols, camera, &dataset);
+        } else {
+            tracker.track(left.data(), right.data(), nullptr, frames, rows, cols, camera, &dataset);
+        }
+    } catch (const std::exception &e) {
+        std::cerr << e.what() << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::cerr << dataset.stereo_obs_list.size() << " observations of " << dataset.num_points << " tracks in " << frames << " frames" << std::endl;
+    if (!dataset.compute_initial_guess()) return EXIT_FAILURE;
+    const bool usable = solveAll(dataset);
+
+    std::cout.precision(17);
+    for (int k = 0; k < frames; ++k) {
+        std::cout << "frame " << k;
+        for (int c = 0; c < 12; ++c) std::cout << " " << dataset.poses[k].data()[c];
+        std::cout << std::endl;
+    }
+    return usable ? EXIT_SUCCESS : EXIT_FAILURE;
+}

@@ -221,6 +221,10 @@ class DatasetProblem {
     const std::vector<uint> &obs_indices_at_state(uint k) const { return state_indices_.at(k); }
     const std::vector<uint> &obs_indices_for_feature(uint j) const { return feature_indices_.at(j); }
 
+    //! Rebuild the per-state / per-feature lists after state_ids / point_ids were filled by something other than read_csv
+    //! (ceres_slam::FeatureTracker, feature_tracks.hpp)
+    void rebuild_indices() { build_indices(); }
+
     //! Reset initialization flags for all points (dataset_problem.cpp:175-177)
     void reset_points() { initialized_point.assign(num_points, false); }
 

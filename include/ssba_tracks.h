@@ -1,0 +1,112 @@
+/*
+ * ssba_tracks.h -- C ABI of libssba_tracks.so: sparse stereo feature tracks from raw 8-bit frames.
+ *
+ * The sparse branch (ssba_frontend_vo, ssba_add_stereo_observations; include/ssba.h) starts at rows [k, j, u, v, d] with
+ * landmark ids.  The reference's own producer of such rows is its stereo-odometry node,
+ * ros/src/ceres_slam/src/sparse_stereo_odometry_node.cpp:127-216: detect and describe in the left and right image, match left
+ * to right with a cross-checked Hamming matcher (cv::BFMatcher(NORM_HAMMING, true)), keep pairs with |dy| < 5 and
+ * x_right < x_left, match the survivors' left descriptors from frame to frame with the same matcher.  This library does that
+ * on the device, from a stack of frames to the arrays ssba_frontend_vo takes, stated entirely in integers: the yardstick is
+ * the numpy statement tests/tracks_reference.py, which the device equals to the bit.  OpenCV can be neither built nor run
+ * where this library is tested, so parity with cv::ORB / cv::BFMatcher is UNPINNED; "this library's own rule" marks each place
+ * where the arithmetic departs from the node on purpose.
+ *
+ * It is a library of its own: it shares no state with a solver handle and exports nothing but the names below.  Status codes
+ * are ssba_status values (include/ssba.h is included for that enum only); the last-error string is this library's own.
+ *
+ * The arithmetic
+ *   detector    the segment test on the 16-pixel Bresenham ring of radius 3 around a centre c, ring pixel i at (dx, dy) =
+ *                   (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3)
+ *               with values I_0 ... I_15.  An arc is 9 consecutive ring pixels, i ... i + 8 with indices wrapping 15 -> 0; there
+ *               are 16.  s = max(0, max over arcs of min (I_i - c), max over arcs of min (c - I_i)): the largest threshold at
+ *               which the segment test still holds, plus one.  A pixel is a candidate when s > fast_threshold and it lies
+ *               at least SSBA_TRACK_BORDER = 15 pixels from every edge (13 for the descriptor's offsets plus 2 for its box), i.e.
+ *               15 <= x < cols - 15 and 15 <= y < rows - 15.  Every other pixel has score 0.
+ *   suppression 3 x 3: a candidate p survives if for each of its eight neighbours q  s(p) > s(q), or s(p) == s(q) and the
+ *               row-major index of p is smaller than that of q.
+ *   selection   at most max_features per image: the highest scores; among equal scores at the cut the smallest row-major
+ *               indices.  The kept keypoints are output in ROW-MAJOR order, not by score (this library's own rule: a position
+ *               that a prefix sum gives, no sort).
+ *   descriptor  BRIEF-256 without orientation (this library's own rule: consecutive frames of a rig barely rotate, and the
+ *               left and right image of a rectified rig do not at all; ORB's steering and pyramid are out of scope).  bit i = 1
+ *               when box(p + a_i) < box(p + b_i), box(q) = the sum of the 5 x 5 pixels around q, an integer, never divided.
+ *               The 256 pairs (a_i, b_i) in [-13, 13]^2 are this project's own, NOT OpenCV's table:
+ *                   s = 20161021;   draw(): s = (s * 1103515245 + 12345) mod 2^31, return ((s >> 16) mod 27) - 13
+ *                   pair i = (ax, ay, bx, by) = four draws in this order, drawn again while a_i == b_i
+ *               tools/brief_pattern.py writes them to csrc/ssba_brief_pattern.h.  A descriptor is 8 uint32 words, bit i at
+ *               word i / 32, position i % 32.
+ *   matching    of a set A against a set B under a gate, cross-checked: for each a the best b minimises the Hamming distance
+ *               over the b that pass the gate with a, the smallest index on ties; the best a of each b likewise; (a, b) is a
+ *               match when each is the other's best and the distance <= max_hamming.  The gate is applied INSIDE the search
+ *               (this library's own rule: the node filters after matching, which discards a feature whose global best lies
+ *               off the epipolar line).
+ *                   SSBA_TRACK_GATE_NONE      every pair passes
+ *                   SSBA_TRACK_GATE_STEREO    A left, B right: |y_a - y_b| < stereo_max_dy (node :157) and 0 < x_a - x_b <= max_disparity
+ *                   SSBA_TRACK_GATE_TEMPORAL  |x_a - x_b| <= temporal_radius and |y_a - y_b| <= temporal_radius; radius 0: no gate
+ *   observation (u, v, d) = (x_l, y_l, x_l - x_r) as doubles for every stereo match of a frame (a "survivor"), in keypoint order.
+ *               With a disp16 stack (the format ssba_stereo_sgbm_batch writes) the right images are not used:
+ *               d = disp16[y][x] / 16.0, and a keypoint whose disp16 is <= 0 (invalid for min_disparity 0, or no positive
+ *               depth) is dropped.  A matcher run with min_disparity >= 2 marks invalid pixels with a positive value; such a map
+ *               must be masked by the caller.
+ *   tracks      only survivors take part (node :170-186).  Frame 0's survivors get ids 0, 1, ... in keypoint order; in frame k a
+ *               survivor matched (temporal gate, A = survivors of frame k - 1, B = those of frame k, left descriptors) to a
+ *               survivor of frame k - 1 inherits its id, every other survivor gets the next free id in keypoint order.  Then
+ *               the observations of tracks shorter than min_track_length are removed and the ids renumbered densely in order of
+ *               first appearance.
+ * No floating point is used before the final conversion of (u, v, d).  Every position in an output comes from a prefix sum, so
+ * two runs give the same bytes.
+ *
+ * SSBA_ERR_INVALID_ARGUMENT, with a message and before a device is looked for: a NULL input or output; both or neither of
+ *   right / disp16; frames < 1 or > 32767 (n likewise, up to 65535); rows or cols < 31 or > 8192; max_features outside
+ *   1 ... 4096; fast_threshold outside 0 ... 254; max_hamming outside 0 ... 256; a negative stereo_max_dy, max_disparity or
+ *   temporal_radius; min_track_length < 1; an unknown gate; na or nb > 65535.  After the work: a capacity below the number of
+ *   observations (the message names the number needed; nothing is written).
+ * All three calls are synchronous: host arrays in and out, the work on a pooled stream.
+ */
+#ifndef SSBA_TRACKS_H_
+#define SSBA_TRACKS_H_
+
+#include "ssba.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SSBA_TRACK_BORDER 15
+#define SSBA_TRACK_MAX_FEATURES 4096
+#define SSBA_TRACK_DESC_WORDS 8
+#define SSBA_TRACK_GATE_NONE 0
+#define SSBA_TRACK_GATE_STEREO 1
+#define SSBA_TRACK_GATE_TEMPORAL 2
+
+/* ssba_track_default_params: fast_threshold 20, max_features 1000, stereo_max_dy 5, max_disparity 128, max_hamming 64,
+ * temporal_radius 0, min_track_length 2 */
+typedef struct {
+    int32_t fast_threshold, max_features, stereo_max_dy, max_disparity, max_hamming, temporal_radius, min_track_length;
+} ssba_track_params;
+SSBA_API void ssba_track_default_params(ssba_track_params *params);
+
+/* Detector and descriptor alone over a stack of n images of rows x cols: count[n]; xy (n * max_features * 2: x, y),
+ * score (n * max_features) and desc (n * max_features * 8) hold image k's keypoints from slot k * max_features on, zeros behind
+ * the count.  Four launches whatever n. */
+SSBA_API int ssba_track_features(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const ssba_track_params *params, int device,
+                                 uint32_t *count, uint16_t *xy, uint8_t *score, uint32_t *desc);
+
+/* The matcher alone: match_a[i] = the index in B of a_i's match or -1, dist_a[i] its Hamming distance or -1.  desc_a / xy_a
+ * may be NULL when na = 0, and likewise for B. */
+SSBA_API int ssba_track_match(const uint32_t *desc_a, const uint16_t *xy_a, uint32_t na, const uint32_t *desc_b, const uint16_t *xy_b, uint32_t nb,
+                              int gate, const ssba_track_params *params, int device, int32_t *match_a, int32_t *dist_a);
+
+/* Everything: left holds `frames` images, then exactly one of right (as many) and disp16 (as many maps, int16) is given.
+ * Outputs in ssba_frontend_vo's input format: state_start (frames + 1), point_id and uvd (3 per observation) with room for
+ * `capacity` observations, *num_observations, *num_points.  The number of launches does not depend on `frames`. */
+SSBA_API int ssba_track_sequence(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
+                                 const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
+                                 double *uvd, uint64_t *num_observations, uint32_t *num_points);
+
+SSBA_API const char *ssba_track_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SSBA_TRACKS_H_ */

@@ -12,6 +12,11 @@
 //   k_tr_best       the same kernel over the F - 1 pairs of consecutive survivors
 //   k_tr_link       ids: one work-group walks the frames                           grid (1)
 //   k_tr_prune      short tracks out, ids renumbered, observations written         grid (1)
+// ssba_track_sequence_subpixel puts two launches in front of k_tr_prune:
+//   k_tr_anchor     per id the survivor slot that issued it                        grid (max_features / 256, frames)
+//   k_tr_refine     one wave per survivor: the anchor's 15 x 15 template placed    grid (max_features / 4, frames)
+//                   in the left image (2-D), then in the right image (x only)
+// and ssba_track_refine runs the same placement (rf_solve) over a list of items: k_tr_refine_items, grid (items / 4).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -421,12 +426,13 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_link(const uint32_t *__restrict
 }
 
 // The same work-group shape: new ids = a running prefix over (length >= min_track_length) in id order, which is the order of
-// first appearance; then the kept observations of every frame in keypoint order.
+// first appearance; then the kept observations of every frame in keypoint order.  refined: NULL, or (u, v, d) in 1/256 pixel
+// per survivor slot from k_tr_refine, which has also set the id of every survivor it dropped to TR_NONE.
 __global__ __launch_bounds__(TR_BLOCK) void k_tr_prune(const uint32_t *__restrict__ surv_count, const uint16_t *__restrict__ surv_xy, const int32_t *__restrict__ surv_d16,
                                                        const uint32_t *__restrict__ id, const uint32_t *__restrict__ length, const uint32_t *__restrict__ num_ids,
-                                                       int frames, uint32_t stride, int min_track_length, uint32_t *__restrict__ new_id,
-                                                       uint32_t *__restrict__ state_start, uint32_t *__restrict__ point_id, double *__restrict__ uvd,
-                                                       uint32_t *__restrict__ totals) {
+                                                       int frames, uint32_t stride, int min_track_length, const int32_t *__restrict__ refined,
+                                                       uint32_t *__restrict__ new_id, uint32_t *__restrict__ state_start, uint32_t *__restrict__ point_id,
+                                                       double *__restrict__ uvd, uint32_t *__restrict__ totals) {
     __shared__ uint32_t part[TR_BLOCK / 64];
     const uint32_t ids = min(*num_ids, (uint32_t)frames * stride);
     uint32_t run = 0;
@@ -468,9 +474,14 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_prune(const uint32_t *__restric
             if (renamed[i] == TR_NONE) continue;
             const uint32_t j = threadIdx.x * TR_ITEMS + i;
             point_id[pos] = renamed[i];                       // pos < frames * stride: at most one observation per survivor slot
-            uvd[3 * (size_t)pos] = (double)surv_xy[2 * (cur + j)];
-            uvd[3 * (size_t)pos + 1] = (double)surv_xy[2 * (cur + j) + 1];
-            uvd[3 * (size_t)pos + 2] = (double)surv_d16[cur + j] / 16.0;
+            if (refined) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) uvd[3 * (size_t)pos + c] = (double)refined[3 * (cur + j) + c] / 256.0;
+            } else {
+                uvd[3 * (size_t)pos] = (double)surv_xy[2 * (cur + j)];
+                uvd[3 * (size_t)pos + 1] = (double)surv_xy[2 * (cur + j) + 1];
+                uvd[3 * (size_t)pos + 2] = (double)surv_d16[cur + j] / 16.0;
+            }
             ++pos;
         }
         written += total;
@@ -479,6 +490,271 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_prune(const uint32_t *__restric
         state_start[frames] = written;
         totals[0] = written;
         totals[1] = run;
+    }
+}
+
+// ---- sub-pixel refinement ---------------------------------------------------------------------------------------------------
+// One wave places one 15 x 15 template.  Lane l owns window pixels l, l + 64, l + 128, l + 192 (< 225) and keeps their T, gx, gy
+// in registers.  Every tap an evaluation can read lies within max_shift + 8 pixels of the start, so that neighbourhood of the
+// target is staged in LDS once, (16 + 2 max_shift)^2 bytes in rows of RF_TILE, and the dependent evaluations read LDS only.
+// The sums are integers and meet in xor butterflies, so every lane holds the same step and the control flow is wave-uniform.
+constexpr int RF_RADIUS = 7;
+constexpr int RF_SIDE = 2 * RF_RADIUS + 1;           // 15
+constexpr int RF_PIXELS = RF_SIDE * RF_SIDE;         // 225
+constexpr int RF_PER_LANE = 4;
+constexpr int RF_TILE = 32;                          // 16 + 2 * 8, the largest max_shift
+constexpr int RF_WAVES = 4;
+constexpr int RF_ITEM = 7;
+
+static_assert(RF_PER_LANE * 64 >= RF_PIXELS, "the lanes of a wave cover the window");
+
+struct RefineTemplate {
+    int T[RF_PER_LANE], gx[RF_PER_LANE], gy[RF_PER_LANE];
+};
+
+struct RefineResult {
+    int x, y, status;
+    uint32_t sad;
+};
+
+// sums modulo 2^32: a signed total is the cast of the result
+__device__ __forceinline__ uint32_t rf_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+__device__ __forceinline__ long long rf_wave_sum64(long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(v >> 32), d, 64);
+        v += (long long)(((unsigned long long)hi << 32) | lo);
+    }
+    return v;
+}
+
+// false: the 17 x 17 support of the anchor leaves its image (nothing is read)
+__device__ __forceinline__ bool rf_template(const uint8_t *__restrict__ A, int rows, int cols, int ax, int ay, int lane, RefineTemplate *t) {
+    if (ax < RF_RADIUS + 1 || ay < RF_RADIUS + 1 || ax >= cols - RF_RADIUS - 1 || ay >= rows - RF_RADIUS - 1) return false;
+#pragma unroll
+    for (int m = 0; m < RF_PER_LANE; ++m) {
+        const int k = lane + 64 * m;
+        t->T[m] = t->gx[m] = t->gy[m] = 0;
+        if (k < RF_PIXELS) {
+            const int j = k / RF_SIDE - RF_RADIUS, i = k % RF_SIDE - RF_RADIUS;
+            const uint8_t *p = A + (size_t)(ay + j) * cols + (ax + i);
+            t->T[m] = p[0];
+            t->gx[m] = (int)p[1] - (int)p[-1];
+            t->gy[m] = (int)p[cols] - (int)p[-cols];
+        }
+    }
+    return true;
+}
+
+// a tap of the window at (px, py) falls outside the image
+__device__ __forceinline__ bool rf_leaves(int px, int py, int rows, int cols) {
+    const int cx = px >> 8, cy = py >> 8;
+    return cx < RF_RADIUS || cy < RF_RADIUS || cx >= cols - RF_RADIUS - 1 || cy >= rows - RF_RADIUS - 1;
+}
+
+// The only floating point of the library before the outputs: IEEE doubles, every product rounded before the subtraction.
+__device__ __forceinline__ void rf_step(int H11, int H12, int H22, long long det, long long bx, long long by, int mode, double *dx, double *dy) {
+#pragma clang fp contract(off)
+    if (mode) {
+        *dx = rint((double)bx / ((double)H11 * 128.0));
+        *dy = 0.0;
+        return;
+    }
+    const double scale = (double)det * 128.0;
+    const double nx = (double)H22 * (double)bx - (double)H12 * (double)by;
+    const double ny = (double)H11 * (double)by - (double)H12 * (double)bx;
+    *dx = rint(nx / scale);
+    *dy = rint(ny / scale);
+}
+
+// The position of template t in image B, started at (x0, y0) in 1/256 pixel; mode 1: x only.  Every thread of the work-group
+// calls it together, because the staging is fenced by two barriers; a wave with live == false only keeps them company and gets
+// {x0, y0, OK, 0}.  `tile` is the wave's own RF_TILE * RF_TILE bytes.
+__device__ __forceinline__ RefineResult rf_solve(uint8_t *tile, bool live, const RefineTemplate &t, const uint8_t *__restrict__ B, int rows, int cols, int x0,
+                                                 int y0, int mode, const ssba_track_refine_params rp, int lane) {
+    RefineResult r = {x0, y0, SSBA_TRACK_REFINE_OK, 0u};
+    if (live && rf_leaves(x0, y0, rows, cols)) {
+        r.status = SSBA_TRACK_REFINE_EDGE;
+        live = false;
+    }
+    const int side = 16 + 2 * rp.max_shift, ox = (x0 >> 8) - rp.max_shift - RF_RADIUS, oy = (y0 >> 8) - rp.max_shift - RF_RADIUS;
+    if (live)
+        for (int k = lane; k < side * side; k += 64) {
+            const int ty = k / side, tx = k - ty * side;
+            const int sx = min(max(ox + tx, 0), cols - 1), sy = min(max(oy + ty, 0), rows - 1);      // a clamped byte is never a tap
+            tile[ty * RF_TILE + tx] = B[(size_t)sy * cols + sx];
+        }
+    __syncthreads();
+    if (live) {
+        int h11 = 0, h12 = 0, h22 = 0;
+#pragma unroll
+        for (int m = 0; m < RF_PER_LANE; ++m) {
+            const int gx = t.gx[m], gy = mode ? 0 : t.gy[m];
+            h11 += gx * gx;
+            h12 += gx * gy;
+            h22 += gy * gy;
+        }
+        const int H11 = (int)rf_wave_sum((uint32_t)h11), H12 = (int)rf_wave_sum((uint32_t)h12), H22 = (int)rf_wave_sum((uint32_t)h22);      // |H| < 2^26
+        const long long det = (long long)H11 * H22 - (long long)H12 * H12;
+        const bool flat = mode ? H11 <= 0 : det <= 0;
+        int px = x0, py = y0, status = SSBA_TRACK_REFINE_ITERATIONS;
+        uint32_t sad = 0;
+        for (int it = 0; it < rp.iterations; ++it) {
+            if (rf_leaves(px, py, rows, cols)) {
+                status = SSBA_TRACK_REFINE_EDGE;
+                break;
+            }
+            if (flat) {
+                status = SSBA_TRACK_REFINE_FLAT;
+                break;
+            }
+            long long bx = 0, by = 0;
+            uint32_t sabs = 0;
+#pragma unroll
+            for (int m = 0; m < RF_PER_LANE; ++m) {
+                const int k = lane + 64 * m;
+                if (k < RF_PIXELS) {
+                    const int j = k / RF_SIDE - RF_RADIUS, i = k % RF_SIDE - RF_RADIUS;
+                    const int X = px + 256 * i, Y = py + 256 * j, fx = X & 255, fy = Y & 255;
+                    // |p - start| <= 256 max_shift (the FAR test of the step before): 0 <= column, row and column + 1, row + 1 < side
+                    const uint8_t *q = tile + ((Y >> 8) - oy) * RF_TILE + ((X >> 8) - ox);
+                    const int S = (256 - fx) * (256 - fy) * q[0] + fx * (256 - fy) * q[1] + (256 - fx) * fy * q[RF_TILE] + fx * fy * q[RF_TILE + 1];
+                    const int e = S - 65536 * t.T[m];
+                    bx += (long long)t.gx[m] * e;
+                    if (!mode) by += (long long)t.gy[m] * e;
+                    sabs += (uint32_t)abs(e);
+                }
+            }
+            bx = rf_wave_sum64(bx);
+            by = rf_wave_sum64(by);
+            sad = rf_wave_sum(sabs) >> 16;                      // the sum is below 225 * 255 * 65536 < 2^32
+            double dx, dy;
+            rf_step(H11, H12, H22, det, bx, by, mode, &dx, &dy);
+            if (!(fabs(dx) < 1e9 && fabs(dy) < 1e9)) {          // far beyond any max_shift; below, the step is an exact int
+                status = SSBA_TRACK_REFINE_FAR;
+                break;
+            }
+            const int sx = (int)dx, sy = (int)dy;
+            px -= sx;
+            py -= sy;
+            if (max(abs(px - x0), abs(py - y0)) > 256 * rp.max_shift) {
+                status = SSBA_TRACK_REFINE_FAR;
+                break;
+            }
+            if (max(abs(sx), abs(sy)) <= 1) {
+                status = SSBA_TRACK_REFINE_OK;
+                break;
+            }
+        }
+        if (status == SSBA_TRACK_REFINE_OK && rp.max_sad > 0 && sad > (uint32_t)rp.max_sad) status = SSBA_TRACK_REFINE_SAD;
+        r.status = status;
+        r.sad = sad;
+        if (status == SSBA_TRACK_REFINE_OK) {
+            r.x = px;
+            r.y = py;
+        }
+    }
+    __syncthreads();          // the tile is free for the next call
+    return r;
+}
+
+// ssba_track_refine: item k = anchor image, ax, ay, target image, x0, y0, mode; the host has checked the image indices and the mode
+__global__ __launch_bounds__(64 * RF_WAVES) void k_tr_refine_items(const uint8_t *__restrict__ images, int rows, int cols, const int32_t *__restrict__ items,
+                                                                    uint32_t num_items, ssba_track_refine_params rp, int32_t *__restrict__ xy,
+                                                                    int32_t *__restrict__ status, uint32_t *__restrict__ sad) {
+    __shared__ uint8_t tiles[RF_WAVES][RF_TILE * RF_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k = blockIdx.x * RF_WAVES + wave;
+    const bool live = k < num_items;
+    int it[RF_ITEM] = {0, 0, 0, 0, 0, 0, 0};
+    if (live)
+#pragma unroll
+        for (int c = 0; c < RF_ITEM; ++c) it[c] = items[(size_t)k * RF_ITEM + c];
+    const size_t npix = (size_t)rows * cols;
+    RefineTemplate t = {};
+    const bool inside = live && rf_template(images + (size_t)it[0] * npix, rows, cols, it[1], it[2], lane, &t);
+    RefineResult r = rf_solve(tiles[wave], inside, t, images + (size_t)it[3] * npix, rows, cols, it[4], it[5], it[6], rp, lane);
+    if (live && lane == 0) {
+        xy[2 * (size_t)k] = r.x;
+        xy[2 * (size_t)k + 1] = r.y;
+        status[k] = inside ? r.status : SSBA_TRACK_REFINE_EDGE;
+        sad[k] = r.sad;
+    }
+}
+
+// anchor[id] = the survivor slot f * stride + j that issued the id: the survivor that inherited none (k_tr_link's test)
+__global__ __launch_bounds__(256) void k_tr_anchor(const uint32_t *__restrict__ surv_count, const uint32_t *__restrict__ best_pn, const uint32_t *__restrict__ best_np,
+                                                   const uint32_t *__restrict__ id, int frames, uint32_t stride, int max_hamming, uint32_t *__restrict__ anchor,
+                                                   uint32_t *__restrict__ dropped) {
+    const int f = blockIdx.y;
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (f == 0 && j == 0) *dropped = 0;           // k_tr_refine counts into it
+    if (j >= min(surv_count[f], stride)) return;
+    const uint32_t np = f ? min(surv_count[f - 1], stride) : 0u;
+    const size_t cur = (size_t)f * stride, prev = (size_t)(f ? f - 1 : 0) * stride;
+    uint32_t a = 0;
+    if (f && tr_mutual(best_np + prev, best_pn + prev, j, np, max_hamming, &a)) return;
+    const uint32_t mine = id[cur + j];
+    if (mine < (uint32_t)frames * stride) anchor[mine] = (uint32_t)(cur + j);
+}
+
+// Survivor j of frame f against the template of its id's anchor: the left position in 2-D from the keypoint (the anchor itself
+// keeps its pixel), then with right images the right position in x only on the refined row, d = x_left - x_right.  A survivor
+// whose status is not OK is dropped: its id slot is masked for k_tr_prune and its track is one shorter (integer atomics, the
+// order does not matter).  refined[slot] = (u, v, d) in 1/256 pixel.
+__global__ __launch_bounds__(64 * RF_WAVES) void k_tr_refine(const uint8_t *__restrict__ images, int frames, int rows, int cols, int has_right,
+                                                              const uint32_t *__restrict__ surv_count, const uint16_t *__restrict__ surv_xy,
+                                                              const int32_t *__restrict__ surv_d16, const uint32_t *__restrict__ anchor, uint32_t stride,
+                                                              ssba_track_refine_params rp, uint32_t *id, uint32_t *length, int32_t *__restrict__ refined,
+                                                              uint32_t *dropped) {
+    __shared__ uint8_t tiles[RF_WAVES][RF_TILE * RF_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int f = blockIdx.y;
+    const uint32_t n = min(surv_count[f], stride), j = blockIdx.x * RF_WAVES + wave;
+    if (blockIdx.x * RF_WAVES >= n) return;          // the whole work-group leaves together
+    const size_t npix = (size_t)rows * cols, cur = (size_t)f * stride, slots = (size_t)frames * stride;
+    bool live = j < n;
+    uint32_t mine = TR_NONE, a = 0;
+    if (live) {
+        mine = id[cur + j];
+        live = mine < slots;
+        if (live) a = anchor[mine];
+        live = live && a < slots;                    // holds: every id has the slot that issued it
+    }
+    int x = 0, y = 0, d16 = 0, ax = 0, ay = 0;
+    if (live) {
+        x = surv_xy[2 * (cur + j)];
+        y = surv_xy[2 * (cur + j) + 1];
+        d16 = surv_d16[cur + j];
+        ax = surv_xy[2 * (size_t)a];
+        ay = surv_xy[2 * (size_t)a + 1];
+    }
+    RefineTemplate t = {};
+    const bool inside = live && rf_template(images + (size_t)(a / stride) * npix, rows, cols, ax, ay, lane, &t);      // holds: keypoints keep 15 pixels
+    const bool self = a == cur + j;
+    const RefineResult l = rf_solve(tiles[wave], inside && !self, t, images + (size_t)f * npix, rows, cols, 256 * x, 256 * y, 0, rp, lane);
+    int status = inside ? l.status : SSBA_TRACK_REFINE_EDGE, dq8 = 16 * d16;
+    const bool pair = has_right && inside && status == SSBA_TRACK_REFINE_OK;
+    const RefineResult r = rf_solve(tiles[wave], pair, t, images + (size_t)(has_right ? frames + f : f) * npix, rows, cols, l.x - 16 * d16, l.y, 1, rp, lane);
+    if (pair) {
+        status = r.status;
+        dq8 = l.x - r.x;
+        if (status == SSBA_TRACK_REFINE_OK && dq8 <= 0) status = SSBA_TRACK_REFINE_DISPARITY;
+    }
+    if (live && lane == 0) {
+        refined[3 * (cur + j)] = l.x;
+        refined[3 * (cur + j) + 1] = l.y;
+        refined[3 * (cur + j) + 2] = dq8;
+        if (status != SSBA_TRACK_REFINE_OK) {
+            id[cur + j] = TR_NONE;
+            atomicSub(&length[mine], 1u);
+            atomicAdd(dropped, 1u);
+        }
     }
 }
 
@@ -516,6 +792,14 @@ int tr_check_params(const char *call, const ssba_track_params *p) {
     if (p->stereo_max_dy < 0 || p->max_disparity < 0 || p->temporal_radius < 0)
         return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "stereo_max_dy, max_disparity and temporal_radius must not be negative");
     if (p->min_track_length < 1) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "min_track_length must be at least 1");
+    return SSBA_OK;
+}
+
+int tr_check_refine_params(const char *call, const ssba_track_refine_params *p) {
+    if (!p) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL refine parameters");
+    if (p->iterations < 1 || p->iterations > 64) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "iterations must be in 1 ... 64");
+    if (p->max_shift < 1 || p->max_shift > 8) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "max_shift must be in 1 ... 8");
+    if (p->max_sad < 0) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "max_sad must not be negative");
     return SSBA_OK;
 }
 
@@ -631,12 +915,14 @@ struct SequenceOut {
     double *uvd;
     uint64_t *num_observations;
     uint32_t *num_points;
+    uint64_t *num_dropped = nullptr;      // ssba_track_sequence_subpixel only
     uint32_t needed = 0;
     bool too_small = false;
 };
 
+// refine: NULL for whole-pixel observations, or the parameters of the two launches that put sub-pixel ones in front of k_tr_prune
 hipError_t tr_run_sequence(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
-                           const ssba_track_params &p, SequenceOut *o, hipStream_t s, std::vector<void *> *temps) {
+                           const ssba_track_params &p, const ssba_track_refine_params *refine, SequenceOut *o, hipStream_t s, std::vector<void *> *temps) {
     const size_t npix = (size_t)rows * cols, stack = npix * frames;
     const uint32_t n = right ? 2 * frames : frames, stride = (uint32_t)p.max_features;
     const size_t slots = (size_t)frames * stride;
@@ -668,7 +954,7 @@ hipError_t tr_run_sequence(const uint8_t *left, const uint8_t *right, const int1
     TR_TRY(tr_alloc(temps, &id, slots));
     TR_TRY(tr_alloc(temps, &length, slots));
     TR_TRY(tr_alloc(temps, &new_id, slots));
-    TR_TRY(tr_alloc(temps, &scalars, (size_t)3));                 // the number of ids; observations and points after pruning
+    TR_TRY(tr_alloc(temps, &scalars, (size_t)4));                 // the number of ids; observations and points after pruning; dropped
     TR_TRY(tr_alloc(temps, &d_start, (size_t)frames + 1));
     TR_TRY(tr_alloc(temps, &d_point, slots));
     TR_TRY(tr_alloc(temps, &d_uvd, slots * 3));
@@ -687,11 +973,25 @@ hipError_t tr_run_sequence(const uint8_t *left, const uint8_t *right, const int1
     hipLaunchKernelGGL(k_tr_link, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)sv.count, (const uint32_t *)best_pn, (const uint32_t *)best_np, (int)frames, stride,
                        p.max_hamming, id, length, scalars);
     TR_TRY(hipGetLastError());
+    int32_t *refined = nullptr;
+    if (refine) {
+        uint32_t *anchor = nullptr;
+        TR_TRY(tr_alloc(temps, &anchor, slots));
+        TR_TRY(tr_alloc(temps, &refined, slots * 3));
+        hipLaunchKernelGGL(k_tr_anchor, dim3((stride + 255) / 256, frames), dim3(256), 0, s, (const uint32_t *)sv.count, (const uint32_t *)best_pn,
+                           (const uint32_t *)best_np, (const uint32_t *)id, (int)frames, stride, p.max_hamming, anchor, scalars + 3);
+        TR_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_tr_refine, dim3((stride + RF_WAVES - 1) / RF_WAVES, frames), dim3(64 * RF_WAVES), 0, s, (const uint8_t *)dimg, (int)frames, (int)rows,
+                           (int)cols, right ? 1 : 0, (const uint32_t *)sv.count, (const uint16_t *)sv.xy, (const int32_t *)sv.d16, (const uint32_t *)anchor, stride,
+                           *refine, id, length, refined, scalars + 3);
+        TR_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_tr_prune, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)sv.count, (const uint16_t *)sv.xy, (const int32_t *)sv.d16, (const uint32_t *)id,
-                       (const uint32_t *)length, (const uint32_t *)scalars, (int)frames, stride, p.min_track_length, new_id, d_start, d_point, d_uvd, scalars + 1);
+                       (const uint32_t *)length, (const uint32_t *)scalars, (int)frames, stride, p.min_track_length, (const int32_t *)refined, new_id, d_start, d_point,
+                       d_uvd, scalars + 1);
     TR_TRY(hipGetLastError());
-    uint32_t totals[2] = {0, 0};
-    TR_TRY(hipMemcpyAsync(totals, scalars + 1, sizeof totals, hipMemcpyDeviceToHost, s));
+    uint32_t totals[3] = {0, 0, 0};
+    TR_TRY(hipMemcpyAsync(totals, scalars + 1, (refine ? 3 : 2) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     TR_TRY(hipStreamSynchronize(s));
     o->needed = totals[0];
     if ((uint64_t)totals[0] > o->capacity) {
@@ -706,7 +1006,30 @@ hipError_t tr_run_sequence(const uint8_t *left, const uint8_t *right, const int1
     TR_TRY(hipStreamSynchronize(s));
     *o->num_observations = totals[0];
     *o->num_points = totals[1];
+    if (o->num_dropped) *o->num_dropped = totals[2];
     return hipSuccess;
+}
+
+hipError_t tr_run_refine(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const int32_t *items, uint32_t num_items,
+                         const ssba_track_refine_params &rp, int32_t *xy, int32_t *status, uint32_t *sad, hipStream_t s, std::vector<void *> *temps) {
+    const size_t all = (size_t)rows * cols * n;
+    uint8_t *dimg = nullptr;
+    int32_t *ditems = nullptr, *dxy = nullptr, *dstatus = nullptr;
+    uint32_t *dsad = nullptr;
+    TR_TRY(tr_alloc(temps, &dimg, all));
+    TR_TRY(tr_alloc(temps, &ditems, (size_t)num_items * RF_ITEM));
+    TR_TRY(tr_alloc(temps, &dxy, (size_t)num_items * 2));
+    TR_TRY(tr_alloc(temps, &dstatus, (size_t)num_items));
+    TR_TRY(tr_alloc(temps, &dsad, (size_t)num_items));
+    TR_TRY(hipMemcpyAsync(dimg, images, all, hipMemcpyHostToDevice, s));
+    TR_TRY(hipMemcpyAsync(ditems, items, (size_t)num_items * RF_ITEM * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tr_refine_items, dim3((num_items + RF_WAVES - 1) / RF_WAVES), dim3(64 * RF_WAVES), 0, s, (const uint8_t *)dimg, (int)rows, (int)cols,
+                       (const int32_t *)ditems, num_items, rp, dxy, dstatus, dsad);
+    TR_TRY(hipGetLastError());
+    TR_TRY(hipMemcpyAsync(xy, dxy, (size_t)num_items * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipMemcpyAsync(status, dstatus, (size_t)num_items * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipMemcpyAsync(sad, dsad, (size_t)num_items * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
 }
 
 int tr_close(const char *call, hipError_t e, hipStream_t s, std::vector<void *> *temps) {
@@ -781,7 +1104,59 @@ int ssba_track_sequence(const uint8_t *left, const uint8_t *right, const int16_t
     if (const int rc = tr_open_device(call, device, &s)) return rc;
     std::vector<void *> temps;
     SequenceOut o = {capacity, state_start, point_id, uvd, num_observations, num_points};
-    const hipError_t e = tr_run_sequence(left, right, disp16, frames, rows, cols, *params, &o, s, &temps);
+    const hipError_t e = tr_run_sequence(left, right, disp16, frames, rows, cols, *params, nullptr, &o, s, &temps);
+    const int rc = tr_close(call, e, s, &temps);
+    if (rc) return rc;
+    if (o.too_small)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(capacity) + " is below the " + std::to_string(o.needed) + " observations found");
+    return SSBA_OK;
+}
+
+void ssba_track_default_refine_params(ssba_track_refine_params *params) {
+    if (!params) return;
+    *params = ssba_track_refine_params{10, 4, 0};
+}
+
+int ssba_track_refine(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const int32_t *items, uint32_t num_items,
+                      const ssba_track_refine_params *refine_params, int device, int32_t *xy_q8, int32_t *status, uint32_t *sad) {
+    const char *call = "ssba_track_refine";
+    if (!images) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL image");
+    if (num_items && !items) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL items");
+    if (num_items && (!xy_q8 || !status || !sad)) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (const int rc = tr_check_refine_params(call, refine_params)) return rc;
+    if (n < 1 || n > 65535) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "n must be in 1 ... 65535");
+    if (const int rc = tr_check_size(call, rows, cols)) return rc;
+    for (uint32_t k = 0; k < num_items; ++k) {
+        const int32_t *it = items + (size_t)k * RF_ITEM;
+        if (it[0] < 0 || (uint32_t)it[0] >= n || it[3] < 0 || (uint32_t)it[3] >= n)
+            return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "item " + std::to_string(k) + " names an image index outside 0 ... n - 1");
+        if (it[6] != 0 && it[6] != 1) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "item " + std::to_string(k) + " has an unknown mode");
+    }
+    if (!num_items) return SSBA_OK;
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    const hipError_t e = tr_run_refine(images, n, rows, cols, items, num_items, *refine_params, xy_q8, status, sad, s, &temps);
+    return tr_close(call, e, s, &temps);
+}
+
+int ssba_track_sequence_subpixel(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
+                                 const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id, double *uvd,
+                                 uint64_t *num_observations, uint32_t *num_points, const ssba_track_refine_params *refine_params, uint64_t *num_dropped) {
+    const char *call = "ssba_track_sequence_subpixel";
+    if (!left) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL left images");
+    if (!right == !disp16) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "exactly one of right and disp16 must be given");
+    if (!state_start || !num_observations || !num_points || !num_dropped || (capacity && (!point_id || !uvd)))
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (const int rc = tr_check_params(call, params)) return rc;
+    if (const int rc = tr_check_refine_params(call, refine_params)) return rc;
+    if (frames < 1 || frames > 32767) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "frames must be in 1 ... 32767");
+    if (const int rc = tr_check_size(call, rows, cols)) return rc;
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    SequenceOut o = {capacity, state_start, point_id, uvd, num_observations, num_points, num_dropped};
+    const hipError_t e = tr_run_sequence(left, right, disp16, frames, rows, cols, *params, refine_params, &o, s, &temps);
     const int rc = tr_close(call, e, s, &temps);
     if (rc) return rc;
     if (o.too_small)

@@ -15,9 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libssba_tracks.so")
 
 #: every symbol include/ssba_tracks.h declares
-SYMBOLS = ["ssba_track_default_params", "ssba_track_features", "ssba_track_match", "ssba_track_sequence", "ssba_track_last_error"]
+SYMBOLS = ["ssba_track_default_params", "ssba_track_features", "ssba_track_match", "ssba_track_sequence", "ssba_track_last_error",
+           "ssba_track_default_refine_params", "ssba_track_refine", "ssba_track_sequence_subpixel"]
 BORDER, MAX_FEATURES, DESC_WORDS = 15, 4096, 8
 GATE_NONE, GATE_STEREO, GATE_TEMPORAL = 0, 1, 2
+REFINE_OK, REFINE_EDGE, REFINE_FLAT, REFINE_FAR, REFINE_ITERATIONS, REFINE_SAD, REFINE_DISPARITY = range(7)
+REFINE_2D, REFINE_X_ONLY = 0, 1
 
 _u8p, _u16p, _u32p, _i16p, _i32p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint16, C.c_uint32, C.c_int16, C.c_int32))
 _dp = C.POINTER(C.c_double)
@@ -27,6 +30,11 @@ class TrackParams(C.Structure):
     """ssba_track_params; track_params(**kw) fills in the library's defaults."""
     _fields_ = [(n, C.c_int32) for n in ("fast_threshold", "max_features", "stereo_max_dy", "max_disparity", "max_hamming", "temporal_radius",
                                          "min_track_length")]
+
+
+class RefineParams(C.Structure):
+    """ssba_track_refine_params; refine_params(**kw) fills in the library's defaults."""
+    _fields_ = [(n, C.c_int32) for n in ("iterations", "max_shift", "max_sad")]
 
 
 _lib = None
@@ -47,6 +55,11 @@ def load():
     L.ssba_track_match.argtypes = [_u32p, _u16p, C.c_uint32, _u32p, _u16p, C.c_uint32, C.c_int, P, C.c_int, _i32p, _i32p]
     L.ssba_track_sequence.argtypes = [_u8p, _u8p, _i16p, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_int, C.c_uint64, _u32p, _u32p, _dp,
                                       C.POINTER(C.c_uint64), _u32p]
+    R = C.POINTER(RefineParams)
+    L.ssba_track_default_refine_params.argtypes = [R]
+    L.ssba_track_default_refine_params.restype = None
+    L.ssba_track_refine.argtypes = [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, _i32p, C.c_uint32, R, C.c_int, _i32p, _i32p, _u32p]
+    L.ssba_track_sequence_subpixel.argtypes = L.ssba_track_sequence.argtypes + [R, C.POINTER(C.c_uint64)]
     L.ssba_track_last_error.restype = C.c_char_p
     _lib = L
     return L
@@ -60,6 +73,16 @@ def check(status: int, where: str):
 def track_params(**kw) -> TrackParams:
     p = TrackParams()
     load().ssba_track_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v))
+    return p
+
+
+def refine_params(**kw) -> RefineParams:
+    p = RefineParams()
+    load().ssba_track_default_refine_params(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -125,3 +148,40 @@ def track_sequence(left, right=None, disp16=None, device: int = -1, capacity: in
                                      C.byref(nobs), C.byref(npts)), "ssba_track_sequence")
     n = int(nobs.value)
     return start, ids[:n].copy(), uvd[:n].copy(), int(npts.value)
+
+
+def track_refine(images, items, device: int = -1, **refine):
+    """The sub-pixel refinement alone (ssba_track_refine).  items (N, 7) int32: anchor image, ax, ay, target image, x0_q8, y0_q8,
+    mode (REFINE_2D or REFINE_X_ONLY).  Returns xy_q8 (N, 2) int32 (the start where the status is not REFINE_OK), status (N,)
+    int32 and sad (N,) uint32."""
+    img = _stack(images, np.uint8, "images")
+    it = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 7)
+    p = refine_params(**refine)
+    n, rows, cols = img.shape
+    xy, status, sad = np.zeros((len(it), 2), np.int32), np.zeros(len(it), np.int32), np.zeros(len(it), np.uint32)
+    check(load().ssba_track_refine(img.ctypes.data_as(_u8p), n, rows, cols, it.ctypes.data_as(_i32p), len(it), C.byref(p), device, xy.ctypes.data_as(_i32p),
+                                   status.ctypes.data_as(_i32p), sad.ctypes.data_as(_u32p)), "ssba_track_refine")
+    return xy, status, sad
+
+
+def track_sequence_subpixel(left, right=None, disp16=None, device: int = -1, capacity: int | None = None, refine=None, **params):
+    """track_sequence with every observation refined to 1/256 pixel against its track's first patch
+    (ssba_track_sequence_subpixel).  refine: a dict of RefineParams fields.  Returns track_sequence's tuple plus num_dropped, the
+    number of observations whose refinement did not end REFINE_OK."""
+    L = _stack(left, np.uint8, "left")
+    F, rows, cols = L.shape
+    R = None if right is None else _stack(right, np.uint8, "right")
+    D = None if disp16 is None else _stack(disp16, np.int16, "disp16")
+    for other, what in ((R, "right"), (D, "disp16")):
+        if other is not None and other.shape != L.shape:
+            raise ValueError(f"{what} must have the shape of left")
+    p, rp = track_params(**params), refine_params(**(refine or {}))
+    cap = F * max(int(p.max_features), 0) if capacity is None else int(capacity)
+    start, ids, uvd = np.zeros(F + 1, np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros((max(cap, 1), 3))
+    nobs, npts, ndrop = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    check(load().ssba_track_sequence_subpixel(L.ctypes.data_as(_u8p), None if R is None else R.ctypes.data_as(_u8p),
+                                              None if D is None else D.ctypes.data_as(_i16p), F, rows, cols, C.byref(p), device, cap, start.ctypes.data_as(_u32p),
+                                              ids.ctypes.data_as(_u32p), uvd.ctypes.data_as(_dp), C.byref(nobs), C.byref(npts), C.byref(rp), C.byref(ndrop)),
+          "ssba_track_sequence_subpixel")
+    n = int(nobs.value)
+    return start, ids[:n].copy(), uvd[:n].copy(), int(npts.value), int(ndrop.value)

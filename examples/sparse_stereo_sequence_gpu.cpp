@@ -5,8 +5,11 @@
 // writes it): the frames, the camera and the matcher's parameters are used, the pyramid fields are not.
 //
 // usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]
+//            [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>]
 // --sgbm takes the disparities from the semi-global matcher (StereoSGBM over all pairs in shared launches, sub-pixel) instead
-// of from left-right feature matches (whole pixels).
+// of from left-right feature matches (whole pixels).  --temporal-radius gates the frame-to-frame matches to r pixels.
+// --subpixel refines every observation to 1/256 pixel against its track's first patch (FeatureTracker::subpixel), --max-sad
+// drops refined observations whose patch difference exceeds s, and --huber puts a ceres::HuberLoss(a) on every residual block.
 // Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
 #include <cmath>
 #include <cstdint>
@@ -22,8 +25,9 @@
 #include "ceres_slam_amd/feature_tracks.hpp"
 
 // tests/dataset_vo.cpp:22-85 over all states, unit stiffness
-static bool solveAll(ceres_slam::DatasetProblem &dataset) {
+static bool solveAll(ceres_slam::DatasetProblem &dataset, double huber) {
     ceres::Problem problem;
+    ceres::LossFunction *loss = huber > 0.0 ? new ceres::HuberLoss(huber) : NULL;
     const double *var = dataset.stereo_obs_var.data();
     const double stiffness[9] = {1.0 / std::sqrt(var[0]), 0, 0, 0, 1.0 / std::sqrt(var[1]), 0, 0, 0, 1.0 / std::sqrt(var[2])};
     ceres::LocalParameterization *se3_perturbation = ceres_slam::SE3Perturbation::Create();
@@ -33,7 +37,7 @@ static bool solveAll(ceres_slam::DatasetProblem &dataset) {
             const ceres_slam::uint j = dataset.point_ids[i];
             if (j >= dataset.num_points || !dataset.initialized_point[j]) continue;     // only initialised map points (:45)
             ceres::CostFunction *cost = ceres_slam::StereoReprojectionErrorAutomatic::Create(dataset.camera, dataset.stereo_obs_list[i].data(), stiffness);
-            problem.AddResidualBlock(cost, NULL, dataset.poses[k].data(), dataset.map_points[j].data());
+            problem.AddResidualBlock(cost, loss, dataset.poses[k].data(), dataset.map_points[j].data());
             used = true;
         }
         if (used) problem.SetParameterization(dataset.poses[k].data(), se3_perturbation);
@@ -50,16 +54,22 @@ static bool solveAll(ceres_slam::DatasetProblem &dataset) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]" << std::endl;
+        std::cerr << "usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]"
+                     " [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>]" << std::endl;
         return EXIT_FAILURE;
     }
     ceres_slam::FeatureTracker tracker;
     bool use_sgbm = false;
+    double huber = 0.0;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--sgbm")) use_sgbm = true;
         else if (!std::strcmp(argv[a], "--fast-threshold") && a + 1 < argc) tracker.params.fast_threshold = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--max-features") && a + 1 < argc) tracker.params.max_features = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--min-track-length") && a + 1 < argc) tracker.params.min_track_length = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--temporal-radius") && a + 1 < argc) tracker.params.temporal_radius = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--subpixel")) tracker.subpixel = true;
+        else if (!std::strcmp(argv[a], "--max-sad") && a + 1 < argc) tracker.refine.max_sad = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--huber") && a + 1 < argc) huber = std::atof(argv[++a]);
         else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
     }
     FILE *f = std::fopen(argv[1], "rb");
@@ -103,8 +113,9 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     std::cerr << dataset.stereo_obs_list.size() << " observations of " << dataset.num_points << " tracks in " << frames << " frames" << std::endl;
+    if (tracker.subpixel) std::cerr << tracker.num_dropped << " observations dropped by the refinement" << std::endl;
     if (!dataset.compute_initial_guess()) return EXIT_FAILURE;
-    const bool usable = solveAll(dataset);
+    const bool usable = solveAll(dataset, huber);
 
     std::cout.precision(17);
     for (int k = 0; k < frames; ++k) {

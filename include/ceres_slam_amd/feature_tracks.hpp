@@ -22,8 +22,17 @@ class FeatureTracker {
     //! ssba_track_default_params; set fields before track()
     ssba_track_params params;
     int device;
+    //! observations refined to 1/256 pixel against each track's first patch (ssba_track_sequence_subpixel) under `refine`
+    bool subpixel = false;
+    //! ssba_track_default_refine_params; used when `subpixel` is set
+    ssba_track_refine_params refine;
+    //! after a track() with `subpixel`: the observations whose refinement failed and that were left out
+    mutable uint64_t num_dropped = 0;
 
-    explicit FeatureTracker(int device_ = -1) : device(device_) { ssba_track_default_params(&params); }
+    explicit FeatureTracker(int device_ = -1) : device(device_) {
+        ssba_track_default_params(&params);
+        ssba_track_default_refine_params(&refine);
+    }
 
     //! `frames` images of rows x cols in `left`, then exactly one of `right` (as many images) and `disp16` (as many int16 maps in
     //! the format StereoSGBM writes).  Fills `out`: the camera, one state per frame (the first pose is `first_pose`, the others
@@ -37,8 +46,11 @@ class FeatureTracker {
         std::vector<double> uvd(3 * (capacity ? capacity : 1));
         uint64_t num_observations = 0;
         uint32_t num_points = 0;
-        const int rc = ssba_track_sequence(left, right, disp16, frames, rows, cols, &params, device, capacity, state_start.data(), point_id.data(), uvd.data(),
-                                           &num_observations, &num_points);
+        num_dropped = 0;
+        const int rc = subpixel ? ssba_track_sequence_subpixel(left, right, disp16, frames, rows, cols, &params, device, capacity, state_start.data(),
+                                                               point_id.data(), uvd.data(), &num_observations, &num_points, &refine, &num_dropped)
+                                : ssba_track_sequence(left, right, disp16, frames, rows, cols, &params, device, capacity, state_start.data(), point_id.data(),
+                                                      uvd.data(), &num_observations, &num_points);
         if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
         out->camera = camera;
         out->num_states = frames;

@@ -56,12 +56,48 @@
  * No floating point is used before the final conversion of (u, v, d).  Every position in an output comes from a prefix sum, so
  * two runs give the same bytes.
  *
+ * Sub-pixel refinement (ssba_track_refine, ssba_track_sequence_subpixel; the numpy statement is tests/tracks_refine_reference.py)
+ *   Every observation of a track becomes the position of ONE template in that image: the 15 x 15 patch around the track's first
+ *   observation, its anchor.  Positions are int32 in units of 1/256 pixel ("q8").
+ *   template    anchor at whole pixel (ax, ay) of image A, offsets i, j in [-7, 7]:  T(i,j) = A[ay+j][ax+i],
+ *               gx = A[ay+j][ax+i+1] - A[ay+j][ax+i-1], gy = A[ay+j+1][ax+i] - A[ay+j-1][ax+i]: twice the central difference,
+ *               never divided.  In x-only mode gy = 0.  H11 = sum gx^2, H12 = sum gx gy, H22 = sum gy^2, integers.  An anchor
+ *               whose 17 x 17 support leaves A (ax < 8, ax + 8 >= cols, likewise in y) has status EDGE.
+ *   evaluation  at p = (px, py) in the target image B, for every (i, j):  X = px + 256 i, x0 = X >> 8 (the floor), fx = X & 255,
+ *               y0 and fy likewise from py + 256 j;
+ *                   S = (256-fx)(256-fy) B[y0][x0] + fx (256-fy) B[y0][x0+1] + (256-fx) fy B[y0+1][x0] + fx fy B[y0+1][x0+1]
+ *                   e = S - 65536 T,   bx = sum gx e,   by = sum gy e   (int64, |b| < 2^41),   sad = (sum |e|) >> 16.
+ *               If any x0 < 0, y0 < 0, x0 + 1 >= cols or y0 + 1 >= rows the status is EDGE and nothing is summed.
+ *   step        det = H11 H22 - H12^2 in int64 (below 2^53, so its conversion to double is exact); det <= 0 is FLAT.  The only
+ *               floating point: IEEE doubles, round to nearest, no contraction, every operand converted from its integer first
+ *               and every product rounded before the subtraction,
+ *                   nx = H22 bx - H12 by,   ny = H11 by - H12 bx,   dx = rint(nx / (det 128)),   dy = rint(ny / (det 128)).
+ *               x-only mode: H11 <= 0 is FLAT, dx = rint(bx / (H11 128)), dy = 0.  Then p <- p - (dx, dy), exactly (a step too
+ *               large for an int32 is FAR).  1/128 = 2 * 256 / 65536: the doubled gradients, the q8 unit, the 65536 of S.
+ *   control     sad = 0;  then up to `iterations` times:  EDGE if the window at p leaves B;  FLAT;  evaluate;  step;
+ *               max(|px - px_0|, |py - py_0|) > 256 max_shift is FAR;  max(|dx|, |dy|) <= 1 is convergence (the step has been
+ *               applied, sad is that of the evaluation just made).  `iterations` evaluations without convergence: ITERATIONS.
+ *               Converged with max_sad > 0 and sad > max_sad: SAD (max_sad 0: no such gate).  Otherwise OK.
+ *               The position returned is p when the status is OK and the start otherwise; sad is that of the last evaluation
+ *               made, 0 when there was none.
+ *   sequence    launches, survivors and ids as ssba_track_sequence.  The anchor of an id is the survivor that was issued it.
+ *               Per survivor at keypoint (x, y) with disparity d16 / 16 in frame f:  (u, v) = (256 x, 256 y) exactly when the
+ *               survivor is its own anchor, else the 2-D refinement in left image f started there.  With right images the right
+ *               position x_r is refined in x only in right image f, against the same (left) template, from u - 16 d16 on the
+ *               row v (a q8 row: the refined one), and d = u - x_r; d <= 0 is DISPARITY.  With a disp16 stack only the left
+ *               position is refined and d = 16 d16.  A survivor whose status is not OK is dropped: it counts in *num_dropped
+ *               and its track is one observation shorter; the track keeps its other observations and its template, also when
+ *               the dropped one is the anchor.  Pruning by min_track_length acts on the remaining lengths, ids are renumbered
+ *               in id order, and (u, v, d) = q8 / 256.0.
+ *
  * SSBA_ERR_INVALID_ARGUMENT, with a message and before a device is looked for: a NULL input or output; both or neither of
  *   right / disp16; frames < 1 or > 32767 (n likewise, up to 65535); rows or cols < 31 or > 8192; max_features outside
  *   1 ... 4096; fast_threshold outside 0 ... 254; max_hamming outside 0 ... 256; a negative stereo_max_dy, max_disparity or
  *   temporal_radius; min_track_length < 1; an unknown gate; na or nb > 65535.  After the work: a capacity below the number of
- *   observations (the message names the number needed; nothing is written).
- * All three calls are synchronous: host arrays in and out, the work on a pooled stream.
+ *   observations (the message names the number needed; nothing is written).  The refinement calls add: NULL refine
+ *   parameters; iterations outside 1 ... 64; max_shift outside 1 ... 8; a negative max_sad; an item whose anchor or target
+ *   image index is not below n; an item whose mode is neither 0 nor 1.
+ * All calls are synchronous: host arrays in and out, the work on a pooled stream.
  */
 #ifndef SSBA_TRACKS_H_
 #define SSBA_TRACKS_H_
@@ -103,6 +139,36 @@ SSBA_API int ssba_track_match(const uint32_t *desc_a, const uint16_t *xy_a, uint
 SSBA_API int ssba_track_sequence(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
                                  const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
                                  double *uvd, uint64_t *num_observations, uint32_t *num_points);
+
+#define SSBA_TRACK_REFINE_OK 0
+#define SSBA_TRACK_REFINE_EDGE 1
+#define SSBA_TRACK_REFINE_FLAT 2
+#define SSBA_TRACK_REFINE_FAR 3
+#define SSBA_TRACK_REFINE_ITERATIONS 4
+#define SSBA_TRACK_REFINE_SAD 5
+#define SSBA_TRACK_REFINE_DISPARITY 6
+#define SSBA_TRACK_REFINE_2D 0
+#define SSBA_TRACK_REFINE_X_ONLY 1
+
+/* ssba_track_default_refine_params: iterations 10, max_shift 4 (pixels), max_sad 0 (no gate) */
+typedef struct {
+    int32_t iterations, max_shift, max_sad;
+} ssba_track_refine_params;
+SSBA_API void ssba_track_default_refine_params(ssba_track_refine_params *params);
+
+/* The refinement alone over a stack of n images: item k is 7 int32 = anchor image, ax, ay, target image, x0_q8, y0_q8, mode
+ * (SSBA_TRACK_REFINE_2D or _X_ONLY).  Per item: xy_q8 (2 int32: the position, the start when the status is not OK), status
+ * (SSBA_TRACK_REFINE_OK ... _SAD; _DISPARITY arises in the sequence only) and sad.  items and the outputs may be NULL when
+ * num_items = 0, which is SSBA_OK without a launch.  One launch whatever num_items. */
+SSBA_API int ssba_track_refine(const uint8_t *images, uint32_t n, uint32_t rows, uint32_t cols, const int32_t *items, uint32_t num_items,
+                               const ssba_track_refine_params *refine_params, int device, int32_t *xy_q8, int32_t *status, uint32_t *sad);
+
+/* ssba_track_sequence with sub-pixel observations: the same arguments, then the refinement's parameters and *num_dropped, the
+ * number of survivors whose refinement did not end OK.  Two launches more than ssba_track_sequence, whatever `frames`. */
+SSBA_API int ssba_track_sequence_subpixel(const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t frames, uint32_t rows, uint32_t cols,
+                                          const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
+                                          double *uvd, uint64_t *num_observations, uint32_t *num_points,
+                                          const ssba_track_refine_params *refine_params, uint64_t *num_dropped);
 
 SSBA_API const char *ssba_track_last_error(void);
 

@@ -14,7 +14,12 @@ Per-kernel medians and launch counts come from runs of their own (no timing wind
 --trace-run makes exactly ONE track_sequence call, so the rows of the trace are the launches of one call: the library's k_tr_*
 kernels, and apart from them the copy kernels the HIP runtime itself launches for some of the transfers.
 
-    python tools/feature_tracks_bench.py [--out profiles/feature_tracks.json] [--shapes a,b] [--calls 10]"""
+    python tools/feature_tracks_bench.py [--out profiles/feature_tracks.json] [--shapes a,b] [--calls 10]
+
+--subpixel measures tracks.track_sequence_subpixel against tracks.track_sequence on the same frames in the same process, the two
+calls taking turns window by window (track_sequence's code is the parent's, so it is the parent's figure), checks that with
+nothing dropped the two calls name the same observations, and writes profiles/feature_tracks_subpixel.json; with --trace-run the
+one call is the sub-pixel one, and --merge-trace counts k_tr_anchor and k_tr_refine with the rest."""
 import argparse
 import collections
 import csv
@@ -43,10 +48,32 @@ def frames_of(name):
     return synth.make_stereo_sequence(s["rows"], s["cols"], s["frames"], seed=10, motion=1.0, min_wavelength_px=8.0)
 
 
-def run(seq, name):
+def run(seq, name, subpixel=False):
+    call = tracks.track_sequence_subpixel if subpixel else tracks.track_sequence
     t = time.perf_counter()
-    out = tracks.track_sequence(seq.left, seq.right, fast_threshold=FAST_THRESHOLD, max_features=SHAPES[name]["max_features"])
+    out = call(seq.left, seq.right, fast_threshold=FAST_THRESHOLD, max_features=SHAPES[name]["max_features"])
     return time.perf_counter() - t, out
+
+
+def compare(seq, name, calls):
+    """Whole-pixel and sub-pixel calls in alternating windows: one warm-up window each, then three timed windows each."""
+    outs = {}
+    for sub in (False, True):
+        for _ in range(calls):
+            _, outs[sub] = run(seq, name, sub)
+    windows = {False: [], True: []}
+    for _ in range(3):
+        for sub in (False, True):
+            windows[sub].append(statistics.mean(run(seq, name, sub)[0] for _ in range(calls)) * 1e3)
+    whole, fine = outs[False], outs[True]
+    same = bool(fine[4] == 0 and whole[0].tobytes() == fine[0].tobytes() and whole[1].tobytes() == fine[1].tobytes())
+    med = {sub: statistics.median(w) for sub, w in windows.items()}
+    return dict(fast_threshold=FAST_THRESHOLD, calls_per_window=calls, track_sequence_ms=round(med[False], 4), track_sequence_subpixel_ms=round(med[True], 4),
+                ratio=round(med[True] / med[False], 4), spread_ms=round(max(windows[False]) - min(windows[False]), 4),
+                spread_subpixel_ms=round(max(windows[True]) - min(windows[True]), 4), windows_ms=[round(w, 4) for w in windows[False]],
+                windows_subpixel_ms=[round(w, 4) for w in windows[True]], observations=int(len(whole[1])), observations_subpixel=int(len(fine[1])),
+                dropped=int(fine[4]), tracks=int(fine[3]), same_observations_as_track_sequence=same,
+                largest_move_px=round(float(abs(fine[2][:, :2] - whole[2][:, :2]).max()), 4) if same else None)
 
 
 def load(path):
@@ -55,14 +82,16 @@ def load(path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "feature_tracks.json"))
+    ap.add_argument("--out")
+    ap.add_argument("--subpixel", action="store_true")
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--trace-run")
     ap.add_argument("--merge-trace", nargs=2)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "feature_tracks_subpixel.json" if a.subpixel else "feature_tracks.json")
     if a.trace_run:
-        run(frames_of(a.trace_run), a.trace_run)
+        run(frames_of(a.trace_run), a.trace_run, a.subpixel)
         return
     doc = load(a.out)
     if a.merge_trace:
@@ -76,7 +105,11 @@ def main():
         doc[name]["runtime_copy_kernels_per_call"] = sum(len(v) for k, v in per.items() if not k.startswith("k_tr_"))
         doc[name]["kernels_us"] = {k: dict(launches=len(v), median_us=round(statistics.median(v), 2), total_us=round(sum(v), 2)) for k, v in sorted(per.items())}
     else:
-        for name in a.shapes.split(","):
+        for name in a.shapes.split(",") if a.subpixel else []:
+            doc.setdefault(name, {}).update(SHAPES[name])
+            doc[name].update(compare(frames_of(name), name, a.calls))
+            print(name, doc[name])
+        for name in [] if a.subpixel else a.shapes.split(","):
             seq = frames_of(name)
             _, out = run(seq, name)                                            # warm-up window
             for _ in range(a.calls - 1):

@@ -17,8 +17,15 @@
 //   k_tr_refine     one wave per survivor: the anchor's 15 x 15 template placed    grid (max_features / 4, frames)
 //                   in the left image (2-D), then in the right image (x only)
 // and ssba_track_refine runs the same placement (rf_solve) over a list of items: k_tr_refine_items, grid (items / 4).
+// A stream (ssba_track_stream_push) runs the kernels up to k_tr_stereo and k_tr_best on one pair, then
+//   k_ts_link       the frame's ids against the retained previous survivors         grid (1)
+//   k_ts_carry      one wave per survivor: the anchor patch inherited or cut        grid (max_features / 4)
+//   k_ts_refine     k_tr_refine with the template from the patch store              grid (max_features / 4)
+//   k_ts_emit       the push outputs compacted, the frame's ring entry              grid (1)
+// and ssba_track_stream_window is one launch, k_ts_window: k_tr_link and k_tr_prune on the ring's stored links, grid (1).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -758,6 +765,289 @@ __global__ __launch_bounds__(64 * RF_WAVES) void k_tr_refine(const uint8_t *__re
     }
 }
 
+// ---- the stream -------------------------------------------------------------------------------------------------------------
+// One frame against the state a stream keeps on the device (include/ssba_tracks.h, "Streaming"; the numpy statement is
+// tests/tracks_stream_reference.py).  The survivors of the previous and of the current frame are two buffers that swap roles;
+// the ring holds one entry per survivor slot for each of the last `window` frames.
+constexpr int TS_SIDE = 2 * RF_RADIUS + 3;           // 17: the template and the ring of pixels its gradients read
+constexpr int TS_PATCH = TS_SIDE * TS_SIDE;          // 289
+constexpr int TS_PATCH_WORDS = (TS_PATCH + 3) / 4;   // a patch starts on a word, so that an inherited one is copied in words
+constexpr int TS_PATCH_STRIDE = 4 * TS_PATCH_WORDS;
+
+static_assert(RF_RADIUS + 1 <= TR_BORDER, "the patch of a keypoint lies inside its image");
+
+struct StreamEntry {
+    uint32_t id;              // as issued
+    uint32_t from;            // the slot of the frame before that the id was inherited from, TR_NONE: the id was issued here
+    uint32_t kept;            // 0: the refinement dropped the observation
+    int32_t v[3];             // whole pixel: x, y, d16; refined: u, v, d in 1/256 pixel
+};
+
+// an entry's observation as k_tr_prune writes it: q8 / 256.0, or (x, y, d16 / 16.0)
+__device__ __forceinline__ void ts_uvd(const int32_t *v, bool refined, double *__restrict__ out) {
+    out[0] = refined ? (double)v[0] / 256.0 : (double)v[0];
+    out[1] = refined ? (double)v[1] / 256.0 : (double)v[1];
+    out[2] = refined ? (double)v[2] / 256.0 : (double)v[2] / 16.0;
+}
+
+// k_tr_link for one frame: B = the current survivors, A = those of the frame before (np = 0 on the first push).  The fresh ids
+// start at *next_id, which is the stream's running id.
+__global__ __launch_bounds__(TR_BLOCK) void k_ts_link(const uint32_t *__restrict__ cur_count, const uint32_t *__restrict__ prev_count, int has_prev,
+                                                      const uint32_t *__restrict__ best_pn, const uint32_t *__restrict__ best_np,
+                                                      const uint32_t *__restrict__ prev_id, uint32_t stride, int max_hamming, uint32_t *__restrict__ cur_id,
+                                                      uint32_t *__restrict__ from, uint32_t *next_id) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    const uint32_t n = min(*cur_count, stride), np = has_prev ? min(*prev_count, stride) : 0u;
+    const uint32_t next = *next_id;
+    uint32_t inherited[TR_ITEMS], src[TR_ITEMS], fresh = 0;
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        const uint32_t j = threadIdx.x * TR_ITEMS + i;
+        inherited[i] = src[i] = TR_NONE;
+        if (j >= n) continue;
+        uint32_t a = 0;
+        if (np && tr_mutual(best_np, best_pn, j, np, max_hamming, &a)) {
+            inherited[i] = prev_id[a];
+            src[i] = a;
+        }
+        fresh += src[i] == TR_NONE;
+    }
+    uint32_t total;
+    uint32_t pos = next + tr_block_exscan(fresh, part, &total);       // its barriers stand between every read of *next_id and the write below
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        const uint32_t j = threadIdx.x * TR_ITEMS + i;
+        if (j >= n) continue;
+        cur_id[j] = src[i] == TR_NONE ? pos++ : inherited[i];
+        from[j] = src[i];
+    }
+    if (threadIdx.x == 0) *next_id = next + total;
+}
+
+// One wave per survivor: the anchor patch of its track.  An inheriting survivor copies its predecessor's, a fresh one cuts its
+// own from the left image.
+__global__ __launch_bounds__(64 * RF_WAVES) void k_ts_carry(const uint8_t *__restrict__ left, int rows, int cols, const uint32_t *__restrict__ cur_count,
+                                                             const uint32_t *__restrict__ prev_count, const uint16_t *__restrict__ xy,
+                                                             const uint32_t *__restrict__ from, uint32_t stride, const uint8_t *__restrict__ prev_patch,
+                                                             uint8_t *__restrict__ cur_patch) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t j = blockIdx.x * RF_WAVES + (threadIdx.x >> 6);
+    if (j >= min(*cur_count, stride)) return;
+    const uint32_t src = from[j];
+    uint8_t *dst = cur_patch + (size_t)j * TS_PATCH_STRIDE;
+    if (src != TR_NONE) {
+        if (src >= min(*prev_count, stride)) return;                  // never: a link names a survivor of the frame before
+        const uint32_t *s = (const uint32_t *)(prev_patch + (size_t)src * TS_PATCH_STRIDE);
+        for (int k = lane; k < TS_PATCH_WORDS; k += 64) ((uint32_t *)dst)[k] = s[k];
+        return;
+    }
+    const int x = xy[2 * j], y = xy[2 * j + 1];
+    // Holds: keypoints keep 15 pixels.  Where rf_template would answer EDGE for such an anchor, a patch of zeros is stored, which
+    // k_ts_refine finds FLAT: the observations of such a track would be dropped either way, under another status.
+    const bool inside = x >= RF_RADIUS + 1 && y >= RF_RADIUS + 1 && x < cols - RF_RADIUS - 1 && y < rows - RF_RADIUS - 1;
+    for (int k = lane; k < TS_PATCH; k += 64) {
+        const int py = k / TS_SIDE, px = k - py * TS_SIDE;
+        dst[k] = inside ? left[(size_t)(y - RF_RADIUS - 1 + py) * cols + (x - RF_RADIUS - 1 + px)] : (uint8_t)0;
+    }
+}
+
+// rf_template from a stored patch: the same T, gx, gy as from the image the patch was cut from
+__device__ __forceinline__ void ts_template(const uint8_t *__restrict__ P, int lane, RefineTemplate *t) {
+#pragma unroll
+    for (int m = 0; m < RF_PER_LANE; ++m) {
+        const int k = lane + 64 * m;
+        t->T[m] = t->gx[m] = t->gy[m] = 0;
+        if (k < RF_PIXELS) {
+            const uint8_t *p = P + (k / RF_SIDE + 1) * TS_SIDE + (k % RF_SIDE + 1);
+            t->T[m] = p[0];
+            t->gx[m] = (int)p[1] - (int)p[-1];
+            t->gy[m] = (int)p[TS_SIDE] - (int)p[-TS_SIDE];
+        }
+    }
+}
+
+// k_tr_refine for one frame with the template from the patch store: images = the left image, then the right one when there is one
+__global__ __launch_bounds__(64 * RF_WAVES) void k_ts_refine(const uint8_t *__restrict__ images, int rows, int cols, int has_right,
+                                                              const uint32_t *__restrict__ cur_count, const uint16_t *__restrict__ xy,
+                                                              const int32_t *__restrict__ d16s, const uint32_t *__restrict__ from,
+                                                              const uint8_t *__restrict__ patch, uint32_t stride, ssba_track_refine_params rp,
+                                                              int32_t *__restrict__ refined, int32_t *__restrict__ status_out) {
+    __shared__ uint8_t tiles[RF_WAVES][RF_TILE * RF_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t n = min(*cur_count, stride), j = blockIdx.x * RF_WAVES + wave;
+    if (blockIdx.x * RF_WAVES >= n) return;          // the whole work-group leaves together
+    const size_t npix = (size_t)rows * cols;
+    const bool live = j < n;
+    int x = 0, y = 0, d16 = 0;
+    bool self = false;
+    RefineTemplate t = {};
+    if (live) {
+        x = xy[2 * j];
+        y = xy[2 * j + 1];
+        d16 = d16s[j];
+        self = from[j] == TR_NONE;
+        ts_template(patch + (size_t)j * TS_PATCH_STRIDE, lane, &t);
+    }
+    const RefineResult l = rf_solve(tiles[wave], live && !self, t, images, rows, cols, 256 * x, 256 * y, 0, rp, lane);
+    int status = l.status, dq8 = 16 * d16;
+    const bool pair = has_right && live && status == SSBA_TRACK_REFINE_OK;
+    const RefineResult r = rf_solve(tiles[wave], pair, t, images + (has_right ? npix : 0), rows, cols, l.x - 16 * d16, l.y, 1, rp, lane);
+    if (pair) {
+        status = r.status;
+        dq8 = l.x - r.x;
+        if (status == SSBA_TRACK_REFINE_OK && dq8 <= 0) status = SSBA_TRACK_REFINE_DISPARITY;
+    }
+    if (live && lane == 0) {
+        refined[3 * j] = l.x;
+        refined[3 * j + 1] = l.y;
+        refined[3 * j + 2] = dq8;
+        status_out[j] = status;
+    }
+}
+
+// The frame's ring entry, and its kept survivors compacted into the push outputs: out_scalars = kept, dropped, the running id.
+// refined / status: NULL for whole-pixel observations.
+__global__ __launch_bounds__(TR_BLOCK) void k_ts_emit(const uint32_t *__restrict__ cur_count, const uint16_t *__restrict__ xy, const int32_t *__restrict__ d16s,
+                                                      const uint32_t *__restrict__ cur_id, const uint32_t *__restrict__ from,
+                                                      const int32_t *__restrict__ refined, const int32_t *__restrict__ status, uint32_t stride,
+                                                      const uint32_t *__restrict__ next_id, StreamEntry *__restrict__ entries, uint32_t *__restrict__ entry_count,
+                                                      uint32_t *__restrict__ out_scalars, double *__restrict__ out_uvd, uint32_t *__restrict__ out_id) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    const uint32_t n = min(*cur_count, stride);
+    StreamEntry e[TR_ITEMS];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        const uint32_t j = threadIdx.x * TR_ITEMS + i;
+        e[i].kept = 0;
+        if (j >= n) continue;
+        e[i].id = cur_id[j];
+        e[i].from = from[j];
+        e[i].kept = status ? status[j] == SSBA_TRACK_REFINE_OK : 1;
+        if (refined) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[i].v[c] = refined[3 * j + c];
+        } else {
+            e[i].v[0] = xy[2 * j];
+            e[i].v[1] = xy[2 * j + 1];
+            e[i].v[2] = d16s[j];
+        }
+        entries[j] = e[i];
+        mine += e[i].kept;
+    }
+    uint32_t total;
+    uint32_t pos = tr_block_exscan(mine, part, &total);
+#pragma unroll
+    for (int i = 0; i < TR_ITEMS; ++i) {
+        if (!e[i].kept) continue;
+        if (pos < stride) {                          // holds: at most one observation per survivor slot
+            out_id[pos] = e[i].id;
+            ts_uvd(e[i].v, refined != nullptr, out_uvd + 3 * (size_t)pos);
+        }
+        ++pos;
+    }
+    if (threadIdx.x == 0) {
+        *entry_count = n;
+        out_scalars[0] = total;
+        out_scalars[1] = n - total;
+        out_scalars[2] = *next_id;
+    }
+}
+
+// k_tr_link and k_tr_prune on stored links: one work-group walks the `frames` ring entries from ring slot `first` on (the ring
+// has `ring` slots and wraps).  A survivor of the walk's first frame starts a track whatever it inherited before the window.
+__global__ __launch_bounds__(TR_BLOCK) void k_ts_window(const StreamEntry *__restrict__ entries, const uint32_t *__restrict__ entry_count, uint32_t ring,
+                                                        uint32_t first, int frames, uint32_t stride, int min_track_length, int refined, uint32_t *local,
+                                                        uint32_t *length, uint32_t *new_id, uint32_t *__restrict__ state_start, uint32_t *__restrict__ point_id,
+                                                        double *__restrict__ uvd, uint32_t *__restrict__ totals) {
+    __shared__ uint32_t part[TR_BLOCK / 64];
+    const uint32_t slots = (uint32_t)frames * stride;
+    for (uint32_t i = threadIdx.x; i < slots; i += TR_BLOCK) length[i] = 0;
+    __syncthreads();
+    uint32_t next = 0, np = 0;
+    for (int f = 0; f < frames; ++f) {
+        const uint32_t r = (first + f) % ring, n = min(entry_count[r], stride);
+        const StreamEntry *in = entries + (size_t)r * stride;
+        const size_t cur = (size_t)f * stride, prev = (size_t)(f ? f - 1 : 0) * stride;
+        uint32_t inherited[TR_ITEMS], kept[TR_ITEMS], fresh = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            inherited[i] = TR_NONE;
+            kept[i] = 0;
+            if (j >= n) continue;
+            const uint32_t src = in[j].from;
+            kept[i] = in[j].kept;
+            if (f && src < np) inherited[i] = local[prev + src];
+            fresh += inherited[i] == TR_NONE;
+        }
+        uint32_t total;
+        uint32_t pos = next + tr_block_exscan(fresh, part, &total);
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            if (j >= n) continue;
+            const uint32_t mine = inherited[i] == TR_NONE ? pos++ : inherited[i];
+            local[cur + j] = mine;
+            if (kept[i] && mine < slots) length[mine] += 1;      // a link is one to one: the thread that owns the survivor adds alone
+        }
+        next += total;
+        np = n;
+        __syncthreads();          // frame f's local ids are read by frame f + 1 of this same work-group
+    }
+    const uint32_t ids = min(next, slots);
+    uint32_t run = 0;
+    for (uint32_t chunk = 0; chunk < ids; chunk += TR_BLOCK * TR_ITEMS) {
+        uint32_t keep[TR_ITEMS], mine = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t t = chunk + threadIdx.x * TR_ITEMS + i;
+            keep[i] = t < ids && length[t] >= (uint32_t)min_track_length;
+            mine += keep[i];
+        }
+        uint32_t total;
+        uint32_t pos = run + tr_block_exscan(mine, part, &total);
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t t = chunk + threadIdx.x * TR_ITEMS + i;
+            if (t < ids) new_id[t] = keep[i] ? pos++ : TR_NONE;
+        }
+        run += total;
+    }
+    __syncthreads();
+    uint32_t written = 0;
+    for (int f = 0; f < frames; ++f) {
+        const uint32_t r = (first + f) % ring, n = min(entry_count[r], stride);
+        const StreamEntry *in = entries + (size_t)r * stride;
+        const size_t cur = (size_t)f * stride;
+        uint32_t renamed[TR_ITEMS], mine = 0;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            renamed[i] = TR_NONE;
+            if (j < n && in[j].kept && local[cur + j] < ids) renamed[i] = new_id[local[cur + j]];
+            mine += renamed[i] != TR_NONE;
+        }
+        uint32_t total;
+        uint32_t pos = written + tr_block_exscan(mine, part, &total);
+        if (threadIdx.x == 0) state_start[f] = written;
+#pragma unroll
+        for (int i = 0; i < TR_ITEMS; ++i) {
+            if (renamed[i] == TR_NONE) continue;
+            const uint32_t j = threadIdx.x * TR_ITEMS + i;
+            point_id[pos] = renamed[i];                           // pos < frames * stride: at most one observation per survivor slot
+            ts_uvd(in[j].v, refined != 0, uvd + 3 * (size_t)pos);
+            ++pos;
+        }
+        written += total;
+    }
+    if (threadIdx.x == 0) {
+        state_start[frames] = written;
+        totals[0] = written;
+        totals[1] = run;
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 std::mutex g_error_mutex;
 std::string g_error;
@@ -825,34 +1115,48 @@ struct Features {
     uint32_t *desc = nullptr;      // n * max_features * 8
 };
 
-// four launches for n images already on the device
-hipError_t tr_enqueue_features(const uint8_t *images, uint32_t n, int rows, int cols, const ssba_track_params &p, bool clear, Features *f, hipStream_t s,
-                               std::vector<void *> *temps) {
+struct FeatureScratch {
+    uint8_t *score = nullptr, *kept = nullptr;     // n * rows * cols each
+    int *hist = nullptr;                           // n * 256
+};
+
+hipError_t tr_alloc_features(uint32_t n, int rows, int cols, const ssba_track_params &p, FeatureScratch *w, Features *f, std::vector<void *> *temps) {
     const size_t npix = (size_t)rows * cols, slots = (size_t)n * p.max_features;
-    uint8_t *score = nullptr, *kept = nullptr;
-    int *hist = nullptr;
-    TR_TRY(tr_alloc(temps, &score, npix * n));
-    TR_TRY(tr_alloc(temps, &kept, npix * n));
-    TR_TRY(tr_alloc(temps, &hist, (size_t)n * 256));
+    TR_TRY(tr_alloc(temps, &w->score, npix * n));
+    TR_TRY(tr_alloc(temps, &w->kept, npix * n));
+    TR_TRY(tr_alloc(temps, &w->hist, (size_t)n * 256));
     TR_TRY(tr_alloc(temps, &f->count, (size_t)n));
     TR_TRY(tr_alloc(temps, &f->xy, slots * 2));
     TR_TRY(tr_alloc(temps, &f->score, slots));
-    TR_TRY(tr_alloc(temps, &f->desc, slots * TR_WORDS));
+    return tr_alloc(temps, &f->desc, slots * TR_WORDS);
+}
+
+// four launches for n images already on the device
+hipError_t tr_launch_features(const uint8_t *images, uint32_t n, int rows, int cols, const ssba_track_params &p, const FeatureScratch &w, const Features &f,
+                              hipStream_t s) {
+    const dim3 grid((cols + 63) / 64, (rows + 3) / 4, n), block(64, 4);
+    hipLaunchKernelGGL(k_tr_score, grid, block, 0, s, images, w.score, w.hist, rows, cols, p.fast_threshold);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_nms, grid, block, 0, s, (const uint8_t *)w.score, w.kept, w.hist, rows, cols);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_select, dim3(n), dim3(TR_BLOCK), 0, s, (const uint8_t *)w.kept, (const int *)w.hist, rows, cols, p.max_features, f.count, f.xy, f.score);
+    TR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tr_describe, dim3(p.max_features, n), dim3(256), 0, s, images, rows, cols, p.max_features, (const uint32_t *)f.count,
+                       (const uint16_t *)f.xy, f.desc);
+    return hipGetLastError();
+}
+
+hipError_t tr_enqueue_features(const uint8_t *images, uint32_t n, int rows, int cols, const ssba_track_params &p, bool clear, Features *f, hipStream_t s,
+                               std::vector<void *> *temps) {
+    const size_t slots = (size_t)n * p.max_features;
+    FeatureScratch w;
+    TR_TRY(tr_alloc_features(n, rows, cols, p, &w, f, temps));
     if (clear) {       // a caller that downloads whole arrays gets zeros behind the counts
         TR_TRY(hipMemsetAsync(f->xy, 0, slots * 2 * sizeof(uint16_t), s));
         TR_TRY(hipMemsetAsync(f->score, 0, slots, s));
         TR_TRY(hipMemsetAsync(f->desc, 0, slots * TR_WORDS * sizeof(uint32_t), s));
     }
-    const dim3 grid((cols + 63) / 64, (rows + 3) / 4, n), block(64, 4);
-    hipLaunchKernelGGL(k_tr_score, grid, block, 0, s, images, score, hist, rows, cols, p.fast_threshold);
-    TR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tr_nms, grid, block, 0, s, (const uint8_t *)score, kept, hist, rows, cols);
-    TR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tr_select, dim3(n), dim3(TR_BLOCK), 0, s, (const uint8_t *)kept, (const int *)hist, rows, cols, p.max_features, f->count, f->xy, f->score);
-    TR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tr_describe, dim3(p.max_features, n), dim3(256), 0, s, images, rows, cols, p.max_features, (const uint32_t *)f->count,
-                       (const uint16_t *)f->xy, f->desc);
-    return hipGetLastError();
+    return tr_launch_features(images, n, rows, cols, p, w, *f, s);
 }
 
 hipError_t tr_enqueue_best(const MatchSets &m, uint32_t pairs, const TrackGate &g, hipStream_t s) {
@@ -1045,7 +1349,280 @@ int tr_close(const char *call, hipError_t e, hipStream_t s, std::vector<void *> 
 
 using namespace ssba;
 
+// Everything a stream owns.  All of it is allocated by ssba_track_stream_create; a push and a window call allocate nothing.
+struct ssba_track_stream {
+    int device = 0;
+    uint32_t rows = 0, cols = 0, window = 0;
+    ssba_track_params p = {};
+    bool refine = false;
+    ssba_track_refine_params rp = {};
+    hipStream_t s = nullptr;
+    std::vector<void *> temps;
+    uint8_t *stage_in = nullptr, *stage_out = nullptr;      // pinned: the frame going up, the push outputs coming down
+    int source = 0;                                         // 0: nothing pushed yet, 1: right images, 2: disp16 maps
+    uint64_t pushed = 0;
+    uint32_t next_id = 0;                                   // the device's running id as of the last push
+    int cur = 0;                                            // which of the two survivor sets the next push fills
+    bool failed = false;                                    // a HIP call failed mid-push or mid-window: the device state is not the host's
+    // the frame: left image, right image, disp16 map; its features (two images) and the matcher's keys
+    uint8_t *images = nullptr;
+    FeatureScratch scratch;
+    Features f;
+    uint32_t *best_lr = nullptr, *best_rl = nullptr, *best_pn = nullptr, *best_np = nullptr;
+    // previous and current survivors
+    Survivors sv[2] = {};
+    uint32_t *id[2] = {nullptr, nullptr};
+    uint8_t *patch[2] = {nullptr, nullptr};                 // refine only
+    uint32_t *from = nullptr, *running_id = nullptr;
+    int32_t *refined = nullptr, *status = nullptr;          // refine only
+    uint8_t *out = nullptr;                                 // 4 uint32 scalars, max_features * 3 doubles, max_features ids
+    // the ring and the window call's work arrays
+    StreamEntry *entries = nullptr;
+    uint32_t *entry_count = nullptr, *local = nullptr, *length = nullptr, *new_id = nullptr, *w_start = nullptr, *w_point = nullptr, *w_totals = nullptr;
+    double *w_uvd = nullptr;
+};
+
+namespace {
+
+constexpr size_t TS_OUT_SCALARS = 4 * sizeof(uint32_t);
+
+size_t ts_out_bytes(uint32_t stride) { return TS_OUT_SCALARS + (size_t)stride * (3 * sizeof(double) + sizeof(uint32_t)); }
+
+hipError_t ts_allocate(ssba_track_stream *st) {
+    const size_t npix = (size_t)st->rows * st->cols, stride = (size_t)st->p.max_features, slots = stride * st->window;
+    std::vector<void *> *t = &st->temps;
+    TR_TRY(tr_alloc(t, &st->images, 4 * npix));                      // left, right, then the int16 map on its even offset
+    TR_TRY(tr_alloc_features(2, (int)st->rows, (int)st->cols, st->p, &st->scratch, &st->f, t));
+    TR_TRY(tr_alloc(t, &st->best_lr, stride));
+    TR_TRY(tr_alloc(t, &st->best_rl, stride));
+    TR_TRY(tr_alloc(t, &st->best_pn, stride));
+    TR_TRY(tr_alloc(t, &st->best_np, stride));
+    for (int b = 0; b < 2; ++b) {
+        TR_TRY(tr_alloc(t, &st->sv[b].count, (size_t)1));
+        TR_TRY(tr_alloc(t, &st->sv[b].desc, stride * TR_WORDS));
+        TR_TRY(tr_alloc(t, &st->sv[b].xy, stride * 2));
+        TR_TRY(tr_alloc(t, &st->sv[b].d16, stride));
+        TR_TRY(tr_alloc(t, &st->id[b], stride));
+        if (st->refine) TR_TRY(tr_alloc(t, &st->patch[b], stride * TS_PATCH_STRIDE));
+    }
+    TR_TRY(tr_alloc(t, &st->from, stride));
+    TR_TRY(tr_alloc(t, &st->running_id, (size_t)1));
+    if (st->refine) {
+        TR_TRY(tr_alloc(t, &st->refined, stride * 3));
+        TR_TRY(tr_alloc(t, &st->status, stride));
+    }
+    TR_TRY(tr_alloc(t, &st->out, ts_out_bytes((uint32_t)stride)));
+    TR_TRY(tr_alloc(t, &st->entries, slots));
+    TR_TRY(tr_alloc(t, &st->entry_count, (size_t)st->window));
+    TR_TRY(tr_alloc(t, &st->local, slots));
+    TR_TRY(tr_alloc(t, &st->length, slots));
+    TR_TRY(tr_alloc(t, &st->new_id, slots));
+    TR_TRY(tr_alloc(t, &st->w_start, (size_t)st->window + 1));
+    TR_TRY(tr_alloc(t, &st->w_point, slots));
+    TR_TRY(tr_alloc(t, &st->w_uvd, slots * 3));
+    TR_TRY(tr_alloc(t, &st->w_totals, (size_t)2));
+    void *pinned = nullptr;
+    TR_TRY(pool_host_malloc(&pinned, 3 * npix + 1));
+    st->stage_in = (uint8_t *)pinned;
+    TR_TRY(pool_host_malloc(&pinned, ts_out_bytes((uint32_t)stride)));
+    st->stage_out = (uint8_t *)pinned;
+    TR_TRY(hipMemsetAsync(st->running_id, 0, sizeof(uint32_t), st->s));
+    return hipStreamSynchronize(st->s);
+}
+
+void ts_free(ssba_track_stream *st) {
+    if (st->s) (void)hipStreamSynchronize(st->s);
+    for (void *t : st->temps) pool_free(t);
+    pool_host_free(st->stage_in);
+    pool_host_free(st->stage_out);
+    if (st->s) pool_stream_release(st->s);
+    delete st;
+}
+
+// The launches of a push: 4 for the features, k_tr_best left-right with right images, k_tr_stereo, k_tr_best against the frame
+// before (not on the first push), k_ts_link, with refinement k_ts_carry and k_ts_refine, k_ts_emit.
+hipError_t ts_push(ssba_track_stream *st, const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t *scalars) {
+    const size_t npix = (size_t)st->rows * st->cols, map_at = (npix + 1) & ~(size_t)1;
+    const uint32_t stride = (uint32_t)st->p.max_features;
+    const int rows = (int)st->rows, cols = (int)st->cols;
+    const ssba_track_params &p = st->p;
+    hipStream_t s = st->s;
+    const int16_t *dd16 = nullptr;
+    memcpy(st->stage_in, left, npix);
+    if (right) {
+        memcpy(st->stage_in + npix, right, npix);
+        TR_TRY(hipMemcpyAsync(st->images, st->stage_in, 2 * npix, hipMemcpyHostToDevice, s));
+    } else {
+        memcpy(st->stage_in + map_at, disp16, npix * sizeof(int16_t));
+        TR_TRY(hipMemcpyAsync(st->images, st->stage_in, npix, hipMemcpyHostToDevice, s));
+        TR_TRY(hipMemcpyAsync(st->images + 2 * npix, st->stage_in + map_at, npix * sizeof(int16_t), hipMemcpyHostToDevice, s));
+        dd16 = (const int16_t *)(st->images + 2 * npix);
+    }
+    TR_TRY(tr_launch_features(st->images, right ? 2 : 1, rows, cols, p, st->scratch, st->f, s));
+    if (right) {      // the pair is a two-image stack: left is image 0, right image 1 of the feature arrays
+        const MatchSets m = {st->f.desc, st->f.desc + (size_t)stride * TR_WORDS, st->f.xy, st->f.xy + (size_t)stride * 2, st->f.count, st->f.count + 1,
+                             st->best_lr, st->best_rl, stride};
+        TR_TRY(tr_enqueue_best(m, 1, TrackGate{SSBA_TRACK_GATE_STEREO, p.stereo_max_dy, p.max_disparity, 0}, s));
+    }
+    const Survivors &now = st->sv[st->cur], &before = st->sv[st->cur ^ 1];
+    hipLaunchKernelGGL(k_tr_stereo, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)st->f.count, (const uint16_t *)st->f.xy, (const uint32_t *)st->f.desc,
+                       (const uint32_t *)st->best_lr, (const uint32_t *)st->best_rl, dd16, 1, rows, cols, stride, p.max_hamming, now);
+    TR_TRY(hipGetLastError());
+    const int has_prev = st->pushed > 0;
+    if (has_prev) {   // A = the survivors of the frame before, B = those of this frame
+        const MatchSets m = {before.desc, now.desc, before.xy, now.xy, before.count, now.count, st->best_pn, st->best_np, stride};
+        TR_TRY(tr_enqueue_best(m, 1, TrackGate{SSBA_TRACK_GATE_TEMPORAL, 0, 0, p.temporal_radius}, s));
+    }
+    hipLaunchKernelGGL(k_ts_link, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)now.count, (const uint32_t *)before.count, has_prev,
+                       (const uint32_t *)st->best_pn, (const uint32_t *)st->best_np, (const uint32_t *)st->id[st->cur ^ 1], stride, p.max_hamming, st->id[st->cur],
+                       st->from, st->running_id);
+    TR_TRY(hipGetLastError());
+    if (st->refine) {
+        const dim3 grid((stride + RF_WAVES - 1) / RF_WAVES), block(64 * RF_WAVES);
+        hipLaunchKernelGGL(k_ts_carry, grid, block, 0, s, (const uint8_t *)st->images, rows, cols, (const uint32_t *)now.count, (const uint32_t *)before.count,
+                           (const uint16_t *)now.xy, (const uint32_t *)st->from, stride, (const uint8_t *)st->patch[st->cur ^ 1], st->patch[st->cur]);
+        TR_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_ts_refine, grid, block, 0, s, (const uint8_t *)st->images, rows, cols, right ? 1 : 0, (const uint32_t *)now.count,
+                           (const uint16_t *)now.xy, (const int32_t *)now.d16, (const uint32_t *)st->from, (const uint8_t *)st->patch[st->cur], stride, st->rp,
+                           st->refined, st->status);
+        TR_TRY(hipGetLastError());
+    }
+    const uint32_t slot = (uint32_t)(st->pushed % st->window);
+    hipLaunchKernelGGL(k_ts_emit, dim3(1), dim3(TR_BLOCK), 0, s, (const uint32_t *)now.count, (const uint16_t *)now.xy, (const int32_t *)now.d16,
+                       (const uint32_t *)st->id[st->cur], (const uint32_t *)st->from, (const int32_t *)st->refined, (const int32_t *)st->status, stride,
+                       (const uint32_t *)st->running_id, st->entries + (size_t)slot * stride, st->entry_count + slot, (uint32_t *)st->out,
+                       (double *)(st->out + TS_OUT_SCALARS), (uint32_t *)(st->out + TS_OUT_SCALARS + (size_t)stride * 3 * sizeof(double)));
+    TR_TRY(hipGetLastError());
+    TR_TRY(hipMemcpyAsync(st->stage_out, st->out, ts_out_bytes(stride), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipStreamSynchronize(s));          // the one synchronisation of a push
+    memcpy(scalars, st->stage_out, 3 * sizeof(uint32_t));
+    return hipSuccess;
+}
+
+// one launch whatever `frames`
+hipError_t ts_window(ssba_track_stream *st, uint32_t frames, SequenceOut *o) {
+    const uint32_t stride = (uint32_t)st->p.max_features, first = (uint32_t)((st->pushed - frames) % st->window);
+    hipStream_t s = st->s;
+    hipLaunchKernelGGL(k_ts_window, dim3(1), dim3(TR_BLOCK), 0, s, (const StreamEntry *)st->entries, (const uint32_t *)st->entry_count, st->window, first,
+                       (int)frames, stride, st->p.min_track_length, st->refine ? 1 : 0, st->local, st->length, st->new_id, st->w_start, st->w_point, st->w_uvd,
+                       st->w_totals);
+    TR_TRY(hipGetLastError());
+    uint32_t *totals = (uint32_t *)st->stage_out;
+    TR_TRY(hipMemcpyAsync(totals, st->w_totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipStreamSynchronize(s));
+    o->needed = totals[0];
+    if ((uint64_t)totals[0] > o->capacity) {
+        o->too_small = true;
+        return hipSuccess;
+    }
+    const uint32_t n = totals[0], points = totals[1];
+    TR_TRY(hipMemcpyAsync(o->state_start, st->w_start, ((size_t)frames + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (n) {
+        TR_TRY(hipMemcpyAsync(o->point_id, st->w_point, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        TR_TRY(hipMemcpyAsync(o->uvd, st->w_uvd, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    TR_TRY(hipStreamSynchronize(s));
+    *o->num_observations = n;
+    *o->num_points = points;
+    return hipSuccess;
+}
+
+}  // namespace
+
 extern "C" {
+
+int ssba_track_stream_create(uint32_t rows, uint32_t cols, const ssba_track_params *params, const ssba_track_refine_params *refine_params, uint32_t window,
+                             int device, ssba_track_stream **stream) {
+    const char *call = "ssba_track_stream_create";
+    if (!stream) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL stream");
+    if (const int rc = tr_check_params(call, params)) return rc;
+    if (refine_params)
+        if (const int rc = tr_check_refine_params(call, refine_params)) return rc;
+    if (const int rc = tr_check_size(call, rows, cols)) return rc;
+    if (window < 1 || window > SSBA_TRACK_STREAM_MAX_WINDOW)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "window must be in 1 ... " + std::to_string(SSBA_TRACK_STREAM_MAX_WINDOW));
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    ssba_track_stream *st = new ssba_track_stream;
+    (void)hipGetDevice(&st->device);
+    st->rows = rows;
+    st->cols = cols;
+    st->window = window;
+    st->p = *params;
+    st->refine = refine_params != nullptr;
+    if (refine_params) st->rp = *refine_params;
+    st->s = s;
+    const hipError_t e = ts_allocate(st);
+    if (e != hipSuccess) {
+        ts_free(st);
+        return tr_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    }
+    *stream = st;
+    return SSBA_OK;
+}
+
+int ssba_track_stream_push(ssba_track_stream *stream, const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t *track_id, double *uvd,
+                           uint32_t *num_observations, uint32_t *num_dropped) {
+    const char *call = "ssba_track_stream_push";
+    if (!left) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL left image");
+    if (!right == !disp16) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "exactly one of right and disp16 must be given");
+    if (!track_id || !uvd || !num_observations || !num_dropped) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (!stream) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL stream");
+    if (stream->failed) return tr_refuse(call, SSBA_ERR_STATE, "an earlier call on this stream ended with a HIP error: destroy it");
+    const int source = right ? 1 : 2;
+    if (stream->source && stream->source != source)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, std::string("the stream's first push fixed its disparity source: ") + (source == 1 ? "disp16" : "right") + " must be given");
+    const uint32_t stride = (uint32_t)stream->p.max_features;
+    if (0xffffffffu - stream->next_id < stride)
+        return tr_refuse(call, SSBA_ERR_STATE, "fewer than max_features ids are left below 2^32 - 1: " + std::to_string(stream->next_id) + " have been issued");
+    if (hipSetDevice(stream->device) != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, "hipSetDevice failed");
+    uint32_t scalars[3] = {0, 0, 0};
+    const hipError_t e = ts_push(stream, left, right, disp16, scalars);
+    if (e != hipSuccess) {
+        stream->failed = true;          // the running id and the current survivor set may have advanced on the device
+        (void)hipStreamSynchronize(stream->s);
+        return tr_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    }
+    const uint32_t n = scalars[0] < stride ? scalars[0] : stride;
+    memcpy(uvd, stream->stage_out + TS_OUT_SCALARS, (size_t)n * 3 * sizeof(double));
+    memcpy(track_id, stream->stage_out + TS_OUT_SCALARS + (size_t)stride * 3 * sizeof(double), (size_t)n * sizeof(uint32_t));
+    *num_observations = n;
+    *num_dropped = scalars[1];
+    stream->next_id = scalars[2];
+    stream->source = source;
+    stream->pushed += 1;
+    stream->cur ^= 1;
+    return SSBA_OK;
+}
+
+int ssba_track_stream_window(ssba_track_stream *stream, uint32_t frames, uint64_t capacity, uint32_t *state_start, uint32_t *point_id, double *uvd,
+                             uint64_t *num_observations, uint32_t *num_points) {
+    const char *call = "ssba_track_stream_window";
+    if (!state_start || !num_observations || !num_points || (capacity && (!point_id || !uvd))) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (frames < 1) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "frames must be at least 1");
+    if (!stream) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL stream");
+    if (stream->failed) return tr_refuse(call, SSBA_ERR_STATE, "an earlier call on this stream ended with a HIP error: destroy it");
+    if (frames > stream->window || frames > stream->pushed)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "frames " + std::to_string(frames) + " exceeds the stream's window " + std::to_string(stream->window) +
+                                                              " or the " + std::to_string(stream->pushed) + " frames pushed");
+    if (hipSetDevice(stream->device) != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, "hipSetDevice failed");
+    SequenceOut o = {capacity, state_start, point_id, uvd, num_observations, num_points};
+    const hipError_t e = ts_window(stream, frames, &o);
+    if (e != hipSuccess) {
+        stream->failed = true;
+        (void)hipStreamSynchronize(stream->s);
+        return tr_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    }
+    if (o.too_small)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(capacity) + " is below the " + std::to_string(o.needed) + " observations found");
+    return SSBA_OK;
+}
+
+void ssba_track_stream_destroy(ssba_track_stream *stream) {
+    if (!stream) return;
+    (void)hipSetDevice(stream->device);
+    ts_free(stream);
+}
 
 void ssba_track_default_params(ssba_track_params *params) {
     if (!params) return;

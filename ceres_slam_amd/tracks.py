@@ -16,11 +16,13 @@ LIB_PATH = os.path.join(_HERE, "libssba_tracks.so")
 
 #: every symbol include/ssba_tracks.h declares
 SYMBOLS = ["ssba_track_default_params", "ssba_track_features", "ssba_track_match", "ssba_track_sequence", "ssba_track_last_error",
-           "ssba_track_default_refine_params", "ssba_track_refine", "ssba_track_sequence_subpixel"]
+           "ssba_track_default_refine_params", "ssba_track_refine", "ssba_track_sequence_subpixel", "ssba_track_stream_create",
+           "ssba_track_stream_push", "ssba_track_stream_window", "ssba_track_stream_destroy"]
 BORDER, MAX_FEATURES, DESC_WORDS = 15, 4096, 8
 GATE_NONE, GATE_STEREO, GATE_TEMPORAL = 0, 1, 2
 REFINE_OK, REFINE_EDGE, REFINE_FLAT, REFINE_FAR, REFINE_ITERATIONS, REFINE_SAD, REFINE_DISPARITY = range(7)
 REFINE_2D, REFINE_X_ONLY = 0, 1
+STREAM_MAX_WINDOW = 256
 
 _u8p, _u16p, _u32p, _i16p, _i32p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint16, C.c_uint32, C.c_int16, C.c_int32))
 _dp = C.POINTER(C.c_double)
@@ -60,6 +62,11 @@ def load():
     L.ssba_track_default_refine_params.restype = None
     L.ssba_track_refine.argtypes = [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, _i32p, C.c_uint32, R, C.c_int, _i32p, _i32p, _u32p]
     L.ssba_track_sequence_subpixel.argtypes = L.ssba_track_sequence.argtypes + [R, C.POINTER(C.c_uint64)]
+    L.ssba_track_stream_create.argtypes = [C.c_uint32, C.c_uint32, P, R, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.ssba_track_stream_push.argtypes = [C.c_void_p, _u8p, _u8p, _i16p, _u32p, _dp, _u32p, _u32p]
+    L.ssba_track_stream_window.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, _u32p, _u32p, _dp, C.POINTER(C.c_uint64), _u32p]
+    L.ssba_track_stream_destroy.argtypes = [C.c_void_p]
+    L.ssba_track_stream_destroy.restype = None
     L.ssba_track_last_error.restype = C.c_char_p
     _lib = L
     return L
@@ -185,3 +192,72 @@ def track_sequence_subpixel(left, right=None, disp16=None, device: int = -1, cap
           "ssba_track_sequence_subpixel")
     n = int(nobs.value)
     return start, ids[:n].copy(), uvd[:n].copy(), int(npts.value), int(ndrop.value)
+
+
+class TrackStream:
+    """Frames pushed one by one into a tracker whose state stays on the device (ssba_track_stream_create).  window: how many of
+    the most recent frames window() can cover.  refine: None for whole-pixel observations, or a dict of RefineParams fields (an
+    empty one: the defaults) for sub-pixel ones against each track's first patch, however long ago that was."""
+
+    def __init__(self, rows: int, cols: int, window: int, device: int = -1, refine=None, **params):
+        self.rows, self.cols, self.window_frames, self.pushed = int(rows), int(cols), int(window), 0
+        self.params = track_params(**params)
+        rp = None if refine is None else refine_params(**refine)
+        self._h = C.c_void_p()
+        check(load().ssba_track_stream_create(self.rows, self.cols, C.byref(self.params), None if rp is None else C.byref(rp), self.window_frames, device,
+                                              C.byref(self._h)), "ssba_track_stream_create")
+
+    def _image(self, a, dtype, what):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (self.rows, self.cols):
+            raise ValueError(f"{what}: a ({self.rows}, {self.cols}) image")
+        return a
+
+    def push(self, left, right=None, disp16=None):
+        """One stereo pair: left and exactly one of right / disp16 (the same one in every push).  Returns ids (n,) uint32 as issued,
+        global to the stream; uvd (n, 3) of the frame's kept survivors in keypoint order; num_dropped."""
+        if self._h is None:
+            raise ValueError("the stream is closed")
+        L = self._image(left, np.uint8, "left")
+        R = None if right is None else self._image(right, np.uint8, "right")
+        D = None if disp16 is None else self._image(disp16, np.int16, "disp16")
+        m = max(int(self.params.max_features), 1)
+        ids, uvd = np.zeros(m, np.uint32), np.zeros((m, 3))
+        nobs, ndrop = C.c_uint32(0), C.c_uint32(0)
+        check(load().ssba_track_stream_push(self._h, L.ctypes.data_as(_u8p), None if R is None else R.ctypes.data_as(_u8p),
+                                            None if D is None else D.ctypes.data_as(_i16p), ids.ctypes.data_as(_u32p), uvd.ctypes.data_as(_dp), C.byref(nobs),
+                                            C.byref(ndrop)), "ssba_track_stream_push")
+        self.pushed += 1
+        n = int(nobs.value)
+        return ids[:n].copy(), uvd[:n].copy(), int(ndrop.value)
+
+    def window(self, frames: int | None = None, capacity: int | None = None):
+        """The last `frames` pushed frames (default: as many as the stream keeps) as track_sequence returns them: state_start,
+        point_id, uvd, num_points."""
+        if self._h is None:
+            raise ValueError("the stream is closed")
+        F = min(self.window_frames, self.pushed) if frames is None else int(frames)
+        cap = max(F, 0) * max(int(self.params.max_features), 0) if capacity is None else int(capacity)
+        start, ids, uvd = np.zeros(max(F, 0) + 1, np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros((max(cap, 1), 3))
+        nobs, npts = C.c_uint64(0), C.c_uint32(0)
+        check(load().ssba_track_stream_window(self._h, max(F, 0), cap, start.ctypes.data_as(_u32p), ids.ctypes.data_as(_u32p), uvd.ctypes.data_as(_dp),
+                                              C.byref(nobs), C.byref(npts)), "ssba_track_stream_window")
+        n = int(nobs.value)
+        return start, ids[:n].copy(), uvd[:n].copy(), int(npts.value)
+
+    def close(self):
+        if self._h is not None:
+            load().ssba_track_stream_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

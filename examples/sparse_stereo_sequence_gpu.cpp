@@ -5,12 +5,18 @@
 // writes it): the frames, the camera and the matcher's parameters are used, the pyramid fields are not.
 //
 // usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]
-//            [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>]
+//            [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W>]
 // --sgbm takes the disparities from the semi-global matcher (StereoSGBM over all pairs in shared launches, sub-pixel) instead
 // of from left-right feature matches (whole pixels).  --temporal-radius gates the frame-to-frame matches to r pixels.
 // --subpixel refines every observation to 1/256 pixel against its track's first patch (FeatureTracker::subpixel), --max-sad
 // drops refined observations whose patch difference exceeds s, and --huber puts a ceres::HuberLoss(a) on every residual block.
+// --stream W pushes the frames one by one into a ceres_slam::FeatureTrackStream, as a camera would deliver them.  After every
+// push from the second on it takes the window of the last min(W, pushed) frames, runs the front end and the solve on it from the
+// trajectory's pose of the window's oldest frame (which stays constant), and the solved poses replace the trajectory's: the
+// newest pose is chained on, the W - 1 before it are refined once more.  With W >= the number of frames and whole pixels the
+// last window is the whole sequence and the output is that of the run without the flag.
 // Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -55,12 +61,13 @@ static bool solveAll(ceres_slam::DatasetProblem &dataset, double huber) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::cerr << "usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]"
-                     " [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>]" << std::endl;
+                     " [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W>]" << std::endl;
         return EXIT_FAILURE;
     }
     ceres_slam::FeatureTracker tracker;
     bool use_sgbm = false;
     double huber = 0.0;
+    int stream_window = 0;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--sgbm")) use_sgbm = true;
         else if (!std::strcmp(argv[a], "--fast-threshold") && a + 1 < argc) tracker.params.fast_threshold = std::atoi(argv[++a]);
@@ -70,6 +77,10 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[a], "--subpixel")) tracker.subpixel = true;
         else if (!std::strcmp(argv[a], "--max-sad") && a + 1 < argc) tracker.refine.max_sad = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--huber") && a + 1 < argc) huber = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--stream") && a + 1 < argc) {
+            stream_window = std::atoi(argv[++a]);
+            if (stream_window < 1) { std::cerr << "--stream takes a window of at least 1 frame, not " << argv[a] << std::endl; return EXIT_FAILURE; }
+        }
         else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
     }
     FILE *f = std::fopen(argv[1], "rb");
@@ -91,8 +102,10 @@ int main(int argc, char **argv) {
     std::fclose(f);
     ceres_slam::DatasetProblem::CameraPtr camera = std::make_shared<const ceres_slam::StereoCamera>(scale_cam[1], scale_cam[2], scale_cam[3], scale_cam[4], scale_cam[5]);
 
-    ceres_slam::DatasetProblem dataset;
+    std::vector<ceres_slam::SE3> trajectory(frames);
+    bool usable = true;
     try {
+        std::vector<int16_t> disp16;
         if (use_sgbm) {
             ceres_slam::StereoSGBM sgbm(sg[0], sg[1], sg[2], sg[3], sg[4], sg[5], sg[6], sg[7], sg[8], sg[9], sg[10] != 0);
             std::vector<ceres_slam::Image8> l, r;
@@ -102,25 +115,41 @@ int main(int argc, char **argv) {
             }
             std::vector<ceres_slam::DisparityMap> maps;
             sgbm(l, r, maps);
-            std::vector<int16_t> disp16(npix * frames);
+            disp16.resize(npix * frames);
             for (int k = 0; k < frames; ++k) std::memcpy(&disp16[npix * k], maps[k].disp16.data(), npix * sizeof(int16_t));
-            tracker.track(left.data(), nullptr, disp16.data(), frames, rows, cols, camera, &dataset);
+        }
+        if (stream_window > 0) {
+            ceres_slam::FeatureTrackStream stream(rows, cols, stream_window, tracker.params, tracker.subpixel ? &tracker.refine : nullptr);
+            for (int k = 0; k < frames; ++k) {
+                const uint32_t kept = stream.push(&left[npix * k], use_sgbm ? nullptr : &right[npix * k], use_sgbm ? &disp16[npix * k] : nullptr);
+                std::cerr << "frame " << k << ": " << kept << " observations, " << stream.num_dropped << " dropped by the refinement" << std::endl;
+                if (!k) continue;
+                const int w = std::min(stream_window, k + 1), oldest = k + 1 - w;
+                ceres_slam::DatasetProblem window;
+                stream.window(w, camera, &window, trajectory[oldest]);
+                std::cerr << window.stereo_obs_list.size() << " observations of " << window.num_points << " tracks in frames " << oldest << " ... " << k << std::endl;
+                if (!window.compute_initial_guess()) return EXIT_FAILURE;
+                usable = solveAll(window, huber) && usable;       // an earlier window's poses seed the later ones
+                for (int i = 0; i < w; ++i) trajectory[oldest + i] = window.poses[i];
+            }
         } else {
-            tracker.track(left.data(), right.data(), nullptr, frames, rows, cols, camera, &dataset);
+            ceres_slam::DatasetProblem dataset;
+            tracker.track(left.data(), use_sgbm ? nullptr : right.data(), use_sgbm ? disp16.data() : nullptr, frames, rows, cols, camera, &dataset);
+            std::cerr << dataset.stereo_obs_list.size() << " observations of " << dataset.num_points << " tracks in " << frames << " frames" << std::endl;
+            if (tracker.subpixel) std::cerr << tracker.num_dropped << " observations dropped by the refinement" << std::endl;
+            if (!dataset.compute_initial_guess()) return EXIT_FAILURE;
+            usable = solveAll(dataset, huber);
+            trajectory = dataset.poses;
         }
     } catch (const std::exception &e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;
     }
-    std::cerr << dataset.stereo_obs_list.size() << " observations of " << dataset.num_points << " tracks in " << frames << " frames" << std::endl;
-    if (tracker.subpixel) std::cerr << tracker.num_dropped << " observations dropped by the refinement" << std::endl;
-    if (!dataset.compute_initial_guess()) return EXIT_FAILURE;
-    const bool usable = solveAll(dataset, huber);
 
     std::cout.precision(17);
     for (int k = 0; k < frames; ++k) {
         std::cout << "frame " << k;
-        for (int c = 0; c < 12; ++c) std::cout << " " << dataset.poses[k].data()[c];
+        for (int c = 0; c < 12; ++c) std::cout << " " << trajectory[k].data()[c];
         std::cout << std::endl;
     }
     return usable ? EXIT_SUCCESS : EXIT_FAILURE;

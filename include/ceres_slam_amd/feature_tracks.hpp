@@ -1,4 +1,5 @@
-// FeatureTracker -- from a stack of rectified stereo frames to a DatasetProblem (dataset_problem.hpp), on the device.
+// FeatureTracker, FeatureTrackStream -- from rectified stereo frames, as a stack or one by one, to a DatasetProblem
+// (dataset_problem.hpp), on the device.
 //
 // The reference's stereo-odometry node (ros/src/ceres_slam/src/sparse_stereo_odometry_node.cpp:127-216) detects and describes
 // features, matches left to right and frame to frame, and hands (u, v, d) rows with landmark ids to the back end.
@@ -16,6 +17,33 @@
 #include "ssba_tracks.h"
 
 namespace ceres_slam {
+
+namespace detail {
+
+//! tracks in ssba_frontend_vo's input format into a DatasetProblem: the camera, one state per frame (the first pose is
+//! `first_pose`, the others the identity), one uninitialised map point per track, the observations grouped by state in keypoint
+//! order, unit observation variances
+inline void fill_dataset(DatasetProblem::CameraPtr camera, uint32_t frames, const std::vector<uint32_t> &state_start, const std::vector<uint32_t> &point_id,
+                         const std::vector<double> &uvd, uint32_t num_points, const SE3 &first_pose, DatasetProblem *out) {
+    out->camera = camera;
+    out->num_states = frames;
+    out->num_points = num_points;
+    out->poses.assign(frames, SE3());
+    if (frames) out->poses[0] = first_pose;
+    out->map_points.assign(num_points, Point());
+    out->initialized_point.assign(num_points, false);
+    for (int c = 0; c < 3; ++c) out->stereo_obs_var.v[c] = 1.0;
+    out->state_ids.clear(); out->point_ids.clear(); out->stereo_obs_list.clear();
+    for (uint32_t k = 0; k < frames; ++k)
+        for (uint32_t i = state_start[k]; i < state_start[k + 1]; ++i) {
+            out->state_ids.push_back(k);
+            out->point_ids.push_back(point_id[i]);
+            out->stereo_obs_list.push_back(DatasetProblem::Observation{{uvd[3 * (size_t)i], uvd[3 * (size_t)i + 1], uvd[3 * (size_t)i + 2]}});
+        }
+    out->rebuild_indices();
+}
+
+}  // namespace detail
 
 class FeatureTracker {
  public:
@@ -52,23 +80,63 @@ class FeatureTracker {
                                 : ssba_track_sequence(left, right, disp16, frames, rows, cols, &params, device, capacity, state_start.data(), point_id.data(),
                                                       uvd.data(), &num_observations, &num_points);
         if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
-        out->camera = camera;
-        out->num_states = frames;
-        out->num_points = num_points;
-        out->poses.assign(frames, SE3());
-        if (frames) out->poses[0] = first_pose;
-        out->map_points.assign(num_points, Point());
-        out->initialized_point.assign(num_points, false);
-        for (int c = 0; c < 3; ++c) out->stereo_obs_var.v[c] = 1.0;
-        out->state_ids.clear(); out->point_ids.clear(); out->stereo_obs_list.clear();
-        for (uint32_t k = 0; k < frames; ++k)
-            for (uint32_t i = state_start[k]; i < state_start[k + 1]; ++i) {
-                out->state_ids.push_back(k);
-                out->point_ids.push_back(point_id[i]);
-                out->stereo_obs_list.push_back(DatasetProblem::Observation{{uvd[3 * (size_t)i], uvd[3 * (size_t)i + 1], uvd[3 * (size_t)i + 2]}});
-            }
-        out->rebuild_indices();
+        detail::fill_dataset(camera, frames, state_start, point_id, uvd, num_points, first_pose, out);
     }
+};
+
+//! The same tracker fed one stereo pair at a time (ssba_track_stream_create): its state stays on the device, a push costs the
+//! same however many frames came before, ids persist for the life of the stream, and with `refine` a track's template is the
+//! patch at its true first observation.  window() hands out the last frames as FeatureTracker::track would a stack.
+class FeatureTrackStream {
+ public:
+    //! the observations of the newest push whose refinement failed and that were left out
+    uint32_t num_dropped = 0;
+
+    //! `window`: how many of the most recent frames window() can cover.  `refine` NULL: whole-pixel observations.
+    FeatureTrackStream(uint32_t rows, uint32_t cols, uint32_t window, const ssba_track_params &params, const ssba_track_refine_params *refine = nullptr,
+                       int device = -1)
+        : max_features_(params.max_features > 0 ? (size_t)params.max_features : 0) {
+        const int rc = ssba_track_stream_create(rows, cols, &params, refine, window, device, &stream_);
+        if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
+        track_id_.resize(max_features_ ? max_features_ : 1);
+        uvd_.resize(3 * (max_features_ ? max_features_ : 1));
+    }
+    ~FeatureTrackStream() { ssba_track_stream_destroy(stream_); }
+    FeatureTrackStream(const FeatureTrackStream &) = delete;
+    FeatureTrackStream &operator=(const FeatureTrackStream &) = delete;
+
+    //! One left image and exactly one of `right` / `disp16`, the same one in every push.  Returns the number of kept survivors;
+    //! track_ids() and uvd() hold them in keypoint order with the ids the stream issued (global, never renumbered).
+    uint32_t push(const uint8_t *left, const uint8_t *right, const int16_t *disp16) {
+        uint32_t n = 0;
+        const int rc = ssba_track_stream_push(stream_, left, right, disp16, track_id_.data(), uvd_.data(), &n, &num_dropped);
+        if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
+        num_observations_ = n;
+        return n;
+    }
+    const uint32_t *track_ids() const { return track_id_.data(); }
+    const double *uvd() const { return uvd_.data(); }
+    uint32_t num_observations() const { return num_observations_; }
+
+    //! The last `frames` pushed frames as FeatureTracker::track fills a dataset: one state per frame, the first at `first_pose`.
+    void window(uint32_t frames, DatasetProblem::CameraPtr camera, DatasetProblem *out, const SE3 &first_pose = SE3()) const {
+        if (!out) throw std::invalid_argument("FeatureTrackStream: NULL dataset");
+        const uint64_t capacity = (uint64_t)frames * max_features_;
+        std::vector<uint32_t> state_start((size_t)frames + 1, 0), point_id(capacity ? capacity : 1);
+        std::vector<double> uvd(3 * (capacity ? capacity : 1));
+        uint64_t num_observations = 0;
+        uint32_t num_points = 0;
+        const int rc = ssba_track_stream_window(stream_, frames, capacity, state_start.data(), point_id.data(), uvd.data(), &num_observations, &num_points);
+        if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
+        detail::fill_dataset(camera, frames, state_start, point_id, uvd, num_points, first_pose, out);
+    }
+
+ private:
+    ssba_track_stream *stream_ = nullptr;
+    size_t max_features_;
+    uint32_t num_observations_ = 0;
+    std::vector<uint32_t> track_id_;
+    std::vector<double> uvd_;
 };
 
 }  // namespace ceres_slam

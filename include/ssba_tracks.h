@@ -90,6 +90,47 @@
  *               the dropped one is the anchor.  Pruning by min_track_length acts on the remaining lengths, ids are renumbered
  *               in id order, and (u, v, d) = q8 / 256.0.
  *
+ * Streaming (the ssba_track_stream_ calls; the numpy statement is tests/tracks_stream_reference.py)
+ *   The node this library restates gets one stereo pair per callback and keeps the previous pair's keypoints and descriptors
+ *   (sparse_stereo_odometry_node.cpp:303-308).  A stream is that mode: a handle whose state stays on the device, frames pushed one
+ *   by one, the work of a push independent of how many frames came before.
+ *   state       the previous frame's survivors (count, positions, descriptors, issued ids), the running id, and a ring of the last
+ *               `window` frames with, per survivor slot: the issued id, the slot of the frame before it inherited from (or none),
+ *               the kept flag and the observation (whole pixel: x, y, d16; refined: u, v, d in q8).  With refinement also the
+ *               ANCHOR PATCH of every survivor's track: the 17 x 17 bytes around the anchor, everything the template reads
+ *               (a keypoint keeps 15 pixels from every edge, so the patch is inside its image).  An inheriting survivor carries
+ *               its predecessor's patch on, a survivor that is issued an id cuts its own.
+ *   push        features, stereo survivors and the temporal match of the new pair exactly as in the sequence calls; ids as the
+ *               sequence calls issue them BEFORE pruning, the fresh ones counted on from the stream's running id: global to
+ *               the stream, never renumbered, never pruned by min_track_length.  With refinement every survivor is placed as
+ *               in "sequence" above against its track's patch; one whose status is not OK is dropped from the outputs and
+ *               counts in *num_dropped, but stays in the state, so the next frame can still inherit its id and its patch (the
+ *               sequence calls link before they refine, too).
+ *   window      over the last `frames` pushed frames: a survivor of the oldest frame starts a track, a later survivor continues
+ *               the track of the slot it inherited from or starts one.  A track's length is the number of its kept
+ *               observations inside the window; tracks shorter than min_track_length go; the new ids are dense in the order of
+ *               each track's first survivor in the window (frame, then keypoint slot; a dropped survivor counts for the order,
+ *               not for the length).
+ *   Two consequences, which the tests hold the device to:
+ *   1. Whole pixel: after any number of pushes, a window over W frames equals ssba_track_sequence on those same W frames byte
+ *      for byte, because the features, stereo survivors and temporal matches of a frame pair do not depend on history.
+ *   2. Sub-pixel: a window over W frames equals ssba_track_sequence_subpixel over ALL frames since the stream began, restricted
+ *      to the last W frames and then pruned and renumbered by the window rule.  With W = the number of pushed frames that is
+ *      ssba_track_sequence_subpixel's output byte for byte.  With a shorter window it differs from the batch call on those W
+ *      frames on purpose: the template is the track's first patch, not the window's.
+ *   launches    per push, whatever came before: 4 for the features, k_tr_best left-right (right images only), k_tr_stereo,
+ *               k_tr_best against the frame before (not on the first push), k_ts_link, with refinement k_ts_carry and
+ *               k_ts_refine, k_ts_emit: 9 with right images (11 refined), one fewer with disp16 maps and on the first push.
+ *               Per window call: 1, k_ts_window, whatever `frames`.  A push synchronises once.
+ *   refusals    SSBA_ERR_INVALID_ARGUMENT before a device is looked for: NULL arguments; rows or cols outside 31 ... 8192; every
+ *               parameter refusal above; window < 1 or > SSBA_TRACK_STREAM_MAX_WINDOW; both or neither of right / disp16; a push
+ *               with the other disparity source than the stream's first; frames < 1 or above min(window, pushed frames); after
+ *               the work, a capacity below the number of observations (the message names it; nothing is written).
+ *               SSBA_ERR_STATE: a push when fewer than max_features ids are left below 2^32 - 1.
+ *   use         a stream is one caller's: no two calls on the same stream may run at the same time (different streams may).  After
+ *               a push or a window call that returned SSBA_ERR_HIP the device's state may be ahead of the host's, so the stream
+ *               is dead: every later push or window call on it is SSBA_ERR_STATE, and only destroying it remains.
+ *
  * SSBA_ERR_INVALID_ARGUMENT, with a message and before a device is looked for: a NULL input or output; both or neither of
  *   right / disp16; frames < 1 or > 32767 (n likewise, up to 65535); rows or cols < 31 or > 8192; max_features outside
  *   1 ... 4096; fast_threshold outside 0 ... 254; max_hamming outside 0 ... 256; a negative stereo_max_dy, max_disparity or
@@ -169,6 +210,32 @@ SSBA_API int ssba_track_sequence_subpixel(const uint8_t *left, const uint8_t *ri
                                           const ssba_track_params *params, int device, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
                                           double *uvd, uint64_t *num_observations, uint32_t *num_points,
                                           const ssba_track_refine_params *refine_params, uint64_t *num_dropped);
+
+/* ---- streaming ---------------------------------------------------------------------------------------------------------- */
+#define SSBA_TRACK_STREAM_MAX_WINDOW 256
+
+typedef struct ssba_track_stream ssba_track_stream;
+
+/* A stream for frames of rows x cols.  refine_params NULL: whole-pixel observations; otherwise sub-pixel ones.  window: how many
+ * of the most recent frames ssba_track_stream_window can cover, 1 ... SSBA_TRACK_STREAM_MAX_WINDOW.  All device and pinned host
+ * memory is allocated here (about 10 images, 64 bytes per keypoint slot and per window frame, 1 KiB per keypoint slot), none per
+ * push; the stream holds one pooled stream until it is destroyed. */
+SSBA_API int ssba_track_stream_create(uint32_t rows, uint32_t cols, const ssba_track_params *params, const ssba_track_refine_params *refine_params,
+                                      uint32_t window, int device, ssba_track_stream **stream);
+
+/* One stereo pair: the left image and exactly one of right / disp16, the same one in every push of a stream.  track_id and uvd
+ * (3 per observation) MUST have room for max_features entries: the frame's kept survivors in keypoint order with their issued
+ * ids.  *num_dropped: this frame's survivors whose refinement did not end OK (0 without refinement). */
+SSBA_API int ssba_track_stream_push(ssba_track_stream *stream, const uint8_t *left, const uint8_t *right, const int16_t *disp16, uint32_t *track_id,
+                                    double *uvd, uint32_t *num_observations, uint32_t *num_dropped);
+
+/* The last `frames` pushed frames, 1 <= frames <= min(window, pushed frames), in ssba_frontend_vo's input format as
+ * ssba_track_sequence writes it: state_start (frames + 1), point_id and uvd with room for `capacity` observations. */
+SSBA_API int ssba_track_stream_window(ssba_track_stream *stream, uint32_t frames, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
+                                      double *uvd, uint64_t *num_observations, uint32_t *num_points);
+
+/* NULL is allowed.  Nothing else may use the stream while or after this runs. */
+SSBA_API void ssba_track_stream_destroy(ssba_track_stream *stream);
 
 SSBA_API const char *ssba_track_last_error(void);
 

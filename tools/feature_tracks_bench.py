@@ -19,7 +19,17 @@ kernels, and apart from them the copy kernels the HIP runtime itself launches fo
 --subpixel measures tracks.track_sequence_subpixel against tracks.track_sequence on the same frames in the same process, the two
 calls taking turns window by window (track_sequence's code is the parent's, so it is the parent's figure), checks that with
 nothing dropped the two calls name the same observations, and writes profiles/feature_tracks_subpixel.json; with --trace-run the
-one call is the sub-pixel one, and --merge-trace counts k_tr_anchor and k_tr_refine with the rest."""
+one call is the sub-pixel one, and --merge-trace counts k_tr_anchor and k_tr_refine with the rest.
+
+--stream measures tracks.TrackStream (frames pushed one by one) and writes profiles/feature_track_stream.json.  The frames are 17
+of the shape's sequence, walked back and forth so that consecutive pushes are neighbours.  Per shape, whole pixel and sub-pixel:
+  push_ms           one push; then per W in 2, 5, 17: push + window(W) against what a live caller does without a stream, the batch
+                    call (track_sequence / track_sequence_subpixel, whose code is the parent's) on the W most recent frames after
+                    every new frame, on the same frames.  One warm-up window, three timed windows of --calls frames each, the two
+                    labels taking turns window by window in one process; median window per frame in ms and the spread.
+  history           one stream of 50 pushes with a host clock around each: the pushes at indices 5 ... 14 against 40 ... 49.
+With --stream, --trace-run makes ONE stream push 17 frames with a window call after each, and --merge-trace splits the trace at
+k_ts_emit (the last launch of a push) and k_ts_window into the launches of every push and of every window call."""
 import argparse
 import collections
 import csv
@@ -76,6 +86,107 @@ def compare(seq, name, calls):
                 largest_move_px=round(float(abs(fine[2][:, :2] - whole[2][:, :2]).max()), 4) if same else None)
 
 
+STREAM_FRAMES, STREAM_WINDOWS = 17, (2, 5, 17)
+
+
+def walk(n, frames=STREAM_FRAMES):
+    """n frame indices 0, 1, ..., frames - 1, frames - 2, ..., 1, 0, 1, ...: neighbours follow each other"""
+    period = list(range(frames)) + list(range(frames - 2, 0, -1))
+    return [period[k % len(period)] for k in range(n)]
+
+
+def stream_frames(name):
+    s = SHAPES[name]
+    return synth.make_stereo_sequence(s["rows"], s["cols"], STREAM_FRAMES, seed=10, motion=1.0, min_wavelength_px=8.0)
+
+
+def stream_compare(seq, name, calls, sub):
+    """Per-frame cost of a stream against the batch call on the last W frames, and the push time early and late in a stream."""
+    shape, kw = SHAPES[name], dict(fast_threshold=FAST_THRESHOLD, max_features=SHAPES[name]["max_features"])
+    refine = {} if sub else None
+    batch = tracks.track_sequence_subpixel if sub else tracks.track_sequence
+    order = walk(4 * calls + max(STREAM_WINDOWS))
+    left, right = seq.left[order], seq.right[order]                     # the caller's frames in arrival order: a slice is the last W
+    out = dict(calls_per_window=calls)
+
+    def timed(step, first):
+        t = time.perf_counter()
+        for k in range(first, first + calls):
+            step(k)
+        return (time.perf_counter() - t) / calls * 1e3
+
+    def summary(windows):
+        return dict(ms=round(statistics.median(windows), 4), spread_ms=round(max(windows) - min(windows), 4), windows_ms=[round(w, 4) for w in windows])
+
+    with tracks.TrackStream(shape["rows"], shape["cols"], 2, refine=refine, **kw) as st:
+        push = lambda k: st.push(left[k], right[k])
+        timed(push, 0)
+        out["push"] = summary([timed(push, (1 + i) * calls) for i in range(3)])
+    for W in STREAM_WINDOWS:
+        with tracks.TrackStream(shape["rows"], shape["cols"], W, refine=refine, **kw) as st:
+            for k in range(W - 1):                                       # both callers start with W - 1 frames behind them
+                st.push(left[k], right[k])
+
+            def streamed(k):
+                st.push(left[k], right[k])
+                return st.window(W)
+
+            def batched(k):
+                return batch(left[k + 1 - W:k + 1], right[k + 1 - W:k + 1], **kw)
+
+            first = W - 1
+            timed(streamed, first)
+            timed(batched, first)
+            windows = {"stream": [], "batch": []}
+            for i in range(3):
+                windows["stream"].append(timed(streamed, first + (1 + i) * calls))
+                windows["batch"].append(timed(batched, first + (1 + i) * calls))
+            last = first + 4 * calls - 1
+            got, want = st.window(W), batched(last)
+            entry = dict(push_and_window=summary(windows["stream"]), batch_on_last_w=summary(windows["batch"]), observations=int(len(got[1])), tracks=int(got[3]))
+            entry["batch_over_stream"] = round(entry["batch_on_last_w"]["ms"] / entry["push_and_window"]["ms"], 3)
+            if not sub:                                                  # whole pixel: the window is the batch call on its frames, byte for byte
+                entry["same_bytes_as_batch"] = bool(all(a.tobytes() == b.tobytes() for a, b in zip(got[:3], want[:3])) and got[3] == want[3])
+            out[f"w{W}"] = entry
+    order = walk(50)
+    with tracks.TrackStream(shape["rows"], shape["cols"], 5, refine=refine, **kw) as st:
+        each = []
+        for k in order:
+            t = time.perf_counter()
+            st.push(seq.left[k], seq.right[k])
+            each.append((time.perf_counter() - t) * 1e3)
+    for label, part in (("pushes_5_to_14", each[5:15]), ("pushes_40_to_49", each[40:50])):
+        out[label] = dict(median_ms=round(statistics.median(part), 4), spread_ms=round(max(part) - min(part), 4))
+    return out
+
+
+def stream_trace_run(name, sub):
+    seq, shape = stream_frames(name), SHAPES[name]
+    with tracks.TrackStream(shape["rows"], shape["cols"], STREAM_FRAMES, refine={} if sub else None, fast_threshold=FAST_THRESHOLD,
+                            max_features=shape["max_features"]) as st:
+        for k in range(STREAM_FRAMES):
+            st.push(seq.left[k], seq.right[k])
+            st.window(k + 1)
+
+
+def stream_merge_trace(path):
+    """The library's launches of every push and of every window call, in the order of the trace."""
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
+    pushes, windows, current, per = [], [], [], collections.defaultdict(list)
+    for row in rows:
+        found = re.search(r"k_t[rs]_\w+", row["Kernel_Name"])
+        if not found:
+            continue
+        per[found.group(0)].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+        current.append(found.group(0))
+        if found.group(0) in ("k_ts_emit", "k_ts_window"):
+            (pushes if found.group(0) == "k_ts_emit" else windows).append(current)
+            current = []
+    return dict(launches_per_push=[len(p) for p in pushes], launches_per_window_call=[len(w) for w in windows],
+                launches_at_pushes_2_5_17=[len(pushes[k - 1]) for k in (2, 5, 17) if k <= len(pushes)], kernels_of_push_2=pushes[1] if len(pushes) > 1 else [],
+                kernels_us={k: dict(launches=len(v), median_us=round(statistics.median(v), 2), total_us=round(sum(v), 2)) for k, v in sorted(per.items())})
+
+
 def load(path):
     return json.load(open(path)) if os.path.exists(path) else {}
 
@@ -84,12 +195,33 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--subpixel", action="store_true")
+    ap.add_argument("--stream", action="store_true")
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--trace-run")
     ap.add_argument("--merge-trace", nargs=2)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "feature_tracks_subpixel.json" if a.subpixel else "feature_tracks.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "feature_track_stream.json" if a.stream else "feature_tracks_subpixel.json" if a.subpixel else "feature_tracks.json")
+    if a.stream:
+        if a.trace_run:
+            stream_trace_run(a.trace_run, a.subpixel)
+            return
+        doc = load(a.out)
+        if a.merge_trace:
+            name, path = a.merge_trace
+            doc.setdefault(name, {}).update(SHAPES[name])
+            doc[name]["trace_subpixel" if a.subpixel else "trace_whole_pixel"] = stream_merge_trace(path)
+        else:
+            for name in a.shapes.split(","):
+                seq = stream_frames(name)
+                doc.setdefault(name, {}).update(SHAPES[name], frames=STREAM_FRAMES, fast_threshold=FAST_THRESHOLD)
+                for sub in (False, True):
+                    doc[name]["subpixel" if sub else "whole_pixel"] = stream_compare(seq, name, a.calls, sub)
+                    print(name, "subpixel" if sub else "whole_pixel", doc[name]["subpixel" if sub else "whole_pixel"])
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     if a.trace_run:
         run(frames_of(a.trace_run), a.trace_run, a.subpixel)
         return

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libssba.so")
 SOURCES = ["ssba_api.hip", "ssba_kernels.hip", "ssba_bcr.hip", "ssba_bcr_mfma.hip", "ssba_phong.hip", "ssba_phong_solver.hip", "ssba_border.hip", "ssba_frontend.hip", "ssba_dense.hip", "ssba_pool.hip", "ssba_wide.hip", "ssba_wide_covariance.hip", "ssba_covariance.hip", "ssba_image.hip", "ssba_image_pyramid.hip", "ssba_sgbm.hip", "ssba_wide_layout.cpp", "ssba_layout.cpp"]
-HEADERS = ["ssba_types.h", "ssba_wide_device.h", "ssba_wide_layout.h", "ssba_pool.h", "ssba_launch.h", "ssba_device.h", "ssba_phong_device.h", "ssba_linesearch.h", "ssba_posefactor_device.h", "ssba_check.h", "ssba_solve6.h", "ssba_image_pyramid.h", "ssba_sgbm.h", "libssba.map", os.path.join("..", "..", "include", "ssba.h")]
+HEADERS = ["ssba_types.h", "ssba_wide_device.h", "ssba_wide_layout.h", "ssba_pool.h", "ssba_launch.h", "ssba_device.h", "ssba_phong_device.h", "ssba_linesearch.h", "ssba_posefactor_device.h", "ssba_check.h", "ssba_solve6.h", "ssba_align3.h", "ssba_image_pyramid.h", "ssba_sgbm.h", "libssba.map", os.path.join("..", "..", "include", "ssba.h")]
 # -fvisibility=hidden + the version script below: the dynamic symbol table of libssba.so holds the entry points of
 # include/ssba.h (SSBA_API) and nothing else -- no unprefixed helpers, no ssba:: C++ symbols next to torch's RCCL or user code
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall", "-Wno-unused-function", *os.environ.get("SSBA_EXTRA_FLAGS", "").split(),
@@ -29,7 +29,7 @@ FILE_FLAGS = {"ssba_bcr_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # share a file.
 TRACKS_LIB = os.path.join(HERE, "libssba_tracks.so")
 TRACKS_SOURCES = ["ssba_tracks.hip", "ssba_pool.hip"]
-TRACKS_HEADERS = ["ssba_pool.h", "ssba_brief_pattern.h", "libssba_tracks.map", os.path.join("..", "..", "include", "ssba.h"),
+TRACKS_HEADERS = ["ssba_pool.h", "ssba_brief_pattern.h", "ssba_align3.h", "ssba_solve6.h", "ssba_device.h", "ssba_types.h", "ssba_tracks_odometry.h", "libssba_tracks.map", os.path.join("..", "..", "include", "ssba.h"),
                   os.path.join("..", "..", "include", "ssba_tracks.h")]
 
 

@@ -23,10 +23,14 @@
 //   k_ts_refine     k_tr_refine with the template from the patch store              grid (max_features / 4)
 //   k_ts_emit       the push outputs compacted, the frame's ring entry              grid (1)
 // and ssba_track_stream_window is one launch, k_ts_window: k_tr_link and k_tr_prune on the ring's stored links, grid (1).
+// A stream with odometry enabled (ssba_track_stream_enable_odometry) adds four launches to a push, ssba_tracks_odometry.h:
+//   k_od_match, k_od_align, k_od_score, k_od_solve: the matches to the frame before triangulated, the 3-point RANSAC, the
+//   two-view Levenberg-Marquardt refinement and the chained pose, which comes down in the push's one copy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1048,6 +1052,14 @@ __global__ __launch_bounds__(TR_BLOCK) void k_ts_window(const StreamEntry *__res
     }
 }
 
+}  // namespace
+}  // namespace ssba
+
+#include "ssba_tracks_odometry.h"      // k_od_match ... k_od_solve: a pose with every push (uses the scan and ts_uvd above)
+
+namespace ssba {
+namespace {
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 std::mutex g_error_mutex;
 std::string g_error;
@@ -1380,6 +1392,15 @@ struct ssba_track_stream {
     StreamEntry *entries = nullptr;
     uint32_t *entry_count = nullptr, *local = nullptr, *length = nullptr, *new_id = nullptr, *w_start = nullptr, *w_point = nullptr, *w_totals = nullptr;
     double *w_uvd = nullptr;
+    // odometry (ssba_track_stream_enable_odometry): the rule, the work arrays, the kept flags and observations of the previous and
+    // the current frame, first_pose on the device, the last push's pose block on the host
+    bool odometry = false;
+    OdRule od_rule = {};
+    OdWork od = {};
+    uint8_t *od_kept[2] = {nullptr, nullptr};
+    double *od_uvd[2] = {nullptr, nullptr};
+    double *od_first = nullptr;
+    OdPose pose = {};
 };
 
 namespace {
@@ -1387,6 +1408,104 @@ namespace {
 constexpr size_t TS_OUT_SCALARS = 4 * sizeof(uint32_t);
 
 size_t ts_out_bytes(uint32_t stride) { return TS_OUT_SCALARS + (size_t)stride * (3 * sizeof(double) + sizeof(uint32_t)); }
+
+// with odometry the pose block follows the push outputs on the next multiple of 8 bytes
+size_t ts_pose_at(uint32_t stride) { return (ts_out_bytes(stride) + 7) & ~(size_t)7; }
+
+int od_check_params(const char *call, const ssba_track_odometry_params *p) {
+    if (!p) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL odometry parameters");
+    if (p->ransac_iterations < 1 || p->ransac_iterations > SSBA_TRACK_ODOMETRY_MAX)
+        return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "ransac_iterations must be in 1 ... 4096");
+    if (p->refine_iterations > SSBA_TRACK_ODOMETRY_MAX_REFINE) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "refine_iterations must not exceed 1024");
+    const double positive[5] = {p->ransac_threshold, p->observation_variance, p->camera.fu, p->camera.fv, p->camera.b};
+    for (double v : positive)
+        if (!(v > 0.0) || !std::isfinite(v))
+            return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "ransac_threshold, observation_variance and the camera's fu, fv and b must be positive");
+    if (!std::isfinite(p->camera.cu) || !std::isfinite(p->camera.cv)) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "the camera's cu and cv must be finite");
+    return SSBA_OK;
+}
+
+OdRule od_rule_of(const ssba_track_odometry_params &p) {
+    return OdRule{Cam{p.camera.fu, p.camera.fv, p.camera.cu, p.camera.cv, p.camera.b}, p.ransac_iterations, p.refine_iterations, p.ransac_threshold,
+                  1.0 / std::sqrt(p.observation_variance)};
+}
+
+hipError_t od_allocate(std::vector<void *> *t, const OdRule &rule, OdWork *w) {
+    const size_t cap = SSBA_TRACK_ODOMETRY_MAX;
+    TR_TRY(tr_alloc(t, &w->n, (size_t)1));
+    for (double **a : {&w->obs0, &w->obs1, &w->pts0, &w->pts1, &w->x, &w->c, &w->scale}) TR_TRY(tr_alloc(t, a, cap * 3));
+    TR_TRY(tr_alloc(t, &w->hyp, (size_t)rule.hypotheses * 12));
+    TR_TRY(tr_alloc(t, &w->count, (size_t)rule.hypotheses));
+    TR_TRY(tr_alloc(t, &w->inlier, cap));
+    TR_TRY(tr_alloc(t, &w->index, cap));
+    TR_TRY(tr_alloc(t, &w->cost_log, (size_t)rule.iterations + 1));
+    TR_TRY(tr_alloc(t, &w->step_ok, (size_t)rule.iterations + 1));
+    TR_TRY(tr_alloc(t, &w->chain, (size_t)12));
+    return hipSuccess;
+}
+
+// the launches behind the match list: k_od_align and k_od_score (not for a stream's first push, mode 1), k_od_solve
+hipError_t od_enqueue(const OdRule &rule, uint32_t frame, const OdWork &w, int mode, const double *first_pose, OdPose *out, hipStream_t s) {
+    if (mode != 1) {
+        hipLaunchKernelGGL(k_od_align, dim3((rule.hypotheses + 255) / 256), dim3(256), 0, s, rule, frame, w);
+        TR_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_od_score, dim3((rule.hypotheses + 3) / 4), dim3(256), 0, s, rule, w);
+        TR_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_od_solve, dim3(1), dim3(OD_BLOCK), 0, s, rule, w, mode, first_pose, out);
+    return hipGetLastError();
+}
+
+void od_info(const OdPose &p, ssba_track_pose_info *info) {
+    if (!info) return;
+    *info = ssba_track_pose_info{p.status, p.num_matches, p.num_inliers, p.num_iterations, p.initial_cost, p.final_cost};
+}
+
+hipError_t od_enable(ssba_track_stream *st, const ssba_track_odometry_params &p) {
+    const uint32_t stride = (uint32_t)st->p.max_features;
+    const size_t bytes = ts_pose_at(stride) + sizeof(OdPose);
+    std::vector<void *> *t = &st->temps;
+    st->od_rule = od_rule_of(p);
+    TR_TRY(od_allocate(t, st->od_rule, &st->od));
+    for (int b = 0; b < 2; ++b) {
+        TR_TRY(tr_alloc(t, &st->od_kept[b], (size_t)stride));
+        TR_TRY(tr_alloc(t, &st->od_uvd[b], (size_t)stride * 3));
+    }
+    TR_TRY(tr_alloc(t, &st->od_first, (size_t)12));
+    TR_TRY(tr_alloc(t, &st->out, bytes));            // the push output block with the pose block behind it; the old one is freed with the stream
+    void *pinned = nullptr;
+    TR_TRY(pool_host_malloc(&pinned, bytes));
+    pool_host_free(st->stage_out);
+    st->stage_out = (uint8_t *)pinned;
+    memcpy(st->stage_out, p.first_pose, 12 * sizeof(double));
+    TR_TRY(hipMemcpyAsync(st->od_first, st->stage_out, 12 * sizeof(double), hipMemcpyHostToDevice, st->s));
+    return hipStreamSynchronize(st->s);
+}
+
+hipError_t od_run_relative(const OdRule &rule, uint32_t frame, uint32_t n, const double *uvd_prev, const double *uvd_cur, double *T_ransac, uint8_t *inlier,
+                           double *cost_log, int32_t *step_ok, OdPose *pose, hipStream_t s, std::vector<void *> *temps) {
+    OdWork w = {};
+    OdPose *dpose = nullptr;
+    double *dprev = nullptr, *dcur = nullptr;
+    TR_TRY(od_allocate(temps, rule, &w));
+    TR_TRY(tr_alloc(temps, &dpose, (size_t)1));
+    TR_TRY(tr_alloc(temps, &dprev, (size_t)n * 3));
+    TR_TRY(tr_alloc(temps, &dcur, (size_t)n * 3));
+    if (n) {
+        TR_TRY(hipMemcpyAsync(dprev, uvd_prev, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        TR_TRY(hipMemcpyAsync(dcur, uvd_cur, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(k_od_pairs, dim3(n ? (n + 255) / 256 : 1), dim3(256), 0, s, rule.cam, (const double *)dprev, (const double *)dcur, n, w);
+    TR_TRY(hipGetLastError());
+    TR_TRY(od_enqueue(rule, frame, w, 2, nullptr, dpose, s));
+    TR_TRY(hipMemcpyAsync(pose, dpose, sizeof(OdPose), hipMemcpyDeviceToHost, s));
+    if (inlier && n) TR_TRY(hipMemcpyAsync(inlier, w.inlier, (size_t)n, hipMemcpyDeviceToHost, s));
+    if (cost_log) TR_TRY(hipMemcpyAsync(cost_log, w.cost_log, ((size_t)rule.iterations + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (step_ok) TR_TRY(hipMemcpyAsync(step_ok, w.step_ok, ((size_t)rule.iterations + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TR_TRY(hipStreamSynchronize(s));
+    if (T_ransac) memcpy(T_ransac, pose->T_ransac, 12 * sizeof(double));
+    return hipSuccess;
+}
 
 hipError_t ts_allocate(ssba_track_stream *st) {
     const size_t npix = (size_t)st->rows * st->cols, stride = (size_t)st->p.max_features, slots = stride * st->window;
@@ -1493,9 +1612,18 @@ hipError_t ts_push(ssba_track_stream *st, const uint8_t *left, const uint8_t *ri
                        (const uint32_t *)st->running_id, st->entries + (size_t)slot * stride, st->entry_count + slot, (uint32_t *)st->out,
                        (double *)(st->out + TS_OUT_SCALARS), (uint32_t *)(st->out + TS_OUT_SCALARS + (size_t)stride * 3 * sizeof(double)));
     TR_TRY(hipGetLastError());
-    TR_TRY(hipMemcpyAsync(st->stage_out, st->out, ts_out_bytes(stride), hipMemcpyDeviceToHost, s));
+    if (st->odometry) {      // 4 launches more (2 on the first push); the pose block comes down in the same copy
+        hipLaunchKernelGGL(k_od_match, dim3(1), dim3(TR_BLOCK), 0, s, st->od_rule.cam, (const uint32_t *)now.count, (const uint16_t *)now.xy,
+                           (const int32_t *)now.d16, (const uint32_t *)st->from, (const int32_t *)st->refined, (const int32_t *)st->status, stride, has_prev,
+                           (const uint8_t *)st->od_kept[st->cur ^ 1], (const double *)st->od_uvd[st->cur ^ 1], st->od_kept[st->cur], st->od_uvd[st->cur], st->od);
+        TR_TRY(hipGetLastError());
+        TR_TRY(od_enqueue(st->od_rule, (uint32_t)st->pushed, st->od, has_prev ? 0 : 1, st->od_first, (OdPose *)(st->out + ts_pose_at(stride)), s));
+    }
+    const size_t down = st->odometry ? ts_pose_at(stride) + sizeof(OdPose) : ts_out_bytes(stride);
+    TR_TRY(hipMemcpyAsync(st->stage_out, st->out, down, hipMemcpyDeviceToHost, s));
     TR_TRY(hipStreamSynchronize(s));          // the one synchronisation of a push
     memcpy(scalars, st->stage_out, 3 * sizeof(uint32_t));
+    if (st->odometry) memcpy(&st->pose, st->stage_out + ts_pose_at(stride), sizeof(OdPose));
     return hipSuccess;
 }
 
@@ -1622,6 +1750,61 @@ void ssba_track_stream_destroy(ssba_track_stream *stream) {
     if (!stream) return;
     (void)hipSetDevice(stream->device);
     ts_free(stream);
+}
+
+void ssba_track_default_odometry_params(ssba_track_odometry_params *params) {
+    if (!params) return;
+    *params = ssba_track_odometry_params{{0.0, 0.0, 0.0, 0.0, 0.0}, 400, 4.0, 20, 4.0, {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1}};
+}
+
+int ssba_track_stream_enable_odometry(ssba_track_stream *stream, const ssba_track_odometry_params *params) {
+    const char *call = "ssba_track_stream_enable_odometry";
+    if (!stream) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL stream");
+    if (const int rc = od_check_params(call, params)) return rc;
+    if (stream->failed) return tr_refuse(call, SSBA_ERR_STATE, "an earlier call on this stream ended with a HIP error: destroy it");
+    if (stream->pushed) return tr_refuse(call, SSBA_ERR_STATE, "odometry is enabled before the first push");
+    if (stream->odometry) return tr_refuse(call, SSBA_ERR_STATE, "odometry is enabled already");
+    if (hipSetDevice(stream->device) != hipSuccess) return tr_refuse(call, SSBA_ERR_HIP, "hipSetDevice failed");
+    const hipError_t e = od_enable(stream, *params);
+    if (e != hipSuccess) {
+        stream->failed = true;
+        (void)hipStreamSynchronize(stream->s);
+        return tr_refuse(call, SSBA_ERR_HIP, hipGetErrorString(e));
+    }
+    stream->odometry = true;
+    return SSBA_OK;
+}
+
+int ssba_track_stream_pose(ssba_track_stream *stream, double T_k_km1[12], double T_k_0[12], ssba_track_pose_info *info) {
+    const char *call = "ssba_track_stream_pose";
+    if (!stream) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL stream");
+    if (!T_k_km1 || !T_k_0) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (!stream->odometry) return tr_refuse(call, SSBA_ERR_STATE, "the stream has no odometry: ssba_track_stream_enable_odometry comes before the first push");
+    if (!stream->pushed) return tr_refuse(call, SSBA_ERR_STATE, "nothing has been pushed yet");
+    if (stream->failed) return tr_refuse(call, SSBA_ERR_STATE, "an earlier call on this stream ended with a HIP error: destroy it");
+    memcpy(T_k_km1, stream->pose.T_rel, 12 * sizeof(double));
+    memcpy(T_k_0, stream->pose.T_abs, 12 * sizeof(double));
+    od_info(stream->pose, info);
+    return SSBA_OK;
+}
+
+int ssba_track_relative_pose(const ssba_track_odometry_params *params, uint32_t frame_index, uint32_t n, const double *uvd_prev, const double *uvd_cur,
+                             int device, double *T_ransac, uint8_t *inlier, double *T, ssba_track_pose_info *info, double *cost_log, int32_t *step_ok) {
+    const char *call = "ssba_track_relative_pose";
+    if (const int rc = od_check_params(call, params)) return rc;
+    if (n && (!uvd_prev || !uvd_cur)) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL observations");
+    if (!T || !info) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "NULL output");
+    if (n > SSBA_TRACK_ODOMETRY_MAX) return tr_refuse(call, SSBA_ERR_INVALID_ARGUMENT, "n must not exceed 4096");
+    hipStream_t s = nullptr;
+    if (const int rc = tr_open_device(call, device, &s)) return rc;
+    std::vector<void *> temps;
+    OdPose pose = {};
+    const hipError_t e = od_run_relative(od_rule_of(*params), frame_index, n, uvd_prev, uvd_cur, T_ransac, inlier, cost_log, step_ok, &pose, s, &temps);
+    const int rc = tr_close(call, e, s, &temps);
+    if (rc) return rc;
+    memcpy(T, pose.T_rel, 12 * sizeof(double));
+    od_info(pose, info);
+    return SSBA_OK;
 }
 
 void ssba_track_default_params(ssba_track_params *params) {

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .capi import SsbaError
+from .capi import Camera, SsbaError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libssba_tracks.so")
@@ -17,12 +17,15 @@ LIB_PATH = os.path.join(_HERE, "libssba_tracks.so")
 #: every symbol include/ssba_tracks.h declares
 SYMBOLS = ["ssba_track_default_params", "ssba_track_features", "ssba_track_match", "ssba_track_sequence", "ssba_track_last_error",
            "ssba_track_default_refine_params", "ssba_track_refine", "ssba_track_sequence_subpixel", "ssba_track_stream_create",
-           "ssba_track_stream_push", "ssba_track_stream_window", "ssba_track_stream_destroy"]
+           "ssba_track_stream_push", "ssba_track_stream_window", "ssba_track_stream_destroy", "ssba_track_default_odometry_params",
+           "ssba_track_stream_enable_odometry", "ssba_track_stream_pose", "ssba_track_relative_pose"]
 BORDER, MAX_FEATURES, DESC_WORDS = 15, 4096, 8
 GATE_NONE, GATE_STEREO, GATE_TEMPORAL = 0, 1, 2
 REFINE_OK, REFINE_EDGE, REFINE_FLAT, REFINE_FAR, REFINE_ITERATIONS, REFINE_SAD, REFINE_DISPARITY = range(7)
 REFINE_2D, REFINE_X_ONLY = 0, 1
 STREAM_MAX_WINDOW = 256
+ODOMETRY_MAX, ODOMETRY_MAX_REFINE = 4096, 1024
+POSE_OK, POSE_FIRST_FRAME, POSE_FEW_MATCHES, POSE_FEW_INLIERS, POSE_NUMERICAL = range(5)
 
 _u8p, _u16p, _u32p, _i16p, _i32p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint16, C.c_uint32, C.c_int16, C.c_int32))
 _dp = C.POINTER(C.c_double)
@@ -37,6 +40,21 @@ class TrackParams(C.Structure):
 class RefineParams(C.Structure):
     """ssba_track_refine_params; refine_params(**kw) fills in the library's defaults."""
     _fields_ = [(n, C.c_int32) for n in ("iterations", "max_shift", "max_sad")]
+
+
+class OdometryParams(C.Structure):
+    """ssba_track_odometry_params; odometry_params(**kw) fills in the library's defaults."""
+    _fields_ = [("camera", Camera), ("ransac_iterations", C.c_uint32), ("ransac_threshold", C.c_double), ("refine_iterations", C.c_uint32),
+                ("observation_variance", C.c_double), ("first_pose", C.c_double * 12)]
+
+
+class PoseInfo(C.Structure):
+    """ssba_track_pose_info"""
+    _fields_ = [("status", C.c_int32), ("num_matches", C.c_uint32), ("num_inliers", C.c_uint32), ("num_iterations", C.c_uint32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 _lib = None
@@ -68,6 +86,12 @@ def load():
     L.ssba_track_stream_destroy.argtypes = [C.c_void_p]
     L.ssba_track_stream_destroy.restype = None
     L.ssba_track_last_error.restype = C.c_char_p
+    O = C.POINTER(OdometryParams)
+    L.ssba_track_default_odometry_params.argtypes = [O]
+    L.ssba_track_default_odometry_params.restype = None
+    L.ssba_track_stream_enable_odometry.argtypes = [C.c_void_p, O]
+    L.ssba_track_stream_pose.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(PoseInfo)]
+    L.ssba_track_relative_pose.argtypes = [O, C.c_uint32, C.c_uint32, _dp, _dp, C.c_int, _dp, _u8p, _dp, C.POINTER(PoseInfo), _dp, _i32p]
     _lib = L
     return L
 
@@ -95,6 +119,40 @@ def refine_params(**kw) -> RefineParams:
             raise AttributeError(k)
         setattr(p, k, int(v))
     return p
+
+
+def odometry_params(**kw) -> OdometryParams:
+    """camera: a dict or a capi.Camera; first_pose: 12 numbers [t | R row-major]; the other fields by name."""
+    p = OdometryParams()
+    load().ssba_track_default_odometry_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        if k == "camera":
+            p.camera = v if isinstance(v, Camera) else Camera(**{n: float(v[n]) for n in ("fu", "fv", "cu", "cv", "b")})
+        elif k == "first_pose":
+            p.first_pose = (C.c_double * 12)(*np.asarray(v, dtype=np.float64).reshape(12))
+        elif k in ("ransac_iterations", "refine_iterations"):
+            setattr(p, k, int(v))
+        else:
+            setattr(p, k, float(v))
+    return p
+
+
+def relative_pose(uvd_prev, uvd_cur, frame_index: int = 0, device: int = -1, **odometry):
+    """The odometry's kernels on a list of matches paired by position (ssba_track_relative_pose).  Returns a dict: T_ransac (12,),
+    inlier (n,) uint8, T (12,), info (PoseInfo.as_dict), cost_log and step_ok (refine_iterations + 1 entries each)."""
+    a = np.ascontiguousarray(uvd_prev, dtype=np.float64).reshape(-1, 3)
+    b = np.ascontiguousarray(uvd_cur, dtype=np.float64).reshape(-1, 3)
+    if len(a) != len(b):
+        raise ValueError("the matches are paired by position")
+    p = odometry_params(**odometry)
+    Tr, T, flags, info = np.zeros(12), np.zeros(12), np.zeros(max(len(a), 1), np.uint8), PoseInfo()
+    log, ok = np.zeros(int(p.refine_iterations) + 1), np.zeros(int(p.refine_iterations) + 1, np.int32)
+    check(load().ssba_track_relative_pose(C.byref(p), int(frame_index), len(a), a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), device, Tr.ctypes.data_as(_dp),
+                                          flags.ctypes.data_as(_u8p), T.ctypes.data_as(_dp), C.byref(info), log.ctypes.data_as(_dp), ok.ctypes.data_as(_i32p)),
+          "ssba_track_relative_pose")
+    return dict(T_ransac=Tr, inlier=flags[:len(a)].copy(), T=T, info=info.as_dict(), cost_log=log, step_ok=ok)
 
 
 def _stack(images, dtype, what):
@@ -197,15 +255,38 @@ def track_sequence_subpixel(left, right=None, disp16=None, device: int = -1, cap
 class TrackStream:
     """Frames pushed one by one into a tracker whose state stays on the device (ssba_track_stream_create).  window: how many of
     the most recent frames window() can cover.  refine: None for whole-pixel observations, or a dict of RefineParams fields (an
-    empty one: the defaults) for sub-pixel ones against each track's first patch, however long ago that was."""
+    empty one: the defaults) for sub-pixel ones against each track's first patch, however long ago that was.  odometry: None, or a
+    dict of OdometryParams fields (camera at least): every push then also yields a pose, see pose()."""
 
-    def __init__(self, rows: int, cols: int, window: int, device: int = -1, refine=None, **params):
+    def __init__(self, rows: int, cols: int, window: int, device: int = -1, refine=None, odometry=None, **params):
         self.rows, self.cols, self.window_frames, self.pushed = int(rows), int(cols), int(window), 0
         self.params = track_params(**params)
         rp = None if refine is None else refine_params(**refine)
         self._h = C.c_void_p()
         check(load().ssba_track_stream_create(self.rows, self.cols, C.byref(self.params), None if rp is None else C.byref(rp), self.window_frames, device,
                                               C.byref(self._h)), "ssba_track_stream_create")
+        if odometry is not None:
+            try:
+                self.enable_odometry(**odometry)
+            except Exception:
+                self.close()
+                raise
+
+    def enable_odometry(self, **odometry):
+        """ssba_track_stream_enable_odometry: before the first push only."""
+        if self._h is None:
+            raise ValueError("the stream is closed")
+        p = odometry_params(**odometry)
+        check(load().ssba_track_stream_enable_odometry(self._h, C.byref(p)), "ssba_track_stream_enable_odometry")
+
+    def pose(self):
+        """The last push's (T_k_km1, T_k_0, info): [t | R row-major] with p_k = R p_km1 + t, T_k_0 = T_k_km1 o T_km1_0; info is a dict
+        of status (POSE_OK ...), num_matches, num_inliers, num_iterations, initial_cost, final_cost.  No device work."""
+        if self._h is None:
+            raise ValueError("the stream is closed")
+        rel, chain, info = np.zeros(12), np.zeros(12), PoseInfo()
+        check(load().ssba_track_stream_pose(self._h, rel.ctypes.data_as(_dp), chain.ctypes.data_as(_dp), C.byref(info)), "ssba_track_stream_pose")
+        return rel, chain, info.as_dict()
 
     def _image(self, a, dtype, what):
         a = np.ascontiguousarray(a, dtype=dtype)

@@ -5,7 +5,7 @@
 // writes it): the frames, the camera and the matcher's parameters are used, the pyramid fields are not.
 //
 // usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]
-//            [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W>]
+//            [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W> [--odometry]]
 // --sgbm takes the disparities from the semi-global matcher (StereoSGBM over all pairs in shared launches, sub-pixel) instead
 // of from left-right feature matches (whole pixels).  --temporal-radius gates the frame-to-frame matches to r pixels.
 // --subpixel refines every observation to 1/256 pixel against its track's first patch (FeatureTracker::subpixel), --max-sad
@@ -15,6 +15,9 @@
 // trajectory's pose of the window's oldest frame (which stays constant), and the solved poses replace the trajectory's: the
 // newest pose is chained on, the W - 1 before it are refined once more.  With W >= the number of frames and whole pixels the
 // last window is the whole sequence and the output is that of the run without the flag.
+// --odometry (with --stream W only) prints the trajectory from the stream's own poses instead: every push triangulates the matches
+// to the frame before, runs the 3-point RANSAC and the two-view refinement on the device and chains the pose
+// (FeatureTrackStream::enable_odometry / pose), so there is no window, no front end and no solve per frame; --huber is not used.
 // Output (17 significant digits): one line "frame <k> <12 doubles of T_k_0>" per frame, frame 0 the identity.
 #include <algorithm>
 #include <cmath>
@@ -61,13 +64,14 @@ static bool solveAll(ceres_slam::DatasetProblem &dataset, double huber) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::cerr << "usage: sparse_stereo_sequence_gpu sequence.raw [--sgbm] [--fast-threshold <n>] [--max-features <n>] [--min-track-length <n>]"
-                     " [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W>]" << std::endl;
+                     " [--temporal-radius <r>] [--subpixel] [--max-sad <s>] [--huber <a>] [--stream <W> [--odometry]]" << std::endl;
         return EXIT_FAILURE;
     }
     ceres_slam::FeatureTracker tracker;
     bool use_sgbm = false;
     double huber = 0.0;
     int stream_window = 0;
+    bool odometry = false;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--sgbm")) use_sgbm = true;
         else if (!std::strcmp(argv[a], "--fast-threshold") && a + 1 < argc) tracker.params.fast_threshold = std::atoi(argv[++a]);
@@ -81,8 +85,10 @@ int main(int argc, char **argv) {
             stream_window = std::atoi(argv[++a]);
             if (stream_window < 1) { std::cerr << "--stream takes a window of at least 1 frame, not " << argv[a] << std::endl; return EXIT_FAILURE; }
         }
+        else if (!std::strcmp(argv[a], "--odometry")) odometry = true;
         else { std::cerr << "unknown option " << argv[a] << std::endl; return EXIT_FAILURE; }
     }
+    if (odometry && stream_window < 1) { std::cerr << "--odometry needs --stream <W>: the poses are the stream's own" << std::endl; return EXIT_FAILURE; }
     FILE *f = std::fopen(argv[1], "rb");
     int32_t head[8], sg[11];
     double scale_cam[6], start[12];
@@ -120,9 +126,17 @@ int main(int argc, char **argv) {
         }
         if (stream_window > 0) {
             ceres_slam::FeatureTrackStream stream(rows, cols, stream_window, tracker.params, tracker.subpixel ? &tracker.refine : nullptr);
+            if (odometry) stream.enable_odometry(*camera);
             for (int k = 0; k < frames; ++k) {
                 const uint32_t kept = stream.push(&left[npix * k], use_sgbm ? nullptr : &right[npix * k], use_sgbm ? &disp16[npix * k] : nullptr);
                 std::cerr << "frame " << k << ": " << kept << " observations, " << stream.num_dropped << " dropped by the refinement" << std::endl;
+                if (odometry) {
+                    ssba_track_pose_info info;
+                    trajectory[k] = stream.pose(nullptr, &info);
+                    std::cerr << "frame " << k << ": status " << info.status << ", " << info.num_inliers << " inliers of " << info.num_matches << " matches, "
+                              << info.num_iterations << " iteration records, cost " << info.initial_cost << " -> " << info.final_cost << std::endl;
+                    continue;
+                }
                 if (!k) continue;
                 const int w = std::min(stream_window, k + 1), oldest = k + 1 - w;
                 ceres_slam::DatasetProblem window;

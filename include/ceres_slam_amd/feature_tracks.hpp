@@ -118,6 +118,26 @@ class FeatureTrackStream {
     const double *uvd() const { return uvd_.data(); }
     uint32_t num_observations() const { return num_observations_; }
 
+    //! A pose with every push (ssba_track_stream_enable_odometry): before the first push only.  `params` NULL: the library's
+    //! defaults (400 hypotheses, threshold 4, 20 refinement iterations, variance 4), the chain starting at `first_pose`.
+    void enable_odometry(const StereoCamera &camera, const SE3 &first_pose = SE3(), const ssba_track_odometry_params *params = nullptr) {
+        ssba_track_odometry_params p;
+        if (params) p = *params;
+        else ssba_track_default_odometry_params(&p);
+        p.camera = ssba_camera{camera.fu, camera.fv, camera.cu, camera.cv, camera.b};
+        for (int c = 0; c < 12; ++c) p.first_pose[c] = first_pose.data()[c];
+        const int rc = ssba_track_stream_enable_odometry(stream_, &p);
+        if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
+    }
+    //! The newest push's T_k_0 (and T_k_km1, and how it came about): no device work, the numbers came down with the push.
+    SE3 pose(SE3 *T_k_km1 = nullptr, ssba_track_pose_info *info = nullptr) const {
+        SE3 rel, chained;
+        const int rc = ssba_track_stream_pose(stream_, rel.data(), chained.data(), info);
+        if (rc) throw std::runtime_error(std::string(ssba_status_string(rc)) + ": " + ssba_track_last_error());
+        if (T_k_km1) *T_k_km1 = rel;
+        return chained;
+    }
+
     //! The last `frames` pushed frames as FeatureTracker::track fills a dataset: one state per frame, the first at `first_pose`.
     void window(uint32_t frames, DatasetProblem::CameraPtr camera, DatasetProblem *out, const SE3 &first_pose = SE3()) const {
         if (!out) throw std::invalid_argument("FeatureTrackStream: NULL dataset");

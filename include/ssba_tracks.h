@@ -131,6 +131,45 @@
  *               a push or a window call that returned SSBA_ERR_HIP the device's state may be ahead of the host's, so the stream
  *               is dead: every later push or window call on it is SSBA_ERR_STATE, and only destroying it remains.
  *
+ * Odometry (ssba_track_stream_enable_odometry, ssba_track_stream_pose, ssba_track_relative_pose; the statement is
+ * tests/tracks_odometry_reference.py)
+ *   The second half of the node's callback (sparse_stereo_odometry_node.cpp:176-301): the matches to the previous frame are
+ *   triangulated, a 3-point RANSAC gives T_k_km1 and the inliers, a two-view solve over the inliers refines it, and the pose is
+ *   chained.  A stream with odometry enabled does this inside every push, on the device, within the push's one synchronisation
+ *   and one download.  Poses are [t | R row-major] with p_k = R p_km1 + t, the convention of ssba_frontend_vo;
+ *   T_k_0 = T_k_km1 o T_km1_0 and T_0_0 = first_pose.
+ *   matches     the ids present in both this push's and the previous push's outputs, in this push's order (the kept survivors
+ *               whose id was inherited from a kept survivor), with exactly the (u, v, d) doubles those pushes returned: a caller
+ *               can rebuild the list.  Both sides are triangulated by StereoCamera::triangulate,
+ *               (x, y, z) = b / d ((u - cu), (v - cv) fu / fv, fu).
+ *   draws       this library's own rule (the node's mt19937 stream needs n on the host): mix(x) is the 32-bit mixer
+ *                   x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *               and hypothesis h of H in frame f (the index of the pushed frame, 0 for the first) uses the counter
+ *               c = 3 (f H + h) mod 2^32:  i0 = mix(c) % n;  i1 = mix(c + 1) % (n - 1), plus 1 if >= i0;
+ *               i2 = mix(c + 2) % (n - 2), plus 1 if >= min(i0, i1), then plus 1 if >= max(i0, i1).  Distinct by construction.
+ *   hypotheses  the 3-point alignment and the inlier test (squared stereo reprojection error < ransac_threshold,
+ *               point_cloud_aligner.cpp:117-124) are those of ssba_frontend_vo, the same source text.  The first hypothesis with
+ *               the largest count wins; the inlier flags are the winner's.
+ *   refinement  the node's two-view problem (:236-285) with the gauge fixed: pose k - 1 constant at the identity, pose k free
+ *               from the RANSAC pose, one free point per inlier from its triangulation in frame k - 1, two
+ *               StereoReprojectionError blocks per point with stiffness I / sqrt(observation_variance), no loss, the pose
+ *               updated by exp(eps) T.  Levenberg-Marquardt exactly as oracle/ssba_oracle.c states it under orc_default_options
+ *               with max_num_iterations = refine_iterations (Jacobi scaling, the diagonal clamps, the radius rule, every
+ *               termination).  The points are eliminated in closed form, leaving one 6 x 6 system.  All fp64; every sum runs
+ *               over the inliers in a fixed order without floating-point atomics, so two runs give the same bytes.
+ *   status      SSBA_TRACK_POSE_OK; _FIRST_FRAME: the identity, T_k_0 = first_pose; _FEW_MATCHES: fewer than 3 matches, the
+ *               identity, the chain continues; _FEW_INLIERS: the winner has fewer than 3 inliers, its pose stands without a
+ *               refinement (the identity when no hypothesis has an inlier); _NUMERICAL: the refinement met a non-finite cost or
+ *               five invalid steps in a row, the RANSAC pose stands.
+ *   launches    per push with odometry 4 more than without: k_od_match, k_od_align, k_od_score, k_od_solve (2 more on the
+ *               first push: k_od_match, k_od_solve).  No further synchronisation, no allocation, still one download: the push
+ *               output block grows by the pose block.  A stream that does not enable odometry launches, allocates and returns
+ *               what it did before.
+ *   refusals    SSBA_ERR_INVALID_ARGUMENT before a device is looked for: NULL arguments; ransac_iterations outside 1 ... 4096;
+ *               a non-positive (or non-finite) ransac_threshold, observation_variance, fu, fv or b; refine_iterations above
+ *               1024; n above 4096.  SSBA_ERR_STATE: enabling odometry after the first push or twice; ssba_track_stream_pose
+ *               on a stream without odometry or before its first push.
+ *
  * SSBA_ERR_INVALID_ARGUMENT, with a message and before a device is looked for: a NULL input or output; both or neither of
  *   right / disp16; frames < 1 or > 32767 (n likewise, up to 65535); rows or cols < 31 or > 8192; max_features outside
  *   1 ... 4096; fast_threshold outside 0 ... 254; max_hamming outside 0 ... 256; a negative stereo_max_dy, max_disparity or
@@ -233,6 +272,50 @@ SSBA_API int ssba_track_stream_push(ssba_track_stream *stream, const uint8_t *le
  * ssba_track_sequence writes it: state_start (frames + 1), point_id and uvd with room for `capacity` observations. */
 SSBA_API int ssba_track_stream_window(ssba_track_stream *stream, uint32_t frames, uint64_t capacity, uint32_t *state_start, uint32_t *point_id,
                                       double *uvd, uint64_t *num_observations, uint32_t *num_points);
+
+/* ---- odometry ----------------------------------------------------------------------------------------------------------- */
+#define SSBA_TRACK_ODOMETRY_MAX 4096          /* matches and hypotheses */
+#define SSBA_TRACK_ODOMETRY_MAX_REFINE 1024   /* refine_iterations */
+#define SSBA_TRACK_POSE_OK 0
+#define SSBA_TRACK_POSE_FIRST_FRAME 1
+#define SSBA_TRACK_POSE_FEW_MATCHES 2
+#define SSBA_TRACK_POSE_FEW_INLIERS 3
+#define SSBA_TRACK_POSE_NUMERICAL 4
+
+/* ssba_track_default_odometry_params: camera all zero (the caller sets it), ransac_iterations 400 and ransac_threshold 4.0 (the
+ * reference's), refine_iterations 20 (0: the RANSAC pose is the answer), observation_variance 4.0 (node :246), first_pose the
+ * identity */
+typedef struct {
+    ssba_camera camera;
+    uint32_t ransac_iterations;
+    double ransac_threshold;
+    uint32_t refine_iterations;
+    double observation_variance;
+    double first_pose[12];
+} ssba_track_odometry_params;
+SSBA_API void ssba_track_default_odometry_params(ssba_track_odometry_params *params);
+
+/* num_iterations counts the minimiser's iteration records, the initial one included (0: no refinement ran); the costs are those
+ * of the refinement (0 when none ran) */
+typedef struct {
+    int32_t status;
+    uint32_t num_matches, num_inliers, num_iterations;
+    double initial_cost, final_cost;
+} ssba_track_pose_info;
+
+/* Only before the stream's first push (SSBA_ERR_STATE afterwards, and when it is enabled already).  Allocates everything the
+ * odometry needs: a push still allocates nothing. */
+SSBA_API int ssba_track_stream_enable_odometry(ssba_track_stream *stream, const ssba_track_odometry_params *params);
+
+/* The result of the last push: no device work, the numbers came down in the push's one copy.  info may be NULL. */
+SSBA_API int ssba_track_stream_pose(ssba_track_stream *stream, double T_k_km1[12], double T_k_0[12], ssba_track_pose_info *info);
+
+/* The odometry's kernels on a list the caller supplies: n matches paired by position, uvd_prev and uvd_cur with 3 doubles each
+ * (NULL allowed when n = 0), frame_index for the draws.  T_ransac (12), inlier (n flags), cost_log and step_ok
+ * (refine_iterations + 1 entries each: the minimiser's records, NaN / 0 behind the last) may be NULL; T (12) and info not. */
+SSBA_API int ssba_track_relative_pose(const ssba_track_odometry_params *params, uint32_t frame_index, uint32_t n, const double *uvd_prev,
+                                      const double *uvd_cur, int device, double *T_ransac, uint8_t *inlier, double *T, ssba_track_pose_info *info,
+                                      double *cost_log, int32_t *step_ok);
 
 /* NULL is allowed.  Nothing else may use the stream while or after this runs. */
 SSBA_API void ssba_track_stream_destroy(ssba_track_stream *stream);

@@ -28,6 +28,10 @@ of the shape's sequence, walked back and forth so that consecutive pushes are ne
                     every new frame, on the same frames.  One warm-up window, three timed windows of --calls frames each, the two
                     labels taking turns window by window in one process; median window per frame in ms and the spread.
   history           one stream of 50 pushes with a host clock around each: the pushes at indices 5 ... 14 against 40 ... 49.
+--stream --odometry measures a stream with odometry enabled (a pose with every push) and writes profiles/feature_track_odometry.json:
+  (a) push_plain / push_odometry   two streams on the same frames taking turns in one process: the cost of the added launches
+  (b) live_caller                  what a caller did for the same output before: push + window(2) + ssba_frontend_vo + a two-state
+                                   StereoBA solve with pose 0 constant, against push_odometry
 With --stream, --trace-run makes ONE stream push 17 frames with a window call after each, and --merge-trace splits the trace at
 k_ts_emit (the last launch of a push) and k_ts_window into the launches of every push and of every window call."""
 import argparse
@@ -160,6 +164,78 @@ def stream_compare(seq, name, calls, sub):
     return out
 
 
+def odometry_compare(seq, name, calls, sub):
+    """(a) and (b) of the module docstring, medians of three alternating windows of `calls` pushes each."""
+    import ctypes as C
+
+    import numpy as np
+
+    from ceres_slam_amd import capi, frontend
+    from ceres_slam_amd.solver import StereoBA
+
+    shape, kw = SHAPES[name], dict(fast_threshold=FAST_THRESHOLD, max_features=SHAPES[name]["max_features"])
+    refine = {} if sub else None
+    order = walk(4 * calls + 2)
+    left, right = seq.left[order], seq.right[order]
+    identity = np.array([0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1.0])
+    variant = 1                                                         # which libstdc++ draw sequence: no matter for the time
+
+    def summary(windows):
+        return dict(ms=round(statistics.median(windows), 4), spread_ms=round(max(windows) - min(windows), 4), windows_ms=[round(w, 4) for w in windows])
+
+    def timed(step, first):
+        t = time.perf_counter()
+        for k in range(first, first + calls):
+            step(k)
+        return (time.perf_counter() - t) / calls * 1e3
+
+    def solve_window(start, ids, uvd, num_points):
+        obs_state = np.repeat(np.arange(2, dtype=np.uint32), np.diff(start.astype(np.int64)))
+        poses, points, init, _ = frontend.compute_initial_guess_device(seq.camera, 2, num_points, obs_state, ids, uvd, identity, variant=variant)
+        sel, keep = init[ids], np.nonzero(init)[0]
+        remap = np.full(num_points, -1, np.int64)
+        remap[keep] = np.arange(len(keep))
+        ba = StereoBA(seq.camera, poses.copy(), points[keep].copy(), obs_state[sel], remap[ids[sel]].astype(np.uint32), uvd[sel], np.eye(3) / 2.0)
+        options, summ = capi.default_options(max_num_iterations=20), capi.Summary()
+        ba.lib.ssba_solve(ba.h, C.byref(options), C.byref(summ))
+        out = ba.poses.copy()
+        ba.close()
+        return out
+
+    infos = []
+    with tracks.TrackStream(shape["rows"], shape["cols"], 2, refine=refine, **kw) as plain, \
+            tracks.TrackStream(shape["rows"], shape["cols"], 2, refine=refine, odometry=dict(camera=seq.camera), **kw) as odo, \
+            tracks.TrackStream(shape["rows"], shape["cols"], 2, refine=refine, **kw) as live:
+        def push_plain(k):
+            plain.push(left[k], right[k])
+
+        def push_odometry(k):
+            odo.push(left[k], right[k])
+            infos.append(odo.pose()[2])
+
+        def live_caller(k):
+            live.push(left[k], right[k])
+            if live.pushed > 1:
+                solve_window(*live.window(2))
+
+        steps = dict(push_plain=push_plain, push_odometry=push_odometry, live_caller=live_caller)
+        for step in steps.values():
+            timed(step, 0)
+        windows = {k: [] for k in steps}
+        for i in range(3):
+            for k, step in steps.items():
+                windows[k].append(timed(step, (1 + i) * calls))
+    out = {k: summary(w) for k, w in windows.items()}
+    out["calls_per_window"] = calls
+    out["odometry_minus_plain_ms"] = round(out["push_odometry"]["ms"] - out["push_plain"]["ms"], 4)
+    out["live_caller_over_push_odometry"] = round(out["live_caller"]["ms"] / out["push_odometry"]["ms"], 3)
+    timed_infos = infos[calls:]
+    out["status_counts"] = {str(k): int(v) for k, v in sorted(collections.Counter(i["status"] for i in timed_infos).items())}
+    for key in ("num_matches", "num_inliers", "num_iterations"):
+        out["median_" + key] = int(statistics.median(i[key] for i in timed_infos))
+    return out
+
+
 def stream_trace_run(name, sub):
     seq, shape = stream_frames(name), SHAPES[name]
     with tracks.TrackStream(shape["rows"], shape["cols"], STREAM_FRAMES, refine={} if sub else None, fast_threshold=FAST_THRESHOLD,
@@ -196,12 +272,27 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--subpixel", action="store_true")
     ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--odometry", action="store_true")
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--trace-run")
     ap.add_argument("--merge-trace", nargs=2)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "feature_track_stream.json" if a.stream else "feature_tracks_subpixel.json" if a.subpixel else "feature_tracks.json")
+    if a.odometry and not a.stream:
+        ap.error("--odometry goes with --stream")
+    a.out = a.out or os.path.join(ROOT, "profiles", "feature_track_odometry.json" if a.odometry else "feature_track_stream.json" if a.stream else "feature_tracks_subpixel.json" if a.subpixel else "feature_tracks.json")
+    if a.odometry:
+        doc = load(a.out)
+        for name in a.shapes.split(","):
+            seq = stream_frames(name)
+            doc.setdefault(name, {}).update(SHAPES[name], frames=STREAM_FRAMES, fast_threshold=FAST_THRESHOLD)
+            for sub in (False, True):
+                doc[name]["subpixel" if sub else "whole_pixel"] = odometry_compare(seq, name, a.calls, sub)
+                print(name, "subpixel" if sub else "whole_pixel", doc[name]["subpixel" if sub else "whole_pixel"])
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     if a.stream:
         if a.trace_run:
             stream_trace_run(a.trace_run, a.subpixel)
